@@ -2,7 +2,11 @@
 """bench.py -- magnified frames/s of the HIP magnification core on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--mode laplace|riesz|color] [--streams B]
-                    [--frames-per-call T] [--no-verify] [--no-subrecords]
+                    [--frames-per-call T] [--dump-outputs DIR] [--full [--no-verify] [--no-subrecords]]
+
+A plain run sets up, primes, warms up, times the K steps, writes the last step's outputs when --dump-outputs is given and
+prints the result line.  Everything else below (float probe + verification against the CPU oracle, cpu_baseline, shader
+clock, per-kernel pass / roofline, value_cold, sub-records) runs only with --full.
 
 A "step" is ONE PASS of the hot path over one batch: one lvm_process_device_frames call of T = --frames-per-call
 consecutive frames (default 32) of each of the B streams of the context, over synthetic frames that are already
@@ -37,7 +41,7 @@ torch.distributed.run (one rank per GPU, rendezvous on 127.0.0.1).  Every rank r
 stream(s) (seeds 1234 + global stream id): the path shards by stream with no data-path collective (weak
 scaling); RCCL only carries the timing barrier and the MAX-reduce of the elapsed time.
 
-Prints ONE JSON line (rank 0) carrying `roofline` and `cpu_baseline`.
+Prints ONE JSON line (rank 0); with --full it carries `verified`, `roofline` and `cpu_baseline` too.
 """
 import argparse
 import ctypes as C
@@ -344,6 +348,34 @@ def oracle_replay(po, np, host_frames, pk, ring, n_frames, check, threads, float
     return keep, fl, dt
 
 
+DUMP_SAMPLE = 1 << 21            # sampled u8 values of the last step (positions drawn with seed 0)
+DUMP_FRAME_BYTES = 32 << 20      # float32 bytes the dumped whole frame may take (halved in both directions until it fits)
+
+
+def dump_outputs(path, R, np, torch):
+    """--dump-outputs: what the last timed step handed its caller -- the u8 BGR output frames of its call, T frames x B
+    streams in device memory, plus the call's produced flags -- as .npy files: `last_frame` (the step's last frame of
+    stream 0, float32 h x w x 3), `step_sample` (float32 values at `step_sample_index`, float64 flat positions into the
+    step's T x B x h x w x 3 frames, drawn with seed 0) and `produced` (float32, one flag per frame of the call; T > 1).
+    The inputs depend only on the arguments, so two builds can be compared file by file.  At most ~56 MB in all."""
+    os.makedirs(path, exist_ok=True)
+    step = torch.stack([R.d_out[R.out_slot(i)] for i in range(R.n - R.T, R.n)])       # (T, B, h, w, 3) u8
+    flat = step.reshape(-1)
+    idx = np.unique(np.random.default_rng(0).integers(0, flat.numel(), min(DUMP_SAMPLE, flat.numel())))
+    frame = step[-1, 0]
+    while frame.numel() * 4 > DUMP_FRAME_BYTES:
+        frame = frame[::2, ::2]
+    files = {"last_frame": frame.cpu().numpy().astype(np.float32),
+             "step_sample": flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy().astype(np.float32),
+             "step_sample_index": idx.astype(np.float64)}
+    if R.T > 1:          # one lvm_process_device_frames call per step: R.prod holds the flags of the last one
+        files["produced"] = np.array(list(R.prod)[:R.T], dtype=np.float32)
+    for name, a in files.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {"dir": path, "files": {name: list(a.shape) for name, a in files.items()},
+            "bytes": sum(a.nbytes for a in files.values()), "frames": [R.n - R.T, R.n]}
+
+
 CLIP_NOISE = None     # --clip-noise
 
 
@@ -374,6 +406,10 @@ def main():
     ap.add_argument("--share-gpu", action="store_true", help="testing only: every rank uses cuda:0")
     ap.add_argument("--no-clock-probe", action="store_true", help="no shader-clock probe beside the timed region (a profiler that serialises kernels would "
                     "make the timed calls wait for the probe's time-out: tools/pmc.sh passes this)")
+    ap.add_argument("--full", action="store_true", help="also verify against the CPU oracle, measure cpu_baseline, the shader clock, the per-kernel "
+                    "pass / roofline, value_cold and the sub-records (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's output frames (float32 .npy: the last frame "
+                    "of stream 0 and a fixed sample over the whole step) to DIR")
     args = ap.parse_args()
     global CLIP_NOISE
     CLIP_NOISE = args.clip_noise
@@ -427,8 +463,9 @@ def main():
     T = max(1, args.frames_per_call)
     ring = ((max(args.ring, T) + T - 1) // T) * T
     T = min(T, ring)
-    verify = not (args.no_verify or args.no_cpu_baseline) and (args.verify_all_ranks or (rank == 0 and world == 1))
-    do_sub = (world == 1 or args.subrecords) and not args.no_subrecords
+    full = args.full
+    verify = full and not (args.no_verify or args.no_cpu_baseline) and (args.verify_all_ranks or (rank == 0 and world == 1))
+    do_sub = full and (world == 1 or args.subrecords) and not args.no_subrecords
 
     ids = lvm.sharding.stream_ids(rank, world, B)
     # K steps = K calls of T frames; W warm-up steps likewise.  Outputs of every frame up to the end of the verified span keep their own
@@ -447,15 +484,16 @@ def main():
     R.run(Wf)
     # ---- float probe: one more call with the pre-quantisation frame kept (stream 0); in front of the timed region so that the oracle
     # replay can stop after the verified span ----
-    probe_n = 0
+    probe_n = T
     float_gpu = None
     probe_first = -1
-    if verify:
+    if not verify:
+        R.run(probe_n)                   # the same call without the float frame: plain and --full runs time (and dump) the same frames
+    else:
         R.ctx.flush(stream)
         pd = args.pipeline
         R.ctx.set_pipeline(0)
         R.ctx.keep_float(True)
-        probe_n = T
         probe_first = R.n                # the kernels keep the float frame of the FIRST frame of a batch (stream 0)
         if args.mode == "color":
             probe_first += 32 * ((probe_n - 1) // 32)      # the colour mode cuts a call into chunks of <= 32 frames
@@ -465,18 +503,21 @@ def main():
         R.ctx.keep_float(False)
         R.ctx.set_pipeline(pd)
     base = R.n
-    assert not verify or base == base_expected, (base, base_expected)
+    assert base == base_expected, (base, base_expected)
     ramp_frames = R.ramp(args.ramp_ms * 1e-3)
     # ---- the timed region: K calls ----
     dt = lvm.sharding.timed_steps(lambda _: R.run(Kf), 1, dist, torch.cuda.synchronize, red_dev, finish=lambda: R.ctx.flush(stream))
     host_enqueue = getattr(lvm.sharding.timed_steps, "host_seconds", 0.0)
     fps = lvm.sharding.aggregate_fps(world, B, Kf, dt)
     n_verify = min(R.n, v_end)
+    dumped = None
+    if args.dump_outputs and rank == 0:      # before the clock pass below reuses the output ring
+        dumped = dump_outputs(args.dump_outputs, R, np, torch)
     # ---- the shader clock under this workload: the SAME K calls once more, right behind the timed region, with a one-lane kernel on the auxiliary
     # stream reading s_memtime / s_memrealtime at both ends (lvm_debug_clock_probe_*).  Not inside the timed region: the probe's wave takes a slot that
     # the persistent / one-round launches count on -- measured on this part: Laplace -1..2 %, Riesz 0, Color -6..10 % (profiles/r06_clock_probe_cost.txt).
     clock = {"mhz": None}
-    if not args.no_clock_probe:
+    if full and not args.no_clock_probe:
         try:
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -551,7 +592,7 @@ def main():
             cpu.update({"kind": "reference", "value": ref_check["fps"], "cores": 1,
                         "sample": "the reference's own MagnificationProcessor (oracle/_ref/libref_magnify.so) on the first %d frames" % nref,
                         "port_value": round(n_verify / cdt, 3)})
-    elif rank == 0 and world == 1 and not args.no_cpu_baseline:
+    elif full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import pyoracle as po
         nthreads = max(1, min(16, os.cpu_count() or 1))
         host = R.d_in[:, 0].cpu().numpy()
@@ -568,7 +609,7 @@ def main():
     Twin = lvm.load().lvm_optimal_buffer_size(int(pk["framerate"]))
     if args.profile_steps < 0:
         args.profile_steps = 2 * T if T > 1 else 60        # whole calls only: every launch then covers exactly T frames
-    if rank == 0 and args.profile_steps > 0:
+    if full and rank == 0 and args.profile_steps > 0:
         kernels, roofline = kernel_pass(lvm, torch, R, args.mode, args.profile_steps, args.ramp_ms * 1e-3)
     b_alg = lvm.load().lvm_algorithmic_bytes(pk["mode"], w, h, ch, levels, pk["framerate"])
     frame_frac = b_alg * (fps / world / B) / (HBM_PEAK_GBS * 1e9)
@@ -592,7 +633,7 @@ def main():
 
     # ---- the timed region's own shape once more WITHOUT the clock ramp (a GPU a few milliseconds out of idle) ----
     value_cold = None
-    if not args.no_subrecords:
+    if full and not args.no_subrecords:
         Rc = Runner(lvm, torch, np, cfg_idx, small, B, ring, T, local_rank, ids, ring)
         Rc.ctx.set_pipeline(args.pipeline)
         dtc = timed_run(lvm, torch, Rc, Kf, Wf, dist, red_dev, ramp=0.0)
@@ -606,7 +647,7 @@ def main():
     sub = {}
     if do_sub:
         sub = sub_records(lvm, torch, np, args, cfg_idx, small, local_rank, rank, world, dist, red_dev)
-    elif world > 1:
+    elif full and world > 1:
         sub = {"cfg4_riesz_4k": config_record(lvm, torch, np, 4, local_rank, rank, world, dist, red_dev, K=64, W=16, T=16, ring=16, extras=False),
                "host_fed": host_fed_record(lvm, torch, np, cfg_idx, small, local_rank, rank, world, dist, red_dev)}
 
@@ -637,6 +678,7 @@ def main():
             "frame_batched_alg_bytes": round(b_bat), "frame_batched_roofline_frac": round(b_bat * (fps / world / B) / (HBM_PEAK_GBS * 1e9), 5),
             "timed_seconds_max_over_ranks": dt,
             "dist": dist_info,
+            "full": full, "outputs_dumped": dumped,
             "ranks": rank_facts,
             "kernels": kernels,
         }

@@ -145,7 +145,7 @@ def test_riesz_4k_strip_kernels_equal_the_tiled_kernels(lvm, hip, monkeypatch, s
 def _bench(args, timeout=900):
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=timeout, env=env, cwd=ROOT)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + args, capture_output=True, text=True, timeout=timeout, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -169,6 +169,51 @@ def test_bench_verifies_itself_and_prices_kernels_below_peak():
     # the shader clock over the timed region (s_memtime / s_memrealtime): a plausible MI355X figure, covering about the timed region
     assert out["clock"]["error"] is None and 500.0 < out["clock_mhz"] < 3000.0, out["clock"]
     assert 0.5 * out["timed_seconds_max_over_ranks"] < out["clock"]["seconds_covered"] < 1.5 * out["timed_seconds_max_over_ranks"] + 1e-3, out["clock"]
+
+
+def test_bench_plain_run_times_the_headline_and_dumps_its_outputs(lvm, po, tmp_path):
+    """A plain run (no --full) times exactly --steps steps and measures nothing else; --dump-outputs writes the last timed
+    step's frames (float32 / float64 .npy, well under 64 MB), the same bytes on a second run, and they are what the CPU
+    oracle computes for those frames of the stream."""
+    args = ["--width", "320", "--height", "180", "--levels", "4", "--steps", "8", "--warmup", "4", "--frames-per-call", "4", "--ring", "8"]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    outs = []
+    for d in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + ["--dump-outputs", str(tmp_path / d)],
+                           capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+        assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, p.stdout[-2000:]
+        outs.append(json.loads(lines[0]))
+    out = outs[0]
+    assert out["full"] is False and out["steps"] == 8 and out["warmup"] == 4 and out["frames_per_step"] == 4
+    assert abs(out["ms_per_step"] - 1e3 * out["timed_seconds_max_over_ranks"] / out["steps"]) <= 1e-3
+    assert out["verified"] is None and out["cpu_baseline"] is None and out["roofline"] is None and out["kernels"] == {}
+    assert out["value_cold"] is None and out["clock_mhz"] is None and "per_frame" not in out
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["last_frame.npy", "produced.npy", "step_sample.npy", "step_sample_index.npy"], files
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    for f in files:
+        assert got[f[:-4]].dtype in (np.float32, np.float64), f
+        assert np.array_equal(got[f[:-4]], np.load(tmp_path / "b" / f)), f
+    # the dumped frames are frames first .. last-1 of stream 0; the oracle replays the same clip up to there
+    first, last = out["outputs_dumped"]["frames"]
+    ck, pk = lvm.synth.config(1, (320, 180, 4))
+    clip = lvm.synth.Clip(seed=lvm.sharding.stream_seed(0), **{k: v for k, v in ck.items() if k != "seed"})
+    orc = po.Oracle()
+    P = po.make_params(**pk)
+    step = np.zeros((last - first, 1, 180, 320, 3), np.float32)
+    for i in range(last):
+        ref, produced = orc.process(clip.frame(i % 8), P)
+        if i >= first:
+            assert bool(got["produced"][i - first]) == bool(produced), i
+            step[i - first, 0] = ref
+    orc.close()
+    du = np.abs(got["last_frame"] - step[-1, 0])
+    assert du.max() <= 1 and (du == 0).mean() >= 0.999, du.max()
+    ds = np.abs(got["step_sample"] - step.reshape(-1)[got["step_sample_index"].astype(np.int64)])
+    assert ds.max() <= 1 and (ds == 0).mean() >= 0.999, ds.max()
 
 
 @pytest.mark.parametrize("mode", ["riesz", "color"])
@@ -210,7 +255,7 @@ def test_bench_one_rank_over_rccl():
         env.pop(k, None)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dist-backend", "nccl", "--steps", "8",
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--dist-backend", "nccl", "--steps", "8",
            "--warmup", "4", "--width", "320", "--height", "180", "--levels", "4", "--no-subrecords", "--frames-per-call", "4", "--ring", "8"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]

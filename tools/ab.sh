@@ -5,7 +5,7 @@ O=gpurun_out/${1:-ab}; mkdir -p $O; shift
 i=0
 while [ $# -gt 0 ]; do
   v="$1"; shift; i=$((i+1))
-  env $v timeout 300 python bench.py --no-cpu-baseline --no-subrecords --steps 128 --warmup 32 ${BENCH_ARGS:-} > $O/v$i.json 2> $O/v$i.err
+  env $v timeout 300 python bench.py --full --no-cpu-baseline --no-subrecords --steps 128 --warmup 32 ${BENCH_ARGS:-} > $O/v$i.json 2> $O/v$i.err
   python - "$v" $O/v$i.json <<'PY'
 import json,sys
 try:

@@ -8,10 +8,10 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 R=r06
 O=$ROOT/gpurun_out/profiles_$R; mkdir -p $O; cd $ROOT
 # (round 6: a step is one 32-frame call; `--steps 20 --warmup 5` IS the default and the driver's command)
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/${R}_bench_laplace_driver_shape.json 2> $O/err.txt
-timeout 600 python bench.py --steps 60 --warmup 10 --no-subrecords > $O/${R}_bench_laplace.json 2>> $O/err.txt
-timeout 400 python bench.py --mode riesz --no-subrecords > $O/${R}_bench_riesz.json 2>> $O/err.txt
-timeout 400 python bench.py --mode color --no-subrecords > $O/${R}_bench_color.json 2>> $O/err.txt
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/${R}_bench_laplace_driver_shape.json 2> $O/err.txt
+timeout 600 python bench.py --full --steps 60 --warmup 10 --no-subrecords > $O/${R}_bench_laplace.json 2>> $O/err.txt
+timeout 400 python bench.py --full --mode riesz --no-subrecords > $O/${R}_bench_riesz.json 2>> $O/err.txt
+timeout 400 python bench.py --full --mode color --no-subrecords > $O/${R}_bench_color.json 2>> $O/err.txt
 tools/ubench_valu > $O/${R}_ubench_valu_issue_rates.txt 2>&1
 SQ1="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE"
 SQ2="SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR"
