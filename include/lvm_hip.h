@@ -87,7 +87,9 @@ int  lvm_process_device(lvm_ctx* ctx, const lvm_params* p, const uint8_t* d_in, 
  * is read at d_in + f*in_frame_stride + s*in_stream_stride and written likewise.  Semantically this
  * IS n_frames calls of lvm_process_device in order (produced[f] per frame); when the mode has a
  * temporally batched schedule (Laplace: stateless kernels take the frames as a batch dimension, the
- * IIR kernels walk over them in order with their state in registers) the frames share launches.  */
+ * IIR kernels walk over them in order with their state in registers) the frames share launches.
+ * Byte for byte: for the same frames in the same memory layout every schedule (this call in any
+ * lengths, per-frame calls, lvm_process, pipeline depth 1, any stream) writes the same bytes.     */
 int  lvm_process_device_frames(lvm_ctx* ctx, const lvm_params* p, int n_frames, const uint8_t* d_in,
                                int w, int h, int channels, ptrdiff_t in_stride,
                                ptrdiff_t in_stream_stride, ptrdiff_t in_frame_stride, uint8_t* d_out,

@@ -218,12 +218,15 @@ __global__ __launch_bounds__(256) void k_down0_v4(const uint8_t* __restrict__ in
             const float4 u = *reinterpret_cast<const float4*>(row);
             const float4 v = *reinterpret_cast<const float4*>(row + 4);
             // taps of output x: u.x u.y u.z u.w v.x ; of output x+1: u.z u.w v.x v.y v.z
-            const float ha = u.z * 6.f + (u.y + u.w) * 4.f + u.x + v.x;
-            const float hb = v.x * 6.f + (u.w + v.y) * 4.f + u.z + v.z;
+            // default flavour: the fma chains of the strip kernels (k_down0_rows, k_down0_lut_rows), so that level 1 -- and the output
+            // bytes -- do not depend on which first kernel the launch size picks (per-frame calls vs temporal batches)
+            constexpr bool FMA = !fl_exact(FL) && LVM_FAST_FMA;
+            const float ha = FMA ? __builtin_fmaf(u.z, 6.f, __builtin_fmaf(u.y + u.w, 4.f, u.x + v.x)) : u.z * 6.f + (u.y + u.w) * 4.f + u.x + v.x;
+            const float hb = FMA ? __builtin_fmaf(v.x, 6.f, __builtin_fmaf(u.w + v.y, 4.f, u.z + v.z)) : v.x * 6.f + (u.w + v.y) * 4.f + u.z + v.z;
             if (rr >= 4 && (rr & 1) == 0) {
                 const int gy = oy0 + 4 * seg + (rr - 4) / 2, gx = ox0 + x;
-                const float oa = (w2a * 6.f + (w1a + w3a) * 4.f + w0a + ha) * (1.f / 256.f);
-                const float ob = (w2b * 6.f + (w1b + w3b) * 4.f + w0b + hb) * (1.f / 256.f);
+                const float oa = (FMA ? __builtin_fmaf(w2a, 6.f, __builtin_fmaf(w1a + w3a, 4.f, w0a + ha)) : w2a * 6.f + (w1a + w3a) * 4.f + w0a + ha) * (1.f / 256.f);
+                const float ob = (FMA ? __builtin_fmaf(w2b, 6.f, __builtin_fmaf(w1b + w3b, 4.f, w0b + hb)) : w2b * 6.f + (w1b + w3b) * 4.f + w0b + hb) * (1.f / 256.f);
                 if (gy < h1) {
                     if ((w1 & 1) == 0 && gx + 1 < w1) *reinterpret_cast<float2*>(&dst[(size_t)gy * w1 + gx]) = make_float2(oa, ob);
                     else {

@@ -1,14 +1,23 @@
 """Shared helpers of the parity tests (test infrastructure)."""
 import numpy as np
 
+# The shipped build against the float-keeping one where the output kernels quantise through the u8 step table (fin_steps in
+# csrc/lvm_internal.h): the step table is OpenCV's unfused spline + scale + round, the float-keeping kernels evaluate the spline as
+# an fma chain -- the two round apart on a few pixels (the bar of tests/test_u8_steps.py).
+STEPS_U8_FRAC = 0.9999
+
 
 def c_params(lvm, pk, key=0):
     return lvm.LvmParams(pk["mode"], pk["levels"], pk["amplification"], pk["coWavelength"], pk["coLow"],
                          pk["coHigh"], pk["chromAttenuation"], pk["framerate"], key)
 
 
+def _channels(f):
+    return 1 if f.ndim == 2 else f.shape[2]
+
+
 def run_pair(lvm, po, lib, clip, pk, nframes, float_tol, n_streams=1, u8_max=1, u8_frac=0.999, exact=False,
-             param_fn=None, exact_lab=None, analytic=False, lab_lut=None):
+             param_fn=None, exact_lab=None, analytic=False, lab_lut=None, shipped=True):
     """Feeds the same frames to the CPU oracle and to the library behind the C ABI `lib`
     (gfx950 build or the CPU emulation build) and checks, frame by frame:
       (i)   produced / passthrough flags identical,
@@ -16,38 +25,65 @@ def run_pair(lvm, po, lib, clip, pk, nframes, float_tol, n_streams=1, u8_max=1, 
       (iii) u8 frame: max abs diff <= u8_max LSB and >= u8_frac identical pixels.
     Both sides run OpenCV 4's default forward Lab (the interpolated 33^3 table) unless analytic=True (the cube-root form
     OpenCV computes with its interpolation switched off: oracle lvmo_set_lab_lut(0), library lvm_debug_lab_analytic).
-    Returns the worst observed (rel, u8 diff, identical fraction)."""
+
+    Reading the float frame (lvm_debug_keep_float) selects other builds of the output kernels (DBG = true, spline quantiser).
+    So a second context of the same library, `shipped`, runs the same frames in the configuration that process(), the chain,
+    export and bench.py run: keep_float off, exact_lab off, lab_analytic as asked.  Per frame it must give
+      (iv)  the oracle's produced flags, and a u8 frame within the u8_max / u8_frac bars of the oracle's
+            (exact=True: the parity bars, 1 LSB / 0.999, since the shipped build is the fast flavour);
+      (v)   against the first context's u8 frame, when both run the same flavour (always in Color mode, which has no Lab):
+            identical bytes where the step table does not apply (Color, gray, the analytic flavour), else <= 1 LSB and
+            >= STEPS_U8_FRAC identical.
+    shipped=False opts out (callers give the reason on the same line).
+    Returns the worst observed figures: [float rel, u8 diff, identical fraction] of the first context, then
+    [u8 diff, identical fraction] of the shipped context against the oracle."""
     P = po.make_params(**pk)
+    exact_lab = exact if exact_lab is None else exact_lab
     ctx = lvm.Context(0, n_streams, lib)
     ctx.keep_float(True)
-    ctx.exact_lab(exact if exact_lab is None else exact_lab)   # bit-exact checks need OpenCV-order Lab math
+    ctx.exact_lab(exact_lab)   # bit-exact checks need OpenCV-order Lab math
     ctx.lab_analytic(analytic)
+    ship = None
+    if shipped:
+        ship = lvm.Context(0, n_streams, lib)
+        ship.lab_analytic(analytic)
     if lab_lut is not None:
         ctx.set_lab_lut(lab_lut)
+        if ship is not None:
+            ship.set_lab_lut(lab_lut)
     po.lib().lvmo_set_lab_lut(0 if analytic else 1)
     orc = po.Oracle()
-    worst = [0.0, 0, 1.0]
+    same_flavour = analytic or not exact_lab
+    ship_max, ship_frac = (1, 0.999) if exact else (u8_max, u8_frac)
+    worst = [0.0, 0, 1.0, 0, 1.0]
     try:
         for t in range(nframes):
+            mode = pk["mode"]
             if param_fn:
                 pk2 = param_fn(t, dict(pk))
                 P = po.make_params(**pk2)
                 cp = c_params(lvm, pk2)
+                mode = pk2["mode"]
             else:
                 cp = c_params(lvm, pk)
             f = clip.frame(t)
             ref, pr = orc.process(f, P)
             out, pg = ctx.process(f, cp)
             assert pr == pg, "produced flag differs at frame %d: oracle %s, lib %s" % (t, pr, pg)
+            if ship is not None:
+                out_s, ps = ship.process(f, cp)
+                assert pr == ps, "shipped build: produced flag differs at frame %d: oracle %s, lib %s" % (t, pr, ps)
             if not pr:
                 assert out is f or np.array_equal(out, f)
+                if ship is not None:
+                    assert out_s is f or np.array_equal(out_s, f), "shipped build: passthrough frame %d changed" % t
                 continue
             fr = orc.last_float()
             fg = ctx.read_float(fr.shape)
             assert np.isfinite(fg).all(), "non-finite values in frame %d" % t
             rel = float(np.abs(fr - fg).max() / max(float(np.abs(fr).max()), 1e-30))
             du = np.abs(ref.astype(np.int32) - out.astype(np.int32))
-            worst = [max(worst[0], rel), max(worst[1], int(du.max())), min(worst[2], float((du == 0).mean()))]
+            worst[:3] = [max(worst[0], rel), max(worst[1], int(du.max())), min(worst[2], float((du == 0).mean()))]
             if exact:
                 assert np.array_equal(fr, fg), "frame %d: float frames differ (max rel %.3e)" % (t, rel)
                 assert np.array_equal(ref, out)
@@ -55,8 +91,237 @@ def run_pair(lvm, po, lib, clip, pk, nframes, float_tol, n_streams=1, u8_max=1, 
                 assert rel <= float_tol, "frame %d: float rel err %.3e > %.1e" % (t, rel, float_tol)
                 assert du.max() <= u8_max, "frame %d: u8 diff %d" % (t, du.max())
                 assert (du == 0).mean() >= u8_frac, "frame %d: identical fraction %.5f" % (t, (du == 0).mean())
+            if ship is None:
+                continue
+            ds = np.abs(ref.astype(np.int32) - out_s.astype(np.int32))
+            worst[3:] = [max(worst[3], int(ds.max())), min(worst[4], float((ds == 0).mean()))]
+            assert ds.max() <= ship_max, "shipped build, frame %d: u8 diff %d against the oracle" % (t, ds.max())
+            assert (ds == 0).mean() >= ship_frac, "shipped build, frame %d: identical fraction %.5f" % (t, (ds == 0).mean())
+            if same_flavour or mode == 2:
+                steps = mode in (0, 1) and _channels(f) == 3 and not analytic
+                dd = np.abs(out.astype(np.int32) - out_s.astype(np.int32))
+                if steps:
+                    assert dd.max() <= 1 and (dd == 0).mean() >= STEPS_U8_FRAC, \
+                        "frame %d: shipped build vs float-keeping build: max %d, identical %.6f" % (t, dd.max(), (dd == 0).mean())
+                else:
+                    assert dd.max() == 0, "frame %d: shipped build vs float-keeping build differ on %d bytes" % (t, int((dd != 0).sum()))
     finally:
         po.lib().lvmo_set_lab_lut(1)
         ctx.close()
+        if ship is not None:
+            ship.close()
+        orc.close()
+    return worst
+
+
+# ---- schedule equivalence: one clip through every surface of the library ------------------------------------------------------
+class HostMem:
+    """'Device' buffers of the emulation build: host arrays."""
+    def upload(self, a):
+        return np.ascontiguousarray(a).copy()
+
+    def zeros_like(self, a):
+        return np.zeros_like(a)
+
+    def ptr(self, a, i=0):
+        return a[i].ctypes.data
+
+    def download(self, a):
+        return np.asarray(a)
+
+    def stream(self):
+        return None
+
+    def sync(self, ctx):
+        ctx.synchronize()
+
+
+class TorchMem:
+    """Device buffers of the gfx950 build: torch tensors on the current HIP stream."""
+    def __init__(self):
+        import torch
+        self.torch = torch
+
+    def upload(self, a):
+        return self.torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+    def zeros_like(self, a):
+        return self.torch.zeros_like(a)
+
+    def ptr(self, a, i=0):
+        return a[i].data_ptr()
+
+    def download(self, a):
+        self.torch.cuda.synchronize()
+        return a.cpu().numpy()
+
+    def stream(self):
+        return self.torch.cuda.current_stream().cuda_stream
+
+    def sync(self, ctx):
+        self.torch.cuda.synchronize()
+
+
+def run_schedules(lvm, lib, mem, frames, other, pk, calls, pipeline=False):
+    """The same clip (`frames`, [n][h][w][3] uint8) through the surfaces include/lvm_hip.h calls equivalent, shipped configuration
+    (no keep_float, default flavour), packed rows (the layout lvm_process stages host frames in) in every schedule:
+      host       lvm_process on host frames
+      device     lvm_process_device, one frame per call
+      frames     lvm_process_device_frames with the call lengths `calls`
+      frames_max the same after lvm_set_max_frames(max(calls))
+      pipelined  lvm_process_device at pipeline depth 1 + lvm_flush (pipeline=True: Laplace)
+      stream1    lvm_process_device_frames on a 2-stream context, the clip as stream 1 and `other` as stream 0
+      chain      lvm_chain_process_batch_ex with preprocessing off (Preprocess -> Grayscale -> Magnification)
+    Returns {schedule: (produced flags, output frames)}; outputs of frames that were not produced are zeroed."""
+    n, h, w, ch = frames.shape
+    assert sum(calls) == n and other.shape == frames.shape
+    fb = w * h * ch
+    cp = c_params(lvm, pk)
+    res = {}
+
+    def finish(produced, out):
+        out = out.copy()
+        out[~np.asarray(produced, bool)] = 0
+        return list(produced), out
+
+    ctx = lvm.Context(0, 1, lib)
+    try:
+        outs, prod = np.zeros_like(frames), []
+        for t in range(n):
+            o, p = ctx.process(frames[t], cp)
+            prod.append(p)
+            if p:
+                outs[t] = o
+        res["host"] = finish(prod, outs)
+    finally:
+        ctx.close()
+
+    d_in = mem.upload(frames)
+    st = mem.stream()
+    for name in ("device", "pipelined") if pipeline else ("device",):
+        ctx = lvm.Context(0, 1, lib)
+        try:
+            if name == "pipelined":
+                ctx.set_pipeline(1)
+            d_out = mem.zeros_like(d_in)
+            prod = [ctx.process_device(cp, mem.ptr(d_in, t), w, h, ch, w * ch, fb, mem.ptr(d_out, t), w * ch, fb, st) for t in range(n)]
+            if name == "pipelined":
+                ctx.flush(st)
+            mem.sync(ctx)
+            res[name] = finish(prod, mem.download(d_out))
+        finally:
+            ctx.close()
+
+    for name, hint in (("frames", 0), ("frames_max", max(calls))):
+        ctx = lvm.Context(0, 1, lib)
+        try:
+            if hint:
+                ctx.set_max_frames(hint)
+            d_out = mem.zeros_like(d_in)
+            prod, t = [], 0
+            for nf in calls:
+                prod += ctx.process_device_frames(cp, nf, mem.ptr(d_in, t), w, h, ch, w * ch, fb, fb, mem.ptr(d_out, t), w * ch, fb, fb, st)
+                t += nf
+            mem.sync(ctx)
+            res[name] = finish(prod, mem.download(d_out))
+        finally:
+            ctx.close()
+    del d_in
+
+    d_in2 = mem.upload(np.stack([other, frames], axis=1))          # [frame][stream][h][w][ch]: the clip is stream 1
+    ctx = lvm.Context(0, 2, lib)
+    try:
+        d_out2 = mem.zeros_like(d_in2)
+        prod, t = [], 0
+        for nf in calls:
+            prod += ctx.process_device_frames(cp, nf, mem.ptr(d_in2, t), w, h, ch, w * ch, fb, 2 * fb, mem.ptr(d_out2, t), w * ch, fb, 2 * fb, st)
+            t += nf
+        mem.sync(ctx)
+        res["stream1"] = finish(prod, mem.download(d_out2)[:, 1])
+    finally:
+        ctx.close()
+    del d_in2
+
+    ctx = lvm.Context(0, 1, lib)
+    pre = lvm.to_c_preprocess(lvm.PreprocessParams(), False)
+    try:
+        outs, prod = np.zeros_like(frames), []
+        for t in range(n):
+            o, _, p = ctx.chain_process_batch_ex([frames[t]], pre, cp)
+            prod.append(p)
+            if p:
+                outs[t] = o[0]
+        res["chain"] = finish(prod, outs)
+    finally:
+        ctx.close()
+    return res
+
+
+def assert_schedules_identical(res):
+    """every schedule: the same produced flags and the same bytes as `host`, frame by frame"""
+    prod0, out0 = res["host"]
+    assert any(prod0), "no frame produced"
+    for name, (prod, out) in res.items():
+        assert prod == prod0, "%s: produced flags differ from lvm_process: %s" % (name, [t for t, (a, b) in enumerate(zip(prod, prod0)) if a != b])
+        bad = [(t, int((out[t] != out0[t]).sum())) for t in range(len(prod0)) if prod0[t] and not np.array_equal(out[t], out0[t])]
+        assert not bad, "%s differs from lvm_process: (frame, bytes) %s" % (name, bad[:8])
+
+
+def oracle_bars(po, frames, pk, prod, outs, n_compare, u8_max=1, u8_frac=0.999):
+    """the first n_compare frames of one schedule against the oracle at the parity bars; returns (worst diff, worst identical)"""
+    P = po.make_params(**pk)
+    orc = po.Oracle()
+    worst = [0, 1.0]
+    try:
+        for t in range(n_compare):
+            ref, pr = orc.process(frames[t], P)
+            assert pr == prod[t], (t, pr, prod[t])
+            if pr:
+                du = np.abs(ref.astype(np.int32) - outs[t].astype(np.int32))
+                worst = [max(worst[0], int(du.max())), min(worst[1], float((du == 0).mean()))]
+                assert du.max() <= u8_max and (du == 0).mean() >= u8_frac, (t, int(du.max()), float((du == 0).mean()))
+    finally:
+        orc.close()
+    return worst
+
+
+def color_shrink_in_batches(lvm, po, lib, mem, size, calls, change_at, fps_to, u8_max, u8_frac):
+    """Color mode through lvm_process_device_frames in the call lengths `calls`; the framerate falls from the clip's 60 to fps_to at
+    the call that starts at frame change_at (SpatialFilter.cpp:80-83: the window cap shrinks, one column dropped per frame), so the
+    following calls cross the shrink.  Every frame against the oracle."""
+    ck, pk = lvm.synth.config(3, size)
+    pk["coLow"], pk["coHigh"] = 0.5, 2.0
+    clip = lvm.synth.Clip(**ck)
+    w, h = ck["w"], ck["h"]
+    n = sum(calls)
+    frames = np.stack([clip.frame(t) for t in range(n)])
+    assert change_at in np.cumsum((0,) + tuple(calls))
+    fb = w * h * 3
+    ctx = lvm.Context(0, 1, lib)
+    d_in = mem.upload(frames)
+    d_out = mem.zeros_like(d_in)
+    prod, t, pks = [], 0, []
+    try:
+        for nf in calls:
+            p = dict(pk, framerate=fps_to) if t >= change_at else pk
+            pks += [p] * nf
+            prod += ctx.process_device_frames(c_params(lvm, p), nf, mem.ptr(d_in, t), w, h, 3, w * 3, fb, fb, mem.ptr(d_out, t), w * 3, fb, fb,
+                                              mem.stream())
+            t += nf
+        mem.sync(ctx)
+        got = mem.download(d_out)
+    finally:
+        ctx.close()
+    orc = po.Oracle()
+    worst = [0, 1.0]
+    try:
+        for t in range(n):
+            ref, pr = orc.process(frames[t], po.make_params(**pks[t]))
+            assert pr == prod[t], (t, pr, prod[t])
+            if pr:
+                du = np.abs(ref.astype(np.int32) - got[t].astype(np.int32))
+                worst = [max(worst[0], int(du.max())), min(worst[1], float((du == 0).mean()))]
+                assert du.max() <= u8_max and (du == 0).mean() >= u8_frac, (t, int(du.max()), float((du == 0).mean()))
+    finally:
         orc.close()
     return worst
