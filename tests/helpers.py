@@ -114,6 +114,138 @@ def run_pair(lvm, po, lib, clip, pk, nframes, float_tol, n_streams=1, u8_max=1, 
     return worst
 
 
+# ---- exact-flavour bodies shared by the emulation and the gfx950 matrices (tests/parity_matrix.py) --------------------------
+def frames_clip(lvm, po, lib, mem, idx, w, h, levels, n_streams, calls, over=None, clip_over=None):
+    """lvm_process_device_frames: batches of consecutive frames (sizes in `calls`) of n_streams streams, OpenCV-order Lab
+    (lvm_debug_exact_lab), must give exactly the bytes the oracle produces frame by frame."""
+    ck, pk = lvm.synth.config(idx, (w, h, levels))
+    pk.update(over or {})
+    ck.update(clip_over or {})
+    clips = [lvm.synth.Clip(seed=1234 + s, **ck) for s in range(n_streams)]
+    P = po.make_params(**pk)
+    cp = c_params(lvm, pk)
+    ctx = lvm.Context(0, n_streams, lib)
+    ctx.exact_lab(True)
+    orcs = [po.Oracle() for _ in range(n_streams)]
+    t = 0
+    fb = w * h * 3
+    try:
+        for nf in calls:
+            fin = np.stack([np.stack([c.frame(t + f) for c in clips]) for f in range(nf)])      # [frame][stream][h][w][3]
+            d_in = mem.upload(fin)
+            d_out = mem.zeros_like(d_in)
+            produced = ctx.process_device_frames(cp, nf, mem.ptr(d_in), w, h, 3, w * 3, fb, fb * n_streams,
+                                                 mem.ptr(d_out), w * 3, fb, fb * n_streams, mem.stream())
+            mem.sync(ctx)
+            fout = mem.download(d_out)
+            for f in range(nf):
+                for s_ in range(n_streams):
+                    ref, pr = orcs[s_].process(fin[f, s_], P)
+                    assert produced[f] == pr, (t + f, produced[f], pr)
+                    if pr:
+                        assert np.array_equal(ref, fout[f, s_]), "frame %d stream %d: %d bytes differ" % (
+                            t + f, s_, int((ref != fout[f, s_]).sum()))
+            t += nf
+    finally:
+        ctx.close()
+        for o in orcs:
+            o.close()
+
+
+def pipelined_clip(lvm, po, lib, mem, w, h, levels, nframes, ring=4):
+    """lvm_process_device with pipeline depth 1 over a ring of in/out buffers + flush, OpenCV-order Lab: every frame's
+    output must equal the oracle's (and therefore the depth-0 schedule's) bit for bit."""
+    ck, pk = lvm.synth.config(0, (w, h, levels))
+    clip = lvm.synth.Clip(**ck)
+    P = po.make_params(**pk)
+    cp = c_params(lvm, pk)
+    ctx = lvm.Context(0, 1, lib)
+    ctx.exact_lab(True)
+    ctx.set_pipeline(1)
+    orc = po.Oracle()
+    d_in = mem.upload(np.zeros((ring, h, w, 3), np.uint8))
+    d_out = mem.zeros_like(d_in)
+    st = mem.stream()
+    refs = {}
+    try:
+        for t in range(nframes):
+            k = t % ring
+            if t >= ring:        # slot k is about to be reused: frame t-ring must already be complete
+                mem.sync(ctx)
+                assert np.array_equal(mem.download(d_out)[k], refs[t - ring]), "frame %d" % (t - ring)
+            f = clip.frame(t)
+            mem.write(d_in, k, f)
+            refs[t], _ = orc.process(f, P)
+            assert ctx.process_device(cp, mem.ptr(d_in, k), w, h, 3, w * 3, w * h * 3, mem.ptr(d_out, k), w * 3, w * h * 3, st)
+        ctx.flush(st)
+        mem.sync(ctx)
+        got = mem.download(d_out)
+        for t in range(max(0, nframes - ring), nframes):
+            assert np.array_equal(got[t % ring], refs[t]), "frame %d" % t
+    finally:
+        ctx.close()
+        orc.close()
+
+
+def two_streams_clip(lvm, po, lib, mem, w=96, h=64, levels=3, nframes=5):
+    """A two-stream context through lvm_process_device, OpenCV-order Lab: each stream equals its own oracle bit for bit."""
+    ck, pk = lvm.synth.config(0, (w, h, levels))
+    clips = [lvm.synth.Clip(seed=1234 + s, **ck) for s in range(2)]
+    ctx = lvm.Context(0, 2, lib)
+    ctx.exact_lab(True)
+    orcs = [po.Oracle(), po.Oracle()]
+    P = po.make_params(**pk)
+    cp = c_params(lvm, pk)
+    try:
+        for t in range(nframes):
+            fin = np.stack([c.frame(t) for c in clips])
+            d_in = mem.upload(fin)
+            d_out = mem.zeros_like(d_in)
+            produced = ctx.process_device(cp, mem.ptr(d_in), w, h, 3, w * 3, w * h * 3, mem.ptr(d_out), w * 3, w * h * 3, mem.stream())
+            mem.sync(ctx)
+            assert produced
+            fout = mem.download(d_out)
+            for s in range(2):
+                ref, _ = orcs[s].process(fin[s], P)
+                assert np.array_equal(ref, fout[s]), "frame %d stream %d" % (t, s)
+    finally:
+        ctx.close()
+        for o in orcs:
+            o.close()
+
+
+def padded_strides_clip(lvm, po, lib, mem, idx, pad_in, pad_out, w=96, h=64, levels=3, nframes=6):
+    """lvm_process_device on frames whose rows are padded (a cv::Mat ROI view has step > cols * channels), OpenCV-order
+    Lab: dword-aligned paddings keep the vectorised kernels, odd ones select the generic byte kernels; the padding bytes
+    of the output must stay untouched and the frame must equal the oracle's bit for bit."""
+    ck, pk = lvm.synth.config(idx, (w, h, levels))
+    clip = lvm.synth.Clip(**ck)
+    P = po.make_params(**pk)
+    cp = c_params(lvm, pk)
+    ctx = lvm.Context(0, 1, lib)
+    ctx.exact_lab(True)
+    orc = po.Oracle()
+    si, so = w * 3 + pad_in, w * 3 + pad_out
+    try:
+        for t in range(nframes):
+            f = clip.frame(t)
+            buf_in = np.full((h, si), 0xAB, np.uint8)
+            buf_in[:, :w * 3] = f.reshape(h, w * 3)
+            d_in = mem.upload(buf_in)
+            d_out = mem.upload(np.full((h, so), 0xCD, np.uint8))
+            ref, pr = orc.process(f, P)
+            pg = ctx.process_device(cp, mem.ptr(d_in), w, h, 3, si, si * h, mem.ptr(d_out), so, so * h, mem.stream())
+            mem.sync(ctx)
+            assert pr == pg
+            buf_out = mem.download(d_out)
+            assert (buf_out[:, w * 3:] == 0xCD).all(), "padding bytes of the output were written"
+            if pr:
+                assert np.array_equal(buf_out[:, :w * 3].reshape(h, w, 3), ref), "frame %d" % t
+    finally:
+        ctx.close()
+        orc.close()
+
+
 # ---- schedule equivalence: one clip through every surface of the library ------------------------------------------------------
 class HostMem:
     """'Device' buffers of the emulation build: host arrays."""
@@ -125,6 +257,9 @@ class HostMem:
 
     def ptr(self, a, i=0):
         return a[i].ctypes.data
+
+    def write(self, a, i, v):
+        a[i][...] = v
 
     def download(self, a):
         return np.asarray(a)
@@ -150,6 +285,9 @@ class TorchMem:
 
     def ptr(self, a, i=0):
         return a[i].data_ptr()
+
+    def write(self, a, i, v):
+        a[i].copy_(self.torch.from_numpy(np.ascontiguousarray(v)))
 
     def download(self, a):
         self.torch.cuda.synchronize()

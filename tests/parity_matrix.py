@@ -1,0 +1,318 @@
+"""The Laplace and Color cases that must equal the CPU oracle BIT FOR BIT in the exact flavour (lvm_debug_exact_lab: OpenCV's
+operation order, no transcendental function on the way) -- one matrix, run on the CPU emulation build by tests/test_emu_parity.py
+and on the gfx950 build by tests/test_gpu_exact.py.  Each body takes the library behind the C ABI (`lib`) and, where it passes
+device pointers, a memory adaptor (helpers.HostMem / helpers.TorchMem).  Lists hold Riesz entries where the emulation test of the
+same name covers all three modes; the GPU module keeps the Laplace and Color ones (Riesz calls acosf / sinf / cosf, see
+tests/test_gpu_exact.py)."""
+import numpy as np
+
+from helpers import frames_clip, run_pair
+
+
+def _color_fps(ck, pk, fps=15.0):
+    ck["fps"] = fps
+    pk["framerate"] = fps
+
+
+# ---- Laplace ---------------------------------------------------------------------------------------
+LAPLACE_SHAPES = [(160, 90, 3, 3), (135, 77, 4, 3), (100, 64, 2, 1), (64, 48, 1, 3), (67, 131, 3, 3), (40, 23, 2, 3), (320, 180, 4, 3),
+                  (404, 300, 5, 3), (330, 200, 6, 3)]
+
+
+def laplace_shape(lvm, po, lib, w, h, levels, ch):
+    ck, pk = lvm.synth.config(0, (w, h, levels))
+    ck["channels"] = ch
+    return run_pair(lvm, po, lib, lvm.synth.Clip(**ck), pk, 6, 0.0, exact=True)
+
+
+ANALYTIC = [(0, 135, 77, 4), (0, 328, 109, 3), (2, 135, 77, 3), (2, 264, 150, 3)]
+
+
+def analytic_flavour(lvm, po, lib, monkeypatch, idx, w, h, levels):
+    """lvm_debug_lab_analytic: the cube-root forward Lab (OpenCV with its interpolation switched off) in the kernels that
+    convert from the u8 frame themselves, against the oracle with lvmo_set_lab_lut(0); scalar and 4-pixel variants, strip
+    first kernel forced on."""
+    monkeypatch.setenv("LVM_D0_MIN_TASKS", "0")
+    ck, pk = lvm.synth.config(idx, (w, h, levels))
+    return run_pair(lvm, po, lib, lvm.synth.Clip(**ck), pk, 5, 0.0, exact=True, analytic=True)
+
+
+def laplace_param_changes_and_reset(lvm, po, lib):
+    ck, pk = lvm.synth.config(0, (96, 64, 3))
+
+    def vary(t, p):
+        if t >= 3:
+            p["amplification"] = 35.0
+            p["coLow"] = 0.0            # exercises the lo == 0 -> 0.01 rule (TemporalFilter.cpp:11-12)
+        if t >= 5:
+            p["levels"] = 2             # structural change -> state reset
+        return p
+    return run_pair(lvm, po, lib, lvm.synth.Clip(**ck), pk, 8, 0.0, exact=True, param_fn=vary)
+
+
+PIPELINED = [(160, 90, 3), (320, 180, 4), (135, 77, 4), (64, 48, 1)]
+
+FUSED_MULTI = [(1000, 760, 6), (800, 600, 4), (1001, 763, 5)]
+
+
+def laplace_shape_3_frames(lvm, po, lib, w, h, levels):
+    ck, pk = lvm.synth.config(0, (w, h, levels))
+    return run_pair(lvm, po, lib, lvm.synth.Clip(**ck), pk, 3, 0.0, exact=True)
+
+
+FIN_ROWS = [4, 8, 16]
+
+
+def laplace_final_strip_height(lvm, po, lib, monkeypatch, rows):
+    """k_lap_final_v4 walks strips of `rows` output rows per wave (the launch code shortens them for small frames): force the
+    long strips, on a height that leaves a partial last strip and a width with a partly filled last wave."""
+    monkeypatch.setenv("LVM_FIN_ROWS", str(rows))
+    monkeypatch.setenv("LVM_FIN_MIN_TASKS", "0")
+    ck, pk = lvm.synth.config(0, (328, 90 + 2 * rows + 3, 3))
+    return run_pair(lvm, po, lib, lvm.synth.Clip(**ck), pk, 4, 0.0, exact=True)
+
+
+ROWS_PYRDOWN = [(328, 109, 3), (1000, 760, 5), (520, 77, 4)]
+
+
+def laplace_wave_strip_pyrdown(lvm, po, lib, monkeypatch, w, h, levels):
+    """k_pyr_down_rows (the pyrDown of large planes) forced onto every level whose width allows it."""
+    monkeypatch.setenv("LVM_ROWS_MIN_ELEMS", "0")
+    return laplace_shape_3_frames(lvm, po, lib, w, h, levels)
+
+
+FIRST_KERNEL = [(0, 328, 109, 3), (0, 1000, 70, 4), (0, 124 * 2 * 2, 40, 2), (3, 264, 90, 3), (3, 96, 77, 2)]
+
+
+def wave_strip_first_kernel(lvm, po, lib, monkeypatch, idx, w, h, levels):
+    """k_down0_rows (u8 -> Lab / float -> pyrDown with DPP halo exchange between lanes) forced onto small frames."""
+    monkeypatch.setenv("LVM_D0_MIN_TASKS", "0")
+    ck, pk = lvm.synth.config(idx, (w, h, levels))
+    if idx == 3:
+        _color_fps(ck, pk)
+    return run_pair(lvm, po, lib, lvm.synth.Clip(**ck), pk, 4, 0.0, exact=True)
+
+
+FUSED_TABLE = [(328, 109, 3, True), (1000, 70, 4, True), (124 * 2 * 2, 40, 2, True), (264, 90, 3, False)]
+
+
+def fused_table_first_kernel(lvm, po, lib, monkeypatch, w, h, levels, exact):
+    """k_down0_lut_rows (OpenCV's forward Lab table + pyrDown + the integer planes of the owned pixels in one pass) forced onto
+    small frames.  exact=False: the default flavour's fma tap sums against the 1e-4 bar."""
+    monkeypatch.setenv("LVM_D0_FUSED_WAVES", "1")
+    ck, pk = lvm.synth.config(0, (w, h, levels))
+    return run_pair(lvm, po, lib, lvm.synth.Clip(**ck), pk, 4, 0.0 if exact else 1e-4, exact=exact)
+
+
+def unfused_conversion_in_batches(lvm, po, lib, mem, monkeypatch):
+    """LVM_D0_FUSED=0: labconv.hip's conversion kernel + the plane-reading first kernels in temporal batches."""
+    monkeypatch.setenv("LVM_D0_FUSED", "0")
+    frames_clip(lvm, po, lib, mem, 0, 320, 180, 4, 1, (1, 6, 5))
+
+
+LEVEL1_GEOMETRIES = [
+    (320, 180, 2, 1, (1, 4, 3)),        # two levels: level 1 is the top live level (no cur_2), too large for the tail kernel
+    (264, 74, 3, 1, (1, 6, 1, 2)),      # partial tiles right and below, per-frame calls in between
+    (132, 70, 3, 2, (1, 5, 3)),         # level 2 with an odd width: level chain for level 2; two streams
+    (160, 91, 3, 1, (1, 4, 4)),         # odd frame height (pyrUp with dsize = 2 n - 1 on both steps)
+    (520, 150, 4, 1, (1, 9)),           # five tiles across: interior tiles without any border lane
+    (128, 16, 2, 1, (1, 3, 3)),         # exactly one tile
+]
+
+
+def laplace_param_change_between_calls(lvm, po, lib):
+    """amplification / chromAttenuation change between calls: the level-1 states carry over, frames keep matching the oracle"""
+    ck, pk = lvm.synth.config(0, (264, 74, 3))
+
+    def vary(t, q):
+        if t >= 5:
+            q["amplification"] = 35.0; q["chromAttenuation"] = 0.4
+        return q
+    return run_pair(lvm, po, lib, lvm.synth.Clip(**ck), pk, 9, 0.0, exact=True, param_fn=vary)
+
+
+def fused_conversion_two_streams(lvm, po, lib, mem, monkeypatch):
+    monkeypatch.setenv("LVM_D0_FUSED_WAVES", "1")
+    frames_clip(lvm, po, lib, mem, 0, 264, 90, 3, 2, (1, 5, 4))
+
+
+LAPLACE_BATCHES = [(160, 90, 3, 1, (1, 4, 3, 1, 5)), (320, 180, 4, 1, (5, 6)), (135, 77, 4, 2, (3, 3, 2)), (404, 300, 5, 1, (2, 7)),
+                   (64, 48, 1, 1, (3, 3)), (200, 120, 4, 1, (1, 11, 17, 9))]   # deeper than the prefetch ring of k_lap_up
+
+SPLIT_LEVELS = [(640, 360, 5, 1, (1, 8, 4)), (256, 256, 6, 1, (1, 4, 6)), (320, 182, 5, 2, (1, 5, 16)), (576, 72, 4, 1, (1, 4, 4)),
+                (512, 384, 7, 1, (1, 4))]   # 7 levels: five decoupled levels, the top one 8 x 6
+
+SPLIT_FROM_2 = SPLIT_LEVELS[:3]
+
+
+def laplace_split_from_2(lvm, po, lib, mem, monkeypatch, w, h, levels, ns, calls):
+    """LVM_LAP_SPLIT_FROM=2: levels 2 .. L-1 all in the IIR + collapse launches."""
+    monkeypatch.setenv("LVM_LAP_SPLIT_FROM", "2")
+    frames_clip(lvm, po, lib, mem, 0, w, h, levels, ns, calls)
+
+
+def laplace_level_chain(lvm, po, lib, mem, monkeypatch):
+    """LVM_LAP_SPLIT=0 keeps the level-by-level chain of fused launches in temporal batches."""
+    monkeypatch.setenv("LVM_LAP_SPLIT", "0")
+    frames_clip(lvm, po, lib, mem, 0, 320, 180, 4, 1, (1, 8, 4))
+
+
+BLOCK_UP = [(328, 109, 3, (1, 4, 8, 2, 3)), (200, 120, 4, (1, 16, 6))]
+
+
+def laplace_tiled_up(lvm, po, lib, mem, monkeypatch):
+    """LVM_UP_ROWS=0 selects the LDS-tiled k_lap_up (the kernel odd-width levels always use)."""
+    monkeypatch.setenv("LVM_UP_ROWS", "0")
+    frames_clip(lvm, po, lib, mem, 0, 200, 120, 4, 1, (1, 8, 5))
+
+
+# ---- Colour ----------------------------------------------------------------------------------------
+# (at least 12 frames per clip: with a window of a few columns the ideal band-pass passes nothing, the magnified signal is zero
+# and neither the pyramid nor the up-chain arithmetic would influence the output -- checked by mutating the kernels)
+COLOR_SHAPES = [(96, 64, 3, 3, 60.0), (135, 77, 4, 3, 30.0), (64, 48, 1, 3, 7.0), (67, 131, 2, 1, 15.0)]
+
+
+def color_shape(lvm, po, lib, w, h, levels, ch, fps):
+    ck, pk = lvm.synth.config(3, (w, h, levels))
+    ck["channels"] = ch
+    _color_fps(ck, pk, fps)
+    return run_pair(lvm, po, lib, lvm.synth.Clip(**ck), pk, 20, 0.0, exact=True)
+
+
+def color_12_frames(lvm, po, lib, monkeypatch, w, h, levels, env):
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    ck, pk = lvm.synth.config(3, (w, h, levels))
+    _color_fps(ck, pk)
+    return run_pair(lvm, po, lib, lvm.synth.Clip(**ck), pk, 12, 0.0, exact=True)
+
+
+COL_OUT_ROWS = [(264, 90, 3, "0"), (264, 90, 3, "2"), (264, 90, 3, "8"), (264, 90, 3, "36"), (96, 77, 2, "16")]
+COL_STRIP_BORDERS = [(516, 40, 2), (772, 24, 2), (256, 64, 3)]
+COL_PREVIOUS_STRIPS = [(264, 90, 3), (512, 128, 4)]
+COL_DOWN01_ROWS = [(264, 90, 3, "7"), (264, 90, 3, "17"), (96, 77, 2, "1"), (96, 77, 2, "4"), (520, 52, 3, "7"), (128, 37, 3, "17"),
+                   (512, 128, 4, "4")]
+
+
+def color_wide_band_and_fps_change(lvm, po, lib):
+    ck, pk = lvm.synth.config(3, (64, 48, 2))
+    pk["coLow"] = 0.0; pk["coHigh"] = 40.0                   # every packed element passes (lo == 0 -> 0.01)
+
+    def vary(t, p):
+        if t >= 12:
+            p["framerate"] = 7.0                              # window cap shrinks 128 -> 16: one column dropped per frame
+        return p
+    return run_pair(lvm, po, lib, lvm.synth.Clip(**ck), pk, 24, 0.0, exact=True, param_fn=vary)
+
+
+COLOR_BATCHES = [(64, 48, 2, 1, (18, 5, 7, 3)), (40, 30, 1, 2, (20, 6)), (80, 52, 3, 1, (17, 16, 9)),
+                 (48, 32, 2, 1, (18, 40, 35))]   # calls longer than one batch (32 frames) are cut
+COLOR_BATCH_PARAMS = ({"framerate": 7.0, "coLow": 0.4, "coHigh": 2.0}, {"fps": 7.0})
+
+NARROW_DFT_BANDS = [(0.8, 1.6), (2.9, 3.5), (0.8, 0.95)]
+
+
+def color_narrow_band_dft(lvm, po, lib, mem, monkeypatch, lo, hi, thin8):
+    monkeypatch.setenv("LVM_COL_THIN8_DFT", thin8)
+    frames_clip(lvm, po, lib, mem, 3, 64, 48, 2, 1, (18, 5, 7, 9), over={"framerate": 7.0, "coLow": lo, "coHigh": hi},
+                clip_over={"fps": 7.0})
+
+
+# ---- every mode: layouts, degenerate content, parameters, shapes ----------------------------------------------------------
+PADDED_STRIDES = [(0, 4, 8), (0, 1, 3), (2, 4, 4), (2, 7, 1), (3, 8, 4), (3, 5, 5)]
+
+
+class PatchedClip:
+    """The synthetic clip with a flat black block, a flat white block and (from frame `const_from`) a constant frame:
+    0/0 in the Riesz phase and amplitude steps (NaN patches, RieszPyramid.cpp:105-106,141), max == min in the colour
+    normalisations (TemporalFilter.cpp:55, MagnifyCore.hpp:200-203)."""
+
+    def __init__(self, clip, const_from=None):
+        self.clip, self.const_from = clip, const_from
+
+    def frame(self, t):
+        f = self.clip.frame(t).copy()
+        h, w = f.shape[:2]
+        f[h // 8:h // 2, w // 8:w // 3] = 0
+        f[h // 2:h - h // 8, w // 2:w - w // 8] = 255
+        if self.const_from is not None and t >= self.const_from:
+            f[...] = 77
+        return f
+
+
+FLAT_REGIONS = [(0, None, (96, 64, 3)), (2, None, (96, 64, 3)), (3, None, (96, 64, 3)), (0, 5, (96, 64, 3)), (2, 5, (96, 64, 3)),
+                (3, 5, (96, 64, 3)),
+                (2, None, (200, 120, 3))]   # black block wider than the 9x9 + 13x13 supports: exact 0/0
+
+
+def flat_regions(lvm, po, lib, idx, const_from, size):
+    ck, pk = lvm.synth.config(idx, size)
+    if idx == 3:
+        _color_fps(ck, pk)
+    return run_pair(lvm, po, lib, PatchedClip(lvm.synth.Clip(**ck), const_from), pk, 9, 0.0, exact=True)
+
+
+class ConstClip:
+    def __init__(self, h, w, v):
+        self.f = np.full((h, w, 3), v, np.uint8)
+
+    def frame(self, t):
+        return self.f
+
+
+def fully_constant_clip(lvm, po, lib, idx):
+    """Every frame the same constant: Color's output range collapses (max == min, 255 / 0 in convertTo:
+    MagnifyCore.hpp:200-203), Riesz sees 0/0 in every phase difference, Laplace must return the Lab round trip."""
+    ck, pk = lvm.synth.config(idx, (96, 64, 3))
+    if idx == 3:
+        pk["framerate"] = 15.0
+    return run_pair(lvm, po, lib, ConstClip(64, 96, 131), pk, 8, 0.0, exact=True)
+
+
+EXTREME_PARAMETERS = [(3, dict(coLow=5.0, coHigh=1.0)),                # colour: empty pass band (mask all zero)
+                      (3, dict(coLow=0.0, coHigh=0.3)),                # colour: lo == 0 -> 0.01, DC excluded, first bins
+                      (2, dict(coLow=0.5, coHigh=20.0)),               # Riesz: cutoff above Nyquist (Wn > 1)
+                      (2, dict(coLow=0.5, coHigh=15.0)),               # Riesz: cutoff exactly at Nyquist (Wn == 1)
+                      (2, dict(coLow=3.0, coHigh=1.0)),                # Riesz: hi < lo
+                      (0, dict(amplification=1000.0, chromAttenuation=1.0)),   # Laplace: far out of gamut
+                      (0, dict(amplification=0.0)),
+                      (2, dict(amplification=0.0, coWavelength=0.0))]  # Riesz: zero gain / zero threshold
+
+
+def extreme_parameters(lvm, po, lib, idx, over):
+    ck, pk = lvm.synth.config(idx, (96, 64, 3))
+    if idx == 3:
+        _color_fps(ck, pk)
+    pk.update(over)
+    return run_pair(lvm, po, lib, lvm.synth.Clip(**ck), pk, 8, 0.0, exact=True)
+
+
+class ShapeShifter:
+    """Frames whose size / channel count changes mid-stream (the structural tracker must drop all state:
+    MagnifyCore.hpp:53-65) and changes back."""
+
+    def __init__(self, lvm, ck):
+        self.a = lvm.synth.Clip(**ck)
+        k2 = dict(ck); k2["w"], k2["h"] = 80, 48
+        self.b = lvm.synth.Clip(**k2)
+
+    def frame(self, t):
+        if t < 4:
+            return self.a.frame(t)
+        if t < 7:
+            return self.b.frame(t)                       # smaller frame
+        if t < 10:
+            return np.ascontiguousarray(self.a.frame(t)[:, :, 1])   # gray frame of the first size
+        return self.a.frame(t)
+
+
+def size_and_channel_changes(lvm, po, lib, idx):
+    ck, pk = lvm.synth.config(idx, (96, 64, 2))
+    if idx == 3:
+        _color_fps(ck, pk)
+    return run_pair(lvm, po, lib, ShapeShifter(lvm, ck), pk, 13, 0.0, exact=True)
+
+
+def no_riesz(cases):
+    """the entries of a matrix list whose first element (synth.config index) is not Riesz"""
+    return [c for c in cases if c[0] != 2]

@@ -64,7 +64,10 @@ def test_random_configurations_bit_exact(lvm, po, emu, seed):
 @pytest.mark.gpu
 @pytest.mark.parametrize("seed", range(12))
 def test_random_configurations_gpu(lvm, po, hip, seed):
-    """The same draw at four times the size on the gfx950 build, default flavour, at the parity bars of SURVEY.md 8c."""
+    """The same draw at four times the size on the gfx950 build, default flavour, at the parity bars of SURVEY.md 8c; Laplace and
+    Color draws also in the exact flavour, bit for bit (Riesz calls acosf / sinf / cosf: tests/test_gpu_exact.py)."""
     ck, pk, vary = configure(lvm, seed, scale=4)
     worst = run_pair(lvm, po, hip, lvm.synth.Clip(**ck), pk, 7, 1e-4, param_fn=vary)
     print("random", seed, (ck["w"], ck["h"], pk["levels"], ck.get("channels", 3), pk["mode"]), "worst rel/u8/frac", worst)
+    if pk["mode"] != 1:          # (mode 1: Riesz)
+        run_pair(lvm, po, hip, lvm.synth.Clip(**ck), pk, 7, 0.0, exact=True, param_fn=vary)

@@ -20,6 +20,7 @@ def test_laplace_small(lvm, po, hip, w, h, levels, ch):
     clip = lvm.synth.Clip(**ck)
     worst = run_pair(lvm, po, hip, clip, pk, 24 if w >= 640 else 10, FLOAT_TOL)
     print("laplace", (w, h, levels, ch), "worst rel/u8/frac", worst)
+    run_pair(lvm, po, hip, clip, pk, 24 if w >= 640 else 10, 0.0, exact=True)     # the exact flavour: bit for bit (test_gpu_exact.py)
 
 
 def test_laplace_cfg0_64_frames(lvm, po, hip):
@@ -273,6 +274,7 @@ def test_color_small(lvm, po, hip, w, h, levels, ch, fps):
     ck["channels"] = ch; ck["fps"] = fps; pk["framerate"] = fps
     worst = run_pair(lvm, po, hip, lvm.synth.Clip(**ck), pk, 40, FLOAT_TOL)
     print("color", (w, h, levels, ch, fps), "worst", worst)
+    run_pair(lvm, po, hip, lvm.synth.Clip(**ck), pk, 40, 0.0, exact=True)       # the exact flavour: bit for bit (test_gpu_exact.py)
 
 
 @pytest.mark.parametrize("rows", ["4", "17"])
