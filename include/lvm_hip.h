@@ -272,6 +272,18 @@ int  lvm_export_frames(lvm_ctx* ctx, const lvm_preprocess_params* pp, const lvm_
  *                              0 = the default, 8 (pass (w + 15) / 16 for one interval per MCU row).  Entropy coding is serial inside an
  *                              interval: short intervals cost < 0.5 % of bytes and make the frames decode in parallel --
  *                              lvm_mjpeg_decode_device gives every interval a lane.                                                              */
+/*   lvm_mjpeg_set_decoder      the arithmetic behind the entropy layer of lvm_mjpeg_decode_device and lvm_export_mjpeg_frames, from the next call on
+ *                              (the entropy layer itself is exact by the standard and shared):
+ *                                LVM_MJPEG_DECODER_REPLICATE (0, the default)  matrix IDCT, 4:2:0 chroma replicated: bit-identical to
+ *                                    oracle/mjpeg_oracle.py::decode_frame, what this library always decoded;
+ *                                LVM_MJPEG_DECODER_LIBJPEG (1)  libjpeg's / libjpeg-turbo's defaults -- JDCT_ISLOW, do_fancy_upsampling (the 9 : 3 : 3 : 1
+ *                                    triangle filter of the chroma planes), no clamp behind the dequantiser: BYTE-identical to what a libjpeg-backed
+ *                                    cv::VideoCapture (or Pillow) hands out, for every stream an encoder makes from 8-bit samples; on others (damaged
+ *                                    streams, where libjpeg builds differ among themselves) the arithmetic wraps in 32 bits.  FFmpeg's own mjpeg
+ *                                    decoder (another IDCT, swscale chroma) is NOT what this kind restates.
+ *                              Any other kind: LVM_ERR_INVALID.                                                                                 */
+enum { LVM_MJPEG_DECODER_REPLICATE = 0, LVM_MJPEG_DECODER_LIBJPEG = 1 };
+int  lvm_mjpeg_set_decoder(lvm_ctx* ctx, int kind);
 size_t lvm_mjpeg_bound(int w, int h);
 int  lvm_mjpeg_set_restart_interval(lvm_ctx* ctx, int mcus);
 int  lvm_export_mjpeg_frames(lvm_ctx* ctx, const lvm_preprocess_params* pp, const lvm_params* p, int split, int n_frames, const uint8_t* jpegs,

@@ -778,6 +778,16 @@ int lvm_mjpeg_set_restart_interval(lvm_ctx* c, int mcus) {
     return LVM_OK;
 }
 
+int lvm_mjpeg_set_decoder(lvm_ctx* c, int kind) {
+    if (!c) return LVM_ERR_INVALID;
+    if (kind != LVM_MJPEG_DECODER_REPLICATE && kind != LVM_MJPEG_DECODER_LIBJPEG) {
+        c->err = "lvm_mjpeg_set_decoder: kind must be LVM_MJPEG_DECODER_REPLICATE (0) or LVM_MJPEG_DECODER_LIBJPEG (1)";
+        return LVM_ERR_INVALID;
+    }
+    c->mjpeg_decoder = kind;
+    return LVM_OK;
+}
+
 size_t lvm_mjpeg_bound(int w, int h) { return (w < 1 || h < 1) ? 0 : lvm::mjpeg_bound(w, h); }
 
 int lvm_mjpeg_encode_device(lvm_ctx* c, const uint8_t* d_bgr, int w, int h, ptrdiff_t stride, ptrdiff_t frame_stride, int n_frames, int quality,

@@ -15,6 +15,12 @@
 //   k_mjd_intervals   RSTn markers of the entropy-coded segment -> start / end of every interval            one workgroup per frame
 //   k_mjd_huffman     bits -> quantised coefficients (zigzag order, int16, zero-filled beforehand)           one lane per interval
 //   k_mjd_pixels      dequantise, IDCT, chroma replication, YCbCr -> BGR                                      one wave per 16 x 16 MCU
+// A context may ask for libjpeg's arithmetic behind the same entropy layer instead (lvm_mjpeg_set_decoder(ctx, LVM_MJPEG_DECODER_LIBJPEG)): the
+// frames are then BYTE-identical to what libjpeg / libjpeg-turbo decode with their defaults (JDCT_ISLOW, do_fancy_upsampling) -- the decoder behind a
+// libjpeg-backed cv::VideoCapture; tests/test_mjpeg_decode_libjpeg.py pins that against Pillow.  The triangle filter of the chroma planes reaches one
+// sample into the neighbouring MCUs, so the pixel stage becomes two launches:
+//   k_mjd_chroma_islow    dequantise + islow IDCT of the Cb and Cr blocks -> two u8 planes per frame (scratch)        one wave per four MCUs
+//   k_mjd_pixels_libjpeg  dequantise + islow IDCT of the four Y blocks, h2v2 fancy upsampling, YCbCr -> BGR            one wave per 16 x 16 MCU
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -59,6 +65,9 @@ struct MjdState {
     uint32_t *d_ulen = nullptr, *d_before = nullptr, *d_changed = nullptr;
     unsigned long long* d_exit[2] = {nullptr, nullptr};
     int sub_cap = 0, par_frames_cap = 0, npar = 0;
+    // LVM_MJPEG_DECODER_LIBJPEG: the Cb / Cr planes between its two launches ([frame][Cb, Cr][mh * 8][mw * 8])
+    uint8_t* d_chroma = nullptr; size_t chroma_cap = 0;
+    int kind = 0;                        // the decoder kind of the current begin .. finish sequence
     std::vector<MjdFrame> frames;
     std::vector<uint32_t> foff;
 };
@@ -635,6 +644,162 @@ __global__ __launch_bounds__(256) void k_mjd_pixels(const int16_t* __restrict__ 
     }
 }
 
+
+// ---- LVM_MJPEG_DECODER_LIBJPEG: jpeg_idct_islow + h2v2_fancy_upsample (libjpeg jidctint.c / jdsample.c), all integer ---------------------------
+// LDS images of 8 x 8 blocks: row pitch 9, block pitch 72.  A lane of the IDCT passes is (block, column) and then (block, row): with a pitch of 8
+// the row pass puts the 32 lanes of a bank group on 4 banks (8-way); with 9 both passes, the stores in between and the 2 x 2 quads' reads
+// of the luminance are conflict-free or 2-way.
+constexpr int MJL_ROW = 9, MJL_BLK = 72;
+
+// One 1-D pass (CONST_BITS = 13): in[0..8) -> out[0..8), descaled by `shift` (11 behind the column pass: CONST_BITS - PASS1_BITS; 18 behind the
+// row pass: CONST_BITS + PASS1_BITS + 3).  Wrap-around unsigned arithmetic, the shift arithmetic on the reinterpreted value: equal to libjpeg
+// wherever libjpeg itself does not overflow (every stream an encoder makes from 8-bit samples), defined behaviour on everything else.
+__device__ __forceinline__ void mjl_islow_1d(const int* in, int* out, int shift) {
+    typedef uint32_t U;
+    const U i0 = (U)in[0], i1 = (U)in[1], i2 = (U)in[2], i3 = (U)in[3], i4 = (U)in[4], i5 = (U)in[5], i6 = (U)in[6], i7 = (U)in[7];
+    U z1 = (i2 + i6) * 4433u;
+    const U tmp2 = z1 - i6 * 15137u, tmp3 = z1 + i2 * 6270u;
+    const U tmp0 = (i0 + i4) << 13, tmp1 = (i0 - i4) << 13;
+    const U tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+    U t0 = i7, t1 = i5, t2 = i3, t3 = i1;
+    z1 = t0 + t3;
+    U z2 = t1 + t2, z3 = t0 + t2, z4 = t1 + t3;
+    const U z5 = (z3 + z4) * 9633u;
+    t0 *= 2446u; t1 *= 16819u; t2 *= 25172u; t3 *= 12299u;
+    z1 *= (U)-7373; z2 *= (U)-20995;
+    z3 = z3 * (U)-16069 + z5; z4 = z4 * (U)-3196 + z5;
+    t0 += z1 + z3; t1 += z2 + z4; t2 += z2 + z3; t3 += z1 + z4;
+    const U r = 1u << (shift - 1);
+    out[0] = (int)(tmp10 + t3 + r) >> shift; out[7] = (int)(tmp10 - t3 + r) >> shift;
+    out[1] = (int)(tmp11 + t2 + r) >> shift; out[6] = (int)(tmp11 - t2 + r) >> shift;
+    out[2] = (int)(tmp12 + t1 + r) >> shift; out[5] = (int)(tmp12 - t1 + r) >> shift;
+    out[3] = (int)(tmp13 + t0 + r) >> shift; out[4] = (int)(tmp13 - t0 + r) >> shift;
+}
+// dequantised coefficients of a block at a[] (natural order) -> samples 0..255 in p[8] of the lane's row y; t[] is the image between the passes.
+// Called by all lanes of a workgroup (two barriers); `on` = this lane has a column / row to do.
+__device__ __forceinline__ void mjl_idct_block(const int* a, int* t, bool on, int k, int* p) {
+    int d[8], o[8];
+    if (on) {               // columns: lane = u
+#pragma unroll
+        for (int v = 0; v < 8; ++v) d[v] = a[v * MJL_ROW + k];
+        mjl_islow_1d(d, o, 11);
+#pragma unroll
+        for (int y = 0; y < 8; ++y) t[y * MJL_ROW + k] = o[y];
+    }
+    __syncthreads();
+    if (on) {               // rows: lane = y
+#pragma unroll
+        for (int u = 0; u < 8; ++u) d[u] = t[k * MJL_ROW + u];
+        mjl_islow_1d(d, o, 18);
+#pragma unroll
+        for (int x = 0; x < 8; ++x) { const int s = o[x] + 128; p[x] = s < 0 ? 0 : (s > 255 ? 255 : s); }
+    }
+    __syncthreads();
+}
+
+// One wave per four MCUs of an MCU row (sixteen per workgroup): lane = zigzag index while dequantising (coef * q, no clamp -- libjpeg has none), then
+// (block, column / row) of the eight Cb / Cr blocks; every row of a block leaves as one 8-byte store into its plane.
+__global__ __launch_bounds__(256) void k_mjd_chroma_islow(const int16_t* __restrict__ coef, const MjdFrame* __restrict__ frames, MjdGeom g, uint8_t* __restrict__ planes) {
+    __shared__ int s_a[4][8 * MJL_BLK], s_b[4][8 * MJL_BLK];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int mx0 = blockIdx.x * 16 + wave * 4, my = blockIdx.y, f = blockIdx.z;
+    const MjdFrame& fr = frames[f];
+    const int nat = fr.zz[lane], at = (nat >> 3) * MJL_ROW + (nat & 7);
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+        const int mx = mx0 + (b >> 1), comp = 1 + (b & 1);
+        if (mx < g.mw) s_a[wave][b * MJL_BLK + at] = coef[(((size_t)f * g.mh + my) * g.mw + mx) * 384 + (3 + comp) * 64 + lane] * (int)fr.q[fr.tq[comp]][lane];
+    }
+    __syncthreads();
+    const int b = lane >> 3, k = lane & 7, mx = mx0 + (b >> 1);
+    const bool on = mx < g.mw;
+    int p[8];
+    mjl_idct_block(&s_a[wave][b * MJL_BLK], &s_b[wave][b * MJL_BLK], on, k, p);
+    if (on) {
+        const size_t pitch = (size_t)g.mw * 8, rows = (size_t)g.mh * 8;
+        uint8_t* o = planes + (((size_t)f * 2 + (b & 1)) * rows + (size_t)my * 8 + k) * pitch + (size_t)mx * 8;      // (8-byte aligned: the pitch is a multiple of 8)
+        uint2 v;
+        v.x = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+        v.y = (uint32_t)p[4] | ((uint32_t)p[5] << 8) | ((uint32_t)p[6] << 16) | ((uint32_t)p[7] << 24);
+        *reinterpret_cast<uint2*>(o) = v;
+    }
+}
+
+// One wave per MCU (four per workgroup), as k_mjd_pixels: islow IDCT of the four Y blocks (32 lanes), meanwhile all lanes gather the MCU's 8 x 8
+// chroma samples and the ring of one sample around them from the planes -- indices clamped to the COMPONENT's size ((w + 1) / 2 x (h + 1) / 2: its
+// own edge samples are what h2v2_fancy_upsample replicates, not the padding of the MCUs) -- as (Cb | Cr << 16) words; then lane = one 2 x 2 quad:
+// 9 : 3 : 3 : 1 of the nearest samples, rounding 8 in even and 7 in odd columns.  libjpeg replicates instead where the chroma planes are at most 2 wide.
+constexpr int MJL_CROW = 40;            // row pitch of the 10 x 10 neighbourhood: the four quad rows of a bank group on four disjoint sets of 8 banks
+__global__ __launch_bounds__(256) void k_mjd_pixels_libjpeg(const int16_t* __restrict__ coef, const MjdFrame* __restrict__ frames, MjdGeom g,
+                                                            const uint8_t* __restrict__ planes, uint8_t* __restrict__ dst) {
+    __shared__ int s_a[4][4 * MJL_BLK], s_b[4][4 * MJL_BLK];
+    __shared__ uint32_t s_c[4][10 * MJL_CROW];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int mx = blockIdx.x * 4 + wave, my = blockIdx.y, f = blockIdx.z;
+    const bool act = mx < g.mw;
+    const MjdFrame& fr = frames[f];
+    if (act) {
+        const int16_t* in = coef + (((size_t)f * g.mh + my) * g.mw + mx) * 384;
+        const int nat = fr.zz[lane], at = (nat >> 3) * MJL_ROW + (nat & 7), q = fr.q[fr.tq[0]][lane];
+#pragma unroll
+        for (int blk = 0; blk < 4; ++blk) s_a[wave][blk * MJL_BLK + at] = in[blk * 64 + lane] * q;
+        const int cw = (g.w + 1) >> 1, ch = (g.h + 1) >> 1;
+        const size_t pitch = (size_t)g.mw * 8, rows = (size_t)g.mh * 8;
+        const uint8_t* cbp = planes + (size_t)f * 2 * rows * pitch;
+        for (int i = lane; i < 100; i += 64) {
+            const int r = i / 10, cc = i - r * 10;
+            int y = my * 8 - 1 + r, x = mx * 8 - 1 + cc;
+            y = y < 0 ? 0 : (y > ch - 1 ? ch - 1 : y); x = x < 0 ? 0 : (x > cw - 1 ? cw - 1 : x);
+            const size_t o = (size_t)y * pitch + (size_t)x;
+            s_c[wave][r * MJL_CROW + cc] = (uint32_t)cbp[o] | ((uint32_t)cbp[rows * pitch + o] << 16);
+        }
+    }
+    __syncthreads();
+    {
+        const int blk = (lane >> 3) & 3, k = lane & 7;
+        const bool on = act && lane < 32;
+        int p[8];
+        mjl_idct_block(&s_a[wave][blk * MJL_BLK], &s_b[wave][blk * MJL_BLK], on, k, p);
+        if (on) {
+#pragma unroll
+            for (int x = 0; x < 8; ++x) s_a[wave][blk * MJL_BLK + k * MJL_ROW + x] = p[x];
+        }
+    }
+    __syncthreads();
+    if (act) {
+        const int qx = lane & 7, qy = lane >> 3;
+        const int fancy = g.w > 4 ? 1 : 0;
+        // the 3 x 3 samples around the quad's own, then per output row v the column sums 3 * own row + neighbouring row
+        uint32_t c[3][3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int cc = 0; cc < 3; ++cc) c[r][cc] = s_c[wave][(qy + 1 + (r - 1) * fancy) * MJL_CROW + qx + 1 + (cc - 1) * fancy];
+        uint8_t* fr_out = dst + (size_t)f * g.fstride;
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy) {
+            const int ly = 2 * qy + dy, py = my * 16 + ly;
+            uint32_t cs[3];             // (both components at once: 16 * 255 fits the 16-bit halves)
+#pragma unroll
+            for (int cc = 0; cc < 3; ++cc) cs[cc] = 3u * c[1][cc] + c[dy ? 2 : 0][cc];
+#pragma unroll
+            for (int dx = 0; dx < 2; ++dx) {
+                const int lx = 2 * qx + dx, px = mx * 16 + lx;
+                if (py < g.h && px < g.w) {
+                    const uint32_t both = 3u * cs[1] + cs[dx ? 2 : 0] + (dx ? 0x00070007u : 0x00080008u);
+                    const int cb = (int)((both & 0xFFFFu) >> 4) - 128, cr = (int)(both >> 20) - 128;
+                    const int dr = (91881 * cr + 32768) >> 16, dg = (-22554 * cb - 46802 * cr + 32768) >> 16, db = (116130 * cb + 32768) >> 16;
+                    const int y = s_a[wave][((ly >> 3) * 2 + (lx >> 3)) * MJL_BLK + (ly & 7) * MJL_ROW + (lx & 7)];
+                    int r = y + dr, gg = y + dg, b = y + db;
+                    r = r < 0 ? 0 : (r > 255 ? 255 : r); gg = gg < 0 ? 0 : (gg > 255 ? 255 : gg); b = b < 0 ? 0 : (b > 255 ? 255 : b);
+                    uint8_t* o = fr_out + (size_t)py * g.stride + (size_t)px * 3;
+                    o[0] = (uint8_t)b; o[1] = (uint8_t)gg; o[2] = (uint8_t)r;
+                }
+            }
+        }
+    }
+}
+
 template <class T>
 int mjd_reserve(Ctx* c, T*& p, size_t count) {
     if (p) (void)hipFree(p);
@@ -648,7 +813,7 @@ int mjd_reserve(Ctx* c, T*& p, size_t count) {
 void mjpeg_decode_release(Ctx* c) {
     MjdState* st = static_cast<MjdState*>(c->mjpeg_dec);
     if (!st) return;
-    void* ptrs[] = {st->d_frames, st->d_bytes, st->d_coef, st->d_ivstart, st->d_ivend, st->d_err, st->d_ubytes, st->d_ulen, st->d_before, st->d_changed, st->d_exit[0], st->d_exit[1]};
+    void* ptrs[] = {st->d_frames, st->d_bytes, st->d_coef, st->d_ivstart, st->d_ivend, st->d_err, st->d_ubytes, st->d_ulen, st->d_before, st->d_changed, st->d_exit[0], st->d_exit[1], st->d_chroma};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     delete st;
     c->mjpeg_dec = nullptr;
@@ -724,6 +889,14 @@ int mjpeg_decode_begin(Ctx* c, const uint8_t* jpegs, const size_t* offsets, int 
             st->par_frames_cap = n; st->sub_cap = cap;
         }
     }
+    st->kind = c->mjpeg_decoder;
+    const size_t nchroma = (size_t)n * 2 * ((size_t)mh * 8) * ((size_t)mw * 8);
+    if (st->kind == LVM_MJPEG_DECODER_LIBJPEG && st->chroma_cap < nchroma) {
+        LVM_HIP_TRY(c, hipStreamSynchronize(s));
+        st->chroma_cap = 0;
+        if ((rc = mjd_reserve(c, st->d_chroma, nchroma)) != LVM_OK) return rc;
+        st->chroma_cap = nchroma;
+    }
     st->n = n; st->max_iv = max_iv;
     st->foff = foff;                                             // (stays alive until the copy below has run)
     LVM_HIP_TRY(c, hipMemcpyAsync(st->d_bytes, jpegs + offsets[0], nbytes, hipMemcpyHostToDevice, s));
@@ -772,6 +945,12 @@ int mjpeg_decode_enqueue(Ctx* c, int f0, int nf, uint8_t* d_bgr, ptrdiff_t strid
     }
     MjdGeom g;
     g.w = w; g.h = h; g.mw = mw; g.mh = mh; g.stride = (long)stride; g.fstride = (long)fstride;
+    if (st->kind == LVM_MJPEG_DECODER_LIBJPEG) {
+        uint8_t* planes = st->d_chroma + (size_t)f0 * 2 * ((size_t)mh * 8) * ((size_t)mw * 8);
+        LVM_LAUNCH(c, "mjd_chroma_islow", k_mjd_chroma_islow, dim3((mw + 15) / 16, mh, nf), dim3(256), s, (const int16_t*)coef, fr, g, planes);
+        LVM_LAUNCH(c, "mjd_pixels_libjpeg", k_mjd_pixels_libjpeg, dim3((mw + 3) / 4, mh, nf), dim3(256), s, (const int16_t*)coef, fr, g, (const uint8_t*)planes, d_bgr);
+        return LVM_OK;
+    }
     LVM_LAUNCH(c, "mjd_pixels", k_mjd_pixels, dim3((mw + 3) / 4, mh, nf), dim3(256), s, (const int16_t*)coef, fr, g, d_bgr);
     return LVM_OK;
 }

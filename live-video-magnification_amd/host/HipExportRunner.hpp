@@ -74,6 +74,11 @@ public:
         return run_impl<true>(src, sink, pre, mag, split, capture_fps, quality);
     }
     int batch() const { return batch_; }
+    // The decode arithmetic of the runner's context for JPEG frames that go in compressed (lvm_export_mjpeg_frames / lvm_mjpeg_decode_device on
+    // handle(); e.g. the frames lvm::MjpegAviReader finds): LVM_MJPEG_DECODER_REPLICATE -- the default, nothing changes without this call -- or
+    // LVM_MJPEG_DECODER_LIBJPEG, the frames a libjpeg-backed cv::VideoCapture hands to Exporter::run.  Throws lvm::Error on any other kind.
+    void set_mjpeg_decoder(int kind) { mag_.mjpeg_set_decoder(kind); }
+    lvm_ctx* handle() const { return mag_.handle(); }
     // request.textOverlay (ExportTypes.hpp:22): `draw` = the reference's label code for one canvas (what compose does for overlay == true,
     // Exporter.cpp:74-77 / :82-85).  It is run on constant canvases whenever the canvas geometry is (re)established and never on a frame:
     // the device applies the resulting tables (lvm_export_set_overlay).  An empty function switches the overlay off.

@@ -103,9 +103,15 @@ private:
 // The other direction (source/FileSource.cpp:99 `cap_.read(frame)` on an AVI / Motion-JPEG file): the frames as they lie in the file, for
 // lvm_mjpeg_decode_device / lvm_export_mjpeg_frames -- the decoder runs on the GPU, this class only finds the chunks.  AVI 1.0 files
 // ('00dc' / '00db' chunks in LIST 'movi', with or without 'idx1'; what this file's writer, OpenCV and FFmpeg write below 4 GiB).
+// `decoder` is the arithmetic the reader's user wants behind the entropy layer -- the value for lvm_mjpeg_set_decoder (include/lvm_hip.h): 0 =
+// LVM_MJPEG_DECODER_REPLICATE, the library's default; 1 = LVM_MJPEG_DECODER_LIBJPEG, the frames a libjpeg-backed cv::VideoCapture would read from this
+// file, byte for byte.  The reader only carries it next to the file (no HIP in this header): lvm::ExportRunner::set_mjpeg_decoder(rd.decoder()) /
+// lvm::Magnifier::mjpeg_set_decoder apply it to the context that decodes.
 class MjpegAviReader {
 public:
-    MjpegAviReader() = default;
+    explicit MjpegAviReader(int decoder = 0) : decoder_(decoder) {}
+    void set_decoder(int kind) { decoder_ = kind; }
+    int decoder() const { return decoder_; }
     ~MjpegAviReader() { close(); }
     MjpegAviReader(const MjpegAviReader&) = delete;
     MjpegAviReader& operator=(const MjpegAviReader&) = delete;
@@ -192,6 +198,7 @@ private:
     double fps_ = 0.0;
     std::vector<Chunk> frames_;
     int strl_seen_ = 0, vid_stream_ = -1;
+    int decoder_ = 0;
 };
 
 }  // namespace lvm

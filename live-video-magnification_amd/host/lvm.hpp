@@ -104,6 +104,10 @@ public:
             throw Error(LVM_ERR_INVALID, "lvm_preprocess_geometry: invalid arguments");
     }
 
+    // The decode arithmetic of lvm_mjpeg_decode_device / lvm_export_mjpeg_frames on this context (LVM_MJPEG_DECODER_REPLICATE, the default, or
+    // LVM_MJPEG_DECODER_LIBJPEG: what a libjpeg-backed cv::VideoCapture reads).  Throws on any other kind.
+    void mjpeg_set_decoder(int kind) { check(lvm_mjpeg_set_decoder(ctx_, kind)); }
+
     void synchronize() { check(lvm_synchronize(ctx_)); }
     lvm_ctx* handle() const { return ctx_; }
 

@@ -92,6 +92,8 @@ class _Torch:
 
     def copy_rows(self, dst, d0, src, s0, n):
         dst[d0:d0 + n].copy_(src[s0:s0 + n])
+        # the copy runs on torch's stream, the next lvm_tile_riesz_* call on the context's own (non-blocking) stream: nothing else orders the two
+        self.torch.cuda.current_stream(self.device).synchronize()
 
     def sync(self, ctx):
         ctx.synchronize()
