@@ -1172,7 +1172,20 @@ struct ColorState : ModeState {
         void* p[] = {arena, win, Y, tw_all, tw_own, mm, xofs, yofs, yslot, xa, ya, tarena, mmt};
         for (void* q : p) if (q) (void)hipFree(q);
     }
+    int process(Ctx* c, const lvm_params& p, const FrameIO& io, hipStream_t s, int* produced) override;
+    int batch_frames(const Ctx* c, const lvm_params& p, const FrameIO& io, int left) const override;
+    int process_frames(Ctx* c, const lvm_params& p, const FrameIO& io, int nt, hipStream_t s) override;
 };
+constexpr int kColorBatchMax = 32;    // frames of one colour-mode temporal batch (spare slots of the window ring)
+
+// Gaussian pyramids, the up chain's images and the column of the rolling window for nt frames (the per-frame arena: nt = 1)
+static void color_layout(const ColorState* st, int nt, float** G, float** up, float** col1, ArenaCursor& a) {
+    const int levels = st->levels;
+    const size_t nL = st->g[levels].n;
+    for (int l = 1; l <= levels; ++l) G[l] = a.take(st->g[l].n * st->planes * nt);
+    for (int k = 0; k < levels; ++k) up[k] = a.take((nL << (2 * k)) * st->planes * nt);
+    *col1 = a.take((size_t)st->rows * nt);
+}
 
 static void resize_tab(int d, int s, std::vector<int>& ofs, std::vector<float>& al) {   // cv::resize INTER_LINEAR tables
     const double scale = 1. / ((double)d / s);
@@ -1195,19 +1208,11 @@ static int color_alloc(Ctx* c, ColorState* st, int w, int h, int channels, int l
         const int lw = (st->g[l - 1].w + 1) / 2, lh = (st->g[l - 1].h + 1) / 2;
         st->g[l] = {lw, lh, (size_t)lw * lh};
     }
-    auto pad = [](size_t n) { return (n + 63) & ~(size_t)63; };
     const size_t nL = st->g[levels].n;
     st->rows_ps = (int)((nL * channels + 255) / 256 * 256);
     st->rows = st->rows_ps * c->nstreams;
-    size_t total = 0;
-    for (int l = 1; l <= levels; ++l) total += pad(st->g[l].n * st->planes);
-    for (int k = 0; k < levels; ++k) total += pad((nL << (2 * k)) * st->planes);
-    total += pad((size_t)st->rows);
-    if (hipMalloc((void**)&st->arena, total * sizeof(float)) != hipSuccess) { st->arena = nullptr; c->err = "color: hipMalloc failed"; return LVM_ERR_OOM; }
-    float* p = st->arena;
-    for (int l = 1; l <= levels; ++l) { st->G[l] = p; p += pad(st->g[l].n * st->planes); }
-    for (int k = 0; k < levels; ++k) { st->up[k] = p; p += pad((nL << (2 * k)) * st->planes); }
-    st->col1 = p;
+    const int arc = arena_alloc(c, &st->arena, 0, "color: hipMalloc failed", [&](ArenaCursor& a) { color_layout(st, 1, st->G, st->up, &st->col1, a); });
+    if (arc != LVM_OK) return arc;
     // resize tables from (w_L 2^L, h_L 2^L) to (w, h); equal sizes => identity taps (cv::resize copies)
     const int UW = st->g[levels].w << levels, UH = st->g[levels].h << levels;
     std::vector<int> xo, yo; std::vector<float> xa, ya;
@@ -1417,7 +1422,7 @@ static void col_up_out(Ctx* c, ColorState* st, const FrameIO& io, const ColBufs&
     a.w = io.w; a.h = io.h; a.V = B.up[levels - 1]; a.vw = uw; a.vh = uh;
     a.xofs = st->xofs; a.xa = st->xa; a.yofs = st->yofs; a.ya = st->ya; a.yslot = st->yslot; a.mm = B.mm;
     a.tiles_x = (io.w + CT_W - 1) / CT_W; a.tiles_y = (io.h + CT_H - 1) / CT_H;
-    a.dbg = c->keep_float ? c->d_float : nullptr;
+    a.dbg = c->keep_float ? c->d_float.as<float>() : nullptr;
     const dim3 grid(a.tiles_x, a.tiles_y, NZ);
     const bool vec4 = C == 3 && io.w == 2 * uw && io.w % 4 == 0 && io.in_stride % 4 == 0 && io.in_sstride % 4 == 0 &&
                       io.out_stride % 4 == 0 && io.out_sstride % 4 == 0 && ((uintptr_t)io.d_in % 4) == 0 && ((uintptr_t)io.d_out % 4) == 0 &&
@@ -1450,29 +1455,34 @@ static void col_up_out(Ctx* c, ColorState* st, const FrameIO& io, const ColBufs&
     }
 }
 
-int color_process(Ctx* c, const lvm_params& p, int levels, const FrameIO& io, hipStream_t s, int* produced) {
+static void color_switches(ColorState* st) {
+    env_switch("LVM_COL_THIN_DFT", st->thin_dft);
+    env_switch("LVM_COL_THIN8_DFT", st->thin8_dft);
+    env_switch("LVM_COL_NORM_IN_UP", st->norm_in_up);
+    env_switch("LVM_COL_UP_ROWS", st->up_rows);
+    env_switch("LVM_D0_ROWS", st->d0_rows_on);
+    env_switch("LVM_D0_MIN_TASKS", st->d0_min_tasks);
+    if (env_switch("LVM_COL_OUT_ROWS", st->out_rows)) st->out_rows_lean = st->out_rows;
+    env_switch("LVM_COL_OUT_LEAN", st->out_lean);
+    env_switch("LVM_COL_DOWN01", st->d01_on);
+    env_switch("LVM_COL_DOWN01_ROWS", st->d01_rows_forced);
+    if (env_switch("LVM_COL_OUT_MIN_TASKS", st->out_min_tasks)) st->out_min_tasks_lean = st->out_min_tasks;
+    env_switch("LVM_COL_THIN_MIN_FRAMES", st->thin_min_frames);
+    env_switch("LVM_ROWS_MIN_ELEMS", st->rows_min_elems);
+}
+
+int color_create(Ctx* c, int levels, const FrameIO& io, hipStream_t s) {
+    ColorState* st = new ColorState();
+    c->state = st;
+    color_switches(st);
+    int rc = color_alloc(c, st, io.w, io.h, io.channels, levels);
+    if (rc == LVM_OK && c->max_frames > 1) rc = color_reserve_frames(c, st, c->max_frames, s);
+    return rc;
+}
+
+int ColorState::process(Ctx* c, const lvm_params& p, const FrameIO& io, hipStream_t s, int* produced) {
+    ColorState* st = this;
     *produced = 0;
-    ColorState* st = static_cast<ColorState*>(c->state);
-    if (!st) {
-        st = new ColorState();
-        c->state = st;
-        if (const char* e = std::getenv("LVM_COL_THIN_DFT")) st->thin_dft = std::atoi(e) != 0;
-        if (const char* e = std::getenv("LVM_COL_THIN8_DFT")) st->thin8_dft = std::atoi(e) != 0;
-        if (const char* e = std::getenv("LVM_COL_NORM_IN_UP")) st->norm_in_up = std::atoi(e) != 0;
-        if (const char* e = std::getenv("LVM_COL_UP_ROWS")) st->up_rows = std::atoi(e) != 0;
-        if (const char* e = std::getenv("LVM_D0_ROWS")) st->d0_rows_on = std::atoi(e) != 0;
-        if (const char* e = std::getenv("LVM_D0_MIN_TASKS")) st->d0_min_tasks = std::atol(e);
-        if (const char* e = std::getenv("LVM_COL_OUT_ROWS")) st->out_rows = st->out_rows_lean = std::atoi(e);
-        if (const char* e = std::getenv("LVM_COL_OUT_LEAN")) st->out_lean = std::atoi(e) != 0;
-        if (const char* e = std::getenv("LVM_COL_DOWN01")) st->d01_on = std::atoi(e) != 0;
-        if (const char* e = std::getenv("LVM_COL_DOWN01_ROWS")) st->d01_rows_forced = std::atoi(e);
-        if (const char* e = std::getenv("LVM_COL_OUT_MIN_TASKS")) st->out_min_tasks = st->out_min_tasks_lean = std::atol(e);
-        if (const char* e = std::getenv("LVM_COL_THIN_MIN_FRAMES")) st->thin_min_frames = std::atoi(e);
-        if (const char* e = std::getenv("LVM_ROWS_MIN_ELEMS")) st->rows_min_elems = std::atol(e);
-        int rc = color_alloc(c, st, io.w, io.h, io.channels, levels);
-        if (rc == LVM_OK && c->max_frames > 1) rc = color_reserve_frames(c, st, c->max_frames, s);
-        if (rc != LVM_OK) return rc;
-    }
     const ColBufs B{st->G, st->up, st->col1, st->mm, 1};
     col_down(c, st, io, B, s);
     // ---- rolling window (:175-176, SpatialFilter.cpp:63-84) ----
@@ -1537,40 +1547,30 @@ static int color_reserve_frames(Ctx* c, ColorState* st, int nt, hipStream_t s) {
     const int hint = c->max_frames < kColorBatchMax ? c->max_frames : kColorBatchMax;
     if (nt < hint) nt = hint;
     if (nt <= st->tcap) return LVM_OK;
-    const int levels = st->levels, NS = c->nstreams;
+    const int NS = c->nstreams;
     LVM_HIP_TRY(c, hipStreamSynchronize(s));
     sync_streams(c);
     if (st->tarena) (void)hipFree(st->tarena);
     if (st->mmt) (void)hipFree(st->mmt);
     st->tarena = nullptr; st->mmt = nullptr; st->tcap = 0;
-    auto pad = [](size_t n) { return (n + 63) & ~(size_t)63; };
-    const size_t nL = st->g[levels].n;
-    size_t total = 64;
-    for (int l = 1; l <= levels; ++l) total += pad(st->g[l].n * st->planes * nt);
-    for (int k = 0; k < levels; ++k) total += pad((nL << (2 * k)) * st->planes * nt);
-    total += pad((size_t)st->rows * nt);
-    if (hipMalloc((void**)&st->tarena, total * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); st->tarena = nullptr; c->err = "color: hipMalloc (frames) failed"; return LVM_ERR_OOM; }
+    const int rc = arena_alloc(c, &st->tarena, 64, "color: hipMalloc (frames) failed", [&](ArenaCursor& a) { color_layout(st, nt, st->Gt, st->upt, &st->col1t, a); });
+    if (rc != LVM_OK) return rc;
     LVM_HIP_TRY(c, hipMalloc((void**)&st->mmt, sizeof(MinMax) * NS * nt));
-    float* q = st->tarena;
-    for (int l = 1; l <= levels; ++l) { st->Gt[l] = q; q += pad(st->g[l].n * st->planes * nt); }
-    for (int k = 0; k < levels; ++k) { st->upt[k] = q; q += pad((nL << (2 * k)) * st->planes * nt); }
-    st->col1t = q;
     st->tcap = nt;
     return LVM_OK;
 }
 
 // Temporal batch: nt consecutive frames; only in the steady state of the rolling window (full window, so
 // its length -- and with it the twiddle table and the mask -- is the same for every frame of the batch).
-bool color_can_batch(const Ctx* c, const lvm_params& p, int nt) {
-    const ColorState* st = dynamic_cast<const ColorState*>(c->state);
-    if (!st) return false;
+int ColorState::batch_frames(const Ctx*, const lvm_params& p, const FrameIO&, int left) const {
+    const int nt = left < kColorBatchMax ? left : kColorBatchMax;      // the window ring keeps that many spare slots
     const int maxImages = optimal_buffer_size((int)p.framerate);
-    return maxImages > 0 && st->max_images == maxImages && st->n == maxImages && st->tw_n == st->n && st->n <= kDftMaxN &&
-           st->cap >= st->n + nt;
+    const bool ok = maxImages > 0 && max_images == maxImages && n == maxImages && tw_n == n && n <= kDftMaxN && cap >= n + nt;
+    return ok ? nt : 0;
 }
 
-int color_process_frames(Ctx* c, const lvm_params& p, const FrameIO& io, int nt, hipStream_t s) {
-    ColorState* st = static_cast<ColorState*>(c->state);
+int ColorState::process_frames(Ctx* c, const lvm_params& p, const FrameIO& io, int nt, hipStream_t s) {
+    ColorState* st = this;
     if (nt > st->tcap) { const int rc = color_reserve_frames(c, st, nt, s); if (rc != LVM_OK) return rc; }
     const ColBufs B{st->Gt, st->upt, st->col1t, st->mmt, nt};
     col_down(c, st, io, B, s);

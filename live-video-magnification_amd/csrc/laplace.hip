@@ -989,10 +989,32 @@ struct LaplaceState : ModeState {
         if (arena) (void)hipFree(arena);
         if (tarena) (void)hipFree(tarena);
     }
+    int process(Ctx* c, const lvm_params& p, const FrameIO& io, hipStream_t s, int* produced) override;
+    int batch_frames(const Ctx* c, const lvm_params&, const FrameIO&, int left) const override { return seeded && c->pipeline_depth == 0 ? left : 0; }
+    int process_frames(Ctx* c, const lvm_params& p, const FrameIO& io, int nt, hipStream_t s) override;
+    int flush(Ctx* c, hipStream_t s) override;
 };
 
 static void laplace_tail_plan(LaplaceState* st);
 static int laplace_reserve_frames(Ctx* c, LaplaceState* st, int nt, hipStream_t s);
+
+// the per-frame arena: pyramids double-buffered by frame parity, integer Lab planes likewise, the IIR states, the tail kernel's cur_T pair
+static void laplace_layout(LaplaceState* st, int NS, ArenaCursor& a) {
+    const int levels = st->levels;
+    for (int q = 0; q < 2; ++q)
+        for (int l = 1; l <= levels; ++l) st->Gp[q][l] = a.take(st->g[l].n * st->planes);
+    for (int l = 1; l <= levels; ++l) st->G[l] = st->Gp[0][l];
+    const size_t npx = st->g[0].n * NS;                          // pixels of one frame set
+    if (st->planes == 3 * NS)
+        for (int q = 0; q < 2; ++q) { st->iabp[q] = a.take<uint32_t>(npx); st->iLp[q] = a.take<uint16_t>((npx + 1) / 2); }
+    for (int l = 1; l < levels; ++l) {
+        st->hi[l] = a.take(st->g[l].n * st->planes);
+        st->lo[l] = a.take(st->g[l].n * st->planes);
+        st->cur[l] = a.take(st->g[l].n * st->planes);
+    }
+    if (st->tailT)
+        for (int q = 0; q < 2; ++q) st->curT[q] = a.take(st->g[st->tailT].n * st->planes);
+}
 
 static int laplace_alloc(Ctx* c, LaplaceState* st, int w, int h, int channels, int levels) {
     st->levels = levels;
@@ -1002,57 +1024,8 @@ static int laplace_alloc(Ctx* c, LaplaceState* st, int w, int h, int channels, i
         const int lw = (st->g[l - 1].w + 1) / 2, lh = (st->g[l - 1].h + 1) / 2;
         st->g[l] = {lw, lh, (size_t)lw * lh};
     }
-    size_t total = 0;
-    auto pad = [](size_t n) { return (n + 63) & ~(size_t)63; };
-    for (int l = 1; l <= levels; ++l) total += 2 * pad(st->g[l].n * st->planes);
-    for (int l = 1; l < levels; ++l) total += 5 * pad(st->g[l].n * st->planes);
-    const size_t npx = st->g[0].n * c->nstreams;                 // pixels of one frame set
-    if (channels == 3) total += 2 * (pad(npx) + pad((npx + 1) / 2));
-    if (total == 0) total = 64;
-    if (hipMalloc((void**)&st->arena, total * sizeof(float)) != hipSuccess) {
-        c->err = "laplace: hipMalloc failed";
-        st->arena = nullptr;
-        return LVM_ERR_OOM;
-    }
-    float* p = st->arena;
-    for (int q = 0; q < 2; ++q)
-        for (int l = 1; l <= levels; ++l) { st->Gp[q][l] = p; p += pad(st->g[l].n * st->planes); }
-    for (int l = 1; l <= levels; ++l) st->G[l] = st->Gp[0][l];
-    if (channels == 3)
-        for (int q = 0; q < 2; ++q) {
-            st->iabp[q] = reinterpret_cast<uint32_t*>(p); p += pad(npx);
-            st->iLp[q] = reinterpret_cast<uint16_t*>(p); p += pad((npx + 1) / 2);
-        }
-    for (int l = 1; l < levels; ++l) {
-        st->hi[l] = p; p += pad(st->g[l].n * st->planes);
-        st->lo[l] = p; p += pad(st->g[l].n * st->planes);
-        st->cur[l] = p; p += pad(st->g[l].n * st->planes);
-    }
     laplace_tail_plan(st);
-    if (const char* e = std::getenv("LVM_FUSE_DOWN")) st->fuse_down = std::atoi(e);
-    if (const char* e = std::getenv("LVM_UP_DEPTH")) st->up_depth = std::atoi(e);
-    if (const char* e = std::getenv("LVM_UP_DEPTH_BIG")) st->up_depth_big = std::atoi(e);
-    if (const char* e = std::getenv("LVM_PD_ROWS")) st->pd_rows = std::atoi(e);
-    if (const char* e = std::getenv("LVM_D0_ROWS")) st->d0_rows_on = std::atoi(e) != 0;
-    if (const char* e = std::getenv("LVM_D0_FUSED")) st->d0_fused = std::atoi(e) != 0;
-    if (const char* e = std::getenv("LVM_D0_FUSED_WAVES")) st->d0_fused_waves = std::atol(e);
-    if (const char* e = std::getenv("LVM_D0_FUSED_GROUPS")) st->d0_fused_groups = std::atol(e);
-    if (const char* e = std::getenv("LVM_D0_FUSED_ROWS")) st->d0_fused_rows = std::atoi(e);
-    if (const char* e = std::getenv("LVM_D0_MIN_TASKS")) st->d0_min_tasks = std::atol(e);
-    if (const char* e = std::getenv("LVM_LAP_SPLIT")) st->split_levels = std::atoi(e);
-    if (const char* e = std::getenv("LVM_LAP_SPLIT_MIN_NT")) st->split_min_nt = std::atoi(e);
-    if (const char* e = std::getenv("LVM_UP_ROWS")) st->up_rows = std::atoi(e);
-    if (const char* e = std::getenv("LVM_UP_ROWS_MAX_BLOCKS")) st->up_rows_max_blocks = std::atol(e);
-    if (const char* e = std::getenv("LVM_ROWS_MIN_ELEMS")) st->rows_min_elems = std::atol(e);
-    if (const char* e = std::getenv("LVM_LAP_SPLIT_FROM")) { const int v = std::atoi(e); if (v == 2 || v == 3) st->split_from = v; }
-    if (const char* e = std::getenv("LVM_FIN_MIN_TASKS")) st->fin_min_tasks = std::atol(e);
-    if (const char* e = std::getenv("LVM_FIN_GROUPS")) st->fin_groups = std::atol(e);
-    if (const char* e = std::getenv("LVM_FIN_ROWS")) { const int v = std::atoi(e); if (v == 2 || v == 4 || v == 8 || v == 16 || v == 32) st->fin_rows = v; }
-    if (st->tailT) {
-        st->curT[0] = p; p += pad(st->g[st->tailT].n * st->planes);
-        st->curT[1] = p; p += pad(st->g[st->tailT].n * st->planes);
-    }
-    return LVM_OK;
+    return arena_alloc(c, &st->arena, 0, "laplace: hipMalloc failed", [&](ArenaCursor& a) { laplace_layout(st, c->nstreams, a); });
 }
 
 // Decide which levels the tail kernel covers and lay out its LDS pool.
@@ -1320,7 +1293,7 @@ static void lap_stage_a(Ctx* c, LaplaceState* st, const lvm_params& p, const Fra
         else LVM_LAUNCH(c, LName("lap_up", l), (k_lap_up<false, 8>), grid, blk, s, a);
     }
     const int fl = lab_flavour(c);
-    float* dbg = (c->keep_float && B.dbg_frame) ? c->d_float : nullptr;   // (the float frame kept is the first one of the batch)
+    float* dbg = (c->keep_float && B.dbg_frame) ? c->d_float.as<float>() : nullptr;   // (the float frame kept is the first one of the batch)
     const int tx = (io.w + UT_W - 1) / UT_W, ty = (io.h + UT_H - 1) / UT_H;
     const int ntiles = tx * ty * NS;
     const dim3 grid(ntiles < 2048 ? ntiles : 2048);
@@ -1352,9 +1325,9 @@ static void lap_stage_a(Ctx* c, LaplaceState* st, const lvm_params& p, const Fra
 }
 
 // Emits stage A of the pending frame (pipelined mode): its output lands in the d_out it was given.
-int laplace_flush(Ctx* c, hipStream_t s) {
-    LaplaceState* st = dynamic_cast<LaplaceState*>(c->state);
-    if (!st || !st->pending.valid) return LVM_OK;
+int LaplaceState::flush(Ctx* c, hipStream_t s) {
+    LaplaceState* st = this;
+    if (!st->pending.valid) return LVM_OK;
     lap_stage_a(c, st, st->pending.p, st->pending.io, lap_bufs_frame(st, st->pending.par), false, s);
     st->pending.valid = false;
     LVM_HIP_TRY(c, hipGetLastError());
@@ -1372,18 +1345,13 @@ static int laplace_reserve_frames(Ctx* c, LaplaceState* st, int nt, hipStream_t 
     sync_streams(c);
     if (st->tarena) (void)hipFree(st->tarena);
     st->tarena = nullptr; st->tcap = 0;
-    auto pad = [](size_t n) { return (n + 63) & ~(size_t)63; };
-    size_t total = 64;
-    for (int l = 1; l <= levels; ++l) total += pad(st->g[l].n * st->planes * nt);
-    for (int l = 1; l < levels; ++l) total += pad(st->g[l].n * st->planes * nt);
-    const size_t npx = st->g[0].n * c->nstreams * nt;
-    const bool lab = st->planes == 3 * c->nstreams;
-    if (lab) total += pad(npx) + pad((npx + 1) / 2);
-    if (hipMalloc((void**)&st->tarena, total * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); st->tarena = nullptr; c->err = "laplace: hipMalloc (frames) failed"; return LVM_ERR_OOM; }
-    float* q = st->tarena;
-    for (int l = 1; l <= levels; ++l) { st->Gt[l] = q; q += pad(st->g[l].n * st->planes * nt); }
-    for (int l = 1; l < levels; ++l) { st->curt[l] = q; q += pad(st->g[l].n * st->planes * nt); }
-    if (lab) { st->iabt = reinterpret_cast<uint32_t*>(q); q += pad(npx); st->iLt = reinterpret_cast<uint16_t*>(q); q += pad((npx + 1) / 2); }
+    const int rc = arena_alloc(c, &st->tarena, 64, "laplace: hipMalloc (frames) failed", [&](ArenaCursor& a) {
+        for (int l = 1; l <= levels; ++l) st->Gt[l] = a.take(st->g[l].n * st->planes * nt);
+        for (int l = 1; l < levels; ++l) st->curt[l] = a.take(st->g[l].n * st->planes * nt);
+        const size_t npx = st->g[0].n * c->nstreams * nt;
+        if (st->planes == 3 * c->nstreams) { st->iabt = a.take<uint32_t>(npx); st->iLt = a.take<uint16_t>((npx + 1) / 2); }
+    });
+    if (rc != LVM_OK) return rc;
     st->tcap = nt;
     return LVM_OK;
 }
@@ -1392,11 +1360,11 @@ static int laplace_reserve_frames(Ctx* c, LaplaceState* st, int nt, hipStream_t 
 // export/Exporter.cpp:216-259, sees its frames in exactly this order).  Frame f of stream b lives at
 // d_in + (f * n_streams + b) * in_sstride.  Preconditions (checked by the caller): state seeded,
 // pipeline depth 0.  Kernels and arithmetic are those of the per-frame path.
-int laplace_process_frames(Ctx* c, const lvm_params& p, const FrameIO& io, int nt, hipStream_t s) {
-    LaplaceState* st = static_cast<LaplaceState*>(c->state);
+int LaplaceState::process_frames(Ctx* c, const lvm_params& p, const FrameIO& io, int nt, hipStream_t s) {
+    LaplaceState* st = this;
     const int levels = st->levels;
     if (nt > st->tcap) { const int rc = laplace_reserve_frames(c, st, nt, s); if (rc != LVM_OK) return rc; }
-    if (st->pending.valid) { const int rc = laplace_flush(c, s); if (rc != LVM_OK) return rc; }
+    if (st->pending.valid) { const int rc = flush(c, s); if (rc != LVM_OK) return rc; }
     // One pass over the batch: the stateless kernels take the frames as one more batch dimension, the IIR kernels walk over them
     // inside the launch.  (Rounds 1-3 also carried two chunked schedules -- the next chunk's table conversion on a second stream, and the
     // last kernel of a chunk sharing a launch with the next chunk's first kernel; both measured slower, profiles/README.md, and were removed.)
@@ -1411,25 +1379,44 @@ int laplace_process_frames(Ctx* c, const lvm_params& p, const FrameIO& io, int n
     return LVM_OK;
 }
 
-bool laplace_can_batch(const Ctx* c) {
-    const LaplaceState* st = dynamic_cast<const LaplaceState*>(c->state);
-    return st && st->seeded && c->pipeline_depth == 0;
+static void laplace_switches(LaplaceState* st) {
+    env_switch("LVM_FUSE_DOWN", st->fuse_down);
+    env_switch("LVM_UP_DEPTH", st->up_depth);
+    env_switch("LVM_UP_DEPTH_BIG", st->up_depth_big);
+    env_switch("LVM_PD_ROWS", st->pd_rows);
+    env_switch("LVM_D0_ROWS", st->d0_rows_on);
+    env_switch("LVM_D0_FUSED", st->d0_fused);
+    env_switch("LVM_D0_FUSED_WAVES", st->d0_fused_waves);
+    env_switch("LVM_D0_FUSED_GROUPS", st->d0_fused_groups);
+    env_switch("LVM_D0_FUSED_ROWS", st->d0_fused_rows);
+    env_switch("LVM_D0_MIN_TASKS", st->d0_min_tasks);
+    env_switch("LVM_LAP_SPLIT", st->split_levels);
+    env_switch("LVM_LAP_SPLIT_MIN_NT", st->split_min_nt);
+    env_switch("LVM_UP_ROWS", st->up_rows);
+    env_switch("LVM_UP_ROWS_MAX_BLOCKS", st->up_rows_max_blocks);
+    env_switch("LVM_ROWS_MIN_ELEMS", st->rows_min_elems);
+    env_switch("LVM_LAP_SPLIT_FROM", st->split_from, [](int v) { return v == 2 || v == 3; });
+    env_switch("LVM_FIN_MIN_TASKS", st->fin_min_tasks);
+    env_switch("LVM_FIN_GROUPS", st->fin_groups);
+    env_switch("LVM_FIN_ROWS", st->fin_rows, [](int v) { return v == 2 || v == 4 || v == 8 || v == 16 || v == 32; });
 }
 
-int laplace_process(Ctx* c, const lvm_params& p, int levels, const FrameIO& io, hipStream_t s, int* produced) {
-    LaplaceState* st = static_cast<LaplaceState*>(c->state);
-    if (!st) {
-        st = new LaplaceState();
-        c->state = st;
-        int rc = laplace_alloc(c, st, io.w, io.h, io.channels, levels);
-        if (rc == LVM_OK && c->max_frames > 1) rc = laplace_reserve_frames(c, st, c->max_frames, s);
-        if (rc != LVM_OK) return rc;
-    }
+int laplace_create(Ctx* c, int levels, const FrameIO& io, hipStream_t s) {
+    LaplaceState* st = new LaplaceState();
+    c->state = st;
+    laplace_switches(st);
+    int rc = laplace_alloc(c, st, io.w, io.h, io.channels, levels);
+    if (rc == LVM_OK && c->max_frames > 1) rc = laplace_reserve_frames(c, st, c->max_frames, s);
+    return rc;
+}
+
+int LaplaceState::process(Ctx* c, const lvm_params& p, const FrameIO& io, hipStream_t s, int* produced) {
+    LaplaceState* st = this;
     const bool first = !st->seeded;
     st->depth = c->pipeline_depth;
     if (first || c->pipeline_depth == 0 || !c->aux_stream) {
         // plain schedule: both stages of this frame back to back on the caller's stream
-        if (st->pending.valid) { const int rc = laplace_flush(c, s); if (rc != LVM_OK) return rc; }
+        if (st->pending.valid) { const int rc = flush(c, s); if (rc != LVM_OK) return rc; }
         lap_stage_b(c, st, p, io, lap_bufs_frame(st, 0), first, s);
         lap_stage_a(c, st, p, io, lap_bufs_frame(st, 0), first, s);
         st->par = 1;

@@ -92,11 +92,12 @@ int upload_lab_lut(Ctx* c) {
     return LVM_OK;
 }
 
-static int run_mode(Ctx* c, const lvm_params* p, int levels, const FrameIO& io, hipStream_t s, int* produced) {
-    switch (p->mode) {                                                                  // MagnificationProcessor.cpp:48-60
-    case LVM_MODE_LAPLACE: return laplace_process(c, *p, levels, io, s, produced);
-    case LVM_MODE_PHASE:   return riesz_process(c, *p, levels, io, s, produced);
-    case LVM_MODE_COLOR:   return color_process(c, *p, levels, io, s, produced);
+// lazy, per mode (MagnificationProcessor.cpp:48-60); Riesz on gray frames creates nothing and the frame passes through
+static int create_state(Ctx* c, int mode, int levels, const FrameIO& io, hipStream_t s) {
+    switch (mode) {
+    case LVM_MODE_LAPLACE: return laplace_create(c, levels, io, s);
+    case LVM_MODE_PHASE:   return riesz_create(c, levels, io, s);
+    case LVM_MODE_COLOR:   return color_create(c, levels, io, s);
     default: break;
     }
     return LVM_OK;
@@ -112,15 +113,13 @@ void fail_state(Ctx* c, hipStream_t s) {
     drop_state(c);
     tracker_disable(c);
 }
-static void tracker_disable(Ctx* c) { c->t_mode = LVM_MODE_NONE; c->t_levels = -1; c->t_channels = -1; c->t_w = c->t_h = 0; }
+static void tracker_disable(Ctx* c) { const uint64_t pre = c->tracked.pre; c->tracked = StructKey{}; c->tracked.pre = pre; }
 
 int ensure_float(Ctx* c, size_t count) {
-    if (count > c->float_cap) {
+    if (count * sizeof(float) > c->d_float.cap) {
         sync_streams(c);            // kernels of earlier calls may still be writing the kept frame
-        if (c->d_float) (void)hipFree(c->d_float);
-        c->d_float = nullptr; c->float_cap = 0;
-        LVM_HIP_TRY(c, hipMalloc((void**)&c->d_float, count * sizeof(float)));
-        c->float_cap = count;
+        const int rc = c->d_float.reserve(c, count * sizeof(float));
+        if (rc != LVM_OK) return rc;
     }
     c->float_count = count;
     return LVM_OK;
@@ -130,9 +129,9 @@ int ensure_float(Ctx* c, size_t count) {
 static int process_device(Ctx* c, const lvm_params* p, const FrameIO& io, hipStream_t s, int* produced) {
     *produced = 0;
     if (p->mode == LVM_MODE_NONE || io.d_in == nullptr || io.w <= 0 || io.h <= 0) {      // :21-29
-        if (c->t_mode != LVM_MODE_NONE) {
+        if (c->tracked.mode != LVM_MODE_NONE) {
             // pipelined mode: the pending frame's output is owed to its caller (same rule as on a structural change)
-            if (c->t_mode == LVM_MODE_LAPLACE) (void)laplace_flush(c, s);
+            if (c->state) (void)c->state->flush(c, s);
             LVM_HIP_TRY(c, hipStreamSynchronize(s));
             sync_streams(c);
             drop_state(c); tracker_disable(c);
@@ -142,28 +141,34 @@ static int process_device(Ctx* c, const lvm_params* p, const FrameIO& io, hipStr
     if (p->mode < 0 || p->mode > LVM_MODE_NONE) { c->err = "invalid mode"; return LVM_ERR_INVALID; }
     if (io.channels != 1 && io.channels != 3) { c->err = "channels must be 1 or 3"; return LVM_ERR_INVALID; }
     if (io.d_out == nullptr) { c->err = "null output"; return LVM_ERR_INVALID; }
-    const int maxLevels = max_levels(io.w, io.h);                                       // :32-33
-    if (maxLevels < 1) return LVM_OK;
-    int levels = p->levels < 1 ? 1 : (p->levels > maxLevels ? maxLevels : p->levels);   // :34
-    if (levels > kMaxLevels) levels = kMaxLevels;
-    const bool change = p->mode != c->t_mode || levels != c->t_levels || io.w != c->t_w || io.h != c->t_h ||
-                        io.channels != c->t_channels || p->preprocess_key != c->t_pre;  // MagnifyCore.hpp:53-65
-    if (change) {
+    const StructKey key = struct_key(*p, io.w, io.h, io.channels);                      // :32-34
+    if (key.levels < 1) return LVM_OK;
+    if (key != c->tracked) {                                                            // MagnifyCore.hpp:53-65
         // buffers of the old geometry may still be in use by queued kernels
-        if (c->t_mode == LVM_MODE_LAPLACE) (void)laplace_flush(c, s);   // pipelined mode: do not lose the pending frame
+        if (c->state) (void)c->state->flush(c, s);                       // pipelined mode: do not lose the pending frame
         LVM_HIP_TRY(c, hipStreamSynchronize(s));
         sync_streams(c);                                                 // earlier calls may have used other streams
-        c->t_mode = p->mode; c->t_levels = levels; c->t_w = io.w; c->t_h = io.h;
-        c->t_channels = io.channels; c->t_pre = p->preprocess_key;
+        c->tracked = key;
         drop_state(c);                                                                  // :39-43
     }
     if (c->keep_float) {
         const int rc = ensure_float(c, (size_t)io.w * io.h * io.channels);
         if (rc != LVM_OK) return rc;
     }
-    const int rc = run_mode(c, p, levels, io, s, produced);
+    int rc = c->state ? LVM_OK : create_state(c, p->mode, key.levels, io, s);
+    if (rc == LVM_OK && c->state) rc = c->state->process(c, *p, io, s, produced);
     mark_enqueued(c, s);
     if (rc != LVM_OK) fail_state(c, s);
+    return rc;
+}
+
+// run the magnifier with pipeline depth 0: the synchronous surfaces complete their own frames
+template <class Run>
+static int at_depth0(Ctx* c, Run&& run) {
+    const int depth = c->pipeline_depth;
+    c->pipeline_depth = 0;
+    const int rc = run();
+    c->pipeline_depth = depth;
     return rc;
 }
 
@@ -229,20 +234,9 @@ void lvm_destroy(lvm_ctx* c) {
     if (c->h_probe) (void)hipHostFree(c->h_probe);
     if (c->d_lab_ab) (void)hipFree(c->d_lab_ab);
     if (c->d_lab_Lcells) (void)hipFree(c->d_lab_Lcells);
-    if (c->d_in) (void)hipFree(c->d_in);
-    if (c->d_out) (void)hipFree(c->d_out);
-    if (c->d_float) (void)hipFree(c->d_float);
     lvm::preprocess_release(c);
     lvm::mjpeg_release(c);
     lvm::mjpeg_decode_release(c);
-    if (c->d_pre_in) (void)hipFree(c->d_pre_in);
-    if (c->d_pre_out) (void)hipFree(c->d_pre_out);
-    if (c->d_chain_out) (void)hipFree(c->d_chain_out);
-    c->d_pre_in = c->d_pre_out = c->d_chain_out = nullptr; c->pre_in_cap = c->pre_out_cap = c->chain_out_cap = 0;
-    if (c->d_canvas) (void)hipFree(c->d_canvas);
-    c->d_canvas = nullptr; c->canvas_cap = 0;
-    if (c->d_pre_tap) (void)hipFree(c->d_pre_tap);
-    c->d_pre_tap = nullptr; c->pre_tap_cap = 0;
     for (auto e : c->ev_up) (void)hipEventDestroy(e);
     for (auto e : c->ev_done) (void)hipEventDestroy(e);
     if (c->up_stream) (void)hipStreamDestroy(c->up_stream);
@@ -252,7 +246,7 @@ void lvm_destroy(lvm_ctx* c) {
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    delete c;
+    delete c;                       // (the staging buffers go with it: DevBuf)
 }
 
 int lvm_reset(lvm_ctx* c) {                       // MagnificationProcessor.cpp:10-15
@@ -261,8 +255,7 @@ int lvm_reset(lvm_ctx* c) {                       // MagnificationProcessor.cpp:
     // (an owed pipelined frame is discarded: reset() means "forget everything", MagnificationProcessor.cpp:10-15)
     lvm::sync_streams(c);
     lvm::drop_state(c);
-    lvm::tracker_disable(c);
-    c->t_pre = 0;
+    c->tracked = lvm::StructKey{};
     c->err.clear();
     return LVM_OK;
 }
@@ -292,29 +285,19 @@ int lvm_process_device_frames(lvm_ctx* c, const lvm_params* p, int n_frames, con
     while (f < n_frames) {
         lvm::FrameIO io{d_in ? d_in + (size_t)f * in_frame_stride : nullptr, in_stride, in_stream_stride,
                         d_out ? d_out + (size_t)f * out_frame_stride : nullptr, out_stride, out_stream_stride, w, h, channels};
-        // temporal batch: same structural key as the tracked state, steady Laplace state, frames laid
-        // out [frame][stream]; everything else (first frames, other modes, odd layouts) goes frame by frame
+        // temporal batch: same structural key as the tracked state, a state that is steady for these parameters, frames laid
+        // out [frame][stream]; everything else (first frames, odd layouts) goes frame by frame
         const int left = n_frames - f;
-        const int maxL = lvm::max_levels(w, h);
-        const int lv = maxL < 1 ? 0 : (p->levels < 1 ? 1 : (p->levels > maxL ? maxL : p->levels));
-        const bool same = p->mode == c->t_mode && lv == c->t_levels && w == c->t_w && h == c->t_h && channels == c->t_channels &&
-                          p->preprocess_key == c->t_pre && d_in && d_out;
+        const bool same = d_in && d_out && lvm::struct_key(*p, w, h, channels) == c->tracked;
         const bool layout = in_frame_stride == in_stream_stride * c->nstreams && out_frame_stride == out_stream_stride * c->nstreams;
-        if (left >= 2 && same && layout) {
-            int rc = 1;
-            if (p->mode == LVM_MODE_LAPLACE && lvm::laplace_can_batch(c)) rc = lvm::laplace_process_frames(c, *p, io, left, s);
-            else if (p->mode == LVM_MODE_PHASE && channels >= 3 && lvm::riesz_can_batch(c, *p)) rc = lvm::riesz_process_frames(c, *p, io, left, s);
-            else if (p->mode == LVM_MODE_COLOR && lvm::color_can_batch(c, *p, left < lvm::kColorBatchMax ? left : lvm::kColorBatchMax)) {
-                const int nb = left < lvm::kColorBatchMax ? left : lvm::kColorBatchMax;      // the window ring keeps that many spare slots
-                rc = lvm::color_process_frames(c, *p, io, nb, s);
-                if (rc == LVM_OK) { lvm::mark_enqueued(c, s); for (int k = f; k < f + nb; ++k) produced[k] = 1; f += nb; continue; }
-            }
-            if (rc <= 0) {
-                lvm::mark_enqueued(c, s);
-                if (rc != LVM_OK) { lvm::fail_state(c, s); return rc; }
-                for (int k = f; k < n_frames; ++k) produced[k] = 1;
-                return LVM_OK;
-            }
+        const int nb = (left >= 2 && same && layout && c->state) ? c->state->batch_frames(c, *p, io, left) : 0;
+        if (nb > 0) {
+            const int rc = c->state->process_frames(c, *p, io, nb, s);
+            lvm::mark_enqueued(c, s);
+            if (rc != LVM_OK) { lvm::fail_state(c, s); return rc; }
+            for (int k = f; k < f + nb; ++k) produced[k] = 1;
+            f += nb;
+            continue;
         }
         const int rc = lvm::process_device(c, p, io, s, &produced[f]);
         if (rc != LVM_OK) return rc;
@@ -395,7 +378,7 @@ int lvm_tile_riesz_stage2(lvm_ctx* c, const lvm_params* p, const uint8_t* d_in, 
     int rc = tile_check(c, p, w, h);
     if (rc != LVM_OK) return rc;
     if (!d_in || !d_out || !d_residual_in || in_stride < (ptrdiff_t)w * 3 || out_stride < (ptrdiff_t)w * 3) { c->err = "tiling: bad frame arguments"; return LVM_ERR_INVALID; }
-    if (c->t_mode != LVM_MODE_PHASE || c->t_w != w || c->t_h != h) { c->err = "tiling: stage 2 without a matching stage 1"; return LVM_ERR_INVALID; }
+    if (c->tracked.mode != LVM_MODE_PHASE || c->tracked.w != w || c->tracked.h != h) { c->err = "tiling: stage 2 without a matching stage 1"; return LVM_ERR_INVALID; }
     LVM_HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
     lvm::FrameIO io{d_in, in_stride, in_stride * h, d_out, out_stride, out_stride * h, w, h, 3};
@@ -444,6 +427,48 @@ static uint64_t preprocess_key_of(const lvm_preprocess_params& pp) {
     return k;
 }
 
+// The host chain in front of the magnifier (PreprocessProcessor + GrayscaleProcessor) for one source geometry: what the chain and export
+// entry points share.
+struct ChainGeom {
+    int channels, rx, ry, rw, rh, ow, oh, och;
+    size_t roi_row, roi_bytes;      // the cropped source frame
+    size_t out_row, out_bytes;      // the frame the magnifier sees and the one it writes
+    bool identity;                  // nothing to do in front of the magnifier (PreprocessProcessor.cpp:15, GrayscaleProcessor.cpp:8-9)
+    // runChainOnce's `original` is chain[0]'s output (ChainBuilder.cpp:25: the tap sits BEFORE GrayscaleProcessor): with grayscale on
+    // a BGR source it is the cropped / decimated COLOUR frame, not the gray frame the magnifier sees
+    bool gray;
+    size_t tap_row, tap_bytes;      // a frame of the tap: 3 channels with `gray`, the magnifier's input frame otherwise
+};
+static ChainGeom chain_geometry(const lvm_preprocess_params& pp, int w, int h, int channels) {
+    ChainGeom g{};
+    g.channels = channels;
+    lvm::preprocess_geometry(pp, w, h, channels, &g.rx, &g.ry, &g.rw, &g.rh, &g.ow, &g.oh, &g.och);
+    g.roi_row = (size_t)g.rw * channels; g.roi_bytes = g.roi_row * g.rh;
+    g.out_row = (size_t)g.ow * g.och; g.out_bytes = g.out_row * g.oh;
+    g.identity = g.ow == g.rw && g.oh == g.rh && g.och == channels;
+    g.gray = g.och == 1 && channels == 3;
+    g.tap_row = g.gray ? (size_t)g.ow * 3 : g.out_row; g.tap_bytes = g.tap_row * g.oh;
+    return g;
+}
+// only the ROI rows cross PCIe (the crop is the pitch of the 2-D copy)
+static hipError_t chain_upload(const ChainGeom& g, uint8_t* d_dst, const uint8_t* frame, ptrdiff_t in_stride, hipStream_t s) {
+    return hipMemcpy2DAsync(d_dst, g.roi_row, frame + (size_t)g.ry * in_stride + (size_t)g.rx * g.channels, (size_t)in_stride, g.roi_row, (size_t)g.rh,
+                            hipMemcpyHostToDevice, s);
+}
+// Preprocess + Grayscale of frames that are cropped already (by the upload, or as a view into a decoded frame)
+static int chain_preprocess(Ctx* c, const lvm_preprocess_params& pp, const ChainGeom& g, const uint8_t* d_src, size_t src_row, size_t src_fbytes, uint8_t* d_dst,
+                            hipStream_t s, uint8_t* d_tap, ptrdiff_t tap_stride, ptrdiff_t tap_sstride) {
+    lvm_preprocess_params q = pp;
+    q.roi_enabled = 0;
+    return lvm::preprocess_device(c, q, d_src, g.rw, g.rh, g.channels, (ptrdiff_t)src_row, (ptrdiff_t)src_fbytes, d_dst, (ptrdiff_t)g.out_row, (ptrdiff_t)g.out_bytes, s,
+                                  d_tap, tap_stride, tap_sstride);
+}
+static lvm_params chain_params(const lvm_params& p, const lvm_preprocess_params& pp) {
+    lvm_params mp = p;
+    mp.preprocess_key = preprocess_key_of(pp);
+    return mp;
+}
+
 int lvm_chain_process_batch(lvm_ctx* c, const lvm_preprocess_params* pp, const lvm_params* p, const uint8_t* const* in, int w, int h,
                             int channels, ptrdiff_t in_stride, uint8_t* const* out, ptrdiff_t out_stride, int* produced) {
     return lvm_chain_process_batch_ex(c, pp, p, in, w, h, channels, in_stride, out, out_stride, nullptr, 0, produced);
@@ -460,61 +485,35 @@ int lvm_chain_process_batch_ex(lvm_ctx* c, const lvm_preprocess_params* pp, cons
     }
     for (int s = 0; s < NS; ++s) if (!in[s] || !out[s]) { c->err = "null frame pointer"; return LVM_ERR_INVALID; }
     LVM_HIP_TRY(c, hipSetDevice(c->device));
-    int rx, ry, rw, rh, ow, oh, och;
-    lvm::preprocess_geometry(*pp, w, h, channels, &rx, &ry, &rw, &rh, &ow, &oh, &och);
-    if (out_stride < (ptrdiff_t)ow * och) { c->err = "output stride too small"; return LVM_ERR_INVALID; }
-    const size_t roi_row = (size_t)rw * channels, roi_bytes = roi_row * rh;
-    const size_t out_row = (size_t)ow * och, out_bytes = out_row * oh;
-    auto reserve = [&](uint8_t*& ptr, size_t& cap, size_t need) -> int {
-        if (need <= cap) return LVM_OK;
-        if (ptr) (void)hipFree(ptr);
-        ptr = nullptr; cap = 0;
-        LVM_HIP_TRY(c, hipMalloc((void**)&ptr, need));
-        cap = need;
-        return LVM_OK;
-    };
+    const ChainGeom g = chain_geometry(*pp, w, h, channels);
+    if (out_stride < (ptrdiff_t)g.out_row) { c->err = "output stride too small"; return LVM_ERR_INVALID; }
     hipStream_t s = c->own_stream;
     LVM_HIP_TRY(c, hipStreamSynchronize(s));      // staging buffers may be replaced below
-    int rc = reserve(c->d_pre_in, c->pre_in_cap, roi_bytes * NS); if (rc != LVM_OK) return rc;
-    rc = reserve(c->d_pre_out, c->pre_out_cap, out_bytes * NS); if (rc != LVM_OK) return rc;
-    rc = reserve(c->d_chain_out, c->chain_out_cap, out_bytes * NS); if (rc != LVM_OK) return rc;
-    // only the ROI rows cross PCIe (the crop is the pitch of the 2-D copy)
-    for (int k = 0; k < NS; ++k)
-        LVM_HIP_TRY(c, hipMemcpy2DAsync(c->d_pre_in + (size_t)k * roi_bytes, roi_row, in[k] + (size_t)ry * in_stride + (size_t)rx * channels,
-                                        (size_t)in_stride, roi_row, (size_t)rh, hipMemcpyHostToDevice, s));
+    int rc = c->d_pre_in.reserve(c, g.roi_bytes * NS); if (rc != LVM_OK) return rc;
+    rc = c->d_pre_out.reserve(c, g.out_bytes * NS); if (rc != LVM_OK) return rc;
+    rc = c->d_chain_out.reserve(c, g.out_bytes * NS); if (rc != LVM_OK) return rc;
+    for (int k = 0; k < NS; ++k) LVM_HIP_TRY(c, chain_upload(g, c->d_pre_in + (size_t)k * g.roi_bytes, in[k], in_stride, s));
     const uint8_t* mag_in = c->d_pre_in;
-    const bool identity = ow == rw && oh == rh && och == channels;      // PreprocessProcessor.cpp:15, GrayscaleProcessor.cpp:8-9
-    // runChainOnce's `original` is chain[0]'s output (ChainBuilder.cpp:25: the tap sits BEFORE GrayscaleProcessor): with grayscale on
-    // a BGR source it is the cropped / decimated COLOUR frame, not the gray frame the magnifier sees
-    const bool gray_tap = pre_out && och == 1 && channels == 3;
-    const size_t tap_row = (size_t)ow * 3, tap_bytes = tap_row * oh;
-    if (gray_tap) { rc = reserve(c->d_pre_tap, c->pre_tap_cap, tap_bytes * NS); if (rc != LVM_OK) return rc; }
-    if (!identity) {
-        lvm_preprocess_params q = *pp;
-        q.roi_enabled = 0;                                               // already cropped by the copy
-        rc = lvm::preprocess_device(c, q, c->d_pre_in, rw, rh, channels, (ptrdiff_t)roi_row, (ptrdiff_t)roi_bytes, c->d_pre_out,
-                                    (ptrdiff_t)out_row, (ptrdiff_t)out_bytes, s, gray_tap ? c->d_pre_tap : nullptr, (ptrdiff_t)tap_row, (ptrdiff_t)tap_bytes);
+    const bool gray_tap = pre_out && g.gray;
+    if (gray_tap) { rc = c->d_pre_tap.reserve(c, g.tap_bytes * NS); if (rc != LVM_OK) return rc; }
+    if (!g.identity) {
+        rc = chain_preprocess(c, *pp, g, c->d_pre_in, g.roi_row, g.roi_bytes, c->d_pre_out, s, gray_tap ? c->d_pre_tap.p : nullptr, (ptrdiff_t)g.tap_row, (ptrdiff_t)g.tap_bytes);
         if (rc != LVM_OK) { (void)hipStreamSynchronize(s); return rc; }
         mag_in = c->d_pre_out;
     }
-    lvm_params mp = *p;
-    mp.preprocess_key = preprocess_key_of(*pp);
-    lvm::FrameIO io{mag_in, (ptrdiff_t)out_row, (ptrdiff_t)out_bytes, c->d_chain_out, (ptrdiff_t)out_row, (ptrdiff_t)out_bytes, ow, oh, och};
-    const int saved_depth = c->pipeline_depth;
-    c->pipeline_depth = 0;
-    rc = lvm::process_device(c, &mp, io, s, produced);
-    c->pipeline_depth = saved_depth;
+    const lvm_params mp = chain_params(*p, *pp);
+    lvm::FrameIO io{mag_in, (ptrdiff_t)g.out_row, (ptrdiff_t)g.out_bytes, c->d_chain_out, (ptrdiff_t)g.out_row, (ptrdiff_t)g.out_bytes, g.ow, g.oh, g.och};
+    rc = lvm::at_depth0(c, [&] { return lvm::process_device(c, &mp, io, s, produced); });
     if (rc != LVM_OK) { (void)hipStreamSynchronize(s); return rc; }
-    const uint8_t* res = *produced ? c->d_chain_out : mag_in;
+    const uint8_t* res = *produced ? c->d_chain_out.p : mag_in;
     for (int k = 0; k < NS; ++k)
-        LVM_HIP_TRY(c, hipMemcpy2DAsync(out[k], (size_t)out_stride, res + (size_t)k * out_bytes, out_row, out_row, (size_t)oh, hipMemcpyDeviceToHost, s));
+        LVM_HIP_TRY(c, hipMemcpy2DAsync(out[k], (size_t)out_stride, res + (size_t)k * g.out_bytes, g.out_row, g.out_row, (size_t)g.oh, hipMemcpyDeviceToHost, s));
     if (pre_out) {     // the pre-magnification tap (runChainOnce's `original`, ChainBuilder.cpp:19-29): the display's left pane
-        const uint8_t* tsrc = gray_tap ? c->d_pre_tap : mag_in;
-        const size_t trow = gray_tap ? tap_row : out_row, tbytes = gray_tap ? tap_bytes : out_bytes;
-        if (pre_stride < (ptrdiff_t)trow) { c->err = "pre_out stride too small"; (void)hipStreamSynchronize(s); return LVM_ERR_INVALID; }
+        const uint8_t* tsrc = gray_tap ? c->d_pre_tap.p : mag_in;
+        if (pre_stride < (ptrdiff_t)g.tap_row) { c->err = "pre_out stride too small"; (void)hipStreamSynchronize(s); return LVM_ERR_INVALID; }
         for (int k = 0; k < NS; ++k)
             if (pre_out[k])
-                LVM_HIP_TRY(c, hipMemcpy2DAsync(pre_out[k], (size_t)pre_stride, tsrc + (size_t)k * tbytes, trow, trow, (size_t)oh, hipMemcpyDeviceToHost, s));
+                LVM_HIP_TRY(c, hipMemcpy2DAsync(pre_out[k], (size_t)pre_stride, tsrc + (size_t)k * g.tap_bytes, g.tap_row, g.tap_row, (size_t)g.oh, hipMemcpyDeviceToHost, s));
     }
     LVM_HIP_TRY(c, hipStreamSynchronize(s));
     return LVM_OK;
@@ -531,55 +530,34 @@ int lvm_chain_present(lvm_ctx* c, const lvm_preprocess_params* pp, const lvm_par
     if (c->nstreams != 1) { c->err = "lvm_chain_present needs a 1-stream context"; return LVM_ERR_INVALID; }
     if (w <= 0 || h <= 0 || (channels != 1 && channels != 3) || in_stride < (ptrdiff_t)w * channels) { c->err = "bad frame arguments"; return LVM_ERR_INVALID; }
     LVM_HIP_TRY(c, hipSetDevice(c->device));
-    int rx, ry, rw, rh, ow, oh, och;
-    lvm::preprocess_geometry(*pp, w, h, channels, &rx, &ry, &rw, &rh, &ow, &oh, &och);
-    const size_t roi_row = (size_t)rw * channels, roi_bytes = roi_row * rh;
-    const size_t out_row = (size_t)ow * och, out_bytes = out_row * oh;
-    const size_t tap_row = (size_t)ow * channels;                       // the tap keeps the source's channel count (ChainBuilder.cpp:25)
-    if (d_proc && proc_stride < (ptrdiff_t)out_row) { c->err = "proc stride too small"; return LVM_ERR_INVALID; }
-    if (d_orig && orig_stride < (ptrdiff_t)tap_row) { c->err = "orig stride too small"; return LVM_ERR_INVALID; }
-    auto reserve = [&](uint8_t*& ptr, size_t& cap, size_t need) -> int {
-        if (need <= cap) return LVM_OK;
-        if (ptr) (void)hipFree(ptr);
-        ptr = nullptr; cap = 0;
-        LVM_HIP_TRY(c, hipMalloc((void**)&ptr, need));
-        cap = need;
-        return LVM_OK;
-    };
+    const ChainGeom g = chain_geometry(*pp, w, h, channels);
+    if (d_proc && proc_stride < (ptrdiff_t)g.out_row) { c->err = "proc stride too small"; return LVM_ERR_INVALID; }
+    if (d_orig && orig_stride < (ptrdiff_t)g.tap_row) { c->err = "orig stride too small"; return LVM_ERR_INVALID; }      // (the tap keeps the source's channel count)
     hipStream_t s = c->own_stream;
     LVM_HIP_TRY(c, hipStreamSynchronize(s));      // staging buffers may be replaced below
-    int rc = reserve(c->d_pre_in, c->pre_in_cap, roi_bytes); if (rc != LVM_OK) return rc;
-    rc = reserve(c->d_pre_out, c->pre_out_cap, out_bytes); if (rc != LVM_OK) return rc;
-    rc = reserve(c->d_chain_out, c->chain_out_cap, out_bytes); if (rc != LVM_OK) return rc;
-    LVM_HIP_TRY(c, hipMemcpy2DAsync(c->d_pre_in, roi_row, in + (size_t)ry * in_stride + (size_t)rx * channels, (size_t)in_stride, roi_row, (size_t)rh,
-                                    hipMemcpyHostToDevice, s));
-    const bool identity = ow == rw && oh == rh && och == channels;
-    const bool gray_tap = d_orig && och == 1 && channels == 3;
+    int rc = c->d_pre_in.reserve(c, g.roi_bytes); if (rc != LVM_OK) return rc;
+    rc = c->d_pre_out.reserve(c, g.out_bytes); if (rc != LVM_OK) return rc;
+    rc = c->d_chain_out.reserve(c, g.out_bytes); if (rc != LVM_OK) return rc;
+    LVM_HIP_TRY(c, chain_upload(g, c->d_pre_in, in, in_stride, s));
+    const bool gray_tap = d_orig && g.gray;
     const uint8_t* mag_in = c->d_pre_in;
-    if (!identity) {
-        lvm_preprocess_params q = *pp;
-        q.roi_enabled = 0;                                               // already cropped by the copy
+    if (!g.identity) {
         // with grayscale on a BGR source the kernel writes the colour tap straight into the caller's `original` buffer
-        rc = lvm::preprocess_device(c, q, c->d_pre_in, rw, rh, channels, (ptrdiff_t)roi_row, (ptrdiff_t)roi_bytes, c->d_pre_out, (ptrdiff_t)out_row,
-                                    (ptrdiff_t)out_bytes, s, gray_tap ? d_orig : nullptr, orig_stride, (ptrdiff_t)orig_stride * oh);
+        rc = chain_preprocess(c, *pp, g, c->d_pre_in, g.roi_row, g.roi_bytes, c->d_pre_out, s, gray_tap ? d_orig : nullptr, orig_stride, (ptrdiff_t)orig_stride * g.oh);
         if (rc != LVM_OK) { (void)hipStreamSynchronize(s); return rc; }
         mag_in = c->d_pre_out;
     }
     if (d_orig && !gray_tap)        // no gray stage in between: the tap IS the frame the magnifier sees
-        LVM_HIP_TRY(c, hipMemcpy2DAsync(d_orig, (size_t)orig_stride, mag_in, out_row, out_row, (size_t)oh, hipMemcpyDeviceToDevice, s));
-    lvm_params mp = *p;
-    mp.preprocess_key = preprocess_key_of(*pp);
+        LVM_HIP_TRY(c, hipMemcpy2DAsync(d_orig, (size_t)orig_stride, mag_in, g.out_row, g.out_row, (size_t)g.oh, hipMemcpyDeviceToDevice, s));
+    const lvm_params mp = chain_params(*p, *pp);
     // the last kernel writes the processed frame straight into the caller's buffer
-    uint8_t* dst = d_proc ? d_proc : c->d_chain_out;
-    const ptrdiff_t dstride = d_proc ? proc_stride : (ptrdiff_t)out_row;
-    lvm::FrameIO io{mag_in, (ptrdiff_t)out_row, (ptrdiff_t)out_bytes, dst, dstride, dstride * oh, ow, oh, och};
-    const int saved_depth = c->pipeline_depth;
-    c->pipeline_depth = 0;
-    rc = lvm::process_device(c, &mp, io, s, produced);
-    c->pipeline_depth = saved_depth;
+    uint8_t* dst = d_proc ? d_proc : c->d_chain_out.p;
+    const ptrdiff_t dstride = d_proc ? proc_stride : (ptrdiff_t)g.out_row;
+    lvm::FrameIO io{mag_in, (ptrdiff_t)g.out_row, (ptrdiff_t)g.out_bytes, dst, dstride, dstride * g.oh, g.ow, g.oh, g.och};
+    rc = lvm::at_depth0(c, [&] { return lvm::process_device(c, &mp, io, s, produced); });
     if (rc != LVM_OK) { (void)hipStreamSynchronize(s); return rc; }
     if (!*produced && d_proc)       // passthrough: the chain hands the magnifier's INPUT on (MagnificationProcessor.cpp:61) -- that is what the display shows
-        LVM_HIP_TRY(c, hipMemcpy2DAsync(d_proc, (size_t)proc_stride, mag_in, out_row, out_row, (size_t)oh, hipMemcpyDeviceToDevice, s));
+        LVM_HIP_TRY(c, hipMemcpy2DAsync(d_proc, (size_t)proc_stride, mag_in, g.out_row, g.out_row, (size_t)g.oh, hipMemcpyDeviceToDevice, s));
     LVM_HIP_TRY(c, hipStreamSynchronize(s));
     return LVM_OK;
 }
@@ -587,9 +565,9 @@ int lvm_chain_present(lvm_ctx* c, const lvm_preprocess_params* pp, const lvm_par
 int lvm_export_geometry(const lvm_preprocess_params* pp, int split, int w, int h, int channels, int* cw, int* ch) {
     if (!pp || w <= 0 || h <= 0 || (channels != 1 && channels != 3) || !cw || !ch) return LVM_ERR_INVALID;
     if (split < LVM_SPLIT_NONE || split > LVM_SPLIT_TOP_BOTTOM) return LVM_ERR_INVALID;
-    int rx, ry, rw, rh, ow, oh, och, pw, ph;
-    lvm::preprocess_geometry(*pp, w, h, channels, &rx, &ry, &rw, &rh, &ow, &oh, &och);
-    (void)lvm::compose_geometry(split, ow, oh, ow, oh, &pw, &ph, cw, ch);      // 0 x 0 where Exporter::compose returns an empty Mat
+    const ChainGeom g = chain_geometry(*pp, w, h, channels);
+    int pw, ph;
+    (void)lvm::compose_geometry(split, g.ow, g.oh, g.ow, g.oh, &pw, &ph, cw, ch);      // 0 x 0 where Exporter::compose returns an empty Mat
     return LVM_OK;
 }
 
@@ -616,41 +594,29 @@ static int export_frames_impl(lvm_ctx* c, const lvm_preprocess_params* pp, const
     if (w <= 0 || h <= 0 || (channels != 1 && channels != 3) || in_stride < (ptrdiff_t)w * channels) { c->err = "bad frame arguments"; return LVM_ERR_INVALID; }
     for (int k = 0; k < n_frames; ++k) { produced[k] = 0; if ((!js && !frames[k]) || (!mj && !canvases[k])) { c->err = "null frame pointer"; return LVM_ERR_INVALID; } }
     LVM_HIP_TRY(c, hipSetDevice(c->device));
-    int rx, ry, rw, rh, ow, oh, och, pw, ph, cw, chh;
-    lvm::preprocess_geometry(*pp, w, h, channels, &rx, &ry, &rw, &rh, &ow, &oh, &och);
+    const ChainGeom g = chain_geometry(*pp, w, h, channels);
+    int pw, ph, cw, chh;
     if (split < LVM_SPLIT_NONE || split > LVM_SPLIT_TOP_BOTTOM) { c->err = "invalid split mode"; return LVM_ERR_INVALID; }
-    if (!lvm::compose_geometry(split, ow, oh, ow, oh, &pw, &ph, &cw, &chh) || cw <= 0 || chh <= 0) {
+    if (!lvm::compose_geometry(split, g.ow, g.oh, g.ow, g.oh, &pw, &ph, &cw, &chh) || cw <= 0 || chh <= 0) {
         c->err = "lvm_export_frames: empty canvas (Exporter::compose returns an empty Mat for this geometry)"; return LVM_ERR_INVALID;
     }
     if (!mj && canvas_stride < (ptrdiff_t)cw * 3) { c->err = "canvas stride too small"; return LVM_ERR_INVALID; }
-    const size_t roi_row = (size_t)rw * channels, roi_bytes = roi_row * rh;
-    const size_t out_row = (size_t)ow * och, out_bytes = out_row * oh;
     const size_t can_row = (size_t)cw * 3, can_bytes = can_row * chh;
-    auto reserve = [&](uint8_t*& ptr, size_t& cap, size_t need) -> int {
-        if (need <= cap) return LVM_OK;
-        if (ptr) (void)hipFree(ptr);
-        ptr = nullptr; cap = 0;
-        LVM_HIP_TRY(c, hipMalloc((void**)&ptr, need));
-        cap = need;
-        return LVM_OK;
-    };
     hipStream_t s = c->own_stream;
     LVM_HIP_TRY(c, hipStreamSynchronize(s));      // staging buffers may be replaced below
-    // the pane Exporter::compose labels "Original" is runChainOnce's tap: chain[0]'s output, i.e. the frame BEFORE GrayscaleProcessor
-    // (ChainBuilder.cpp:25).  With grayscale on a BGR source that is the cropped / decimated colour frame.
-    const bool gray_tap = och == 1 && channels == 3 && split != LVM_SPLIT_NONE;
-    const size_t tap_row = (size_t)ow * 3, tap_bytes = tap_row * oh;
+    // the pane Exporter::compose labels "Original" is runChainOnce's tap (ChainGeom::gray)
+    const bool gray_tap = g.gray && split != LVM_SPLIT_NONE;
     // where stage 1 leaves frame k: the cropped copy (host frames), or the ROI inside the decoded frame (JPEG frames)
     const size_t full_row = (size_t)w * channels, full_bytes = full_row * h;
-    const size_t src_row = js ? full_row : roi_row, src_fbytes = js ? full_bytes : roi_bytes;
-    int rc = reserve(c->d_pre_in, c->pre_in_cap, src_fbytes * n_frames); if (rc != LVM_OK) return rc;
-    const uint8_t* src_base = js ? c->d_pre_in + (size_t)ry * full_row + (size_t)rx * channels : c->d_pre_in;
-    rc = reserve(c->d_pre_out, c->pre_out_cap, out_bytes * n_frames); if (rc != LVM_OK) return rc;
-    rc = reserve(c->d_chain_out, c->chain_out_cap, out_bytes * n_frames); if (rc != LVM_OK) return rc;
-    rc = reserve(c->d_canvas, c->canvas_cap, can_bytes * n_frames); if (rc != LVM_OK) return rc;
-    if (gray_tap) { rc = reserve(c->d_pre_tap, c->pre_tap_cap, tap_bytes * n_frames); if (rc != LVM_OK) return rc; }
+    const size_t src_row = js ? full_row : g.roi_row, src_fbytes = js ? full_bytes : g.roi_bytes;
+    int rc = c->d_pre_in.reserve(c, src_fbytes * n_frames); if (rc != LVM_OK) return rc;
+    const uint8_t* src_base = js ? c->d_pre_in + (size_t)g.ry * full_row + (size_t)g.rx * channels : c->d_pre_in;
+    rc = c->d_pre_out.reserve(c, g.out_bytes * n_frames); if (rc != LVM_OK) return rc;
+    rc = c->d_chain_out.reserve(c, g.out_bytes * n_frames); if (rc != LVM_OK) return rc;
+    rc = c->d_canvas.reserve(c, can_bytes * n_frames); if (rc != LVM_OK) return rc;
+    if (gray_tap) { rc = c->d_pre_tap.reserve(c, g.tap_bytes * n_frames); if (rc != LVM_OK) return rc; }
     int chunk = mj ? 4 : 2;      // (JPEG frames: nothing large to download, the encoder's launches want more frames each)
-    if (const char* e = std::getenv(mj ? "LVM_EXPORT_MJPEG_CHUNK" : "LVM_EXPORT_CHUNK")) { const int v = std::atoi(e); if (v >= 1) chunk = v; }
+    lvm::env_switch(mj ? "LVM_EXPORT_MJPEG_CHUNK" : "LVM_EXPORT_CHUNK", chunk, [](int v) { return v >= 1; });
     const int nchunks = (n_frames + chunk - 1) / chunk;
 
     if (!c->up_stream) LVM_HIP_TRY(c, hipStreamCreateWithFlags(&c->up_stream, hipStreamNonBlocking));
@@ -660,12 +626,9 @@ static int export_frames_impl(lvm_ctx* c, const lvm_preprocess_params* pp, const
     if (mj) { rc = lvm::mjpeg_begin(c, cw, chh, mj->quality, chunk < n_frames ? chunk : n_frames, (size_t)n_frames, mj->capacity, c->down_stream); if (rc != LVM_OK) return rc; }
     auto drain = [&]() { (void)hipStreamSynchronize(c->up_stream); (void)hipStreamSynchronize(s); (void)hipStreamSynchronize(c->down_stream); if (mj) lvm::mjpeg_abort(c); };
 #define LVM_EXPORT_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { c->err = std::string(#expr) + ": " + hipGetErrorString(e_); drain(); return LVM_ERR_HIP; } } while (0)
-    const bool identity = ow == rw && oh == rh && och == channels;      // PreprocessProcessor.cpp:15, GrayscaleProcessor.cpp:8-9
-    const uint8_t* mag_base = identity ? src_base : c->d_pre_out;
-    const size_t mag_row = identity ? src_row : out_row, mag_fbytes = identity ? src_fbytes : out_bytes;
-    lvm_params mp = *p;
-    mp.preprocess_key = preprocess_key_of(*pp);
-    const int saved_depth = c->pipeline_depth;
+    const uint8_t* mag_base = g.identity ? src_base : c->d_pre_out;
+    const size_t mag_row = g.identity ? src_row : g.out_row, mag_fbytes = g.identity ? src_fbytes : g.out_bytes;
+    const lvm_params mp = chain_params(*p, *pp);
     if (js) {
         // JPEG frames: only the compressed bytes cross PCIe, and ALL frames of the call are decoded by one set of launches -- Huffman decoding
         // is serial inside a restart interval (a lane each), its time is a latency that does not grow with the number of frames
@@ -678,34 +641,30 @@ static int export_frames_impl(lvm_ctx* c, const lvm_preprocess_params* pp, const
         // stage 1 (up_stream): only the ROI rows cross PCIe (the crop is the pitch of the 2-D copy)
         if (!js) {
             for (int k = f0; k < f0 + nf; ++k)
-                LVM_EXPORT_TRY(hipMemcpy2DAsync(c->d_pre_in + (size_t)k * roi_bytes, roi_row, frames[k] + (size_t)ry * in_stride + (size_t)rx * channels,
-                                                (size_t)in_stride, roi_row, (size_t)rh, hipMemcpyHostToDevice, c->up_stream));
+                LVM_EXPORT_TRY(chain_upload(g, c->d_pre_in + (size_t)k * g.roi_bytes, frames[k], in_stride, c->up_stream));
         }
         LVM_EXPORT_TRY(hipEventRecord(c->ev_up[q], c->up_stream));
         // stage 2 (the context's stream): Preprocess + Grayscale, the magnifier as one temporal batch, compose
         LVM_EXPORT_TRY(hipStreamWaitEvent(s, c->ev_up[q], 0));
-        if (!identity) {
-            lvm_preprocess_params qp = *pp;
-            qp.roi_enabled = 0;                                          // already cropped by the copy
+        if (!g.identity) {
             for (int k = f0; k < f0 + nf; ++k) {                         // (stateless: a frame of the batch is one more "stream" of a 1-stream context)
-                rc = lvm::preprocess_device(c, qp, src_base + (size_t)k * src_fbytes, rw, rh, channels, (ptrdiff_t)src_row, (ptrdiff_t)src_fbytes,
-                                            c->d_pre_out + (size_t)k * out_bytes, (ptrdiff_t)out_row, (ptrdiff_t)out_bytes, s,
-                                            gray_tap ? c->d_pre_tap + (size_t)k * tap_bytes : nullptr, (ptrdiff_t)tap_row, (ptrdiff_t)tap_bytes);
+                rc = chain_preprocess(c, *pp, g, src_base + (size_t)k * src_fbytes, src_row, src_fbytes, c->d_pre_out + (size_t)k * g.out_bytes, s,
+                                      gray_tap ? c->d_pre_tap + (size_t)k * g.tap_bytes : nullptr, (ptrdiff_t)g.tap_row, (ptrdiff_t)g.tap_bytes);
                 if (rc != LVM_OK) { drain(); return rc; }
             }
         }
-        c->pipeline_depth = 0;                                           // (the synchronous surface completes its own frames)
-        rc = lvm_process_device_frames(c, &mp, nf, mag_base + (size_t)f0 * mag_fbytes, ow, oh, och, (ptrdiff_t)mag_row, (ptrdiff_t)mag_fbytes, (ptrdiff_t)mag_fbytes,
-                                       c->d_chain_out + (size_t)f0 * out_bytes, (ptrdiff_t)out_row, (ptrdiff_t)out_bytes, (ptrdiff_t)out_bytes, produced + f0, s);
-        c->pipeline_depth = saved_depth;
+        rc = lvm::at_depth0(c, [&] {
+            return lvm_process_device_frames(c, &mp, nf, mag_base + (size_t)f0 * mag_fbytes, g.ow, g.oh, g.och, (ptrdiff_t)mag_row, (ptrdiff_t)mag_fbytes, (ptrdiff_t)mag_fbytes,
+                                             c->d_chain_out + (size_t)f0 * g.out_bytes, (ptrdiff_t)g.out_row, (ptrdiff_t)g.out_bytes, (ptrdiff_t)g.out_bytes, produced + f0, s);
+        });
         if (rc != LVM_OK) { drain(); return rc; }
         for (int k = f0; k < f0 + nf; ++k) {
             const uint8_t* seen = mag_base + (size_t)k * mag_fbytes;                                // what the magnifier saw
             const bool pr = produced[k] != 0;
-            const uint8_t* proc = pr ? c->d_chain_out + (size_t)k * out_bytes : seen;               // MagnificationProcessor.cpp:61
-            const uint8_t* orig = gray_tap ? c->d_pre_tap + (size_t)k * tap_bytes : seen;           // ChainBuilder.cpp:25
-            rc = lvm::compose_device(c, split, orig, ow, oh, gray_tap ? 3 : och, (ptrdiff_t)(gray_tap ? tap_row : mag_row), (ptrdiff_t)(gray_tap ? tap_bytes : mag_fbytes),
-                                     proc, ow, oh, och, (ptrdiff_t)(pr ? out_row : mag_row), (ptrdiff_t)(pr ? out_bytes : mag_fbytes), c->d_canvas + (size_t)k * can_bytes,
+            const uint8_t* proc = pr ? c->d_chain_out + (size_t)k * g.out_bytes : seen;               // MagnificationProcessor.cpp:61
+            const uint8_t* orig = gray_tap ? c->d_pre_tap + (size_t)k * g.tap_bytes : seen;           // ChainBuilder.cpp:25
+            rc = lvm::compose_device(c, split, orig, g.ow, g.oh, gray_tap ? 3 : g.och, (ptrdiff_t)(gray_tap ? g.tap_row : mag_row), (ptrdiff_t)(gray_tap ? g.tap_bytes : mag_fbytes),
+                                     proc, g.ow, g.oh, g.och, (ptrdiff_t)(pr ? g.out_row : mag_row), (ptrdiff_t)(pr ? g.out_bytes : mag_fbytes), c->d_canvas + (size_t)k * can_bytes,
                                      (ptrdiff_t)can_row, (ptrdiff_t)can_bytes, s);
             if (rc != LVM_OK) { drain(); return rc; }
         }
@@ -846,27 +805,21 @@ int lvm_process(lvm_ctx* c, const lvm_params* p, const uint8_t* in, int w, int h
     if (!out || (channels != 1 && channels != 3) || in_stride < (ptrdiff_t)w * channels ||
         out_stride < (ptrdiff_t)w * channels) { c->err = "bad frame arguments"; return LVM_ERR_INVALID; }
     const size_t row = (size_t)w * channels, bytes = row * h;
-    static const bool zero_copy = [] { const char* e = std::getenv("LVM_ZERO_COPY"); return !(e && std::atoi(e) == 0); }();
+    static const bool zero_copy = [] { bool on = true; lvm::env_switch("LVM_ZERO_COPY", on); return on; }();
     const bool one_reader = channels == 3 && !c->lab_analytic && (p->mode == LVM_MODE_LAPLACE || p->mode == LVM_MODE_PHASE);
     const uint8_t* in_alias = (zero_copy && one_reader) ? pinned_alias(in) : nullptr;
     uint8_t* out_alias = zero_copy ? pinned_alias(out) : nullptr;
-    if (bytes > c->stage_cap && (!in_alias || !out_alias)) {
+    if ((bytes > c->d_in.cap || bytes > c->d_out.cap) && (!in_alias || !out_alias)) {
         lvm::sync_streams(c);
-        if (c->d_in) (void)hipFree(c->d_in);
-        if (c->d_out) (void)hipFree(c->d_out);
-        c->d_in = c->d_out = nullptr; c->stage_cap = 0;
-        LVM_HIP_TRY(c, hipMalloc((void**)&c->d_in, bytes));
-        LVM_HIP_TRY(c, hipMalloc((void**)&c->d_out, bytes));
-        c->stage_cap = bytes;
+        int rc = c->d_in.reserve(c, bytes);
+        if (rc == LVM_OK) rc = c->d_out.reserve(c, bytes);
+        if (rc != LVM_OK) return rc;
     }
     hipStream_t s = c->own_stream;
     if (!in_alias) LVM_HIP_TRY(c, hipMemcpy2DAsync(c->d_in, row, in, (size_t)in_stride, row, (size_t)h, hipMemcpyHostToDevice, s));
-    lvm::FrameIO io{in_alias ? in_alias : c->d_in, in_alias ? in_stride : (ptrdiff_t)row, in_alias ? in_stride * h : (ptrdiff_t)bytes,
-                    out_alias ? out_alias : c->d_out, out_alias ? out_stride : (ptrdiff_t)row, out_alias ? out_stride * h : (ptrdiff_t)bytes, w, h, channels};
-    const int saved_depth = c->pipeline_depth;
-    c->pipeline_depth = 0;                       // the synchronous surface completes its own frame
-    const int rc = lvm::process_device(c, p, io, s, produced);
-    c->pipeline_depth = saved_depth;
+    lvm::FrameIO io{in_alias ? in_alias : c->d_in.p, in_alias ? in_stride : (ptrdiff_t)row, in_alias ? in_stride * h : (ptrdiff_t)bytes,
+                    out_alias ? out_alias : c->d_out.p, out_alias ? out_stride : (ptrdiff_t)row, out_alias ? out_stride * h : (ptrdiff_t)bytes, w, h, channels};
+    const int rc = lvm::at_depth0(c, [&] { return lvm::process_device(c, p, io, s, produced); });
     if (rc != LVM_OK) { (void)hipStreamSynchronize(s); return rc; }
     if (*produced && !out_alias)
         LVM_HIP_TRY(c, hipMemcpy2DAsync(out, (size_t)out_stride, c->d_out, row, row, (size_t)h, hipMemcpyDeviceToHost, s));
@@ -946,9 +899,9 @@ int lvm_set_lab_lut(lvm_ctx* c, const int16_t* src) {
 
 int lvm_debug_read_float(lvm_ctx* c, float* dst, size_t count) {
     if (!c || !dst) return LVM_ERR_INVALID;
-    if (!c->d_float || count > c->float_count) { c->err = "no float frame kept"; return LVM_ERR_INVALID; }
+    if (!c->d_float.p || count > c->float_count) { c->err = "no float frame kept"; return LVM_ERR_INVALID; }
     lvm::sync_streams(c);
-    LVM_HIP_TRY(c, hipMemcpy(dst, c->d_float, count * sizeof(float), hipMemcpyDeviceToHost));
+    LVM_HIP_TRY(c, hipMemcpy(dst, c->d_float.p, count * sizeof(float), hipMemcpyDeviceToHost));
     return LVM_OK;
 }
 
@@ -992,7 +945,7 @@ int lvm_set_pipeline(lvm_ctx* c, int depth) {
     if (!c || depth < 0 || depth > 1) return LVM_ERR_INVALID;
     if (depth != c->pipeline_depth) {
         lvm::sync_streams(c);
-        if (c->t_mode == LVM_MODE_LAPLACE) (void)lvm::laplace_flush(c, c->own_stream);
+        if (c->state) (void)c->state->flush(c, c->own_stream);
         lvm::sync_streams(c);
             c->pipeline_depth = depth;
     }
@@ -1003,8 +956,7 @@ int lvm_flush(lvm_ctx* c, void* hip_stream) {
     if (!c) return LVM_ERR_INVALID;
     LVM_HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
-    if (c->t_mode == LVM_MODE_LAPLACE) return lvm::laplace_flush(c, s);
-    return LVM_OK;
+    return c->state ? c->state->flush(c, s) : LVM_OK;
 }
 
 // compulsory traffic only -- every input byte read once, every output byte

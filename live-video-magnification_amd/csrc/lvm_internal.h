@@ -11,6 +11,7 @@
 #include <cstdint>
 #include <cstring>
 #include <cstdio>
+#include <cstdlib>
 #include <string>
 #include <utility>
 #include <vector>
@@ -413,18 +414,54 @@ struct FrameIO {
     int w, h, channels;
 };
 
+// The per-mode state (laplace.hip / riesz.hip / color.hip) and the interface lvm_api.hip drives it through.  A state exists only for the tracked
+// structural key (StructKey below): it is created lazily by <mode>_create on the first frame of a key and dropped when the key changes.
 struct ModeState {
     virtual ~ModeState() {}
+    // one frame of every stream; *produced follows the reference's passthrough rules
+    virtual int process(Ctx* c, const lvm_params& p, const FrameIO& io, hipStream_t s, int* produced) = 0;
+    // how many of the `left` frames the next process_frames call may take with these parameters; 0 = go frame by frame
+    virtual int batch_frames(const Ctx* c, const lvm_params& p, const FrameIO& io, int left) const = 0;
+    // temporal batch: nt consecutive frames laid out [frame][stream], every one of them produced
+    virtual int process_frames(Ctx* c, const lvm_params& p, const FrameIO& io, int nt, hipStream_t s) = 0;
+    // pipelined schedules: emit the output a previous call still owes
+    virtual int flush(Ctx*, hipStream_t) { return LVM_OK; }
 };
+
+// Owning, growable device buffer.  Growth is exact-size and does not keep the contents; a caller whose queued work may still use the old
+// allocation synchronises before it calls reserve.
+struct DevBuf {
+    uint8_t* p = nullptr; size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    int reserve(Ctx* c, size_t bytes);
+    template <class T> T* as() const { return reinterpret_cast<T*>(p); }
+    operator uint8_t*() const { return p; }
+};
+
+// What the reference's StructuralTracker compares (MagnifyCore.hpp:45-80), with the level count already clamped
+// (MagnificationProcessor.cpp:32-34).  levels == 0: the frame is too small for a pyramid and passes through.
+int max_levels(int w, int h);
+struct StructKey {
+    int mode = LVM_MODE_NONE, levels = -1, w = 0, h = 0, channels = -1; uint64_t pre = 0;
+    bool operator==(const StructKey& o) const { return mode == o.mode && levels == o.levels && w == o.w && h == o.h && channels == o.channels && pre == o.pre; }
+    bool operator!=(const StructKey& o) const { return !(*this == o); }
+};
+inline StructKey struct_key(const lvm_params& p, int w, int h, int channels) {
+    const int maxL = max_levels(w, h);
+    int levels = maxL < 1 ? 0 : (p.levels < 1 ? 1 : (p.levels > maxL ? maxL : p.levels));
+    if (levels > kMaxLevels) levels = kMaxLevels;
+    return StructKey{p.mode, levels, w, h, channels, p.preprocess_key};
+}
 
 struct Ctx {
     int device = 0;
     int nstreams = 1;
     hipStream_t own_stream = nullptr;
     std::string err;
-    // StructuralTracker (reference: MagnifyCore.hpp:45-80)
-    int t_mode = LVM_MODE_NONE, t_levels = -1, t_channels = -1, t_w = 0, t_h = 0;
-    uint64_t t_pre = 0;
+    StructKey tracked;                // StructuralTracker (reference: MagnifyCore.hpp:45-80)
     // constant tables
     float* d_gamma_u8 = nullptr;
     float* d_invgamma = nullptr;
@@ -439,11 +476,10 @@ struct Ctx {
     // per-mode state (allocated for the tracked geometry)
     ModeState* state = nullptr;
     // host-path staging
-    uint8_t *d_in = nullptr, *d_out = nullptr;
-    size_t stage_cap = 0;
+    DevBuf d_in, d_out;
     // instrumentation
     bool keep_float = false;
-    float* d_float = nullptr; size_t float_cap = 0; size_t float_count = 0;
+    DevBuf d_float; size_t float_count = 0;
     bool profiling = false;
     std::string prof_only; bool prof_skip = false;   // lvm_profile_only: bracket launches of this report name only
     std::vector<ProfEvent> prof_events;
@@ -462,9 +498,9 @@ struct Ctx {
     std::vector<int16_t> lab_lut_compact;   // the same table, [r][q][p][3] (lvm_get_lab_lut)
     // preprocess stage (preprocess.hip): area tables of the current geometry, staging of the host chain
     void* pre_tables = nullptr;
-    uint8_t *d_pre_in = nullptr, *d_pre_out = nullptr, *d_chain_out = nullptr; size_t pre_in_cap = 0, pre_out_cap = 0, chain_out_cap = 0;
-    uint8_t* d_canvas = nullptr; size_t canvas_cap = 0;     // lvm_export_frames: the composed canvases of a batch
-    uint8_t* d_pre_tap = nullptr; size_t pre_tap_cap = 0;   // the colour frames in front of GrayscaleProcessor (runChainOnce's `original`)
+    DevBuf d_pre_in, d_pre_out, d_chain_out;
+    DevBuf d_canvas;      // lvm_export_frames: the composed canvases of a batch
+    DevBuf d_pre_tap;     // the colour frames in front of GrayscaleProcessor (runChainOnce's `original`)
     // lvm_export_frames' three-stage pipeline: uploads, kernels and downloads of consecutive sub-batches on their own queues
     hipStream_t up_stream = nullptr, down_stream = nullptr;
     std::vector<hipEvent_t> ev_up, ev_done;
@@ -493,6 +529,63 @@ void prof_end(Ctx* c, hipStream_t s);
             return LVM_ERR_HIP;                                                           \
         }                                                                                 \
     } while (0)
+
+// the one place a device buffer is replaced: free, then allocate exactly `count` elements (contents are not kept)
+template <class T>
+int dev_realloc(Ctx* c, T*& p, size_t count) {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    LVM_HIP_TRY(c, hipMalloc((void**)&p, count * sizeof(T)));
+    return LVM_OK;
+}
+inline int DevBuf::reserve(Ctx* c, size_t bytes) {
+    if (bytes <= cap) return LVM_OK;
+    cap = 0;
+    const int rc = dev_realloc(c, p, bytes);
+    if (rc == LVM_OK) cap = bytes;
+    return rc;
+}
+
+// Hands out the 64-float-padded planes of an arena; with a null base it only counts.  Every arena's plane list is ONE layout function that
+// arena_alloc runs twice: once to size the allocation, once to carve it.
+struct ArenaCursor {
+    float* base; size_t used = 0;
+    explicit ArenaCursor(float* b) : base(b) {}
+    template <class T = float> T* take(size_t nfloats) {
+        T* q = base ? reinterpret_cast<T*>(base + used) : nullptr;
+        used += (nfloats + 63) & ~(size_t)63;
+        return q;
+    }
+};
+// `extra` floats behind the planes; an empty layout still gets 64 floats
+template <class Layout>
+int arena_alloc(Ctx* c, float** arena, size_t extra, const char* oom, Layout&& layout) {
+    ArenaCursor count(nullptr);
+    layout(count);
+    const size_t total = count.used + extra ? count.used + extra : 64;
+    if (hipMalloc((void**)arena, total * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); *arena = nullptr; c->err = oom; return LVM_ERR_OOM; }
+    ArenaCursor carve(*arena);
+    layout(carve);
+    return LVM_OK;
+}
+
+// The LVM_* environment switches: `v` keeps its default unless the variable is set (and, with `ok`, its value accepted).  Numbers are
+// parsed by atoi / atol, a bool is "non-zero".  Returns whether v was assigned.
+inline bool env_switch(const char* name, bool& v) { const char* e = std::getenv(name); if (e) v = std::atoi(e) != 0; return e != nullptr; }
+inline bool env_switch(const char* name, int& v, bool (*ok)(int) = nullptr) {
+    const char* e = std::getenv(name);
+    if (!e) return false;
+    const int x = std::atoi(e);
+    if (ok && !ok(x)) return false;
+    v = x; return true;
+}
+inline bool env_switch(const char* name, long& v, bool (*ok)(long) = nullptr) {
+    const char* e = std::getenv(name);
+    if (!e) return false;
+    const long x = std::atol(e);
+    if (ok && !ok(x)) return false;
+    v = x; return true;
+}
 
 // Report name of a per-level launch ("lap_up_l1"); only built while profiling (the macro below evaluates its
 // name argument inside the profiling branch).
@@ -548,22 +641,13 @@ int compose_device(Ctx* c, int split, const uint8_t* d_orig, int ow, int oh, int
                    const uint8_t* d_proc, int pw, int ph, int pch, ptrdiff_t pstride, ptrdiff_t psstride, uint8_t* d_canvas,
                    ptrdiff_t cstride, ptrdiff_t csstride, hipStream_t s);
 
-constexpr int kColorBatchMax = 32;    // frames of one colour-mode temporal batch (spare slots of the window ring)
-
-// mode entry points (laplace.hip / riesz.hip / color.hip).  Return LVM_OK or an error;
-// *produced follows the reference's passthrough rules.
-int laplace_flush(Ctx* c, hipStream_t s);
-int laplace_process_frames(Ctx* c, const lvm_params& p, const FrameIO& io, int nt, hipStream_t s);
-bool laplace_can_batch(const Ctx* c);
-int riesz_process_frames(Ctx* c, const lvm_params& p, const FrameIO& io, int nt, hipStream_t s);
+// The modes (laplace.hip / riesz.hip / color.hip): create the state of the tracked key and install it as c->state -- before its buffers are
+// allocated, so that a failed creation is dropped by fail_state.  riesz_create leaves c->state null for gray frames (MagnifyCore.hpp:212).
+int laplace_create(Ctx* c, int levels, const FrameIO& io, hipStream_t s);
+int riesz_create(Ctx* c, int levels, const FrameIO& io, hipStream_t s);
+int color_create(Ctx* c, int levels, const FrameIO& io, hipStream_t s);
 int riesz_tile_residual(Ctx* c, float* d_dst, int* rw, int* rh, hipStream_t s);
 int riesz_tile_finish(Ctx* c, const lvm_params& p, const FrameIO& io, const float* d_residual, hipStream_t s);
-bool riesz_can_batch(const Ctx* c, const lvm_params& p);
-int color_process_frames(Ctx* c, const lvm_params& p, const FrameIO& io, int nt, hipStream_t s);
-bool color_can_batch(const Ctx* c, const lvm_params& p, int nt);
-int laplace_process(Ctx* c, const lvm_params& p, int levels, const FrameIO& io, hipStream_t s, int* produced);
-int riesz_process(Ctx* c, const lvm_params& p, int levels, const FrameIO& io, hipStream_t s, int* produced);
-int color_process(Ctx* c, const lvm_params& p, int levels, const FrameIO& io, hipStream_t s, int* produced);
 
 // host tables (lab_tables.cpp)
 void build_lab_tables(float gamma_u8[256], float invgamma[4096], float fwd[9], float inv[9]);
@@ -576,7 +660,6 @@ void lab_lut_device_tables(const int16_t* compact, std::vector<uint32_t>& ab, st
 bool lab_lut_fine_index_ok();
 int upload_lab_lut(Ctx* c);
 void butterworth2(double Wn, double a[3], double b[3]);
-int max_levels(int w, int h);
 int optimal_buffer_size(int fps);
 
 }  // namespace lvm

@@ -71,7 +71,7 @@ struct MjState {
     uint32_t *d_ibits = nullptr, *d_isize = nullptr, *d_blk = nullptr;
     unsigned long long *d_ioff = nullptr, *d_foff = nullptr, *d_run = nullptr;     // d_run[0] running byte count, d_run[1] overflow flag
     unsigned long long* d_fsz = nullptr;                                            // per frame of a call: its size, then its start
-    uint8_t* d_jpeg = nullptr; size_t jpeg_cap = 0;
+    DevBuf d_jpeg;
     size_t foff_cap = 0;
     // incremental download: a page-locked mirror of d_foff, one event per encode call, the copy queue, what has been queued so far
     unsigned long long* h_foff = nullptr;
@@ -514,14 +514,6 @@ __global__ __launch_bounds__(256) void k_mj_write(const uint32_t* __restrict__ r
     }
 }
 
-template <class T>
-int mj_reserve(Ctx* c, T*& p, size_t count) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    LVM_HIP_TRY(c, hipMalloc((void**)&p, count * sizeof(T)));
-    return LVM_OK;
-}
-
 }  // namespace
 
 size_t mjpeg_bound(int w, int h) {
@@ -538,7 +530,7 @@ void mjpeg_set_restart(Ctx* c, int mcus) {
 void mjpeg_release(Ctx* c) {
     MjState* st = static_cast<MjState*>(c->mjpeg);
     if (!st) return;
-    void* ptrs[] = {st->d_tab, st->d_header, st->d_coef, st->d_raw, st->d_blk, st->d_fsz, st->d_ibits, st->d_isize, st->d_ioff, st->d_foff, st->d_run, st->d_jpeg};
+    void* ptrs[] = {st->d_tab, st->d_header, st->d_coef, st->d_raw, st->d_blk, st->d_fsz, st->d_ibits, st->d_isize, st->d_ioff, st->d_foff, st->d_run};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (st->h_foff) (void)hipHostFree(st->h_foff);
     for (hipEvent_t e : st->ev) (void)hipEventDestroy(e);
@@ -562,9 +554,9 @@ int mjpeg_begin(Ctx* c, int w, int h, int quality, int max_frames_per_call, size
     if ((mw * mh + ri - 1) / ri > 65535) ri = (mw * mh + 65534) / 65535;
     const int nintf = (mw * mh + ri - 1) / ri;
     int rc;
-    if (!st->d_tab) { rc = mj_reserve(c, st->d_tab, 1); if (rc != LVM_OK) return rc; }
-    if (!st->d_header) { rc = mj_reserve(c, st->d_header, (size_t)MJ_MAX_HEADER); if (rc != LVM_OK) return rc; }
-    if (!st->d_run) { rc = mj_reserve(c, st->d_run, 2); if (rc != LVM_OK) return rc; }
+    if (!st->d_tab) { rc = dev_realloc(c, st->d_tab, 1); if (rc != LVM_OK) return rc; }
+    if (!st->d_header) { rc = dev_realloc(c, st->d_header, (size_t)MJ_MAX_HEADER); if (rc != LVM_OK) return rc; }
+    if (!st->d_run) { rc = dev_realloc(c, st->d_run, 2); if (rc != LVM_OK) return rc; }
     if (st->quality != quality || st->w != w || st->h != h || st->ri != ri) {
         LVM_HIP_TRY(c, hipStreamSynchronize(s));                   // (earlier launches may still read the tables)
         MjTables t;
@@ -595,29 +587,27 @@ int mjpeg_begin(Ctx* c, int w, int h, int quality, int max_frames_per_call, size
         LVM_HIP_TRY(c, hipStreamSynchronize(s));
         const size_t nint = (size_t)nintf * max_frames_per_call, nmcu = (size_t)mh * mw * max_frames_per_call;
         st->frames_cap = 0;
-        if ((rc = mj_reserve(c, st->d_coef, nmcu * 384)) != LVM_OK) return rc;
-        if ((rc = mj_reserve(c, st->d_raw, nmcu * 6 * MJ_BLOCK_WORDS)) != LVM_OK) return rc;
-        if ((rc = mj_reserve(c, st->d_blk, nmcu * 6)) != LVM_OK) return rc;
-        if ((rc = mj_reserve(c, st->d_ibits, nint)) != LVM_OK) return rc;
-        if ((rc = mj_reserve(c, st->d_isize, nint)) != LVM_OK) return rc;
-        if ((rc = mj_reserve(c, st->d_ioff, nint)) != LVM_OK) return rc;
-        if ((rc = mj_reserve(c, st->d_fsz, (size_t)max_frames_per_call * 2)) != LVM_OK) return rc;
+        if ((rc = dev_realloc(c, st->d_coef, nmcu * 384)) != LVM_OK) return rc;
+        if ((rc = dev_realloc(c, st->d_raw, nmcu * 6 * MJ_BLOCK_WORDS)) != LVM_OK) return rc;
+        if ((rc = dev_realloc(c, st->d_blk, nmcu * 6)) != LVM_OK) return rc;
+        if ((rc = dev_realloc(c, st->d_ibits, nint)) != LVM_OK) return rc;
+        if ((rc = dev_realloc(c, st->d_isize, nint)) != LVM_OK) return rc;
+        if ((rc = dev_realloc(c, st->d_ioff, nint)) != LVM_OK) return rc;
+        if ((rc = dev_realloc(c, st->d_fsz, (size_t)max_frames_per_call * 2)) != LVM_OK) return rc;
         st->frames_cap = max_frames_per_call;
     }
     if (st->foff_cap < total_frames + 1) {
         LVM_HIP_TRY(c, hipStreamSynchronize(s));
         st->foff_cap = 0;
-        if ((rc = mj_reserve(c, st->d_foff, total_frames + 1)) != LVM_OK) return rc;
+        if ((rc = dev_realloc(c, st->d_foff, total_frames + 1)) != LVM_OK) return rc;
         if (st->h_foff) (void)hipHostFree(st->h_foff);
         st->h_foff = nullptr;
         LVM_HIP_TRY(c, hipHostMalloc((void**)&st->h_foff, (total_frames + 1) * sizeof(unsigned long long), 0));
         st->foff_cap = total_frames + 1;
     }
-    if (st->jpeg_cap < capacity) {
+    if (st->d_jpeg.cap < capacity) {
         LVM_HIP_TRY(c, hipStreamSynchronize(s));
-        st->jpeg_cap = 0;
-        if ((rc = mj_reserve(c, st->d_jpeg, capacity)) != LVM_OK) return rc;
-        st->jpeg_cap = capacity;
+        if ((rc = st->d_jpeg.reserve(c, capacity)) != LVM_OK) return rc;
     }
     LVM_HIP_TRY(c, hipMemsetAsync(st->d_run, 0, 2 * sizeof(unsigned long long), s));
     if (!st->dl) LVM_HIP_TRY(c, hipStreamCreateWithFlags(&st->dl, hipStreamNonBlocking));
@@ -629,7 +619,7 @@ int mjpeg_begin(Ctx* c, int w, int h, int quality, int max_frames_per_call, size
 // first one in the offsets array.  Everything is enqueued on `s`.
 int mjpeg_encode_device(Ctx* c, const uint8_t* d_bgr, ptrdiff_t stride, ptrdiff_t fstride, int nframes, int frame0, size_t capacity, hipStream_t s) {
     MjState* st = static_cast<MjState*>(c->mjpeg);
-    if (!st || nframes < 1 || nframes > st->frames_cap || (size_t)(frame0 + nframes + 1) > st->foff_cap || capacity > st->jpeg_cap) { c->err = "lvm_mjpeg: encode without begin"; return LVM_ERR_INVALID; }
+    if (!st || nframes < 1 || nframes > st->frames_cap || (size_t)(frame0 + nframes + 1) > st->foff_cap || capacity > st->d_jpeg.cap) { c->err = "lvm_mjpeg: encode without begin"; return LVM_ERR_INVALID; }
     MjGeom g;
     g.w = st->w; g.h = st->h; g.mw = (st->w + 15) / 16; g.mh = (st->h + 15) / 16; g.stride = (long)stride; g.fstride = (long)fstride;
     g.ri = st->ri; g.nint = st->nint;
@@ -643,7 +633,7 @@ int mjpeg_encode_device(Ctx* c, const uint8_t* d_bgr, ptrdiff_t stride, ptrdiff_
     LVM_LAUNCH(c, "mj_offsets", k_mj_offsets, dim3(1), dim3(64), s, nframes, (const unsigned long long*)st->d_fsz, st->d_fsz + nframes, st->d_foff + frame0, st->d_run,
                (unsigned long long)capacity);
     LVM_LAUNCH(c, "mj_write", k_mj_write, dim3(g.nint, nframes), blk, s, (const uint32_t*)st->d_raw, g, (const uint32_t*)st->d_ibits, (const uint32_t*)st->d_isize,
-               (const unsigned long long*)st->d_ioff, (const unsigned long long*)(st->d_fsz + nframes), (const uint8_t*)st->d_header, st->header_bytes, st->d_jpeg);
+               (const unsigned long long*)st->d_ioff, (const unsigned long long*)(st->d_fsz + nframes), (const uint8_t*)st->d_header, st->header_bytes, st->d_jpeg.p);
     // where these frames ended up: to the page-locked mirror, then an event -- mjpeg_drain downloads finished frames while later calls run
     LVM_HIP_TRY(c, hipMemcpyAsync(st->h_foff + frame0, st->d_foff + frame0, (size_t)(nframes + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     const size_t k = st->calls.size();

@@ -53,20 +53,19 @@ struct MjdFrame {
 
 struct MjdState {
     int frames_cap = 0, w = 0, h = 0;
-    size_t bytes_cap = 0;
     MjdFrame* d_frames = nullptr;
-    uint8_t* d_bytes = nullptr;
+    DevBuf d_bytes;
     int16_t* d_coef = nullptr;
     uint32_t *d_ivstart = nullptr, *d_ivend = nullptr, *d_err = nullptr;
     int iv_cap = 0;
     int n = 0, max_iv = 1;               // the frames of the current begin .. finish sequence
     // self-synchronising path (frames without restart markers)
-    uint8_t* d_ubytes = nullptr; size_t ubytes_cap = 0;
+    DevBuf d_ubytes;
     uint32_t *d_ulen = nullptr, *d_before = nullptr, *d_changed = nullptr;
     unsigned long long* d_exit[2] = {nullptr, nullptr};
     int sub_cap = 0, par_frames_cap = 0, npar = 0;
     // LVM_MJPEG_DECODER_LIBJPEG: the Cb / Cr planes between its two launches ([frame][Cb, Cr][mh * 8][mw * 8])
-    uint8_t* d_chroma = nullptr; size_t chroma_cap = 0;
+    DevBuf d_chroma;
     int kind = 0;                        // the decoder kind of the current begin .. finish sequence
     std::vector<MjdFrame> frames;
     std::vector<uint32_t> foff;
@@ -800,20 +799,12 @@ __global__ __launch_bounds__(256) void k_mjd_pixels_libjpeg(const int16_t* __res
     }
 }
 
-template <class T>
-int mjd_reserve(Ctx* c, T*& p, size_t count) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    LVM_HIP_TRY(c, hipMalloc((void**)&p, count * sizeof(T)));
-    return LVM_OK;
-}
-
 }  // namespace
 
 void mjpeg_decode_release(Ctx* c) {
     MjdState* st = static_cast<MjdState*>(c->mjpeg_dec);
     if (!st) return;
-    void* ptrs[] = {st->d_frames, st->d_bytes, st->d_coef, st->d_ivstart, st->d_ivend, st->d_err, st->d_ubytes, st->d_ulen, st->d_before, st->d_changed, st->d_exit[0], st->d_exit[1], st->d_chroma};
+    void* ptrs[] = {st->d_frames, st->d_coef, st->d_ivstart, st->d_ivend, st->d_err, st->d_ulen, st->d_before, st->d_changed, st->d_exit[0], st->d_exit[1]};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     delete st;
     c->mjpeg_dec = nullptr;
@@ -839,7 +830,7 @@ int mjpeg_decode_begin(Ctx* c, const uint8_t* jpegs, const size_t* offsets, int 
         f.nintervals = f.restart ? (uint32_t)((nmcu + (int)f.restart - 1) / (int)f.restart) : 1u;
         if ((int)f.nintervals > max_iv) max_iv = (int)f.nintervals;
         // no restart markers: one lane would decode the whole frame -- the self-synchronising kernels take it (LVM_MJD_PARALLEL=0: never, =2: also tiny frames)
-        static const int par_mode = [] { const char* e = std::getenv("LVM_MJD_PARALLEL"); return e ? std::atoi(e) : 1; }();
+        static const int par_mode = [] { int v = 1; env_switch("LVM_MJD_PARALLEL", v); return v; }();
         f.par = (f.restart == 0 && par_mode != 0 && (f.data_len >= 2048u || par_mode == 2)) ? 1u : 0u;
         f.usub = (f.data_len * 8u + MJP_SUB_BITS - 1) / MJP_SUB_BITS + 1u;
         if (f.par) { ++npar; if ((int)f.usub > max_sub) max_sub = (int)f.usub; }
@@ -851,55 +842,49 @@ int mjpeg_decode_begin(Ctx* c, const uint8_t* jpegs, const size_t* offsets, int 
     if (st->frames_cap < n || st->w != w || st->h != h) {
         LVM_HIP_TRY(c, hipStreamSynchronize(s));
         st->frames_cap = 0;
-        if ((rc = mjd_reserve(c, st->d_frames, (size_t)n)) != LVM_OK) return rc;
-        if ((rc = mjd_reserve(c, st->d_coef, (size_t)n * nmcu * 384)) != LVM_OK) return rc;
-        if ((rc = mjd_reserve(c, st->d_err, (size_t)n * 2 + 2)) != LVM_OK) return rc;       // error flags, then the frame offsets (n + 1)
+        if ((rc = dev_realloc(c, st->d_frames, (size_t)n)) != LVM_OK) return rc;
+        if ((rc = dev_realloc(c, st->d_coef, (size_t)n * nmcu * 384)) != LVM_OK) return rc;
+        if ((rc = dev_realloc(c, st->d_err, (size_t)n * 2 + 2)) != LVM_OK) return rc;       // error flags, then the frame offsets (n + 1)
         st->frames_cap = n; st->w = w; st->h = h; st->iv_cap = 0;
     }
     if (st->iv_cap < max_iv) {
         LVM_HIP_TRY(c, hipStreamSynchronize(s));
         st->iv_cap = 0;
-        if ((rc = mjd_reserve(c, st->d_ivstart, (size_t)st->frames_cap * max_iv)) != LVM_OK) return rc;
-        if ((rc = mjd_reserve(c, st->d_ivend, (size_t)st->frames_cap * max_iv)) != LVM_OK) return rc;
+        if ((rc = dev_realloc(c, st->d_ivstart, (size_t)st->frames_cap * max_iv)) != LVM_OK) return rc;
+        if ((rc = dev_realloc(c, st->d_ivend, (size_t)st->frames_cap * max_iv)) != LVM_OK) return rc;
         st->iv_cap = max_iv;
     }
-    if (st->bytes_cap < nbytes + 32) {
+    if (st->d_bytes.cap < nbytes + 32) {
         LVM_HIP_TRY(c, hipStreamSynchronize(s));
-        st->bytes_cap = 0;
-        if ((rc = mjd_reserve(c, st->d_bytes, nbytes + 32)) != LVM_OK) return rc;      // (+ 32: the word readers look one or two words ahead)
-        st->bytes_cap = nbytes + 32;
+        if ((rc = st->d_bytes.reserve(c, nbytes + 32)) != LVM_OK) return rc;           // (+ 32: the word readers look one or two words ahead)
     }
     st->npar = npar;
     if (npar) {
-        if (st->ubytes_cap < nbytes + 64) {
+        if (st->d_ubytes.cap < nbytes + 64) {
             LVM_HIP_TRY(c, hipStreamSynchronize(s));
-            st->ubytes_cap = 0;
-            if ((rc = mjd_reserve(c, st->d_ubytes, nbytes + 64)) != LVM_OK) return rc;
-            st->ubytes_cap = nbytes + 64;
+            if ((rc = st->d_ubytes.reserve(c, nbytes + 64)) != LVM_OK) return rc;
         }
         if (st->par_frames_cap < n || st->sub_cap < max_sub) {
             LVM_HIP_TRY(c, hipStreamSynchronize(s));
             st->par_frames_cap = 0;
             const int cap = max_sub > st->sub_cap ? max_sub : st->sub_cap;
-            if ((rc = mjd_reserve(c, st->d_ulen, (size_t)n)) != LVM_OK) return rc;
-            if ((rc = mjd_reserve(c, st->d_before, (size_t)n * cap)) != LVM_OK) return rc;
-            if ((rc = mjd_reserve(c, st->d_exit[0], (size_t)n * cap)) != LVM_OK) return rc;
-            if ((rc = mjd_reserve(c, st->d_exit[1], (size_t)n * cap)) != LVM_OK) return rc;
-            if (!st->d_changed && (rc = mjd_reserve(c, st->d_changed, (size_t)1)) != LVM_OK) return rc;
+            if ((rc = dev_realloc(c, st->d_ulen, (size_t)n)) != LVM_OK) return rc;
+            if ((rc = dev_realloc(c, st->d_before, (size_t)n * cap)) != LVM_OK) return rc;
+            if ((rc = dev_realloc(c, st->d_exit[0], (size_t)n * cap)) != LVM_OK) return rc;
+            if ((rc = dev_realloc(c, st->d_exit[1], (size_t)n * cap)) != LVM_OK) return rc;
+            if (!st->d_changed && (rc = dev_realloc(c, st->d_changed, (size_t)1)) != LVM_OK) return rc;
             st->par_frames_cap = n; st->sub_cap = cap;
         }
     }
     st->kind = c->mjpeg_decoder;
     const size_t nchroma = (size_t)n * 2 * ((size_t)mh * 8) * ((size_t)mw * 8);
-    if (st->kind == LVM_MJPEG_DECODER_LIBJPEG && st->chroma_cap < nchroma) {
+    if (st->kind == LVM_MJPEG_DECODER_LIBJPEG && st->d_chroma.cap < nchroma) {
         LVM_HIP_TRY(c, hipStreamSynchronize(s));
-        st->chroma_cap = 0;
-        if ((rc = mjd_reserve(c, st->d_chroma, nchroma)) != LVM_OK) return rc;
-        st->chroma_cap = nchroma;
+        if ((rc = st->d_chroma.reserve(c, nchroma)) != LVM_OK) return rc;
     }
     st->n = n; st->max_iv = max_iv;
     st->foff = foff;                                             // (stays alive until the copy below has run)
-    LVM_HIP_TRY(c, hipMemcpyAsync(st->d_bytes, jpegs + offsets[0], nbytes, hipMemcpyHostToDevice, s));
+    LVM_HIP_TRY(c, hipMemcpyAsync(st->d_bytes.p, jpegs + offsets[0], nbytes, hipMemcpyHostToDevice, s));
     LVM_HIP_TRY(c, hipMemcpyAsync(st->d_frames, st->frames.data(), (size_t)n * sizeof(MjdFrame), hipMemcpyHostToDevice, s));
     LVM_HIP_TRY(c, hipMemsetAsync(st->d_err, 0, (size_t)n * sizeof(uint32_t), s));
     LVM_HIP_TRY(c, hipMemcpyAsync(st->d_err + n, st->foff.data(), ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
@@ -925,7 +910,7 @@ int mjpeg_decode_enqueue(Ctx* c, int f0, int nf, uint8_t* d_bgr, ptrdiff_t strid
         unsigned long long* ex[2] = {st->d_exit[0] + (size_t)f0 * st->sub_cap, st->d_exit[1] + (size_t)f0 * st->sub_cap};
         uint32_t* before = st->d_before + (size_t)f0 * st->sub_cap;
         const dim3 gsub((unsigned)((st->sub_cap + 63) / 64), (unsigned)nf);
-        LVM_LAUNCH(c, "mjp_unstuff", k_mjp_unstuff, dim3(nf), dim3(256), s, (const uint8_t*)st->d_bytes, fr, d_foff, st->d_ubytes, st->d_ulen + f0);
+        LVM_LAUNCH(c, "mjp_unstuff", k_mjp_unstuff, dim3(nf), dim3(256), s, (const uint8_t*)st->d_bytes, fr, d_foff, st->d_ubytes.p, st->d_ulen + f0);
         LVM_LAUNCH(c, "mjp_sync", k_mjp_sync, gsub, dim3(64), s, (const uint8_t*)st->d_ubytes, fr, d_foff, ulen, st->sub_cap, 1, (const unsigned long long*)ex[1], ex[0], st->d_changed);
         int cur = 0;                                               // ex[cur] holds the latest exits
         for (int it = 0; it <= st->sub_cap; ++it) {                // (every pass makes at least one more lane exact: sub_cap passes always suffice)

@@ -1542,6 +1542,9 @@ struct RieszState : ModeState {
         return inited && lo_freq == p.coLow && hi_freq == p.coHigh && !std::isnan(la[0]) && !std::isnan(ha[0]);
     }
     ~RieszState() override { if (arena) (void)hipFree(arena); if (tarena) (void)hipFree(tarena); }
+    int process(Ctx* c, const lvm_params& p, const FrameIO& io, hipStream_t s, int* produced) override;
+    int batch_frames(const Ctx*, const lvm_params& p, const FrameIO& io, int left) const override { return io.channels >= 3 && steady(p) ? left : 0; }
+    int process_frames(Ctx* c, const lvm_params& p, const FrameIO& io, int nt, hipStream_t s) override;
 };
 enum { F_BAND, F_P, F_R1, F_R2, F_PHC, F_PHS, F_LO0C, F_LO0S, F_LO1C, F_LO1S, F_HI0C, F_HI0S, F_HI1C, F_HI1S, F_AMP, F_TC, F_TS, F_BANDA, F_COUNT,
        F_R1C = F_COUNT, F_R2C, F_ALL };   // F_R1C / F_R2C: per-frame Riesz pair (aliases F_R1 / F_R2 in per-frame mode)
@@ -1555,21 +1558,14 @@ static int riesz_alloc(Ctx* c, RieszState* st, int w, int h, int levels) {
         const int lw = st->g[l - 1].w / 2 + (st->g[l - 1].w % 2), lh = st->g[l - 1].h / 2 + (st->g[l - 1].h % 2);
         st->g[l] = {lw, lh, (size_t)lw * lh};
     }
-    auto pad = [](size_t n) { return (n + 63) & ~(size_t)63; };
-    size_t total = 0;
-    for (int l = 0; l < levels; ++l) total += 2 * pad(st->g[l].n * NS);                 // oct, res
-    for (int l = 0; l < levels - 1; ++l) total += (size_t)F_COUNT * pad(st->g[l].n * NS);
-    total += pad(st->g[0].n * NS);                                                      // iab
-    if (hipMalloc((void**)&st->arena, (total ? total : 64) * sizeof(float)) != hipSuccess) {
-        st->arena = nullptr; c->err = "riesz: hipMalloc failed"; return LVM_ERR_OOM;
-    }
-    float* p = st->arena;
-    for (int l = 0; l < levels; ++l) { st->oct[l] = p; p += pad(st->g[l].n * NS); st->res[l] = p; p += pad(st->g[l].n * NS); }
-    for (int l = 0; l < levels - 1; ++l)
-        for (int k = 0; k < F_COUNT; ++k) { st->f[l][k] = p; p += pad(st->g[l].n * NS); }
-    for (int l = 0; l < levels - 1; ++l) { st->f[l][F_R1C] = st->f[l][F_R1]; st->f[l][F_R2C] = st->f[l][F_R2]; }
-    st->iab = reinterpret_cast<uint32_t*>(p); p += pad(st->g[0].n * NS);
-    return LVM_OK;
+    return arena_alloc(c, &st->arena, 0, "riesz: hipMalloc failed", [&](ArenaCursor& a) {
+        for (int l = 0; l < levels; ++l) { st->oct[l] = a.take(st->g[l].n * NS); st->res[l] = a.take(st->g[l].n * NS); }
+        for (int l = 0; l < levels - 1; ++l) {
+            for (int k = 0; k < F_COUNT; ++k) st->f[l][k] = a.take(st->g[l].n * NS);
+            st->f[l][F_R1C] = st->f[l][F_R1]; st->f[l][F_R2C] = st->f[l][F_R2];
+        }
+        st->iab = a.take<uint32_t>(st->g[0].n * NS);
+    });
 }
 
 static void riesz_coeffs(double frq, double fps, double a[3], double b[3]) {   // TemporalFilter.cpp:324-327
@@ -1781,7 +1777,7 @@ static void rz_collapse_out(Ctx* c, RieszState* st, const lvm_params& p, const F
     // 5120: 441-446, 10240: 427-433, 20480: 441, one tile per workgroup 487.
     const int gcap = st->fin_groups > 0 ? st->fin_groups : (ntiles / 6 > 2048 ? ntiles / 6 : 2048);
     const dim3 grid(ntiles < gcap ? ntiles : gcap);
-    float* dbg = c->keep_float ? c->d_float : nullptr;
+    float* dbg = c->keep_float ? c->d_float.as<float>() : nullptr;
     const bool vec = w % 4 == 0 && io.in_stride % 4 == 0 && io.in_sstride % 4 == 0 && io.out_stride % 4 == 0 &&
                      io.out_sstride % 4 == 0 && ((uintptr_t)io.d_in % 4) == 0 && ((uintptr_t)io.d_out % 4) == 0;
     const int fl = lab_flavour(c);
@@ -1819,33 +1815,38 @@ static void rz_collapse_out(Ctx* c, RieszState* st, const lvm_params& p, const F
                    c->lab, tx, ty, NZ, dbg, (const float*)B.oct[0], (const uint32_t*)B.iab);
 }
 
-int riesz_process(Ctx* c, const lvm_params& p, int levels, const FrameIO& io, hipStream_t s, int* produced) {
+static void riesz_switches(RieszState* st) {
+    env_switch("LVM_RZ_BLUR4", st->blur4);
+    env_switch("LVM_RZ_BLUR_STRIPS", st->blur_strips);
+    env_switch("LVM_RZ_BLUR_STRIPS_MIN", st->blur_strips_min);
+    env_switch("LVM_RZ_BLUR_STRIP_ROWS", st->blur_strip_rows);
+    env_switch("LVM_RZ_SPLIT2", st->split2);
+    env_switch("LVM_RZ_SPLIT2_MIN", st->split2_min);
+    env_switch("LVM_RZ_PHASE4_MIN_FRAMES", st->phase4_min_frames);
+    env_switch("LVM_RZ_COMPACT", st->compact);
+    env_switch("LVM_RZ_PHASE4", st->phase4);
+    env_switch("LVM_RZ_FIN_GROUPS", st->fin_groups);
+    env_switch("LVM_RZ_SPLIT_STRIP", st->split_strip, [](int v) { return v >= 2 && v % 2 == 0; });
+    env_switch("LVM_RZ_SPLIT_ROWS", st->split_rows);
+    env_switch("LVM_RZ_COLLAPSE_STRIPS", st->collapse_strips);
+    env_switch("LVM_RZ_COLLAPSE_STRIPS_MIN", st->collapse_strips_min);
+    env_switch("LVM_RZ_COLLAPSE_STRIP", st->collapse_strip, [](int v) { return v >= 2 && v % 2 == 0; });
+    env_switch("LVM_RZ_SPLIT_ROWS_MIN", st->split_rows_min);
+}
+
+int riesz_create(Ctx* c, int levels, const FrameIO& io, hipStream_t s) {
+    if (io.channels < 3) return LVM_OK;                                          // MagnifyCore.hpp:212: gray frames pass through, nothing is allocated
+    RieszState* st = new RieszState();
+    riesz_switches(st);
+    c->state = st;
+    int rc = riesz_alloc(c, st, io.w, io.h, levels);
+    if (rc == LVM_OK && c->max_frames > 1) rc = riesz_reserve_frames(c, st, c->max_frames, s);
+    return rc;
+}
+
+int RieszState::process(Ctx* c, const lvm_params& p, const FrameIO& io, hipStream_t s, int* produced) {
+    RieszState* st = this;
     *produced = 0;
-    if (io.channels < 3) return LVM_OK;                                          // MagnifyCore.hpp:212
-    RieszState* st = static_cast<RieszState*>(c->state);
-    if (!st) {
-        st = new RieszState();
-        if (const char* e = std::getenv("LVM_RZ_BLUR4")) st->blur4 = std::atoi(e) != 0;
-        if (const char* e = std::getenv("LVM_RZ_BLUR_STRIPS")) st->blur_strips = std::atoi(e) != 0;
-        if (const char* e = std::getenv("LVM_RZ_BLUR_STRIPS_MIN")) st->blur_strips_min = std::atol(e);
-        if (const char* e = std::getenv("LVM_RZ_BLUR_STRIP_ROWS")) st->blur_strip_rows = std::atoi(e);
-        if (const char* e = std::getenv("LVM_RZ_SPLIT2")) st->split2 = std::atoi(e) != 0;
-        if (const char* e = std::getenv("LVM_RZ_SPLIT2_MIN")) st->split2_min = std::atol(e);
-        if (const char* e = std::getenv("LVM_RZ_PHASE4_MIN_FRAMES")) st->phase4_min_frames = std::atoi(e);
-        if (const char* e = std::getenv("LVM_RZ_COMPACT")) st->compact = std::atoi(e) != 0;
-        if (const char* e = std::getenv("LVM_RZ_PHASE4")) st->phase4 = std::atoi(e) != 0;
-        if (const char* e = std::getenv("LVM_RZ_FIN_GROUPS")) st->fin_groups = std::atoi(e);
-        if (const char* e = std::getenv("LVM_RZ_SPLIT_STRIP")) { const int v = std::atoi(e); if (v >= 2 && v % 2 == 0) st->split_strip = v; }
-        if (const char* e = std::getenv("LVM_RZ_SPLIT_ROWS")) st->split_rows = std::atoi(e) != 0;
-        if (const char* e = std::getenv("LVM_RZ_COLLAPSE_STRIPS")) st->collapse_strips = std::atoi(e) != 0;
-        if (const char* e = std::getenv("LVM_RZ_COLLAPSE_STRIPS_MIN")) st->collapse_strips_min = std::atol(e);
-        if (const char* e = std::getenv("LVM_RZ_COLLAPSE_STRIP")) { const int v = std::atoi(e); if (v >= 2 && v % 2 == 0) st->collapse_strip = v; }
-        if (const char* e = std::getenv("LVM_RZ_SPLIT_ROWS_MIN")) st->split_rows_min = std::atol(e);
-        c->state = st;
-        int rc = riesz_alloc(c, st, io.w, io.h, levels);
-        if (rc == LVM_OK && c->max_frames > 1) rc = riesz_reserve_frames(c, st, c->max_frames, s);
-        if (rc != LVM_OK) return rc;
-    }
     const RzBufs B{st->oct, st->res, st->f, 1, st->iab};
     rz_build(c, st, io, B, s);               // L plane + pyramid of the current frame (needed by every path below)
     // first frame ever, or degenerate coefficients: init and pass the frame through (:226-240)
@@ -1900,35 +1901,31 @@ static int riesz_reserve_frames(Ctx* c, RieszState* st, int nt, hipStream_t s) {
     sync_streams(c);
     if (st->tarena) (void)hipFree(st->tarena);
     st->tarena = nullptr; st->tcap = 0;
-    auto pad = [](size_t n) { return (n + 63) & ~(size_t)63; };
     static const int kPer[] = {F_BAND, F_AMP, F_TC, F_TS, F_BANDA, F_R1C, F_R2C};
-    size_t total = 64;
-    for (int l = 0; l < levels; ++l) total += 2 * pad(st->g[l].n * NS * nt);
-    // Levels whose amplify stage runs as strips for EVERY batch size of this context (rz_level_uses_strips already at one
-    // frame per launch: level 0 of a 1080p stream) never touch a per-frame copy of the Riesz pair -- rz_phase points those
-    // slots at the state planes and the strip kernel recomputes the pair -- so none is allocated (0.5 GB per 32 frames of
-    // 1080p at level 0 alone).
-    auto needs_pair = [&](int l) { return !rz_level_uses_strips(st, l, NS); };
-    for (int l = 0; l < levels - 1; ++l) total += (needs_pair(l) ? 7 : 5) * pad(st->g[l].n * NS * nt);
-    total += pad(st->g[0].n * NS * nt);
-    if (hipMalloc((void**)&st->tarena, total * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); st->tarena = nullptr; c->err = "riesz: hipMalloc (frames) failed"; return LVM_ERR_OOM; }
-    float* q = st->tarena;
-    for (int l = 0; l < levels; ++l) { st->oct_t[l] = q; q += pad(st->g[l].n * NS * nt); st->res_t[l] = q; q += pad(st->g[l].n * NS * nt); }
-    for (int l = 0; l < levels - 1; ++l) {
-        for (int k = 0; k < F_ALL_N; ++k) st->ft[l][k] = st->f[l][k];          // state planes are shared
-        for (int k : kPer) {
-            if ((k == F_R1C || k == F_R2C) && !needs_pair(l)) { st->ft[l][k] = st->f[l][k == F_R1C ? F_R1 : F_R2]; continue; }   // as riesz_alloc does for per-frame calls
-            st->ft[l][k] = q; q += pad(st->g[l].n * NS * nt);
+    const int rc = arena_alloc(c, &st->tarena, 64, "riesz: hipMalloc (frames) failed", [&](ArenaCursor& a) {
+        for (int l = 0; l < levels; ++l) { st->oct_t[l] = a.take(st->g[l].n * NS * nt); st->res_t[l] = a.take(st->g[l].n * NS * nt); }
+        for (int l = 0; l < levels - 1; ++l) {
+            // Levels whose amplify stage runs as strips for EVERY batch size of this context (rz_level_uses_strips already at one
+            // frame per launch: level 0 of a 1080p stream) never touch a per-frame copy of the Riesz pair -- rz_phase points those
+            // slots at the state planes and the strip kernel recomputes the pair -- so none is allocated (0.5 GB per 32 frames of
+            // 1080p at level 0 alone).
+            const bool needs_pair = !rz_level_uses_strips(st, l, NS);
+            for (int k = 0; k < F_ALL_N; ++k) st->ft[l][k] = st->f[l][k];          // state planes are shared
+            for (int k : kPer) {
+                if ((k == F_R1C || k == F_R2C) && !needs_pair) continue;           // (stays the alias of F_R1 / F_R2 that riesz_alloc set up)
+                st->ft[l][k] = a.take(st->g[l].n * NS * nt);
+            }
         }
-    }
-    st->iab_t = reinterpret_cast<uint32_t*>(q); q += pad(st->g[0].n * NS * nt);
+        st->iab_t = a.take<uint32_t>(st->g[0].n * NS * nt);
+    });
+    if (rc != LVM_OK) return rc;
     st->tcap = nt;
     return LVM_OK;
 }
 
-// Temporal batch (see laplace_process_frames): nt consecutive frames, steady state only.
-int riesz_process_frames(Ctx* c, const lvm_params& p, const FrameIO& io, int nt, hipStream_t s) {
-    RieszState* st = static_cast<RieszState*>(c->state);
+// Temporal batch (see LaplaceState::process_frames): nt consecutive frames, steady state only.
+int RieszState::process_frames(Ctx* c, const lvm_params& p, const FrameIO& io, int nt, hipStream_t s) {
+    RieszState* st = this;
     if (nt > st->tcap) { const int rc = riesz_reserve_frames(c, st, nt, s); if (rc != LVM_OK) return rc; }
     const RzBufs B{st->oct_t, st->res_t, st->ft, nt, st->iab_t};
     rz_build(c, st, io, B, s);
@@ -1936,11 +1933,6 @@ int riesz_process_frames(Ctx* c, const lvm_params& p, const FrameIO& io, int nt,
     rz_finish(c, st, p, io, B, s);
     LVM_HIP_TRY(c, hipGetLastError());
     return LVM_OK;
-}
-
-bool riesz_can_batch(const Ctx* c, const lvm_params& p) {
-    const RieszState* st = dynamic_cast<const RieszState*>(c->state);
-    return st && st->steady(p);
 }
 
 }  // namespace lvm

@@ -13,7 +13,7 @@ def _read(pattern):
 
 def test_every_switch_the_tests_set_is_read_by_the_library():
     csrc = "\n".join(_read("live-video-magnification_amd/csrc/*").values())
-    read = {n for line in csrc.splitlines() if "getenv(" in line for n in re.findall(r'"(LVM_[A-Z0-9_]+)"', line)}
+    read = {n for line in csrc.splitlines() if "env_switch(" in line for n in re.findall(r'"(LVM_[A-Z0-9_]+)"', line)}
     assert len(read) > 30, sorted(read)
     tests = _read("tests/*.py")
     used = {}
@@ -26,4 +26,4 @@ def test_every_switch_the_tests_set_is_read_by_the_library():
     used.pop("LVM_EMU_LIB", None)          # the emulation fixture's library path (tests/conftest.py), not a library switch
     assert "LVM_RZ_SPLIT_STRIP" in used and "LVM_COL_OUT_ROWS" in used, sorted(used)
     missing = {n: sorted(f) for n, f in used.items() if n not in read}
-    assert not missing, "switches set by tests but read by no getenv in csrc/: %s" % missing
+    assert not missing, "switches set by tests but read by no env_switch in csrc/: %s" % missing
