@@ -263,7 +263,8 @@ int  lvm_export_frames(lvm_ctx* ctx, const lvm_preprocess_params* pp, const lvm_
  *                              frames come down.  host/HipMjpegWriter.hpp wraps the frames into the AVI container.                       */
 /*   lvm_mjpeg_decode_device    the other direction (cv::VideoCapture::read on an AVI / Motion-JPEG file, source/FileSource.cpp:99): n_frames
  *                              JPEG frames in host memory (jpegs[offsets[i] .. offsets[i + 1])) -> BGR frames of w x h in DEVICE memory.
- *                              Baseline 4:2:0 in one scan, any tables; frames with restart intervals decode a lane per interval, frames
+ *                              Baseline 4:2:0 in one scan (4:2:2, 4:4:4 and one-component frames too where lvm_mjpeg_set_samplings allows them;
+ *                              all frames of a call share one sampling), any tables; frames with restart intervals decode a lane per interval, frames
  *                              without through self-synchronising lanes of 1024 bits (a call's time is mostly latency: pass many frames); anything else, a size other
  *                              than w x h or a malformed stream is LVM_ERR_INVALID (lvm_last_error says which frame and why).  Synchronous. */
 /*   lvm_export_mjpeg_frames    lvm_export_frames_mjpeg with JPEG frames IN as well (an AVI / Motion-JPEG source file): decode, chain, compose and
@@ -281,9 +282,21 @@ int  lvm_export_frames(lvm_ctx* ctx, const lvm_preprocess_params* pp, const lvm_
  *                                    cv::VideoCapture (or Pillow) hands out, for every stream an encoder makes from 8-bit samples; on others (damaged
  *                                    streams, where libjpeg builds differ among themselves) the arithmetic wraps in 32 bits.  FFmpeg's own mjpeg
  *                                    decoder (another IDCT, swscale chroma) is NOT what this kind restates.
- *                              Any other kind: LVM_ERR_INVALID.                                                                                 */
+ *                              Any other kind: LVM_ERR_INVALID.  Frames other than 4:2:0 (lvm_mjpeg_set_samplings) have libjpeg's arithmetic only:
+ *                              under LVM_MJPEG_DECODER_REPLICATE they are refused ("frame 0: 4:2:2 needs LVM_MJPEG_DECODER_LIBJPEG").  The frames of a
+ *                              call share frame 0's sampling, so this is decided at frame 0, before the later frames are parsed: it is reported
+ *                              even where a later frame is malformed.                                                                            */
 enum { LVM_MJPEG_DECODER_REPLICATE = 0, LVM_MJPEG_DECODER_LIBJPEG = 1 };
 int  lvm_mjpeg_set_decoder(lvm_ctx* ctx, int kind);
+/*   lvm_mjpeg_set_samplings    the samplings lvm_mjpeg_decode_device and lvm_export_mjpeg_frames accept from the next call on, a mask of
+ *                                LVM_MJPEG_SAMPLING_420 (Y 2x2, the default mask: every refusal and message stays what it was), LVM_MJPEG_SAMPLING_422
+ *                                (Y 2x1: UVC cameras, capture cards, FFmpeg's yuvj422p), LVM_MJPEG_SAMPLING_444 (FFmpeg's yuvj444p) and
+ *                                LVM_MJPEG_SAMPLING_GRAY (one component; its sampling factors are ignored, T.81 A.2.2; decoded to b = g = r).
+ *                              Cb and Cr are 1x1 in every one.  4:2:2, 4:4:4 and gray frames are byte-identical to libjpeg's (h2v1 fancy upsampling
+ *                              for 4:2:2) and need LVM_MJPEG_DECODER_LIBJPEG.  Still refused: 4:4:0, 4:1:1, four components, progressive,
+ *                              arithmetic-coded and 12-bit frames.  A mask of 0 or with other bits: LVM_ERR_INVALID, nothing changes.             */
+enum { LVM_MJPEG_SAMPLING_420 = 1, LVM_MJPEG_SAMPLING_422 = 2, LVM_MJPEG_SAMPLING_444 = 4, LVM_MJPEG_SAMPLING_GRAY = 8, LVM_MJPEG_SAMPLING_ALL = 15 };
+int  lvm_mjpeg_set_samplings(lvm_ctx* ctx, unsigned mask);
 size_t lvm_mjpeg_bound(int w, int h);
 int  lvm_mjpeg_set_restart_interval(lvm_ctx* ctx, int mcus);
 int  lvm_export_mjpeg_frames(lvm_ctx* ctx, const lvm_preprocess_params* pp, const lvm_params* p, int split, int n_frames, const uint8_t* jpegs,

@@ -71,6 +71,7 @@ class ProcessorConfig:
 
 LAB_LUT_ENTRIES = 33 * 33 * 33 * 3
 MJPEG_DECODER_REPLICATE, MJPEG_DECODER_LIBJPEG = 0, 1      # lvm_mjpeg_set_decoder (include/lvm_hip.h)
+MJPEG_SAMPLING_420, MJPEG_SAMPLING_422, MJPEG_SAMPLING_444, MJPEG_SAMPLING_GRAY, MJPEG_SAMPLING_ALL = 1, 2, 4, 8, 15      # lvm_mjpeg_set_samplings
 
 
 class LvmParams(C.Structure):
@@ -107,7 +108,7 @@ SYMBOLS = ["lvm_create", "lvm_destroy", "lvm_reset", "lvm_process", "lvm_process
            "lvm_profile_entry", "lvm_algorithmic_bytes", "lvm_export_geometry", "lvm_export_frames", "lvm_export_set_overlay", "lvm_overlay_device", "lvm_tile_riesz_stage1", "lvm_tile_riesz_planes", "lvm_tile_riesz_stage2",
            "lvm_preprocess_geometry", "lvm_preprocess_device", "lvm_chain_process", "lvm_chain_process_batch",
            "lvm_set_max_frames", "lvm_host_alloc", "lvm_host_free", "lvm_compose_geometry", "lvm_compose_device", "lvm_chain_process_batch_ex",
-           "lvm_chain_present", "lvm_mjpeg_bound", "lvm_mjpeg_encode_device", "lvm_export_frames_mjpeg", "lvm_mjpeg_decode_device", "lvm_export_mjpeg_frames", "lvm_mjpeg_set_restart_interval", "lvm_mjpeg_set_decoder"]
+           "lvm_chain_present", "lvm_mjpeg_bound", "lvm_mjpeg_encode_device", "lvm_export_frames_mjpeg", "lvm_mjpeg_decode_device", "lvm_export_mjpeg_frames", "lvm_mjpeg_set_restart_interval", "lvm_mjpeg_set_decoder", "lvm_mjpeg_set_samplings"]
 
 
 def bind(lib):
@@ -169,6 +170,7 @@ def bind(lib):
     lib.lvm_mjpeg_encode_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_ssize_t, C.c_ssize_t, C.c_int, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.lvm_mjpeg_set_restart_interval.argtypes = [vp, C.c_int]
     lib.lvm_mjpeg_set_decoder.argtypes = [vp, C.c_int]
+    lib.lvm_mjpeg_set_samplings.argtypes = [vp, C.c_uint]
     lib.lvm_mjpeg_decode_device.argtypes = [vp, vp, C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_int, vp, C.c_ssize_t, C.c_ssize_t]
     lib.lvm_export_mjpeg_frames.argtypes = [vp, C.POINTER(LvmPreprocessParams), C.POINTER(LvmParams), C.c_int, C.c_int, vp, C.POINTER(C.c_size_t), C.c_int, C.c_int,
                                             C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t), ip]
@@ -373,6 +375,11 @@ class Context:
         """lvm_mjpeg_set_decoder: MJPEG_DECODER_REPLICATE (0, the default: == oracle/mjpeg_oracle.py::decode_frame) or MJPEG_DECODER_LIBJPEG (1: byte-identical
         to libjpeg's islow IDCT + fancy upsampling) for the following mjpeg_decode_device / export_mjpeg_frames calls."""
         self._check(self.lib.lvm_mjpeg_set_decoder(self.h, int(kind)))
+
+    def mjpeg_set_samplings(self, mask):
+        """lvm_mjpeg_set_samplings: the samplings the following mjpeg_decode_device / export_mjpeg_frames calls accept, a mask of MJPEG_SAMPLING_420 (the
+        default), _422, _444 and _GRAY.  The frames of one call share one sampling; all but 4:2:0 need MJPEG_DECODER_LIBJPEG."""
+        self._check(self.lib.lvm_mjpeg_set_samplings(self.h, int(mask) & 0xFFFFFFFF))
 
     def mjpeg_decode_device(self, jpegs, w, h, d_ptr, stride=None, frame_stride=None):
         """lvm_mjpeg_decode_device: a list of JPEG frames (bytes) -> BGR frames in device memory at d_ptr."""

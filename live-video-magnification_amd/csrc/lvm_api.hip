@@ -747,6 +747,16 @@ int lvm_mjpeg_set_decoder(lvm_ctx* c, int kind) {
     return LVM_OK;
 }
 
+int lvm_mjpeg_set_samplings(lvm_ctx* c, unsigned mask) {
+    if (!c) return LVM_ERR_INVALID;
+    if (mask == 0 || (mask & ~(unsigned)LVM_MJPEG_SAMPLING_ALL)) {
+        c->err = "lvm_mjpeg_set_samplings: mask must be a non-empty combination of LVM_MJPEG_SAMPLING_420 (1), _422 (2), _444 (4), _GRAY (8)";
+        return LVM_ERR_INVALID;
+    }
+    c->mjpeg_samplings = mask;
+    return LVM_OK;
+}
+
 size_t lvm_mjpeg_bound(int w, int h) { return (w < 1 || h < 1) ? 0 : lvm::mjpeg_bound(w, h); }
 
 int lvm_mjpeg_encode_device(lvm_ctx* c, const uint8_t* d_bgr, int w, int h, ptrdiff_t stride, ptrdiff_t frame_stride, int n_frames, int quality,

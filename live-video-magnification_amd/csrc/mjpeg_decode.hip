@@ -2,7 +2,7 @@
 //
 // Replaces what `cv::VideoCapture::read(frame)` does for an AVI / Motion-JPEG file (reference: source/FileSource.cpp:99): the compressed
 // frames go up (a tenth of the pixels), the decoded BGR frames appear where the chain wants them -- in device memory.
-// Accepted: ITU-T T.81 baseline sequential, 8 bit, three components sampled 2x2 / 1x1 / 1x1 (YCbCr 4:2:0, JFIF) in one scan, any quantiser and
+// Accepted by default: ITU-T T.81 baseline sequential, 8 bit, three components sampled 2x2 / 1x1 / 1x1 (YCbCr 4:2:0, JFIF) in one scan, any quantiser and
 // Huffman tables (frames without DHT get the Annex K tables, as AVI MJPEG implies), with or without restart intervals -- what this
 // repository's encoder, libjpeg and FFmpeg's mjpeg encoder write.  Everything else is refused (LVM_ERR_INVALID), nothing is guessed.
 // The entropy layer is exact by the standard; the arithmetic behind it is the decoder's choice and is restated line by line by
@@ -21,6 +21,14 @@
 // sample into the neighbouring MCUs, so the pixel stage becomes two launches:
 //   k_mjd_chroma_islow    dequantise + islow IDCT of the Cb and Cr blocks -> two u8 planes per frame (scratch)        one wave per four MCUs
 //   k_mjd_pixels_libjpeg  dequantise + islow IDCT of the four Y blocks, h2v2 fancy upsampling, YCbCr -> BGR            one wave per 16 x 16 MCU
+// The other samplings of a baseline Motion-JPEG file are accepted where the context's mask allows them (lvm_mjpeg_set_samplings; the default mask is
+// 4:2:0 alone and leaves every refusal and message what it was): 4:2:2 (Y 2x1 -- UVC cameras, FFmpeg's yuvj422p), 4:4:4 and one component (b = g = r).
+// The MCU is a property of the CALL (MjdSamp: all frames of a call share one sampling) -- 16 x 16 / 6 blocks, 16 x 8 / 4, 8 x 8 / 3, 8 x 8 / 1 -- and
+// the entropy kernels walk its block list (nblk blocks, the first ny of them luminance); a one-component scan is not interleaved, its restart interval
+// counts blocks.  These samplings have libjpeg's arithmetic only (the oracle defines none for them):
+//   k_mjd_pixels_direct   4:4:4 and gray: islow IDCT of 3 x 8 (8) blocks, YCbCr -> BGR, no scratch planes                  one wave per eight 8 x 8 MCUs
+//   k_mjd_chroma_islow + k_mjd_pixels_h2v1   4:2:2: the Cb / Cr planes, then islow IDCT of the Y blocks + h2v1 fancy upsampling     one wave per four 16 x 8 MCUs
+// Still refused: progressive, arithmetic-coded, 12-bit, 4:4:0 / 4:1:1, four components.  tests/test_mjpeg_decode_samplings.py pins all of it against Pillow.
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -45,14 +53,28 @@ struct MjdFrame {
     uint32_t nintervals;                // expected
     uint32_t par;                       // 1: no restart markers -> decoded by the self-synchronising kernels (k_mjp_*), not a lane per interval
     uint32_t usub;                      // upper bound of its subsequences (from the stuffed length)
+    uint32_t samp;                      // LVM_MJPEG_SAMPLING_* of the frame header
     uint32_t tq[3], td[3], ta[3];
     uint16_t q[4][64];                  // quantisers in ZIGZAG order
     uint8_t zz[64];                     // zigzag index -> natural position
     MjdHuff huff[2][2];                 // [class: 0 DC, 1 AC][id 0, 1]
 };
 
+// The MCU of a sampling: its size in pixels and its block list -- ny luminance blocks, then (three components) one Cb and one Cr block.
+// A single-component scan is not interleaved (T.81 A.2.2): its "MCU" is one block, and the restart interval counts blocks.
+struct MjdSamp { int mcu_w, mcu_h, nblk, ny, ncomp; const char* name; };
+MjdSamp samp_of(uint32_t samp) {
+    switch (samp) {
+        case LVM_MJPEG_SAMPLING_422: return {16, 8, 4, 2, 3, "4:2:2"};
+        case LVM_MJPEG_SAMPLING_444: return {8, 8, 3, 1, 3, "4:4:4"};
+        case LVM_MJPEG_SAMPLING_GRAY: return {8, 8, 1, 1, 1, "gray"};
+        default: return {16, 16, 6, 4, 3, "4:2:0"};
+    }
+}
+
 struct MjdState {
     int frames_cap = 0, w = 0, h = 0;
+    uint32_t samp = LVM_MJPEG_SAMPLING_420;   // of the frames the buffers are sized for / of the current begin .. finish sequence
     MjdFrame* d_frames = nullptr;
     DevBuf d_bytes;
     int16_t* d_coef = nullptr;
@@ -97,11 +119,13 @@ bool build_decode_table(const uint8_t* bits, const uint8_t* vals, int nvals, Mjd
 }
 
 // SOI .. SOS of one frame (oracle: parse_header).  Returns nullptr, or what is unsupported / malformed.
-const char* parse_frame(const uint8_t* j, size_t n, int w, int h, MjdFrame& f) {
+const char* parse_frame(const uint8_t* j, size_t n, int w, int h, unsigned mask, MjdFrame& f) {
     if (n < 4 || j[0] != 0xFF || j[1] != 0xD8) return "no SOI";
     bool have_q[4] = {false, false, false, false}, have_h[2][2] = {{false, false}, {false, false}}, sof = false;
     uint32_t cid[3] = {0, 0, 0};
     f.restart = 0;
+    f.samp = LVM_MJPEG_SAMPLING_420;
+    int nc = 3;
     for (int z = 0; z < 64; ++z) f.zz[z] = kZigzag[z];
     size_t i = 2;
     for (;;) {
@@ -130,10 +154,20 @@ const char* parse_frame(const uint8_t* j, size_t n, int w, int h, MjdFrame& f) {
                 k += 17 + (size_t)nv;
             }
         } else if (m == 0xC0) {
-            if (pn < 15 || p[0] != 8 || p[5] != 3) return "not 8-bit three-component";
+            // one component (its sampling factors mean nothing, T.81 A.2.2) where the mask of lvm_mjpeg_set_samplings allows it
+            const bool gray = (mask & LVM_MJPEG_SAMPLING_GRAY) && pn >= 9 && p[0] == 8 && p[5] == 1;
+            if (!gray && (pn < 15 || p[0] != 8 || p[5] != 3)) return "not 8-bit three-component";
             if (be16(p + 1) != h || be16(p + 3) != w) return "frame size differs from the call's";
-            for (int c = 0; c < 3; ++c) { cid[c] = p[6 + 3 * c]; f.tq[c] = p[8 + 3 * c]; if (f.tq[c] > 3) return "quantiser id"; }
-            if (p[7] != 0x22 || p[10] != 0x11 || p[13] != 0x11) return "sampling is not 4:2:0";
+            nc = gray ? 1 : 3;
+            for (int c = 0; c < nc; ++c) { cid[c] = p[6 + 3 * c]; f.tq[c] = p[8 + 3 * c]; if (f.tq[c] > 3) return "quantiser id"; }
+            if (gray) f.samp = LVM_MJPEG_SAMPLING_GRAY;
+            else {
+                const bool c11 = p[10] == 0x11 && p[13] == 0x11;
+                f.samp = !c11 ? 0u : p[7] == 0x22 ? LVM_MJPEG_SAMPLING_420 : p[7] == 0x21 ? LVM_MJPEG_SAMPLING_422 : p[7] == 0x11 ? LVM_MJPEG_SAMPLING_444 : 0u;
+                if (mask == LVM_MJPEG_SAMPLING_420) { if (f.samp != LVM_MJPEG_SAMPLING_420) return "sampling is not 4:2:0"; }
+                else if (!f.samp) return "sampling is none of 4:2:0, 4:2:2, 4:4:4";
+                else if (!(mask & f.samp)) return "sampling is not in the mask of lvm_mjpeg_set_samplings";
+            }
             sof = true;
         } else if (m == 0xC1 || m == 0xC2 || m == 0xC3 || (m >= 0xC5 && m <= 0xCF && m != 0xC8 && m != 0xCC)) {
             return "not baseline sequential";
@@ -141,14 +175,14 @@ const char* parse_frame(const uint8_t* j, size_t n, int w, int h, MjdFrame& f) {
             if (pn < 2) return "DRI";
             f.restart = (uint32_t)be16(p);
         } else if (m == 0xDA) {
-            if (!sof || pn < 10 || p[0] != 3) return "scan without frame header / not three components";
-            for (int c = 0; c < 3; ++c) {
+            if (!sof || pn < 4 + 2 * (size_t)nc || p[0] != nc) return nc == 3 ? "scan without frame header / not three components" : "scan of a one-component frame with other components";
+            for (int c = 0; c < nc; ++c) {
                 if (p[1 + 2 * c] != cid[c]) return "scan component order";
                 f.td[c] = p[2 + 2 * c] >> 4; f.ta[c] = p[2 + 2 * c] & 15;
                 if (f.td[c] > 1 || f.ta[c] > 1) return "Huffman table id";
             }
-            if (p[7] != 0 || p[8] != 63 || p[9] != 0) return "not a full baseline scan";        // Ss, Se, Ah | Al
-            for (int c = 0; c < 3; ++c) if (!have_q[f.tq[c]]) return "quantiser table missing";
+            if (p[1 + 2 * nc] != 0 || p[2 + 2 * nc] != 63 || p[3 + 2 * nc] != 0) return "not a full baseline scan";        // Ss, Se, Ah | Al
+            for (int c = 0; c < nc; ++c) if (!have_q[f.tq[c]]) return "quantiser table missing";
             // frames of an AVI may leave the Huffman tables out: the Annex K tables are implied
             if (!have_h[0][0]) build_decode_table(kDcLumaBits, kDcVals, 12, f.huff[0][0]);
             if (!have_h[1][0]) build_decode_table(kAcLumaBits, kAcLumaVals, 162, f.huff[1][0]);
@@ -275,7 +309,7 @@ __device__ __forceinline__ int mjd_extend(uint32_t v, int s) { return (s == 0 ||
 // A lane per restart interval; the 64 lanes of a workgroup are consecutive intervals of ONE frame, whose look-up tables sit in LDS.
 __global__ __launch_bounds__(64) void k_mjd_huffman(const uint8_t* __restrict__ bytes, const MjdFrame* __restrict__ frames, const uint32_t* __restrict__ foff,
                                                     const uint32_t* __restrict__ ivstart, const uint32_t* __restrict__ ivend, int iv_cap, int nmcu,
-                                                    int16_t* __restrict__ coef, uint32_t* __restrict__ err) {
+                                                    int nblk, int ny, int16_t* __restrict__ coef, uint32_t* __restrict__ err) {
     __shared__ uint16_t s_lut[2][2][1 << MJD_LUT_BITS];
     const int f = blockIdx.y, tid = threadIdx.x;
     const MjdFrame& fr = frames[f];
@@ -292,9 +326,9 @@ __global__ __launch_bounds__(64) void k_mjd_huffman(const uint8_t* __restrict__ 
     int pred[3] = {0, 0, 0};
     bool bad = false;
     for (uint32_t m = m0; m < m1 && !bad; ++m) {
-        int16_t* out = coef + ((size_t)f * nmcu + m) * 384;
-        for (int bi = 0; bi < 6 && !bad; ++bi) {
-            const int comp = bi < 4 ? 0 : bi - 3;
+        int16_t* out = coef + ((size_t)f * nmcu + m) * (size_t)(nblk * 64);
+        for (int bi = 0; bi < nblk && !bad; ++bi) {
+            const int comp = bi < ny ? 0 : bi - ny + 1;
             const uint32_t td = fr.td[comp], ta = fr.ta[comp];
             int s = mjd_symbol(br, s_lut[0][td], fr.huff[0][td]);
             if (s < 0 || s > 11) { bad = true; break; }
@@ -325,7 +359,7 @@ __global__ __launch_bounds__(64) void k_mjd_huffman(const uint8_t* __restrict__ 
 //                   last left ITS subsequence, and publishes its own exit (position, state, blocks completed).  First pass: every lane
 //                   guesses (start of its subsequence, start of an MCU).  Repeated until no exit changes: lane 0's entry is exact, hence by
 //                   induction every lane's.  Code word boundaries are found again within a few symbols, the position inside the MCU (the four
-//                   luminance blocks share their tables) takes longer -- hence the look-back of the first pass (8 subsequences): 6 / 16 / 29 changing passes for 102 / 581 / 1 116 subsequences
+//                   luminance blocks of 4:2:0 share their tables; two do in 4:2:2, none in 4:4:4, gray has no position) takes longer -- hence the look-back of the first pass (8 subsequences): 6 / 16 / 29 changing passes for 102 / 581 / 1 116 subsequences
 //                   without it, 0 / 2 / 7 with it.
 //   k_mjp_scan      blocks completed before every lane (prefix sum)
 //   k_mjp_write     the same decoding once more from the exact entries, now storing coefficients (DC as differences)
@@ -364,8 +398,8 @@ __device__ __forceinline__ int mjp_symbol(MjpBits& br, const uint16_t* lut, cons
 }
 // One symbol in state (bi = block of the MCU, kk = next coefficient index; kk == 0: a DC code comes next).  Returns the zigzag index of the
 // coefficient it produced (`value`), -1 for a symbol without one, -2 for what the one-lane decoder calls an error.  `done` = the block ended.
-__device__ __forceinline__ int mjp_step(MjpBits& br, int& bi, int& kk, const MjdFrame& fr, const uint16_t (*s_lut)[2][1 << MJD_LUT_BITS], int& value, bool& done) {
-    const int comp = bi < 4 ? 0 : bi - 3;
+__device__ __forceinline__ int mjp_step(MjpBits& br, int& bi, int& kk, const MjdFrame& fr, const uint16_t (*s_lut)[2][1 << MJD_LUT_BITS], int nblk, int ny, int& value, bool& done) {
+    const int comp = bi < ny ? 0 : bi - ny + 1;
     int ci = -1;
     done = false;
     if (kk == 0) {
@@ -388,7 +422,7 @@ __device__ __forceinline__ int mjp_step(MjpBits& br, int& bi, int& kk, const Mjd
             ci = kk; ++kk;
         }
     }
-    if (kk >= 64) { kk = 0; bi = bi == 5 ? 0 : bi + 1; done = true; }
+    if (kk >= 64) { kk = 0; bi = bi == nblk - 1 ? 0 : bi + 1; done = true; }
     return ci;
 }
 
@@ -424,7 +458,7 @@ __global__ __launch_bounds__(256) void k_mjp_unstuff(const uint8_t* __restrict__
 __device__ __forceinline__ unsigned long long mjp_pack(uint32_t pos, int bi, int kk, uint32_t blocks) { return (unsigned long long)pos | ((unsigned long long)(bi * 64 + kk) << 32) | ((unsigned long long)blocks << 41); }
 
 __global__ __launch_bounds__(64) void k_mjp_sync(const uint8_t* __restrict__ ubytes, const MjdFrame* __restrict__ frames, const uint32_t* __restrict__ foff,
-                                                 const uint32_t* __restrict__ ulen, int sub_cap, int first, const unsigned long long* __restrict__ ein,
+                                                 const uint32_t* __restrict__ ulen, int sub_cap, int first, int nblk, int ny, const unsigned long long* __restrict__ ein,
                                                  unsigned long long* __restrict__ eout, uint32_t* __restrict__ changed) {
     __shared__ uint16_t s_lut[2][2][1 << MJD_LUT_BITS];
     const int f = blockIdx.y, tid = threadIdx.x;
@@ -449,13 +483,13 @@ __global__ __launch_bounds__(64) void k_mjp_sync(const uint8_t* __restrict__ uby
         const uint32_t own = i * MJP_SUB_BITS;
         while (br.pos < own) {
             int value; bool done;
-            if (mjp_step(br, bi, kk, fr, s_lut, value, done) == -2) br.skip(1);
+            if (mjp_step(br, bi, kk, fr, s_lut, nblk, ny, value, done) == -2) br.skip(1);
         }
     }
     uint32_t blocks = 0;
     while (br.pos < end) {
         int value; bool done;
-        if (mjp_step(br, bi, kk, fr, s_lut, value, done) == -2) { br.skip(1); continue; }     // (a wrong guess runs into impossible codes: move on)
+        if (mjp_step(br, bi, kk, fr, s_lut, nblk, ny, value, done) == -2) { br.skip(1); continue; }     // (a wrong guess runs into impossible codes: move on)
         blocks += done ? 1u : 0u;
     }
     const unsigned long long e = mjp_pack(br.pos, bi, kk, blocks);
@@ -501,7 +535,7 @@ __global__ __launch_bounds__(256) void k_mjp_scan(const MjdFrame* __restrict__ f
 
 __global__ __launch_bounds__(64) void k_mjp_write(const uint8_t* __restrict__ ubytes, const MjdFrame* __restrict__ frames, const uint32_t* __restrict__ foff,
                                                   const uint32_t* __restrict__ ulen, int sub_cap, const unsigned long long* __restrict__ e, const uint32_t* __restrict__ before,
-                                                  int nmcu, int16_t* __restrict__ coef, uint32_t* __restrict__ err) {
+                                                  int nmcu, int nblk, int ny, int16_t* __restrict__ coef, uint32_t* __restrict__ err) {
     __shared__ uint16_t s_lut[2][2][1 << MJD_LUT_BITS];
     const int f = blockIdx.y, tid = threadIdx.x;
     const MjdFrame& fr = frames[f];
@@ -517,37 +551,39 @@ __global__ __launch_bounds__(64) void k_mjp_write(const uint8_t* __restrict__ ub
     if (i > 0) { const unsigned long long x = e[(size_t)f * sub_cap + i - 1]; p0 = (uint32_t)x; const int st = (int)((x >> 32) & 511u); bi = st >> 6; kk = st & 63; }
     const bool last = i + 1 == nsub;
     const uint32_t end = last ? total_bits + 64u : (uint32_t)e[(size_t)f * sub_cap + i];
-    const uint32_t nblk = (uint32_t)nmcu * 6u;
+    const uint32_t nall = (uint32_t)nmcu * (uint32_t)nblk;
     uint32_t b = before[(size_t)f * sub_cap + i];
-    bool bad = (uint32_t)bi != b % 6u;                                    // (the state and the count must tell the same story)
+    bool bad = (uint32_t)bi != b % (uint32_t)nblk;                                   // (the state and the count must tell the same story)
     MjpBits br;
     br.init(words, (ulen[f] + 3u) >> 2, p0);
-    int16_t* out = coef + (size_t)f * nmcu * 384;
-    while (!bad && b < nblk && br.pos < end) {
+    int16_t* out = coef + (size_t)f * nmcu * (size_t)(nblk * 64);
+    while (!bad && b < nall && br.pos < end) {
         int value = 0; bool done;
-        const int ci = mjp_step(br, bi, kk, fr, s_lut, value, done);
+        const int ci = mjp_step(br, bi, kk, fr, s_lut, nblk, ny, value, done);
         if (ci == -2) { bad = true; break; }
         if (ci >= 0) out[(size_t)b * 64 + ci] = (int16_t)value;
         b += done ? 1u : 0u;
     }
-    if (last && b < nblk) bad = true;                                     // the stream ended before the frame did
+    if (last && b < nall) bad = true;                                     // the stream ended before the frame did
     if (bad) atomicOr(err + f, 2u);
 }
 
 // one workgroup per (component, frame): DC coefficients = prefix sums of the differences over the blocks of the component, in scan order
-__global__ __launch_bounds__(256) void k_mjp_dc(const MjdFrame* __restrict__ frames, int nmcu, int16_t* __restrict__ coef) {
+__global__ __launch_bounds__(256) void k_mjp_dc(const MjdFrame* __restrict__ frames, int nmcu, int nblk, int ny, int16_t* __restrict__ coef) {
     __shared__ int s_v[1024];
     __shared__ int s_part[256];
     __shared__ int s_carry;
     const int tid = threadIdx.x, comp = blockIdx.x, f = blockIdx.y;
     if (!frames[f].par) return;
-    int16_t* c = coef + (size_t)f * nmcu * 384;
-    const int n_all = comp == 0 ? nmcu * 4 : nmcu;
+    int16_t* c = coef + (size_t)f * nmcu * (size_t)(nblk * 64);
+    const int n_all = comp == 0 ? nmcu * ny : nmcu;
+    // element el of the component -> its block: the ny luminance blocks lead every MCU, Cb and Cr follow
+    auto block_of = [&](int el) { return comp == 0 ? (el / ny) * nblk + el % ny : el * nblk + ny + comp - 1; };
     if (tid == 0) s_carry = 0;
     __syncthreads();
     for (int c0 = 0; c0 < n_all; c0 += 1024) {
         const int n = n_all - c0 < 1024 ? n_all - c0 : 1024;
-        for (int i = tid; i < n; i += 256) { const int el = c0 + i; const int b = comp == 0 ? (el >> 2) * 6 + (el & 3) : el * 6 + 3 + comp; s_v[i] = c[(size_t)b * 64]; }
+        for (int i = tid; i < n; i += 256) { s_v[i] = c[(size_t)block_of(c0 + i) * 64]; }
         __syncthreads();
         const int per = (n + 255) / 256, lo = tid * per, hi = lo + per < n ? lo + per : n;
         int sum = 0;
@@ -562,7 +598,7 @@ __global__ __launch_bounds__(256) void k_mjp_dc(const MjdFrame* __restrict__ fra
         }
         const int carry = s_carry;
         int run = carry + (tid ? s_part[tid - 1] : 0);
-        for (int i = lo; i < hi; ++i) { run += s_v[i]; const int el = c0 + i; const int b = comp == 0 ? (el >> 2) * 6 + (el & 3) : el * 6 + 3 + comp; c[(size_t)b * 64] = (int16_t)run; }
+        for (int i = lo; i < hi; ++i) { run += s_v[i]; c[(size_t)block_of(c0 + i) * 64] = (int16_t)run; }
         __syncthreads();
         if (tid == 0) s_carry = carry + s_part[255];
         __syncthreads();
@@ -698,7 +734,7 @@ __device__ __forceinline__ void mjl_idct_block(const int* a, int* t, bool on, in
 
 // One wave per four MCUs of an MCU row (sixteen per workgroup): lane = zigzag index while dequantising (coef * q, no clamp -- libjpeg has none), then
 // (block, column / row) of the eight Cb / Cr blocks; every row of a block leaves as one 8-byte store into its plane.
-__global__ __launch_bounds__(256) void k_mjd_chroma_islow(const int16_t* __restrict__ coef, const MjdFrame* __restrict__ frames, MjdGeom g, uint8_t* __restrict__ planes) {
+__global__ __launch_bounds__(256) void k_mjd_chroma_islow(const int16_t* __restrict__ coef, const MjdFrame* __restrict__ frames, MjdGeom g, int nblk, int ny, uint8_t* __restrict__ planes) {
     __shared__ int s_a[4][8 * MJL_BLK], s_b[4][8 * MJL_BLK];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int mx0 = blockIdx.x * 16 + wave * 4, my = blockIdx.y, f = blockIdx.z;
@@ -707,7 +743,7 @@ __global__ __launch_bounds__(256) void k_mjd_chroma_islow(const int16_t* __restr
 #pragma unroll
     for (int b = 0; b < 8; ++b) {
         const int mx = mx0 + (b >> 1), comp = 1 + (b & 1);
-        if (mx < g.mw) s_a[wave][b * MJL_BLK + at] = coef[(((size_t)f * g.mh + my) * g.mw + mx) * 384 + (3 + comp) * 64 + lane] * (int)fr.q[fr.tq[comp]][lane];
+        if (mx < g.mw) s_a[wave][b * MJL_BLK + at] = coef[(((size_t)f * g.mh + my) * g.mw + mx) * (size_t)(nblk * 64) + (ny - 1 + comp) * 64 + lane] * (int)fr.q[fr.tq[comp]][lane];
     }
     __syncthreads();
     const int b = lane >> 3, k = lane & 7, mx = mx0 + (b >> 1);
@@ -799,6 +835,128 @@ __global__ __launch_bounds__(256) void k_mjd_pixels_libjpeg(const int16_t* __res
     }
 }
 
+// ---- the other samplings of a baseline file (lvm_mjpeg_set_samplings), libjpeg's arithmetic only -------------------------------------------------
+// All three kernels below give a wave the same piece of the frame: 64 pixels x 8 rows = eight 8 x 8 luminance blocks side by side (eight MCUs of
+// 4:4:4 / gray, four of 4:2:2).  Why eight: the IDCT passes want (block, column) / (block, row) on all 64 lanes, and in the output stage lane = pixel
+// column, so that every row of the piece leaves the wave as ONE contiguous run of 192 bytes (a wave of 2 2/3 4:4:4 MCUs would fill the IDCT as
+// well, but end its rows in the middle of a block of the next wave).  With the chroma blocks of 4:4:4 that is three IDCT rounds of eight blocks
+// each, all lanes busy in every one.
+// LDS (ds_read_b32 / ds_write_b32: 32 banks, the two 32-lane halves apart): the IDCT passes are those of k_mjd_chroma_islow (pitch 9 / 72);
+// the output stage reads block lane >> 3, row r, column lane & 7 = word 72 (lane >> 3) + 9 r + (lane & 7) = lane + 9 r (mod 32): conflict-free.
+
+// 4:4:4 (nc = 3) and gray (nc = 1): no sample of another MCU is needed, so one launch and no scratch planes.  One wave per eight MCUs of an MCU
+// row, 32 MCUs per workgroup.  NC is a template parameter: gray then holds 9.2 + 9.2 KB of LDS per workgroup where 4:4:4 holds 27.6 + 9.2 KB (the
+// LDS that caps the workgroups per CU is the sampling's own), and the store loop carries no test of the sampling.
+template <int NC>
+__global__ __launch_bounds__(256) void k_mjd_pixels_direct(const int16_t* __restrict__ coef, const MjdFrame* __restrict__ frames, MjdGeom g, uint8_t* __restrict__ dst) {
+    constexpr int nc = NC;
+    __shared__ int s_a[4][NC * 8 * MJL_BLK], s_t[4][8 * MJL_BLK];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int mx0 = blockIdx.x * 32 + wave * 8, my = blockIdx.y, f = blockIdx.z;
+    const MjdFrame& fr = frames[f];
+    const int nat = fr.zz[lane], at = (nat >> 3) * MJL_ROW + (nat & 7);
+    const int16_t* in = coef + ((size_t)f * g.mh + my) * g.mw * (size_t)(nc * 64);
+    for (int c = 0; c < nc; ++c) {
+        const int q = fr.q[fr.tq[c]][lane];
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            if (mx0 + i < g.mw) s_a[wave][(c * 8 + i) * MJL_BLK + at] = in[((size_t)(mx0 + i) * nc + c) * 64 + lane] * q;
+    }
+    __syncthreads();
+    const int b = lane >> 3, k = lane & 7;
+    const bool on = mx0 + b < g.mw;
+    for (int c = 0; c < nc; ++c) {
+        int p[8];
+        int* blk = &s_a[wave][(c * 8 + b) * MJL_BLK];
+        mjl_idct_block(blk, &s_t[wave][b * MJL_BLK], on, k, p);
+        if (on) {
+#pragma unroll
+            for (int x = 0; x < 8; ++x) blk[k * MJL_ROW + x] = p[x];
+        }
+    }
+    __syncthreads();
+    const int px = mx0 * 8 + lane;
+    if (px < g.w) {
+        uint8_t* o = dst + (size_t)f * g.fstride + (size_t)(my * 8) * g.stride + (size_t)px * 3;
+        const int* yb = &s_a[wave][b * MJL_BLK + k];
+        const int rows = g.h - my * 8 < 8 ? g.h - my * 8 : 8;
+        for (int r = 0; r < rows; ++r, o += g.stride) {
+            const int y = yb[r * MJL_ROW];
+            if constexpr (NC == 1) { o[0] = (uint8_t)y; o[1] = (uint8_t)y; o[2] = (uint8_t)y; continue; }          // gray: b = g = r
+            const int cb = yb[8 * MJL_BLK + r * MJL_ROW] - 128, cr = yb[16 * MJL_BLK + r * MJL_ROW] - 128;
+            const int dr = (91881 * cr + 32768) >> 16, dg = (-22554 * cb - 46802 * cr + 32768) >> 16, db = (116130 * cb + 32768) >> 16;
+            int rr = y + dr, gg = y + dg, bb = y + db;
+            rr = rr < 0 ? 0 : (rr > 255 ? 255 : rr); gg = gg < 0 ? 0 : (gg > 255 ? 255 : gg); bb = bb < 0 ? 0 : (bb > 255 ? 255 : bb);
+            o[0] = (uint8_t)bb; o[1] = (uint8_t)gg; o[2] = (uint8_t)rr;
+        }
+    }
+}
+
+// 4:2:2 (Y 2 x 1, MCU 16 x 8; the Cb / Cr planes come from k_mjd_chroma_islow as for 4:2:0): libjpeg's h2v1_fancy_upsample, per chroma row c[0..n),
+// n = (w + 1) / 2:  out[2i] = (3 c[i] + c[i-1] + 1) >> 2,  out[2i+1] = (3 c[i] + c[i+1] + 2) >> 2,  out[0] = c[0],  out[2n-1] = c[n-1]; nothing vertical.
+// With the neighbour index clamped to the component's own width the two edge rules ARE the general ones ((3 c + c + 1 or 2) >> 2 = c).  Where
+// n <= 2 libjpeg replicates: the neighbour is then the sample itself.  One wave per four MCUs of an MCU row, sixteen per workgroup: IDCT of their
+// eight Y blocks, meanwhile all lanes gather the 8 rows x (32 + one either side) chroma samples as (Cb | Cr << 16) words -- both components
+// filter at once, 4 * 255 + 2 fits the halves.  The gather stores word i from lane i (mod 64) into a row pitch of 34 = consecutive words; the
+// output stage reads words 1 + (lane >> 1) and that +- 1 of ONE row: 17 consecutive words per half-wave, pairs of lanes on the same word
+// (broadcast): both conflict-free.
+constexpr int MJL_HROW = 34;
+__global__ __launch_bounds__(256) void k_mjd_pixels_h2v1(const int16_t* __restrict__ coef, const MjdFrame* __restrict__ frames, MjdGeom g,
+                                                         const uint8_t* __restrict__ planes, uint8_t* __restrict__ dst) {
+    __shared__ int s_a[4][8 * MJL_BLK], s_t[4][8 * MJL_BLK];
+    __shared__ uint32_t s_c[4][8 * MJL_HROW];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int mx0 = blockIdx.x * 16 + wave * 4, my = blockIdx.y, f = blockIdx.z;
+    const MjdFrame& fr = frames[f];
+    const int nat = fr.zz[lane], at = (nat >> 3) * MJL_ROW + (nat & 7), q = fr.q[fr.tq[0]][lane];
+    const int16_t* in = coef + ((size_t)f * g.mh + my) * g.mw * 256;
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+        if (mx0 + (i >> 1) < g.mw) s_a[wave][i * MJL_BLK + at] = in[((size_t)(mx0 + (i >> 1)) * 4 + (i & 1)) * 64 + lane] * q;
+    if (mx0 < g.mw) {
+        const int cw = (g.w + 1) >> 1;
+        const size_t pitch = (size_t)g.mw * 8, rows = (size_t)g.mh * 8;
+        const uint8_t* cbp = planes + (size_t)f * 2 * rows * pitch + (size_t)(my * 8) * pitch;
+        for (int i = lane; i < 8 * MJL_HROW; i += 64) {
+            const int r = i / MJL_HROW, cc = i - r * MJL_HROW;
+            int x = mx0 * 8 - 1 + cc;
+            x = x < 0 ? 0 : (x > cw - 1 ? cw - 1 : x);
+            const size_t o = (size_t)r * pitch + (size_t)x;
+            s_c[wave][i] = (uint32_t)cbp[o] | ((uint32_t)cbp[rows * pitch + o] << 16);
+        }
+    }
+    __syncthreads();
+    const int b = lane >> 3, k = lane & 7;
+    {
+        const bool on = mx0 + (b >> 1) < g.mw;
+        int p[8];
+        int* blk = &s_a[wave][b * MJL_BLK];
+        mjl_idct_block(blk, &s_t[wave][b * MJL_BLK], on, k, p);
+        if (on) {
+#pragma unroll
+            for (int x = 0; x < 8; ++x) blk[k * MJL_ROW + x] = p[x];
+        }
+    }
+    __syncthreads();
+    const int px = mx0 * 16 + lane;
+    if (px < g.w) {
+        const int odd = lane & 1, own = 1 + (lane >> 1), nb = g.w > 4 ? own + (odd ? 1 : -1) : own;
+        const uint32_t rnd = odd ? 0x00020002u : 0x00010001u;
+        uint8_t* o = dst + (size_t)f * g.fstride + (size_t)(my * 8) * g.stride + (size_t)px * 3;
+        const int* yb = &s_a[wave][b * MJL_BLK + k];
+        const int rows = g.h - my * 8 < 8 ? g.h - my * 8 : 8;
+        for (int r = 0; r < rows; ++r, o += g.stride) {
+            const uint32_t both = 3u * s_c[wave][r * MJL_HROW + own] + s_c[wave][r * MJL_HROW + nb] + rnd;
+            const int cb = (int)((both & 0xFFFFu) >> 2) - 128, cr = (int)(both >> 18) - 128;
+            const int dr = (91881 * cr + 32768) >> 16, dg = (-22554 * cb - 46802 * cr + 32768) >> 16, db = (116130 * cb + 32768) >> 16;
+            const int y = yb[r * MJL_ROW];
+            int rr = y + dr, gg = y + dg, bb = y + db;
+            rr = rr < 0 ? 0 : (rr > 255 ? 255 : rr); gg = gg < 0 ? 0 : (gg > 255 ? 255 : gg); bb = bb < 0 ? 0 : (bb > 255 ? 255 : bb);
+            o[0] = (uint8_t)bb; o[1] = (uint8_t)gg; o[2] = (uint8_t)rr;
+        }
+    }
+}
+
 }  // namespace
 
 void mjpeg_decode_release(Ctx* c) {
@@ -818,15 +976,25 @@ int mjpeg_decode_begin(Ctx* c, const uint8_t* jpegs, const size_t* offsets, int 
     if (w < 1 || h < 1 || w > 8192 || h > 16384) { c->err = "lvm_mjpeg_decode: frame size out of range (1..8192 x 1..16384)"; return LVM_ERR_INVALID; }
     MjdState* st = static_cast<MjdState*>(c->mjpeg_dec);
     if (!st) { st = new MjdState; c->mjpeg_dec = st; }
-    const int mw = (w + 15) / 16, mh = (h + 15) / 16, nmcu = mw * mh;
     st->frames.resize((size_t)n);
+    MjdSamp sp = samp_of(LVM_MJPEG_SAMPLING_420);
+    int mw = 0, mh = 0, nmcu = 0;
     std::vector<uint32_t> foff((size_t)n + 1);
     int max_iv = 1, max_sub = 1, npar = 0;
     for (int i = 0; i < n; ++i) {
         if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[0] > 0xFFFFFFF0ull) { c->err = "lvm_mjpeg_decode: bad offsets"; return LVM_ERR_INVALID; }
         MjdFrame& f = st->frames[(size_t)i];
-        const char* why = parse_frame(jpegs + offsets[i], offsets[i + 1] - offsets[i], w, h, f);
+        const char* why = parse_frame(jpegs + offsets[i], offsets[i + 1] - offsets[i], w, h, c->mjpeg_samplings, f);
+        if (!why && f.samp != st->frames[0].samp) why = "sampling differs from frame 0's";
         if (why) { c->err = std::string("lvm_mjpeg_decode: frame ") + std::to_string(i) + ": " + why; return LVM_ERR_INVALID; }
+        if (i == 0) {       // the frames of a call share one sampling, as the frames of a file do: the MCU is a property of the call.  The kind is
+                            // checked here, before frames 1.. are parsed: a sampling the kind cannot decode is reported ahead of a later frame's damage
+            sp = samp_of(f.samp);
+            if (f.samp != LVM_MJPEG_SAMPLING_420 && c->mjpeg_decoder != LVM_MJPEG_DECODER_LIBJPEG) {
+                c->err = std::string("lvm_mjpeg_decode: frame 0: ") + sp.name + " needs LVM_MJPEG_DECODER_LIBJPEG"; return LVM_ERR_INVALID;
+            }
+            mw = (w + sp.mcu_w - 1) / sp.mcu_w; mh = (h + sp.mcu_h - 1) / sp.mcu_h; nmcu = mw * mh;
+        }
         f.nintervals = f.restart ? (uint32_t)((nmcu + (int)f.restart - 1) / (int)f.restart) : 1u;
         if ((int)f.nintervals > max_iv) max_iv = (int)f.nintervals;
         // no restart markers: one lane would decode the whole frame -- the self-synchronising kernels take it (LVM_MJD_PARALLEL=0: never, =2: also tiny frames)
@@ -839,13 +1007,14 @@ int mjpeg_decode_begin(Ctx* c, const uint8_t* jpegs, const size_t* offsets, int 
     foff[(size_t)n] = (uint32_t)(offsets[n] - offsets[0]);
     const size_t nbytes = offsets[n] - offsets[0];
     int rc;
-    if (st->frames_cap < n || st->w != w || st->h != h) {
+    const uint32_t samp = st->frames[0].samp;
+    if (st->frames_cap < n || st->w != w || st->h != h || st->samp != samp) {
         LVM_HIP_TRY(c, hipStreamSynchronize(s));
         st->frames_cap = 0;
         if ((rc = dev_realloc(c, st->d_frames, (size_t)n)) != LVM_OK) return rc;
-        if ((rc = dev_realloc(c, st->d_coef, (size_t)n * nmcu * 384)) != LVM_OK) return rc;
+        if ((rc = dev_realloc(c, st->d_coef, (size_t)n * nmcu * sp.nblk * 64)) != LVM_OK) return rc;
         if ((rc = dev_realloc(c, st->d_err, (size_t)n * 2 + 2)) != LVM_OK) return rc;       // error flags, then the frame offsets (n + 1)
-        st->frames_cap = n; st->w = w; st->h = h; st->iv_cap = 0;
+        st->frames_cap = n; st->w = w; st->h = h; st->samp = samp; st->iv_cap = 0;
     }
     if (st->iv_cap < max_iv) {
         LVM_HIP_TRY(c, hipStreamSynchronize(s));
@@ -878,7 +1047,7 @@ int mjpeg_decode_begin(Ctx* c, const uint8_t* jpegs, const size_t* offsets, int 
     }
     st->kind = c->mjpeg_decoder;
     const size_t nchroma = (size_t)n * 2 * ((size_t)mh * 8) * ((size_t)mw * 8);
-    if (st->kind == LVM_MJPEG_DECODER_LIBJPEG && st->d_chroma.cap < nchroma) {
+    if (st->kind == LVM_MJPEG_DECODER_LIBJPEG && sp.ny > 1 && st->d_chroma.cap < nchroma) {
         LVM_HIP_TRY(c, hipStreamSynchronize(s));
         if ((rc = st->d_chroma.reserve(c, nchroma)) != LVM_OK) return rc;
     }
@@ -894,15 +1063,17 @@ int mjpeg_decode_begin(Ctx* c, const uint8_t* jpegs, const size_t* offsets, int 
 int mjpeg_decode_enqueue(Ctx* c, int f0, int nf, uint8_t* d_bgr, ptrdiff_t stride, ptrdiff_t fstride, hipStream_t s) {
     MjdState* st = static_cast<MjdState*>(c->mjpeg_dec);
     if (!st || f0 < 0 || nf < 1 || f0 + nf > st->n) { c->err = "lvm_mjpeg_decode: enqueue without begin"; return LVM_ERR_INVALID; }
-    const int w = st->w, h = st->h, mw = (w + 15) / 16, mh = (h + 15) / 16, nmcu = mw * mh;
+    const MjdSamp sp = samp_of(st->samp);
+    const int w = st->w, h = st->h, mw = (w + sp.mcu_w - 1) / sp.mcu_w, mh = (h + sp.mcu_h - 1) / sp.mcu_h, nmcu = mw * mh;
+    const size_t mcu_coefs = (size_t)sp.nblk * 64;
     const MjdFrame* fr = st->d_frames + f0;
     const uint32_t* d_foff = st->d_err + st->n + f0;
-    int16_t* coef = st->d_coef + (size_t)f0 * nmcu * 384;
+    int16_t* coef = st->d_coef + (size_t)f0 * nmcu * mcu_coefs;
     uint32_t *ivs = st->d_ivstart + (size_t)f0 * st->iv_cap, *ive = st->d_ivend + (size_t)f0 * st->iv_cap, *err = st->d_err + f0;
-    LVM_HIP_TRY(c, hipMemsetAsync(coef, 0, (size_t)nf * nmcu * 384 * sizeof(int16_t), s));
+    LVM_HIP_TRY(c, hipMemsetAsync(coef, 0, (size_t)nf * nmcu * mcu_coefs * sizeof(int16_t), s));
     LVM_LAUNCH(c, "mjd_intervals", k_mjd_intervals, dim3(nf), dim3(256), s, (const uint8_t*)st->d_bytes, fr, d_foff, ivs, ive, st->iv_cap, err);
     LVM_LAUNCH(c, "mjd_huffman", k_mjd_huffman, dim3((st->max_iv + 63) / 64, nf), dim3(64), s, (const uint8_t*)st->d_bytes, fr, d_foff, (const uint32_t*)ivs,
-               (const uint32_t*)ive, st->iv_cap, nmcu, coef, err);
+               (const uint32_t*)ive, st->iv_cap, nmcu, sp.nblk, sp.ny, coef, err);
     bool any_par = false;
     for (int i = f0; i < f0 + nf; ++i) any_par = any_par || st->frames[(size_t)i].par;
     if (any_par) {
@@ -911,12 +1082,12 @@ int mjpeg_decode_enqueue(Ctx* c, int f0, int nf, uint8_t* d_bgr, ptrdiff_t strid
         uint32_t* before = st->d_before + (size_t)f0 * st->sub_cap;
         const dim3 gsub((unsigned)((st->sub_cap + 63) / 64), (unsigned)nf);
         LVM_LAUNCH(c, "mjp_unstuff", k_mjp_unstuff, dim3(nf), dim3(256), s, (const uint8_t*)st->d_bytes, fr, d_foff, st->d_ubytes.p, st->d_ulen + f0);
-        LVM_LAUNCH(c, "mjp_sync", k_mjp_sync, gsub, dim3(64), s, (const uint8_t*)st->d_ubytes, fr, d_foff, ulen, st->sub_cap, 1, (const unsigned long long*)ex[1], ex[0], st->d_changed);
+        LVM_LAUNCH(c, "mjp_sync", k_mjp_sync, gsub, dim3(64), s, (const uint8_t*)st->d_ubytes, fr, d_foff, ulen, st->sub_cap, 1, sp.nblk, sp.ny, (const unsigned long long*)ex[1], ex[0], st->d_changed);
         int cur = 0;                                               // ex[cur] holds the latest exits
         for (int it = 0; it <= st->sub_cap; ++it) {                // (every pass makes at least one more lane exact: sub_cap passes always suffice)
             uint32_t changed = 0;
             LVM_HIP_TRY(c, hipMemsetAsync(st->d_changed, 0, sizeof(uint32_t), s));
-            LVM_LAUNCH(c, "mjp_sync", k_mjp_sync, gsub, dim3(64), s, (const uint8_t*)st->d_ubytes, fr, d_foff, ulen, st->sub_cap, 0, (const unsigned long long*)ex[cur], ex[cur ^ 1],
+            LVM_LAUNCH(c, "mjp_sync", k_mjp_sync, gsub, dim3(64), s, (const uint8_t*)st->d_ubytes, fr, d_foff, ulen, st->sub_cap, 0, sp.nblk, sp.ny, (const unsigned long long*)ex[cur], ex[cur ^ 1],
                        st->d_changed);
             LVM_HIP_TRY(c, hipMemcpyAsync(&changed, st->d_changed, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
             LVM_HIP_TRY(c, hipStreamSynchronize(s));
@@ -925,14 +1096,25 @@ int mjpeg_decode_enqueue(Ctx* c, int f0, int nf, uint8_t* d_bgr, ptrdiff_t strid
         }
         LVM_LAUNCH(c, "mjp_scan", k_mjp_scan, dim3(nf), dim3(256), s, fr, ulen, st->sub_cap, (const unsigned long long*)ex[cur], before);
         LVM_LAUNCH(c, "mjp_write", k_mjp_write, gsub, dim3(64), s, (const uint8_t*)st->d_ubytes, fr, d_foff, ulen, st->sub_cap, (const unsigned long long*)ex[cur],
-                   (const uint32_t*)before, nmcu, coef, err);
-        LVM_LAUNCH(c, "mjp_dc", k_mjp_dc, dim3(3, nf), dim3(256), s, fr, nmcu, coef);
+                   (const uint32_t*)before, nmcu, sp.nblk, sp.ny, coef, err);
+        LVM_LAUNCH(c, "mjp_dc", k_mjp_dc, dim3(sp.ncomp, nf), dim3(256), s, fr, nmcu, sp.nblk, sp.ny, coef);
     }
     MjdGeom g;
     g.w = w; g.h = h; g.mw = mw; g.mh = mh; g.stride = (long)stride; g.fstride = (long)fstride;
+    if (st->samp == LVM_MJPEG_SAMPLING_444 || st->samp == LVM_MJPEG_SAMPLING_GRAY) {
+        if (sp.ncomp == 1) LVM_LAUNCH(c, "mjd_pixels_direct", k_mjd_pixels_direct<1>, dim3((mw + 31) / 32, mh, nf), dim3(256), s, (const int16_t*)coef, fr, g, d_bgr);
+        else LVM_LAUNCH(c, "mjd_pixels_direct", k_mjd_pixels_direct<3>, dim3((mw + 31) / 32, mh, nf), dim3(256), s, (const int16_t*)coef, fr, g, d_bgr);
+        return LVM_OK;
+    }
+    if (st->samp == LVM_MJPEG_SAMPLING_422) {
+        uint8_t* planes = st->d_chroma + (size_t)f0 * 2 * ((size_t)mh * 8) * ((size_t)mw * 8);
+        LVM_LAUNCH(c, "mjd_chroma_islow", k_mjd_chroma_islow, dim3((mw + 15) / 16, mh, nf), dim3(256), s, (const int16_t*)coef, fr, g, sp.nblk, sp.ny, planes);
+        LVM_LAUNCH(c, "mjd_pixels_h2v1", k_mjd_pixels_h2v1, dim3((mw + 15) / 16, mh, nf), dim3(256), s, (const int16_t*)coef, fr, g, (const uint8_t*)planes, d_bgr);
+        return LVM_OK;
+    }
     if (st->kind == LVM_MJPEG_DECODER_LIBJPEG) {
         uint8_t* planes = st->d_chroma + (size_t)f0 * 2 * ((size_t)mh * 8) * ((size_t)mw * 8);
-        LVM_LAUNCH(c, "mjd_chroma_islow", k_mjd_chroma_islow, dim3((mw + 15) / 16, mh, nf), dim3(256), s, (const int16_t*)coef, fr, g, planes);
+        LVM_LAUNCH(c, "mjd_chroma_islow", k_mjd_chroma_islow, dim3((mw + 15) / 16, mh, nf), dim3(256), s, (const int16_t*)coef, fr, g, sp.nblk, sp.ny, planes);
         LVM_LAUNCH(c, "mjd_pixels_libjpeg", k_mjd_pixels_libjpeg, dim3((mw + 3) / 4, mh, nf), dim3(256), s, (const int16_t*)coef, fr, g, (const uint8_t*)planes, d_bgr);
         return LVM_OK;
     }

@@ -78,6 +78,9 @@ public:
     // handle(); e.g. the frames lvm::MjpegAviReader finds): LVM_MJPEG_DECODER_REPLICATE -- the default, nothing changes without this call -- or
     // LVM_MJPEG_DECODER_LIBJPEG, the frames a libjpeg-backed cv::VideoCapture hands to Exporter::run.  Throws lvm::Error on any other kind.
     void set_mjpeg_decoder(int kind) { mag_.mjpeg_set_decoder(kind); }
+    // The samplings the runner's context accepts in such frames: a mask of LVM_MJPEG_SAMPLING_* (the default is 4:2:0 alone; 4:2:2, 4:4:4 and gray
+    // frames -- UVC cameras, FFmpeg's yuvj422p / yuvj444p, industrial cameras -- need LVM_MJPEG_DECODER_LIBJPEG).  Throws lvm::Error on a bad mask.
+    void set_mjpeg_samplings(unsigned mask) { mag_.mjpeg_set_samplings(mask); }
     lvm_ctx* handle() const { return mag_.handle(); }
     // request.textOverlay (ExportTypes.hpp:22): `draw` = the reference's label code for one canvas (what compose does for overlay == true,
     // Exporter.cpp:74-77 / :82-85).  It is run on constant canvases whenever the canvas geometry is (re)established and never on a frame:

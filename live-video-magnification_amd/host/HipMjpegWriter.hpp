@@ -106,12 +106,16 @@ private:
 // `decoder` is the arithmetic the reader's user wants behind the entropy layer -- the value for lvm_mjpeg_set_decoder (include/lvm_hip.h): 0 =
 // LVM_MJPEG_DECODER_REPLICATE, the library's default; 1 = LVM_MJPEG_DECODER_LIBJPEG, the frames a libjpeg-backed cv::VideoCapture would read from this
 // file, byte for byte.  The reader only carries it next to the file (no HIP in this header): lvm::ExportRunner::set_mjpeg_decoder(rd.decoder()) /
-// lvm::Magnifier::mjpeg_set_decoder apply it to the context that decodes.
+// lvm::Magnifier::mjpeg_set_decoder apply it to the context that decodes.  `samplings` likewise is the value for lvm_mjpeg_set_samplings: the mask
+// of samplings the file may have (1 = LVM_MJPEG_SAMPLING_420, the library's default; 2 = 4:2:2, 4 = 4:4:4, 8 = gray, 15 = all of them -- the frames
+// of one file share one), applied with lvm::ExportRunner::set_mjpeg_samplings(rd.samplings()) / lvm::Magnifier::mjpeg_set_samplings.
 class MjpegAviReader {
 public:
-    explicit MjpegAviReader(int decoder = 0) : decoder_(decoder) {}
+    explicit MjpegAviReader(int decoder = 0, unsigned samplings = 1) : decoder_(decoder), samplings_(samplings) {}
     void set_decoder(int kind) { decoder_ = kind; }
     int decoder() const { return decoder_; }
+    void set_samplings(unsigned mask) { samplings_ = mask; }
+    unsigned samplings() const { return samplings_; }
     ~MjpegAviReader() { close(); }
     MjpegAviReader(const MjpegAviReader&) = delete;
     MjpegAviReader& operator=(const MjpegAviReader&) = delete;
@@ -199,6 +203,7 @@ private:
     std::vector<Chunk> frames_;
     int strl_seen_ = 0, vid_stream_ = -1;
     int decoder_ = 0;
+    unsigned samplings_ = 1;
 };
 
 }  // namespace lvm

@@ -107,6 +107,9 @@ public:
     // The decode arithmetic of lvm_mjpeg_decode_device / lvm_export_mjpeg_frames on this context (LVM_MJPEG_DECODER_REPLICATE, the default, or
     // LVM_MJPEG_DECODER_LIBJPEG: what a libjpeg-backed cv::VideoCapture reads).  Throws on any other kind.
     void mjpeg_set_decoder(int kind) { check(lvm_mjpeg_set_decoder(ctx_, kind)); }
+    // The samplings those two calls accept (a mask of LVM_MJPEG_SAMPLING_*; the default is 4:2:0 alone).  4:2:2, 4:4:4 and gray frames need
+    // LVM_MJPEG_DECODER_LIBJPEG.  Throws on an empty mask or unknown bits.
+    void mjpeg_set_samplings(unsigned mask) { check(lvm_mjpeg_set_samplings(ctx_, mask)); }
 
     void synchronize() { check(lvm_synchronize(ctx_)); }
     lvm_ctx* handle() const { return ctx_; }
