@@ -385,6 +385,33 @@ __device__ __forceinline__ void load_invgamma(float* s_igt, const float* g) {
     for (int i = threadIdx.x; i < 1024; i += 256) dst[i] = src[i];
 }
 
+// ---- scans by the 256 threads of a workgroup (mjpeg.hip, mjpeg_decode.hip) ---------------------------------------------------------
+// inclusive scan of one value per thread (Hillis-Steele over part[256] in LDS): behind it part[tid] = the sum of v over threads 0 .. tid,
+// part[255] the total.  Ends with a barrier.
+template <class T>
+__device__ __forceinline__ void wg_inclusive_scan(T v, T* part, int tid) {
+    part[tid] = v;
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {
+        const T t = tid >= d ? part[tid - d] : T(0);
+        __syncthreads();
+        part[tid] += t;
+        __syncthreads();
+    }
+}
+// exclusive scan of s[0 .. n) in place (a run of s per thread; part: 256 elements of LDS); returns the total
+template <class T>
+__device__ __forceinline__ T wg_exclusive_scan(T* s, int n, T* part, int tid) {
+    const int per = (n + 255) / 256, lo = tid * per, hi = lo + per < n ? lo + per : n;
+    T sum = 0;
+    for (int i = lo; i < hi; ++i) sum += s[i];
+    wg_inclusive_scan(sum, part, tid);
+    T run = tid ? part[tid - 1] : T(0);
+    for (int i = lo; i < hi; ++i) { const T t = s[i]; s[i] = run; run += t; }
+    const T total = part[255];
+    __syncthreads();
+    return total;
+}
 // pyrUp horizontal pass for destination column gx from source row `s` whose element for
 // source column i sits at s[i - sx0] (OpenCV pyrUp_ border rules, see laplace.hip).
 __device__ __forceinline__ float pyrup_h(const float* s, int gx, int sx0, int sw) {

@@ -271,26 +271,6 @@ __device__ __forceinline__ void put_bits(uint32_t* __restrict__ out, uint32_t of
     if ((uint32_t)v) atomicOr(out + w + 1, (uint32_t)v);
 }
 
-// exclusive scan of s[0 .. n) in place by the 256 threads of a workgroup (part: 256 words of LDS); returns the total
-__device__ __forceinline__ uint32_t wg_exclusive_scan(uint32_t* s, int n, uint32_t* part, int tid) {
-    const int per = (n + 255) / 256, lo = tid * per, hi = lo + per < n ? lo + per : n;
-    uint32_t sum = 0;
-    for (int i = lo; i < hi; ++i) sum += s[i];
-    part[tid] = sum;
-    __syncthreads();
-    for (int d = 1; d < 256; d <<= 1) {
-        const uint32_t t = tid >= d ? part[tid - d] : 0u;
-        __syncthreads();
-        part[tid] += t;
-        __syncthreads();
-    }
-    uint32_t run = tid ? part[tid - 1] : 0u;
-    for (int i = lo; i < hi; ++i) { const uint32_t t = s[i]; s[i] = run; run += t; }
-    const uint32_t total = part[255];
-    __syncthreads();
-    return total;
-}
-
 __device__ __forceinline__ void load_huff(uint32_t (*s_ac)[256], uint32_t (*s_dc)[12], const MjTables* __restrict__ tb, int tid) {
     for (int i = tid; i < 512; i += 256) s_ac[i >> 8][i & 255] = tb->ac[i >> 8][i & 255];
     if (tid < 24) s_dc[tid / 12][tid % 12] = tb->dc[tid / 12][tid % 12];
@@ -490,14 +470,7 @@ __global__ __launch_bounds__(256) void k_mj_write(const uint32_t* __restrict__ r
     const uint32_t per = (nwords + 255u) / 256u, lo = tid * per, hi = lo + per < nwords ? lo + per : nwords;     // a run of words per thread
     uint32_t ff = 0;
     for (uint32_t i = lo; i < hi; ++i) ff += ff_bytes(raw_word(in, i, nbytes, bits), nbytes - 4u * i < 4u ? nbytes - 4u * i : 4u);
-    s_part[tid] = ff;
-    __syncthreads();
-    for (int d = 1; d < 256; d <<= 1) {
-        const uint32_t t = tid >= d ? s_part[tid - d] : 0u;
-        __syncthreads();
-        s_part[tid] += t;
-        __syncthreads();
-    }
+    wg_inclusive_scan(ff, s_part, tid);
     uint32_t pos = 4u * lo + (tid ? s_part[tid - 1] : 0u);
     for (uint32_t i = lo; i < hi; ++i) {
         const uint32_t w = raw_word(in, i, nbytes, bits), n = nbytes - 4u * i < 4u ? nbytes - 4u * i : 4u;

@@ -29,6 +29,15 @@
 //   k_mjd_pixels_direct   4:4:4 and gray: islow IDCT of 3 x 8 (8) blocks, YCbCr -> BGR, no scratch planes                  one wave per eight 8 x 8 MCUs
 //   k_mjd_chroma_islow + k_mjd_pixels_h2v1   4:2:2: the Cb / Cr planes, then islow IDCT of the Y blocks + h2v1 fancy upsampling     one wave per four 16 x 8 MCUs
 // Still refused: progressive, arithmetic-coded, 12-bit, 4:4:0 / 4:1:1, four components.  tests/test_mjpeg_decode_samplings.py pins all of it against Pillow.
+//
+// The kernels are put together from one set of pieces:
+//   lvm_internal.h     wg_inclusive_scan: the 256-thread scan inside k_mjd_intervals, k_mjp_unstuff, k_mjp_scan, k_mjp_dc (and the encoder's kernels)
+//   entropy layer      mjd_stage_luts (the look-up tables into LDS), MjpExit (the exit word of a subsequence, packed and unpacked in one place),
+//                      wg_chunked_scan (k_mjp_scan, k_mjp_dc: 1024 values at a time with a carry); k_mjp_sync keeps the parent's own staging and
+//                      unpacking (measured: HISTORY.md, profiles/r10_mjpeg_decode_refactor_ab.txt)
+//   pixel stage        MjdGeom (frame in MCUs, addresses of the chroma planes), mjd_chroma_word (the gather of the fancy upsamplers),
+//                      mjl_idct_block / mjl_idct_block_inplace, mjd_store_bgr (YCbCr -> BGR, the one place with the constants)
+//   host               mjd_layout ((w, h, sampling) -> MjdSamp + MjdGeom, made by begin, read by enqueue); MjdState owns every buffer as a DevBuf
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -72,21 +81,37 @@ MjdSamp samp_of(uint32_t samp) {
     }
 }
 
+// The frames of a call: size in pixels and in MCUs, the pitches of the BGR output.  The Cb / Cr planes between the two launches of 4:2:0 and 4:2:2 under
+// the libjpeg kind are [frame][Cb, Cr][mh * 8][mw * 8] bytes: whole blocks, so that k_mjd_chroma_islow stores unconditionally.
+struct MjdGeom {
+    int w, h, mw, mh; long stride, fstride;
+    __host__ __device__ int nmcu() const { return mw * mh; }
+    __host__ __device__ size_t chroma_pitch() const { return (size_t)mw * 8; }
+    __host__ __device__ size_t chroma_rows() const { return (size_t)mh * 8; }
+    __host__ __device__ size_t chroma_row(int f, int comp, size_t y) const { return (((size_t)f * 2 + comp) * chroma_rows() + y) * chroma_pitch(); }     // byte offset; comp: 0 Cb, 1 Cr
+};
+// (w, h, sampling of the frame header) -> the MCU and the frames in MCUs; the pitches are the enqueue's
+void mjd_layout(int w, int h, uint32_t samp, MjdSamp& sp, MjdGeom& g) {
+    sp = samp_of(samp);
+    g = MjdGeom{w, h, (w + sp.mcu_w - 1) / sp.mcu_w, (h + sp.mcu_h - 1) / sp.mcu_h, 0, 0};
+}
+
+// Every device buffer is an owning DevBuf: deleting the state frees them.
 struct MjdState {
-    int frames_cap = 0, w = 0, h = 0;
-    uint32_t samp = LVM_MJPEG_SAMPLING_420;   // of the frames the buffers are sized for / of the current begin .. finish sequence
-    MjdFrame* d_frames = nullptr;
+    uint32_t samp = 0;                   // the sampling sp and g were made for (0: none yet)
+    MjdSamp sp{}; MjdGeom g{};           // of the current begin .. finish sequence
+    DevBuf d_frames;                     // MjdFrame[n]
     DevBuf d_bytes;
-    int16_t* d_coef = nullptr;
-    uint32_t *d_ivstart = nullptr, *d_ivend = nullptr, *d_err = nullptr;
-    int iv_cap = 0;
-    int n = 0, max_iv = 1;               // the frames of the current begin .. finish sequence
+    DevBuf d_coef;                       // int16_t[n][nmcu][nblk * 64]
+    DevBuf d_err;                        // uint32_t: n error flags, then the n + 1 frame offsets
+    DevBuf d_ivstart, d_ivend;           // uint32_t[n][max_iv]
+    int n = 0, max_iv = 1;               // the frames of the current begin .. finish sequence, the most intervals one of them has
     // self-synchronising path (frames without restart markers)
     DevBuf d_ubytes;
-    uint32_t *d_ulen = nullptr, *d_before = nullptr, *d_changed = nullptr;
-    unsigned long long* d_exit[2] = {nullptr, nullptr};
-    int sub_cap = 0, par_frames_cap = 0, npar = 0;
-    // LVM_MJPEG_DECODER_LIBJPEG: the Cb / Cr planes between its two launches ([frame][Cb, Cr][mh * 8][mw * 8])
+    DevBuf d_ulen, d_before, d_changed;  // uint32_t[n], [n][sub_cap], [1]
+    DevBuf d_exit[2];                    // unsigned long long[n][sub_cap]
+    int sub_cap = 0;                     // (only grows: it is the grid of the k_mjp_* launches as well)
+    // LVM_MJPEG_DECODER_LIBJPEG: the Cb / Cr planes between its two launches (MjdGeom::chroma_row)
     DevBuf d_chroma;
     int kind = 0;                        // the decoder kind of the current begin .. finish sequence
     std::vector<MjdFrame> frames;
@@ -231,14 +256,7 @@ __global__ __launch_bounds__(256) void k_mjd_intervals(const uint8_t* __restrict
     };
     uint32_t cnt = 0;
     scan([&](uint32_t) { ++cnt; });
-    s_part[tid] = cnt;
-    __syncthreads();
-    for (int dd = 1; dd < 256; dd <<= 1) {
-        const uint32_t t = tid >= dd ? s_part[tid - dd] : 0u;
-        __syncthreads();
-        s_part[tid] += t;
-        __syncthreads();
-    }
+    wg_inclusive_scan(cnt, s_part, tid);
     uint32_t k = tid ? s_part[tid - 1] : 0u;
     uint32_t* st = ivstart + (size_t)f * iv_cap;
     uint32_t* en = ivend + (size_t)f * iv_cap;
@@ -292,7 +310,7 @@ struct MjdBits {
     __device__ __forceinline__ uint32_t get(int n) { if (n == 0) return 0u; fill(); const uint32_t v = peek(n); skip(n); return v; }
 };
 
-// one Huffman symbol (T.81 F.2.2.3); -1 = no such code
+// one Huffman symbol (T.81 F.2.2.3); -1 = no such code.  (mjp_symbol below is its twin over the other bit reader; why they stay two: HISTORY.md)
 __device__ __forceinline__ int mjd_symbol(MjdBits& br, const uint16_t* lut, const MjdHuff& t) {
     br.fill();
     const uint32_t e = lut[br.peek(MJD_LUT_BITS)];
@@ -304,18 +322,23 @@ __device__ __forceinline__ int mjd_symbol(MjdBits& br, const uint16_t* lut, cons
     }
     return -1;
 }
+// the four 9-bit look-up tables of a frame into LDS, by the 64 lanes of a workgroup (ends with a barrier)
+typedef uint16_t MjdLuts[2][2][1 << MJD_LUT_BITS];
+__device__ __forceinline__ void mjd_stage_luts(MjdLuts& s_lut, const MjdFrame& fr, int tid) {
+    for (int i = tid; i < 4 << MJD_LUT_BITS; i += 64) s_lut[i >> (MJD_LUT_BITS + 1)][(i >> MJD_LUT_BITS) & 1][i & ((1 << MJD_LUT_BITS) - 1)] =
+        fr.huff[i >> (MJD_LUT_BITS + 1)][(i >> MJD_LUT_BITS) & 1].lut[i & ((1 << MJD_LUT_BITS) - 1)];
+    __syncthreads();
+}
 __device__ __forceinline__ int mjd_extend(uint32_t v, int s) { return (s == 0 || v >= (1u << (s - 1))) ? (int)v : (int)v - (1 << s) + 1; }
 
 // A lane per restart interval; the 64 lanes of a workgroup are consecutive intervals of ONE frame, whose look-up tables sit in LDS.
 __global__ __launch_bounds__(64) void k_mjd_huffman(const uint8_t* __restrict__ bytes, const MjdFrame* __restrict__ frames, const uint32_t* __restrict__ foff,
                                                     const uint32_t* __restrict__ ivstart, const uint32_t* __restrict__ ivend, int iv_cap, int nmcu,
                                                     int nblk, int ny, int16_t* __restrict__ coef, uint32_t* __restrict__ err) {
-    __shared__ uint16_t s_lut[2][2][1 << MJD_LUT_BITS];
+    __shared__ MjdLuts s_lut;
     const int f = blockIdx.y, tid = threadIdx.x;
     const MjdFrame& fr = frames[f];
-    for (int i = tid; i < 4 << MJD_LUT_BITS; i += 64) s_lut[i >> (MJD_LUT_BITS + 1)][(i >> MJD_LUT_BITS) & 1][i & ((1 << MJD_LUT_BITS) - 1)] =
-        fr.huff[i >> (MJD_LUT_BITS + 1)][(i >> MJD_LUT_BITS) & 1].lut[i & ((1 << MJD_LUT_BITS) - 1)];
-    __syncthreads();
+    mjd_stage_luts(s_lut, fr, tid);
     const uint32_t k = blockIdx.x * 64u + (uint32_t)tid;
     if (k >= fr.nintervals || err[f] || fr.par) return;
     const uint8_t* d = bytes + foff[f] + fr.data_off;
@@ -398,7 +421,7 @@ __device__ __forceinline__ int mjp_symbol(MjpBits& br, const uint16_t* lut, cons
 }
 // One symbol in state (bi = block of the MCU, kk = next coefficient index; kk == 0: a DC code comes next).  Returns the zigzag index of the
 // coefficient it produced (`value`), -1 for a symbol without one, -2 for what the one-lane decoder calls an error.  `done` = the block ended.
-__device__ __forceinline__ int mjp_step(MjpBits& br, int& bi, int& kk, const MjdFrame& fr, const uint16_t (*s_lut)[2][1 << MJD_LUT_BITS], int nblk, int ny, int& value, bool& done) {
+__device__ __forceinline__ int mjp_step(MjpBits& br, int& bi, int& kk, const MjdFrame& fr, const MjdLuts& s_lut, int nblk, int ny, int& value, bool& done) {
     const int comp = bi < ny ? 0 : bi - ny + 1;
     int ci = -1;
     done = false;
@@ -439,14 +462,7 @@ __global__ __launch_bounds__(256) void k_mjp_unstuff(const uint8_t* __restrict__
     const uint32_t per = (n + 255u) / 256u, lo = tid * per, hi = lo + per < n ? lo + per : n;
     uint32_t keep = 0;
     for (uint32_t i = lo; i < hi; ++i) keep += (d[i] == 0 && i > 0 && d[i - 1] == 0xFF) ? 0u : 1u;
-    s_part[tid] = keep;
-    __syncthreads();
-    for (int dd = 1; dd < 256; dd <<= 1) {
-        const uint32_t t = tid >= dd ? s_part[tid - dd] : 0u;
-        __syncthreads();
-        s_part[tid] += t;
-        __syncthreads();
-    }
+    wg_inclusive_scan(keep, s_part, tid);
     uint32_t k = tid ? s_part[tid - 1] : 0u;
     for (uint32_t i = lo; i < hi; ++i) if (!(d[i] == 0 && i > 0 && d[i - 1] == 0xFF)) u[k++] = d[i];
     const uint32_t total = s_part[255];
@@ -454,8 +470,16 @@ __global__ __launch_bounds__(256) void k_mjp_unstuff(const uint8_t* __restrict__
     if (tid == 0) ulen[f] = total;
 }
 
-// exit of a subsequence: bit position in the low half, state and the blocks completed on the way in the high half
-__device__ __forceinline__ unsigned long long mjp_pack(uint32_t pos, int bi, int kk, uint32_t blocks) { return (unsigned long long)pos | ((unsigned long long)(bi * 64 + kk) << 32) | ((unsigned long long)blocks << 41); }
+// exit of a subsequence as the 64-bit word the passes exchange: the bit position in the low half; above it the state (bi * 64 + kk, 9 bits) and the
+// blocks completed on the way
+struct MjpExit {
+    uint32_t pos; int bi, kk; uint32_t blocks;
+    __device__ __forceinline__ unsigned long long pack() const { return (unsigned long long)pos | ((unsigned long long)(bi * 64 + kk) << 32) | ((unsigned long long)blocks << 41); }
+    __device__ __forceinline__ static MjpExit unpack(unsigned long long e) {
+        const int st = (int)((e >> 32) & 511u);
+        return {(uint32_t)e, st >> 6, st & 63, (uint32_t)(e >> 41)};
+    }
+};
 
 __global__ __launch_bounds__(64) void k_mjp_sync(const uint8_t* __restrict__ ubytes, const MjdFrame* __restrict__ frames, const uint32_t* __restrict__ foff,
                                                  const uint32_t* __restrict__ ulen, int sub_cap, int first, int nblk, int ny, const unsigned long long* __restrict__ ein,
@@ -492,9 +516,32 @@ __global__ __launch_bounds__(64) void k_mjp_sync(const uint8_t* __restrict__ uby
         if (mjp_step(br, bi, kk, fr, s_lut, nblk, ny, value, done) == -2) { br.skip(1); continue; }     // (a wrong guess runs into impossible codes: move on)
         blocks += done ? 1u : 0u;
     }
-    const unsigned long long e = mjp_pack(br.pos, bi, kk, blocks);
+    const unsigned long long e = MjpExit{br.pos, bi, kk, blocks}.pack();
     if (first || e != ein[(size_t)f * sub_cap + i]) { if (!first) atomicOr(changed, 1u); }
     eout[(size_t)f * sub_cap + i] = e;
+}
+
+// n values in chunks of 1024 with a carry, by one workgroup of 256 threads: put(i, the sum of get(0 .. i), get(i)) for every i < n_all.  s_v: 1024 elements of LDS,
+// s_part: 256, s_carry: one.
+template <class T, class Get, class Put>
+__device__ __forceinline__ void wg_chunked_scan(int n_all, T* s_v, T* s_part, T* s_carry, int tid, Get get, Put put) {
+    if (tid == 0) *s_carry = 0;
+    __syncthreads();
+    for (int c0 = 0; c0 < n_all; c0 += 1024) {
+        const int n = n_all - c0 < 1024 ? n_all - c0 : 1024;
+        for (int i = tid; i < n; i += 256) s_v[i] = get(c0 + i);
+        __syncthreads();
+        const int per = (n + 255) / 256, lo = tid * per, hi = lo + per < n ? lo + per : n;          // a run of the chunk per thread
+        T sum = 0;
+        for (int i = lo; i < hi; ++i) sum += s_v[i];
+        wg_inclusive_scan(sum, s_part, tid);
+        const T carry = *s_carry;
+        T run = carry + (tid ? s_part[tid - 1] : T(0));
+        for (int i = lo; i < hi; ++i) { put(c0 + i, run, s_v[i]); run += s_v[i]; }
+        __syncthreads();
+        if (tid == 0) *s_carry = carry + s_part[255];
+        __syncthreads();
+    }
 }
 
 // one workgroup per frame: blocks completed before every subsequence
@@ -506,51 +553,26 @@ __global__ __launch_bounds__(256) void k_mjp_scan(const MjdFrame* __restrict__ f
     const int tid = threadIdx.x, f = blockIdx.x;
     if (!frames[f].par) return;
     const int nsub = (int)((ulen[f] * 8u + MJP_SUB_BITS - 1) / MJP_SUB_BITS);
-    if (tid == 0) s_carry = 0;
-    __syncthreads();
-    for (int c0 = 0; c0 < nsub; c0 += 1024) {
-        const int n = nsub - c0 < 1024 ? nsub - c0 : 1024;
-        for (int i = tid; i < n; i += 256) s_v[i] = (uint32_t)(e[(size_t)f * sub_cap + c0 + i] >> 41);
-        __syncthreads();
-        // exclusive scan of s_v[0 .. n)
-        const int per = (n + 255) / 256, lo = tid * per, hi = lo + per < n ? lo + per : n;
-        uint32_t sum = 0;
-        for (int i = lo; i < hi; ++i) sum += s_v[i];
-        s_part[tid] = sum;
-        __syncthreads();
-        for (int dd = 1; dd < 256; dd <<= 1) {
-            const uint32_t t = tid >= dd ? s_part[tid - dd] : 0u;
-            __syncthreads();
-            s_part[tid] += t;
-            __syncthreads();
-        }
-        const uint32_t carry = s_carry;
-        uint32_t run = carry + (tid ? s_part[tid - 1] : 0u);
-        for (int i = lo; i < hi; ++i) { before[(size_t)f * sub_cap + c0 + i] = run; run += s_v[i]; }
-        __syncthreads();
-        if (tid == 0) s_carry = carry + s_part[255];
-        __syncthreads();
-    }
+    wg_chunked_scan(nsub, s_v, s_part, &s_carry, tid, [&](int i) { return MjpExit::unpack(e[(size_t)f * sub_cap + i]).blocks; },
+                    [&](int i, uint32_t sum, uint32_t) { before[(size_t)f * sub_cap + i] = sum; });
 }
 
 __global__ __launch_bounds__(64) void k_mjp_write(const uint8_t* __restrict__ ubytes, const MjdFrame* __restrict__ frames, const uint32_t* __restrict__ foff,
                                                   const uint32_t* __restrict__ ulen, int sub_cap, const unsigned long long* __restrict__ e, const uint32_t* __restrict__ before,
                                                   int nmcu, int nblk, int ny, int16_t* __restrict__ coef, uint32_t* __restrict__ err) {
-    __shared__ uint16_t s_lut[2][2][1 << MJD_LUT_BITS];
+    __shared__ MjdLuts s_lut;
     const int f = blockIdx.y, tid = threadIdx.x;
     const MjdFrame& fr = frames[f];
-    for (int i = tid; i < 4 << MJD_LUT_BITS; i += 64) s_lut[i >> (MJD_LUT_BITS + 1)][(i >> MJD_LUT_BITS) & 1][i & ((1 << MJD_LUT_BITS) - 1)] =
-        fr.huff[i >> (MJD_LUT_BITS + 1)][(i >> MJD_LUT_BITS) & 1].lut[i & ((1 << MJD_LUT_BITS) - 1)];
-    __syncthreads();
+    mjd_stage_luts(s_lut, fr, tid);
     if (!fr.par) return;
     const uint32_t total_bits = ulen[f] * 8u, nsub = (total_bits + MJP_SUB_BITS - 1) / MJP_SUB_BITS, i = blockIdx.x * 64u + (uint32_t)tid;
     if (i >= nsub) return;
     const uint32_t* words = reinterpret_cast<const uint32_t*>(ubytes + ((foff[f] + fr.data_off + 3u) & ~3u));
     uint32_t p0 = 0;
     int bi = 0, kk = 0;
-    if (i > 0) { const unsigned long long x = e[(size_t)f * sub_cap + i - 1]; p0 = (uint32_t)x; const int st = (int)((x >> 32) & 511u); bi = st >> 6; kk = st & 63; }
+    if (i > 0) { const MjpExit x = MjpExit::unpack(e[(size_t)f * sub_cap + i - 1]); p0 = x.pos; bi = x.bi; kk = x.kk; }
     const bool last = i + 1 == nsub;
-    const uint32_t end = last ? total_bits + 64u : (uint32_t)e[(size_t)f * sub_cap + i];
+    const uint32_t end = last ? total_bits + 64u : MjpExit::unpack(e[(size_t)f * sub_cap + i]).pos;
     const uint32_t nall = (uint32_t)nmcu * (uint32_t)nblk;
     uint32_t b = before[(size_t)f * sub_cap + i];
     bool bad = (uint32_t)bi != b % (uint32_t)nblk;                                   // (the state and the count must tell the same story)
@@ -579,33 +601,24 @@ __global__ __launch_bounds__(256) void k_mjp_dc(const MjdFrame* __restrict__ fra
     const int n_all = comp == 0 ? nmcu * ny : nmcu;
     // element el of the component -> its block: the ny luminance blocks lead every MCU, Cb and Cr follow
     auto block_of = [&](int el) { return comp == 0 ? (el / ny) * nblk + el % ny : el * nblk + ny + comp - 1; };
-    if (tid == 0) s_carry = 0;
-    __syncthreads();
-    for (int c0 = 0; c0 < n_all; c0 += 1024) {
-        const int n = n_all - c0 < 1024 ? n_all - c0 : 1024;
-        for (int i = tid; i < n; i += 256) { s_v[i] = c[(size_t)block_of(c0 + i) * 64]; }
-        __syncthreads();
-        const int per = (n + 255) / 256, lo = tid * per, hi = lo + per < n ? lo + per : n;
-        int sum = 0;
-        for (int i = lo; i < hi; ++i) sum += s_v[i];
-        s_part[tid] = sum;
-        __syncthreads();
-        for (int dd = 1; dd < 256; dd <<= 1) {
-            const int t = tid >= dd ? s_part[tid - dd] : 0;
-            __syncthreads();
-            s_part[tid] += t;
-            __syncthreads();
-        }
-        const int carry = s_carry;
-        int run = carry + (tid ? s_part[tid - 1] : 0);
-        for (int i = lo; i < hi; ++i) { run += s_v[i]; c[(size_t)block_of(c0 + i) * 64] = (int16_t)run; }
-        __syncthreads();
-        if (tid == 0) s_carry = carry + s_part[255];
-        __syncthreads();
-    }
+    wg_chunked_scan(n_all, s_v, s_part, &s_carry, tid, [&](int i) { return (int)c[(size_t)block_of(i) * 64]; },
+                    [&](int i, int sum, int v) { c[(size_t)block_of(i) * 64] = (int16_t)(sum + v); });
 }
 
-struct MjdGeom { int w, h, mw, mh; long stride, fstride; };
+// the (Cb | Cr << 16) word of the sample x columns and y rows from cb, a position in a frame's Cb plane; x clamped to the COMPONENT's own width cw: its
+// edge samples are what libjpeg's fancy upsampling replicates, not the padding of the MCUs
+__device__ __forceinline__ uint32_t mjd_chroma_word(const uint8_t* __restrict__ cb, const MjdGeom& g, int y, int x, int cw) {
+    x = x < 0 ? 0 : (x > cw - 1 ? cw - 1 : x);
+    const size_t o = (size_t)y * g.chroma_pitch() + (size_t)x;
+    return (uint32_t)cb[o] | ((uint32_t)cb[g.chroma_row(0, 1, 0) + o] << 16);
+}
+// JFIF YCbCr (samples 0..255) -> the three bytes of a BGR pixel, 16-bit fixed point with rounding, clamped: both kinds' last step
+__device__ __forceinline__ void mjd_store_bgr(uint8_t* o, int y, int cb, int cr) {
+    cb -= 128; cr -= 128;
+    int r = y + ((91881 * cr + 32768) >> 16), g = y + ((-22554 * cb - 46802 * cr + 32768) >> 16), b = y + ((116130 * cb + 32768) >> 16);
+    r = r < 0 ? 0 : (r > 255 ? 255 : r); g = g < 0 ? 0 : (g > 255 ? 255 : g); b = b < 0 ? 0 : (b > 255 ? 255 : b);
+    o[0] = (uint8_t)b; o[1] = (uint8_t)g; o[2] = (uint8_t)r;
+}
 
 // One wave per MCU (four per workgroup): dequantise + un-zigzag (lane = zigzag index), IDCT (48 of the 64 lanes: a column / row of one of
 // the six blocks each), then lane = one 2 x 2 pixel quad with its replicated chroma sample -> four BGR pixels.
@@ -658,8 +671,7 @@ __global__ __launch_bounds__(256) void k_mjd_pixels(const int16_t* __restrict__ 
     __syncthreads();
     if (act) {
         const int qx = lane & 7, qy = lane >> 3;
-        const int cb = s_a[wave][4][lane] - 128, cr = s_a[wave][5][lane] - 128;
-        const int dr = (91881 * cr + 32768) >> 16, dg = (-22554 * cb - 46802 * cr + 32768) >> 16, db = (116130 * cb + 32768) >> 16;
+        const int cb = s_a[wave][4][lane], cr = s_a[wave][5][lane];
         uint8_t* fr_out = dst + (size_t)f * g.fstride;
 #pragma unroll
         for (int dy = 0; dy < 2; ++dy) {
@@ -667,13 +679,8 @@ __global__ __launch_bounds__(256) void k_mjd_pixels(const int16_t* __restrict__ 
 #pragma unroll
             for (int dx = 0; dx < 2; ++dx) {
                 const int lx = 2 * qx + dx, px = mx * 16 + lx;
-                if (py < g.h && px < g.w) {
-                    const int y = s_a[wave][(ly >> 3) * 2 + (lx >> 3)][(ly & 7) * 8 + (lx & 7)];
-                    int r = y + dr, gg = y + dg, b = y + db;
-                    r = r < 0 ? 0 : (r > 255 ? 255 : r); gg = gg < 0 ? 0 : (gg > 255 ? 255 : gg); b = b < 0 ? 0 : (b > 255 ? 255 : b);
-                    uint8_t* o = fr_out + (size_t)py * g.stride + (size_t)px * 3;
-                    o[0] = (uint8_t)b; o[1] = (uint8_t)gg; o[2] = (uint8_t)r;
-                }
+                if (py < g.h && px < g.w)
+                    mjd_store_bgr(fr_out + (size_t)py * g.stride + (size_t)px * 3, s_a[wave][(ly >> 3) * 2 + (lx >> 3)][(ly & 7) * 8 + (lx & 7)], cb, cr);
             }
         }
     }
@@ -710,7 +717,7 @@ __device__ __forceinline__ void mjl_islow_1d(const int* in, int* out, int shift)
     out[2] = (int)(tmp12 + t1 + r) >> shift; out[5] = (int)(tmp12 - t1 + r) >> shift;
     out[3] = (int)(tmp13 + t0 + r) >> shift; out[4] = (int)(tmp13 - t0 + r) >> shift;
 }
-// dequantised coefficients of a block at a[] (natural order) -> samples 0..255 in p[8] of the lane's row y; t[] is the image between the passes.
+// dequantised coefficients of a block at a[] (natural order) -> samples 0..255 in p[8] of the lane's row k; t[] is the image between the passes.
 // Called by all lanes of a workgroup (two barriers); `on` = this lane has a column / row to do.
 __device__ __forceinline__ void mjl_idct_block(const int* a, int* t, bool on, int k, int* p) {
     int d[8], o[8];
@@ -732,6 +739,16 @@ __device__ __forceinline__ void mjl_idct_block(const int* a, int* t, bool on, in
     __syncthreads();
 }
 
+// ... in place: the lane's row of samples goes back into the block's own row of a[] (the callers put a barrier behind it)
+__device__ __forceinline__ void mjl_idct_block_inplace(int* a, int* t, bool on, int k) {
+    int p[8];
+    mjl_idct_block(a, t, on, k, p);
+    if (on) {
+#pragma unroll
+        for (int x = 0; x < 8; ++x) a[k * MJL_ROW + x] = p[x];
+    }
+}
+
 // One wave per four MCUs of an MCU row (sixteen per workgroup): lane = zigzag index while dequantising (coef * q, no clamp -- libjpeg has none), then
 // (block, column / row) of the eight Cb / Cr blocks; every row of a block leaves as one 8-byte store into its plane.
 __global__ __launch_bounds__(256) void k_mjd_chroma_islow(const int16_t* __restrict__ coef, const MjdFrame* __restrict__ frames, MjdGeom g, int nblk, int ny, uint8_t* __restrict__ planes) {
@@ -751,8 +768,7 @@ __global__ __launch_bounds__(256) void k_mjd_chroma_islow(const int16_t* __restr
     int p[8];
     mjl_idct_block(&s_a[wave][b * MJL_BLK], &s_b[wave][b * MJL_BLK], on, k, p);
     if (on) {
-        const size_t pitch = (size_t)g.mw * 8, rows = (size_t)g.mh * 8;
-        uint8_t* o = planes + (((size_t)f * 2 + (b & 1)) * rows + (size_t)my * 8 + k) * pitch + (size_t)mx * 8;      // (8-byte aligned: the pitch is a multiple of 8)
+        uint8_t* o = planes + g.chroma_row(f, b & 1, (size_t)my * 8 + k) + (size_t)mx * 8;      // (8-byte aligned: the pitch is a multiple of 8)
         uint2 v;
         v.x = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
         v.y = (uint32_t)p[4] | ((uint32_t)p[5] << 8) | ((uint32_t)p[6] << 16) | ((uint32_t)p[7] << 24);
@@ -779,26 +795,18 @@ __global__ __launch_bounds__(256) void k_mjd_pixels_libjpeg(const int16_t* __res
 #pragma unroll
         for (int blk = 0; blk < 4; ++blk) s_a[wave][blk * MJL_BLK + at] = in[blk * 64 + lane] * q;
         const int cw = (g.w + 1) >> 1, ch = (g.h + 1) >> 1;
-        const size_t pitch = (size_t)g.mw * 8, rows = (size_t)g.mh * 8;
-        const uint8_t* cbp = planes + (size_t)f * 2 * rows * pitch;
+        const uint8_t* cbp = planes + g.chroma_row(f, 0, 0);
         for (int i = lane; i < 100; i += 64) {
             const int r = i / 10, cc = i - r * 10;
-            int y = my * 8 - 1 + r, x = mx * 8 - 1 + cc;
-            y = y < 0 ? 0 : (y > ch - 1 ? ch - 1 : y); x = x < 0 ? 0 : (x > cw - 1 ? cw - 1 : x);
-            const size_t o = (size_t)y * pitch + (size_t)x;
-            s_c[wave][r * MJL_CROW + cc] = (uint32_t)cbp[o] | ((uint32_t)cbp[rows * pitch + o] << 16);
+            int y = my * 8 - 1 + r;
+            y = y < 0 ? 0 : (y > ch - 1 ? ch - 1 : y);
+            s_c[wave][r * MJL_CROW + cc] = mjd_chroma_word(cbp, g, y, mx * 8 - 1 + cc, cw);
         }
     }
     __syncthreads();
     {
-        const int blk = (lane >> 3) & 3, k = lane & 7;
-        const bool on = act && lane < 32;
-        int p[8];
-        mjl_idct_block(&s_a[wave][blk * MJL_BLK], &s_b[wave][blk * MJL_BLK], on, k, p);
-        if (on) {
-#pragma unroll
-            for (int x = 0; x < 8; ++x) s_a[wave][blk * MJL_BLK + k * MJL_ROW + x] = p[x];
-        }
+        const int blk = (lane >> 3) & 3;
+        mjl_idct_block_inplace(&s_a[wave][blk * MJL_BLK], &s_b[wave][blk * MJL_BLK], act && lane < 32, lane & 7);
     }
     __syncthreads();
     if (act) {
@@ -822,13 +830,8 @@ __global__ __launch_bounds__(256) void k_mjd_pixels_libjpeg(const int16_t* __res
                 const int lx = 2 * qx + dx, px = mx * 16 + lx;
                 if (py < g.h && px < g.w) {
                     const uint32_t both = 3u * cs[1] + cs[dx ? 2 : 0] + (dx ? 0x00070007u : 0x00080008u);
-                    const int cb = (int)((both & 0xFFFFu) >> 4) - 128, cr = (int)(both >> 20) - 128;
-                    const int dr = (91881 * cr + 32768) >> 16, dg = (-22554 * cb - 46802 * cr + 32768) >> 16, db = (116130 * cb + 32768) >> 16;
-                    const int y = s_a[wave][((ly >> 3) * 2 + (lx >> 3)) * MJL_BLK + (ly & 7) * MJL_ROW + (lx & 7)];
-                    int r = y + dr, gg = y + dg, b = y + db;
-                    r = r < 0 ? 0 : (r > 255 ? 255 : r); gg = gg < 0 ? 0 : (gg > 255 ? 255 : gg); b = b < 0 ? 0 : (b > 255 ? 255 : b);
-                    uint8_t* o = fr_out + (size_t)py * g.stride + (size_t)px * 3;
-                    o[0] = (uint8_t)b; o[1] = (uint8_t)gg; o[2] = (uint8_t)r;
+                    mjd_store_bgr(fr_out + (size_t)py * g.stride + (size_t)px * 3, s_a[wave][((ly >> 3) * 2 + (lx >> 3)) * MJL_BLK + (ly & 7) * MJL_ROW + (lx & 7)],
+                                  (int)((both & 0xFFFFu) >> 4), (int)(both >> 20));
                 }
             }
         }
@@ -865,7 +868,7 @@ __global__ __launch_bounds__(256) void k_mjd_pixels_direct(const int16_t* __rest
     __syncthreads();
     const int b = lane >> 3, k = lane & 7;
     const bool on = mx0 + b < g.mw;
-    for (int c = 0; c < nc; ++c) {
+    for (int c = 0; c < nc; ++c) {      // (mjl_idct_block_inplace spelled out: HISTORY.md)
         int p[8];
         int* blk = &s_a[wave][(c * 8 + b) * MJL_BLK];
         mjl_idct_block(blk, &s_t[wave][b * MJL_BLK], on, k, p);
@@ -883,11 +886,7 @@ __global__ __launch_bounds__(256) void k_mjd_pixels_direct(const int16_t* __rest
         for (int r = 0; r < rows; ++r, o += g.stride) {
             const int y = yb[r * MJL_ROW];
             if constexpr (NC == 1) { o[0] = (uint8_t)y; o[1] = (uint8_t)y; o[2] = (uint8_t)y; continue; }          // gray: b = g = r
-            const int cb = yb[8 * MJL_BLK + r * MJL_ROW] - 128, cr = yb[16 * MJL_BLK + r * MJL_ROW] - 128;
-            const int dr = (91881 * cr + 32768) >> 16, dg = (-22554 * cb - 46802 * cr + 32768) >> 16, db = (116130 * cb + 32768) >> 16;
-            int rr = y + dr, gg = y + dg, bb = y + db;
-            rr = rr < 0 ? 0 : (rr > 255 ? 255 : rr); gg = gg < 0 ? 0 : (gg > 255 ? 255 : gg); bb = bb < 0 ? 0 : (bb > 255 ? 255 : bb);
-            o[0] = (uint8_t)bb; o[1] = (uint8_t)gg; o[2] = (uint8_t)rr;
+            mjd_store_bgr(o, y, yb[8 * MJL_BLK + r * MJL_ROW], yb[16 * MJL_BLK + r * MJL_ROW]);
         }
     }
 }
@@ -915,28 +914,15 @@ __global__ __launch_bounds__(256) void k_mjd_pixels_h2v1(const int16_t* __restri
         if (mx0 + (i >> 1) < g.mw) s_a[wave][i * MJL_BLK + at] = in[((size_t)(mx0 + (i >> 1)) * 4 + (i & 1)) * 64 + lane] * q;
     if (mx0 < g.mw) {
         const int cw = (g.w + 1) >> 1;
-        const size_t pitch = (size_t)g.mw * 8, rows = (size_t)g.mh * 8;
-        const uint8_t* cbp = planes + (size_t)f * 2 * rows * pitch + (size_t)(my * 8) * pitch;
+        const uint8_t* cbp = planes + g.chroma_row(f, 0, 0) + (size_t)(my * 8) * g.chroma_pitch();      // (= chroma_row(f, 0, my * 8), which costs a scalar register here)
         for (int i = lane; i < 8 * MJL_HROW; i += 64) {
             const int r = i / MJL_HROW, cc = i - r * MJL_HROW;
-            int x = mx0 * 8 - 1 + cc;
-            x = x < 0 ? 0 : (x > cw - 1 ? cw - 1 : x);
-            const size_t o = (size_t)r * pitch + (size_t)x;
-            s_c[wave][i] = (uint32_t)cbp[o] | ((uint32_t)cbp[rows * pitch + o] << 16);
+            s_c[wave][i] = mjd_chroma_word(cbp, g, r, mx0 * 8 - 1 + cc, cw);
         }
     }
     __syncthreads();
     const int b = lane >> 3, k = lane & 7;
-    {
-        const bool on = mx0 + (b >> 1) < g.mw;
-        int p[8];
-        int* blk = &s_a[wave][b * MJL_BLK];
-        mjl_idct_block(blk, &s_t[wave][b * MJL_BLK], on, k, p);
-        if (on) {
-#pragma unroll
-            for (int x = 0; x < 8; ++x) blk[k * MJL_ROW + x] = p[x];
-        }
-    }
+    mjl_idct_block_inplace(&s_a[wave][b * MJL_BLK], &s_t[wave][b * MJL_BLK], mx0 + (b >> 1) < g.mw, k);
     __syncthreads();
     const int px = mx0 * 16 + lane;
     if (px < g.w) {
@@ -947,12 +933,7 @@ __global__ __launch_bounds__(256) void k_mjd_pixels_h2v1(const int16_t* __restri
         const int rows = g.h - my * 8 < 8 ? g.h - my * 8 : 8;
         for (int r = 0; r < rows; ++r, o += g.stride) {
             const uint32_t both = 3u * s_c[wave][r * MJL_HROW + own] + s_c[wave][r * MJL_HROW + nb] + rnd;
-            const int cb = (int)((both & 0xFFFFu) >> 2) - 128, cr = (int)(both >> 18) - 128;
-            const int dr = (91881 * cr + 32768) >> 16, dg = (-22554 * cb - 46802 * cr + 32768) >> 16, db = (116130 * cb + 32768) >> 16;
-            const int y = yb[r * MJL_ROW];
-            int rr = y + dr, gg = y + dg, bb = y + db;
-            rr = rr < 0 ? 0 : (rr > 255 ? 255 : rr); gg = gg < 0 ? 0 : (gg > 255 ? 255 : gg); bb = bb < 0 ? 0 : (bb > 255 ? 255 : bb);
-            o[0] = (uint8_t)bb; o[1] = (uint8_t)gg; o[2] = (uint8_t)rr;
+            mjd_store_bgr(o, yb[r * MJL_ROW], (int)((both & 0xFFFFu) >> 2), (int)(both >> 18));
         }
     }
 }
@@ -960,11 +941,7 @@ __global__ __launch_bounds__(256) void k_mjd_pixels_h2v1(const int16_t* __restri
 }  // namespace
 
 void mjpeg_decode_release(Ctx* c) {
-    MjdState* st = static_cast<MjdState*>(c->mjpeg_dec);
-    if (!st) return;
-    void* ptrs[] = {st->d_frames, st->d_coef, st->d_ivstart, st->d_ivend, st->d_err, st->d_ulen, st->d_before, st->d_changed, st->d_exit[0], st->d_exit[1]};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    delete st;
+    delete static_cast<MjdState*>(c->mjpeg_dec);
     c->mjpeg_dec = nullptr;
 }
 
@@ -977,8 +954,7 @@ int mjpeg_decode_begin(Ctx* c, const uint8_t* jpegs, const size_t* offsets, int 
     MjdState* st = static_cast<MjdState*>(c->mjpeg_dec);
     if (!st) { st = new MjdState; c->mjpeg_dec = st; }
     st->frames.resize((size_t)n);
-    MjdSamp sp = samp_of(LVM_MJPEG_SAMPLING_420);
-    int mw = 0, mh = 0, nmcu = 0;
+    MjdSamp sp{}; MjdGeom g{};
     std::vector<uint32_t> foff((size_t)n + 1);
     int max_iv = 1, max_sub = 1, npar = 0;
     for (int i = 0; i < n; ++i) {
@@ -989,13 +965,12 @@ int mjpeg_decode_begin(Ctx* c, const uint8_t* jpegs, const size_t* offsets, int 
         if (why) { c->err = std::string("lvm_mjpeg_decode: frame ") + std::to_string(i) + ": " + why; return LVM_ERR_INVALID; }
         if (i == 0) {       // the frames of a call share one sampling, as the frames of a file do: the MCU is a property of the call.  The kind is
                             // checked here, before frames 1.. are parsed: a sampling the kind cannot decode is reported ahead of a later frame's damage
-            sp = samp_of(f.samp);
+            mjd_layout(w, h, f.samp, sp, g);
             if (f.samp != LVM_MJPEG_SAMPLING_420 && c->mjpeg_decoder != LVM_MJPEG_DECODER_LIBJPEG) {
                 c->err = std::string("lvm_mjpeg_decode: frame 0: ") + sp.name + " needs LVM_MJPEG_DECODER_LIBJPEG"; return LVM_ERR_INVALID;
             }
-            mw = (w + sp.mcu_w - 1) / sp.mcu_w; mh = (h + sp.mcu_h - 1) / sp.mcu_h; nmcu = mw * mh;
         }
-        f.nintervals = f.restart ? (uint32_t)((nmcu + (int)f.restart - 1) / (int)f.restart) : 1u;
+        f.nintervals = f.restart ? (uint32_t)((g.nmcu() + (int)f.restart - 1) / (int)f.restart) : 1u;
         if ((int)f.nintervals > max_iv) max_iv = (int)f.nintervals;
         // no restart markers: one lane would decode the whole frame -- the self-synchronising kernels take it (LVM_MJD_PARALLEL=0: never, =2: also tiny frames)
         static const int par_mode = [] { int v = 1; env_switch("LVM_MJD_PARALLEL", v); return v; }();
@@ -1006,119 +981,90 @@ int mjpeg_decode_begin(Ctx* c, const uint8_t* jpegs, const size_t* offsets, int 
     }
     foff[(size_t)n] = (uint32_t)(offsets[n] - offsets[0]);
     const size_t nbytes = offsets[n] - offsets[0];
-    int rc;
-    const uint32_t samp = st->frames[0].samp;
-    if (st->frames_cap < n || st->w != w || st->h != h || st->samp != samp) {
-        LVM_HIP_TRY(c, hipStreamSynchronize(s));
-        st->frames_cap = 0;
-        if ((rc = dev_realloc(c, st->d_frames, (size_t)n)) != LVM_OK) return rc;
-        if ((rc = dev_realloc(c, st->d_coef, (size_t)n * nmcu * sp.nblk * 64)) != LVM_OK) return rc;
-        if ((rc = dev_realloc(c, st->d_err, (size_t)n * 2 + 2)) != LVM_OK) return rc;       // error flags, then the frame offsets (n + 1)
-        st->frames_cap = n; st->w = w; st->h = h; st->samp = samp; st->iv_cap = 0;
-    }
-    if (st->iv_cap < max_iv) {
-        LVM_HIP_TRY(c, hipStreamSynchronize(s));
-        st->iv_cap = 0;
-        if ((rc = dev_realloc(c, st->d_ivstart, (size_t)st->frames_cap * max_iv)) != LVM_OK) return rc;
-        if ((rc = dev_realloc(c, st->d_ivend, (size_t)st->frames_cap * max_iv)) != LVM_OK) return rc;
-        st->iv_cap = max_iv;
-    }
-    if (st->d_bytes.cap < nbytes + 32) {
-        LVM_HIP_TRY(c, hipStreamSynchronize(s));
-        if ((rc = st->d_bytes.reserve(c, nbytes + 32)) != LVM_OK) return rc;           // (+ 32: the word readers look one or two words ahead)
-    }
-    st->npar = npar;
-    if (npar) {
-        if (st->d_ubytes.cap < nbytes + 64) {
-            LVM_HIP_TRY(c, hipStreamSynchronize(s));
-            if ((rc = st->d_ubytes.reserve(c, nbytes + 64)) != LVM_OK) return rc;
-        }
-        if (st->par_frames_cap < n || st->sub_cap < max_sub) {
-            LVM_HIP_TRY(c, hipStreamSynchronize(s));
-            st->par_frames_cap = 0;
-            const int cap = max_sub > st->sub_cap ? max_sub : st->sub_cap;
-            if ((rc = dev_realloc(c, st->d_ulen, (size_t)n)) != LVM_OK) return rc;
-            if ((rc = dev_realloc(c, st->d_before, (size_t)n * cap)) != LVM_OK) return rc;
-            if ((rc = dev_realloc(c, st->d_exit[0], (size_t)n * cap)) != LVM_OK) return rc;
-            if ((rc = dev_realloc(c, st->d_exit[1], (size_t)n * cap)) != LVM_OK) return rc;
-            if (!st->d_changed && (rc = dev_realloc(c, st->d_changed, (size_t)1)) != LVM_OK) return rc;
-            st->par_frames_cap = n; st->sub_cap = cap;
-        }
-    }
+    // What this call needs of every buffer; the self-synchronising path's only with a frame for it, the chroma planes only where the pixel stage has two
+    // launches.  (+ 32 / + 64: the word readers look one or two words ahead.)  A buffer grows to the exact size and keeps no contents; work queued by
+    // an earlier call may still use the old allocation, hence one wait in front of the first growth.
+    const int sub_cap = npar && max_sub > st->sub_cap ? max_sub : st->sub_cap;
+    const size_t par = npar ? (size_t)n : 0, subs = par * (size_t)sub_cap, ivs = (size_t)n * max_iv * sizeof(uint32_t);
+    const bool planes = c->mjpeg_decoder == LVM_MJPEG_DECODER_LIBJPEG && sp.ny > 1;
+    const struct { DevBuf& b; size_t bytes; } need[] = {
+        {st->d_frames, (size_t)n * sizeof(MjdFrame)}, {st->d_coef, (size_t)n * g.nmcu() * sp.nblk * 64 * sizeof(int16_t)}, {st->d_err, ((size_t)n * 2 + 2) * sizeof(uint32_t)},
+        {st->d_ivstart, ivs}, {st->d_ivend, ivs}, {st->d_bytes, nbytes + 32},
+        {st->d_ubytes, npar ? nbytes + 64 : 0}, {st->d_ulen, par * sizeof(uint32_t)}, {st->d_before, subs * sizeof(uint32_t)}, {st->d_changed, npar ? sizeof(uint32_t) : 0},
+        {st->d_exit[0], subs * sizeof(unsigned long long)}, {st->d_exit[1], subs * sizeof(unsigned long long)},
+        {st->d_chroma, planes ? g.chroma_row(n, 0, 0) : 0}};
+    bool grow = false;
+    for (const auto& x : need) grow = grow || x.b.cap < x.bytes;
+    if (grow) LVM_HIP_TRY(c, hipStreamSynchronize(s));
+    for (const auto& x : need) { const int rc = x.b.reserve(c, x.bytes); if (rc != LVM_OK) return rc; }
+    st->samp = st->frames[0].samp; st->sp = sp; st->g = g;
     st->kind = c->mjpeg_decoder;
-    const size_t nchroma = (size_t)n * 2 * ((size_t)mh * 8) * ((size_t)mw * 8);
-    if (st->kind == LVM_MJPEG_DECODER_LIBJPEG && sp.ny > 1 && st->d_chroma.cap < nchroma) {
-        LVM_HIP_TRY(c, hipStreamSynchronize(s));
-        if ((rc = st->d_chroma.reserve(c, nchroma)) != LVM_OK) return rc;
-    }
-    st->n = n; st->max_iv = max_iv;
+    st->n = n; st->max_iv = max_iv; st->sub_cap = sub_cap;
     st->foff = foff;                                             // (stays alive until the copy below has run)
     LVM_HIP_TRY(c, hipMemcpyAsync(st->d_bytes.p, jpegs + offsets[0], nbytes, hipMemcpyHostToDevice, s));
-    LVM_HIP_TRY(c, hipMemcpyAsync(st->d_frames, st->frames.data(), (size_t)n * sizeof(MjdFrame), hipMemcpyHostToDevice, s));
-    LVM_HIP_TRY(c, hipMemsetAsync(st->d_err, 0, (size_t)n * sizeof(uint32_t), s));
-    LVM_HIP_TRY(c, hipMemcpyAsync(st->d_err + n, st->foff.data(), ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    LVM_HIP_TRY(c, hipMemcpyAsync(st->d_frames.p, st->frames.data(), (size_t)n * sizeof(MjdFrame), hipMemcpyHostToDevice, s));
+    LVM_HIP_TRY(c, hipMemsetAsync(st->d_err.p, 0, (size_t)n * sizeof(uint32_t), s));
+    LVM_HIP_TRY(c, hipMemcpyAsync(st->d_err.as<uint32_t>() + n, st->foff.data(), ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     return LVM_OK;
 }
 
 int mjpeg_decode_enqueue(Ctx* c, int f0, int nf, uint8_t* d_bgr, ptrdiff_t stride, ptrdiff_t fstride, hipStream_t s) {
     MjdState* st = static_cast<MjdState*>(c->mjpeg_dec);
     if (!st || f0 < 0 || nf < 1 || f0 + nf > st->n) { c->err = "lvm_mjpeg_decode: enqueue without begin"; return LVM_ERR_INVALID; }
-    const MjdSamp sp = samp_of(st->samp);
-    const int w = st->w, h = st->h, mw = (w + sp.mcu_w - 1) / sp.mcu_w, mh = (h + sp.mcu_h - 1) / sp.mcu_h, nmcu = mw * mh;
+    const MjdSamp& sp = st->sp;
+    MjdGeom g = st->g;
+    g.stride = (long)stride; g.fstride = (long)fstride;
+    const int nmcu = g.nmcu(), mw = g.mw, mh = g.mh;
     const size_t mcu_coefs = (size_t)sp.nblk * 64;
-    const MjdFrame* fr = st->d_frames + f0;
-    const uint32_t* d_foff = st->d_err + st->n + f0;
-    int16_t* coef = st->d_coef + (size_t)f0 * nmcu * mcu_coefs;
-    uint32_t *ivs = st->d_ivstart + (size_t)f0 * st->iv_cap, *ive = st->d_ivend + (size_t)f0 * st->iv_cap, *err = st->d_err + f0;
+    const MjdFrame* fr = st->d_frames.as<MjdFrame>() + f0;
+    uint32_t* err = st->d_err.as<uint32_t>() + f0;
+    const uint32_t* d_foff = err + st->n;
+    int16_t* coef = st->d_coef.as<int16_t>() + (size_t)f0 * nmcu * mcu_coefs;
+    uint32_t *ivs = st->d_ivstart.as<uint32_t>() + (size_t)f0 * st->max_iv, *ive = st->d_ivend.as<uint32_t>() + (size_t)f0 * st->max_iv;
     LVM_HIP_TRY(c, hipMemsetAsync(coef, 0, (size_t)nf * nmcu * mcu_coefs * sizeof(int16_t), s));
-    LVM_LAUNCH(c, "mjd_intervals", k_mjd_intervals, dim3(nf), dim3(256), s, (const uint8_t*)st->d_bytes, fr, d_foff, ivs, ive, st->iv_cap, err);
+    LVM_LAUNCH(c, "mjd_intervals", k_mjd_intervals, dim3(nf), dim3(256), s, (const uint8_t*)st->d_bytes, fr, d_foff, ivs, ive, st->max_iv, err);
     LVM_LAUNCH(c, "mjd_huffman", k_mjd_huffman, dim3((st->max_iv + 63) / 64, nf), dim3(64), s, (const uint8_t*)st->d_bytes, fr, d_foff, (const uint32_t*)ivs,
-               (const uint32_t*)ive, st->iv_cap, nmcu, sp.nblk, sp.ny, coef, err);
+               (const uint32_t*)ive, st->max_iv, nmcu, sp.nblk, sp.ny, coef, err);
     bool any_par = false;
     for (int i = f0; i < f0 + nf; ++i) any_par = any_par || st->frames[(size_t)i].par;
     if (any_par) {
-        const uint32_t* ulen = st->d_ulen + f0;
-        unsigned long long* ex[2] = {st->d_exit[0] + (size_t)f0 * st->sub_cap, st->d_exit[1] + (size_t)f0 * st->sub_cap};
-        uint32_t* before = st->d_before + (size_t)f0 * st->sub_cap;
+        uint32_t *ulen = st->d_ulen.as<uint32_t>() + f0, *before = st->d_before.as<uint32_t>() + (size_t)f0 * st->sub_cap, *d_changed = st->d_changed.as<uint32_t>();
+        unsigned long long* ex[2] = {st->d_exit[0].as<unsigned long long>() + (size_t)f0 * st->sub_cap, st->d_exit[1].as<unsigned long long>() + (size_t)f0 * st->sub_cap};
         const dim3 gsub((unsigned)((st->sub_cap + 63) / 64), (unsigned)nf);
-        LVM_LAUNCH(c, "mjp_unstuff", k_mjp_unstuff, dim3(nf), dim3(256), s, (const uint8_t*)st->d_bytes, fr, d_foff, st->d_ubytes.p, st->d_ulen + f0);
-        LVM_LAUNCH(c, "mjp_sync", k_mjp_sync, gsub, dim3(64), s, (const uint8_t*)st->d_ubytes, fr, d_foff, ulen, st->sub_cap, 1, sp.nblk, sp.ny, (const unsigned long long*)ex[1], ex[0], st->d_changed);
+        LVM_LAUNCH(c, "mjp_unstuff", k_mjp_unstuff, dim3(nf), dim3(256), s, (const uint8_t*)st->d_bytes, fr, d_foff, st->d_ubytes.p, ulen);
+        LVM_LAUNCH(c, "mjp_sync", k_mjp_sync, gsub, dim3(64), s, (const uint8_t*)st->d_ubytes, fr, d_foff, (const uint32_t*)ulen, st->sub_cap, 1, sp.nblk, sp.ny, (const unsigned long long*)ex[1], ex[0], d_changed);
         int cur = 0;                                               // ex[cur] holds the latest exits
         for (int it = 0; it <= st->sub_cap; ++it) {                // (every pass makes at least one more lane exact: sub_cap passes always suffice)
             uint32_t changed = 0;
-            LVM_HIP_TRY(c, hipMemsetAsync(st->d_changed, 0, sizeof(uint32_t), s));
-            LVM_LAUNCH(c, "mjp_sync", k_mjp_sync, gsub, dim3(64), s, (const uint8_t*)st->d_ubytes, fr, d_foff, ulen, st->sub_cap, 0, sp.nblk, sp.ny, (const unsigned long long*)ex[cur], ex[cur ^ 1],
-                       st->d_changed);
-            LVM_HIP_TRY(c, hipMemcpyAsync(&changed, st->d_changed, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            LVM_HIP_TRY(c, hipMemsetAsync(d_changed, 0, sizeof(uint32_t), s));
+            LVM_LAUNCH(c, "mjp_sync", k_mjp_sync, gsub, dim3(64), s, (const uint8_t*)st->d_ubytes, fr, d_foff, (const uint32_t*)ulen, st->sub_cap, 0, sp.nblk, sp.ny, (const unsigned long long*)ex[cur], ex[cur ^ 1],
+                       d_changed);
+            LVM_HIP_TRY(c, hipMemcpyAsync(&changed, d_changed, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
             LVM_HIP_TRY(c, hipStreamSynchronize(s));
             cur ^= 1;
             if (!changed) break;
         }
-        LVM_LAUNCH(c, "mjp_scan", k_mjp_scan, dim3(nf), dim3(256), s, fr, ulen, st->sub_cap, (const unsigned long long*)ex[cur], before);
-        LVM_LAUNCH(c, "mjp_write", k_mjp_write, gsub, dim3(64), s, (const uint8_t*)st->d_ubytes, fr, d_foff, ulen, st->sub_cap, (const unsigned long long*)ex[cur],
+        LVM_LAUNCH(c, "mjp_scan", k_mjp_scan, dim3(nf), dim3(256), s, fr, (const uint32_t*)ulen, st->sub_cap, (const unsigned long long*)ex[cur], before);
+        LVM_LAUNCH(c, "mjp_write", k_mjp_write, gsub, dim3(64), s, (const uint8_t*)st->d_ubytes, fr, d_foff, (const uint32_t*)ulen, st->sub_cap, (const unsigned long long*)ex[cur],
                    (const uint32_t*)before, nmcu, sp.nblk, sp.ny, coef, err);
         LVM_LAUNCH(c, "mjp_dc", k_mjp_dc, dim3(sp.ncomp, nf), dim3(256), s, fr, nmcu, sp.nblk, sp.ny, coef);
     }
-    MjdGeom g;
-    g.w = w; g.h = h; g.mw = mw; g.mh = mh; g.stride = (long)stride; g.fstride = (long)fstride;
-    if (st->samp == LVM_MJPEG_SAMPLING_444 || st->samp == LVM_MJPEG_SAMPLING_GRAY) {
-        if (sp.ncomp == 1) LVM_LAUNCH(c, "mjd_pixels_direct", k_mjd_pixels_direct<1>, dim3((mw + 31) / 32, mh, nf), dim3(256), s, (const int16_t*)coef, fr, g, d_bgr);
-        else LVM_LAUNCH(c, "mjd_pixels_direct", k_mjd_pixels_direct<3>, dim3((mw + 31) / 32, mh, nf), dim3(256), s, (const int16_t*)coef, fr, g, d_bgr);
-        return LVM_OK;
+    // the pixel stage: under the libjpeg kind the samplings with subsampled chroma get their Cb / Cr planes first, then one launch writes the frames
+    const dim3 b256(256);
+    const uint8_t* planes = nullptr;
+    if (st->kind == LVM_MJPEG_DECODER_LIBJPEG && sp.ny > 1) {
+        uint8_t* p = st->d_chroma.p + g.chroma_row(f0, 0, 0);
+        LVM_LAUNCH(c, "mjd_chroma_islow", k_mjd_chroma_islow, dim3((mw + 15) / 16, mh, nf), b256, s, (const int16_t*)coef, fr, g, sp.nblk, sp.ny, p);
+        planes = p;
     }
-    if (st->samp == LVM_MJPEG_SAMPLING_422) {
-        uint8_t* planes = st->d_chroma + (size_t)f0 * 2 * ((size_t)mh * 8) * ((size_t)mw * 8);
-        LVM_LAUNCH(c, "mjd_chroma_islow", k_mjd_chroma_islow, dim3((mw + 15) / 16, mh, nf), dim3(256), s, (const int16_t*)coef, fr, g, sp.nblk, sp.ny, planes);
-        LVM_LAUNCH(c, "mjd_pixels_h2v1", k_mjd_pixels_h2v1, dim3((mw + 15) / 16, mh, nf), dim3(256), s, (const int16_t*)coef, fr, g, (const uint8_t*)planes, d_bgr);
-        return LVM_OK;
+    switch (st->samp) {
+        case LVM_MJPEG_SAMPLING_GRAY: LVM_LAUNCH(c, "mjd_pixels_direct", k_mjd_pixels_direct<1>, dim3((mw + 31) / 32, mh, nf), b256, s, (const int16_t*)coef, fr, g, d_bgr); break;
+        case LVM_MJPEG_SAMPLING_444: LVM_LAUNCH(c, "mjd_pixels_direct", k_mjd_pixels_direct<3>, dim3((mw + 31) / 32, mh, nf), b256, s, (const int16_t*)coef, fr, g, d_bgr); break;
+        case LVM_MJPEG_SAMPLING_422: LVM_LAUNCH(c, "mjd_pixels_h2v1", k_mjd_pixels_h2v1, dim3((mw + 15) / 16, mh, nf), b256, s, (const int16_t*)coef, fr, g, planes, d_bgr); break;
+        default:
+            if (planes) LVM_LAUNCH(c, "mjd_pixels_libjpeg", k_mjd_pixels_libjpeg, dim3((mw + 3) / 4, mh, nf), b256, s, (const int16_t*)coef, fr, g, planes, d_bgr);
+            else LVM_LAUNCH(c, "mjd_pixels", k_mjd_pixels, dim3((mw + 3) / 4, mh, nf), b256, s, (const int16_t*)coef, fr, g, d_bgr);
     }
-    if (st->kind == LVM_MJPEG_DECODER_LIBJPEG) {
-        uint8_t* planes = st->d_chroma + (size_t)f0 * 2 * ((size_t)mh * 8) * ((size_t)mw * 8);
-        LVM_LAUNCH(c, "mjd_chroma_islow", k_mjd_chroma_islow, dim3((mw + 15) / 16, mh, nf), dim3(256), s, (const int16_t*)coef, fr, g, sp.nblk, sp.ny, planes);
-        LVM_LAUNCH(c, "mjd_pixels_libjpeg", k_mjd_pixels_libjpeg, dim3((mw + 3) / 4, mh, nf), dim3(256), s, (const int16_t*)coef, fr, g, (const uint8_t*)planes, d_bgr);
-        return LVM_OK;
-    }
-    LVM_LAUNCH(c, "mjd_pixels", k_mjd_pixels, dim3((mw + 3) / 4, mh, nf), dim3(256), s, (const int16_t*)coef, fr, g, d_bgr);
     return LVM_OK;
 }
 
@@ -1126,7 +1072,7 @@ int mjpeg_decode_finish(Ctx* c, hipStream_t s) {
     MjdState* st = static_cast<MjdState*>(c->mjpeg_dec);
     if (!st) { c->err = "lvm_mjpeg_decode: finish without begin"; return LVM_ERR_INVALID; }
     std::vector<uint32_t> err((size_t)st->n);
-    LVM_HIP_TRY(c, hipMemcpyAsync(err.data(), st->d_err, (size_t)st->n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    LVM_HIP_TRY(c, hipMemcpyAsync(err.data(), st->d_err.p, (size_t)st->n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     LVM_HIP_TRY(c, hipStreamSynchronize(s));
     for (int i = 0; i < st->n; ++i)
         if (err[(size_t)i]) {

@@ -7,6 +7,7 @@ As in tests/test_mjpeg_decode_libjpeg.py the bar is EQUALITY everywhere:
   the HIP kernels                         ==  both                        -- emulation build here, the GPU through the C ABI
 and a file -> file export and a Riesz magnification fed by the device decoder equal, byte for byte, the ones fed by Pillow's frames."""
 import ctypes
+import functools
 import io
 import os
 import subprocess
@@ -148,6 +149,58 @@ def test_samplings_emu_long_streams_without_restart_markers(lvm, emu, name, samp
             assert hd["restart"] == 0 and len(j) - hd["data_start"] > 2048 + 2
         return js
     _decode_and_compare(lvm, emu, *_numpy_alloc(), [(160, 96, 97), (130, 34, 100)], samp, batch=batch)
+
+
+# ---- the second chunk of the chunked scans ---------------------------------------------------------------------------------------------------------------
+# k_mjp_scan and k_mjp_dc scan 1024 values at a time with a carry: a frame reaches their second chunk with more than 1024 subsequences of 1024 bits and more
+# than 1024 blocks of a component.  384 x 256 of uniform noise at quality 100 has 1536 luminance blocks in every sampling and 1198 (gray) .. 3136 (4:4:4)
+# subsequences with libjpeg-turbo's tables; the batch asserts both from the stream it got, so that another encoder cannot make the case vacuous.
+ALL4 = (("4:2:0", S420),) + NEW
+SECOND_CHUNK = (384, 256, 100)
+
+
+@functools.lru_cache(maxsize=None)
+def _second_chunk_batch(w, h, q, samp):
+    j = enc(np.random.default_rng(5).integers(0, 256, (h, w, 3), dtype=np.uint8), q, samp)
+    hd = mo.parse_header(j)
+    assert hd["restart"] == 0 and j[-2:] == b"\xff\xd9"
+    data = j[hd["data_start"]:-2]
+    bits = 8 * (len(data) - data.count(b"\xff\x00"))
+    hs, vs = hd["comps"][0][1:3] if len(hd["comps"]) == 3 else (1, 1)          # (a one-component scan is not interleaved: its factors mean nothing)
+    yblocks = -(-w // (8 * hs)) * -(-h // (8 * vs)) * hs * vs
+    assert bits > 1024 * 1024 and yblocks > 1024, (bits, yblocks)
+    return [j, j]
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle_frame(j):
+    return mo.decode_frame(j)
+
+
+def _second_chunk(lvm, lib, alloc, read, samp):
+    """byte-identical to Pillow under the libjpeg kind (the numpy entropy decoder would take too long here: Pillow alone is the reference); 4:2:0 also
+    under the replicating kind, bit-identical to the oracle's decode_frame"""
+    _decode_and_compare(lvm, lib, alloc, read, [SECOND_CHUNK], samp, ref=False, batch=_second_chunk_batch)
+    if samp != S420:
+        return
+    w, h, q = SECOND_CHUNK
+    js = _second_chunk_batch(w, h, q, samp)
+    want = _oracle_frame(js[0])
+    ctx = lvm.Context(0, 1, lib)
+    try:
+        ctx.mjpeg_set_decoder(REPLICATE)
+        buf = alloc(len(js), h, w * 3)
+        ctx.mjpeg_decode_device(js, w, h, buf[0], stride=w * 3, frame_stride=w * 3 * h)
+        got = read(buf)
+        for k in range(len(js)):
+            assert np.array_equal(got[k].reshape(h, w, 3), want), "replicating kind, stream %d against the oracle" % k
+    finally:
+        ctx.close()
+
+
+@pytest.mark.parametrize("name,samp", ALL4)
+def test_samplings_emu_second_chunk_of_the_scans(lvm, emu, name, samp):
+    _second_chunk(lvm, emu, *_numpy_alloc(), samp)
 
 
 def test_samplings_emu_both_entropy_paths():
@@ -411,6 +464,12 @@ def test_samplings_gpu_322x182_and_1920_wide(lvm, hip, name, samp):
             assert mo.parse_header(js[0])["restart"] == 0 and len(js[0]) > 2048 and mo.parse_header(js[2])["restart"] == 8
         return js
     _decode_and_compare(lvm, hip, *_torch_alloc(), [(322, 182, 90), (1920, 24, 90)], samp, ref=False, batch=batch)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,samp", ALL4)
+def test_samplings_gpu_second_chunk_of_the_scans(lvm, hip, name, samp):
+    _second_chunk(lvm, hip, *_torch_alloc(), samp)
 
 
 @pytest.mark.gpu

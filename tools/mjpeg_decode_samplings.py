@@ -6,8 +6,9 @@ of one MCU row (a lane per interval), 32 frames per call, in ONE process on ONE 
   2. per-launch times (HIP events around the launches, lvm_profile_*) and the mjp_sync launches per call: 1 guessing pass + the passes that changed
      an exit + 1 that confirmed -- the look-back of the first pass (MJP_LOOKBACK) was tuned on 4:2:0, this is where the other samplings are recorded.
 With --parent LIB (a liblvm_hip.so built from the parent commit) it then alternates that library and this one, each on a fresh context of its own and taking turns to go
-first, on the 4:2:0 streams of tools/mjpeg_decode_kinds.py under the libjpeg kind, and prints both sides' per-launch times: the generalised entropy layer
-must not cost the 4:2:0 path anything.
+first: every sampling under the libjpeg kind and 4:2:0 under the replicating kind, each without restart markers and with one interval per MCU row, 4:2:0
+also with the encoder's default intervals of 8 MCUs.  Per case: both sides' call times, whether this library's median lies inside the parent's own
+min .. max, whether the decoded frames are byte-identical, and both sides' per-launch times (to locate a difference, not to judge one).
 Prints to stdout."""
 import ctypes as C
 import importlib
@@ -38,25 +39,6 @@ def pil_encode(f, q, subsampling, **kw):
 def packed(js8, n):
     js = (js8 * ((n + 7) // 8))[:n]
     return np.frombuffer(b"".join(js), np.uint8), (C.c_size_t * (n + 1))(*np.concatenate([[0], np.cumsum([len(j) for j in js])]).tolist())
-
-
-def bind_parent(path):
-    """The parent commit's library with the few functions this tool calls on it: binding.bind() attaches every symbol of this tree's header, and the
-    parent's library does not export lvm_mjpeg_set_samplings."""
-    vp = C.c_void_p
-    old = C.CDLL(path)
-    old.lvm_create.argtypes = [C.c_int, C.c_int, C.POINTER(vp)]
-    old.lvm_destroy.argtypes = [vp]
-    old.lvm_destroy.restype = None
-    old.lvm_last_error.argtypes = [vp]
-    old.lvm_last_error.restype = C.c_char_p
-    old.lvm_mjpeg_set_decoder.argtypes = [vp, C.c_int]
-    old.lvm_mjpeg_decode_device.argtypes = [vp, vp, C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_int, vp, C.c_ssize_t, C.c_ssize_t]
-    old.lvm_profile_enable.argtypes = [vp, C.c_int]
-    old.lvm_profile_collect.argtypes = [vp]
-    old.lvm_profile_only.argtypes = [vp, C.c_char_p]
-    old.lvm_profile_entry.argtypes = [vp, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]
-    return old
 
 
 def main():
@@ -101,21 +83,26 @@ def main():
             if "mjp_sync" in prof and prof["mjp_sync"][1]:
                 print("      mjp_sync passes that changed an exit: %.1f per call" % (prof["mjp_sync"][1] / 5 - 2))
 
+    ctx.close()                                      # (the comparison below runs on fresh contexts: no buffer of the runs above is kept)
     if parent:
-        old = bind_parent(parent)
-        ctx.close()                                  # both sides on a fresh context with the default mask: no buffer of the run above is kept
-        ctx = lvm.Context(0, 1)
-        sides = (("parent", lvm.Context(0, 1, old), old), ("this", ctx, lib))
-        for _n, cx, _l in sides:
-            cx.mjpeg_set_decoder(lvm.MJPEG_DECODER_LIBJPEG)
+        old = lvm.bind(C.CDLL(parent))
+        enc_ctx = lvm.Context(0, 1)
         src = torch.from_numpy(frames).cuda()
-        own8 = ctx.mjpeg_encode_device(C.c_void_p(src.data_ptr()), w, h, 8, quality=90)
-        ctx.mjpeg_set_restart_interval((w + 15) // 16)
-        row = ctx.mjpeg_encode_device(C.c_void_p(src.data_ptr()), w, h, 8, quality=90)
-        ctx.mjpeg_set_restart_interval(0)
-        pil8 = [pil_encode(frames[k], 90, 2) for k in range(8)]
-        print("4:2:0, libjpeg kind, the parent commit's library against this one, alternating call by call (%d timed calls each after 3 warm-up calls):" % (2 * reps))
-        for label, js8 in (("one restart interval per MCU row", row), ("restart intervals of 8 MCUs, the encoder's default", own8), ("libjpeg-turbo's stream, no restart markers", pil8)):
+        own8 = enc_ctx.mjpeg_encode_device(C.c_void_p(src.data_ptr()), w, h, 8, quality=90)       # restart intervals of 8 MCUs, the encoder's default
+        enc_ctx.close()
+        cases = []
+        for kind_name, kind in (("libjpeg kind", lvm.MJPEG_DECODER_LIBJPEG), ("replicating kind", lvm.MJPEG_DECODER_REPLICATE)):
+            for name, mask, sub in SAMPLINGS if kind == lvm.MJPEG_DECODER_LIBJPEG else SAMPLINGS[:1]:
+                cases.append((kind, mask, "%s, %s, no restart markers" % (name, kind_name), [pil_encode(frames[k], 90, sub) for k in range(8)]))
+                cases.append((kind, mask, "%s, %s, one restart interval per MCU row" % (name, kind_name), [pil_encode(frames[k], 90, sub, restart_marker_rows=1) for k in range(8)]))
+                if sub == 2:
+                    cases.append((kind, mask, "%s, %s, restart intervals of 8 MCUs (this encoder's stream)" % (name, kind_name), own8))
+        print("the parent commit's library against this one, alternating call by call (%d timed calls each after 3 warm-up calls), fresh contexts per case:" % (2 * reps))
+        for kind, mask, label, js8 in cases:
+            sides = (("parent", lvm.Context(0, 1, old), old), ("this", lvm.Context(0, 1), lib))
+            for _n, cx, _l in sides:
+                cx.mjpeg_set_decoder(kind)
+                cx.mjpeg_set_samplings(mask)
             blob, offs = packed(js8, n)
             ms = {name: [] for name, _c, _l in sides}
             for it in range(3 + 2 * reps):
@@ -130,6 +117,13 @@ def main():
             po, med = np.sort(ms["parent"]), float(np.median(ms["this"]))
             print("    this library's median lies %s the parent's min .. max (%+.1f %% against the parent's median)" % (
                 "INSIDE" if po[0] <= med <= po[-1] else "OUTSIDE", 100 * (med / np.median(po) - 1)))
+            decoded = []
+            for name, cx, lb in sides:
+                out.fill_(0xEE)
+                timed(cx, lb, blob, offs)
+                decoded.append(out.clone())
+            print("    decoded frames: %s" % ("byte-identical on both sides" if torch.equal(decoded[0], decoded[1]) else "DIFFERENT"))
+            del decoded
             prof = {}
             for name, cx, lb in sides:
                 cx.profile_only(None)
@@ -142,8 +136,8 @@ def main():
                 (t, cnt), (to, co) = prof["this"][kn], prof["parent"].get(kn, (0.0, 0))
                 if (kn.startswith("mjd_") or kn.startswith("mjp_")) and cnt and co:
                     print("      %-20s parent %9.1f us per launch (%.1f launches per call), this %9.1f us (%.1f)" % (kn, 1e3 * to / co, co / 5, 1e3 * t / cnt, cnt / 5))
-        sides[0][1].close()
-    ctx.close()
+            for _n, cx, _l in sides:
+                cx.close()
 
 
 if __name__ == "__main__":
