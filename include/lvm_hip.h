@@ -76,7 +76,17 @@ int  lvm_process(lvm_ctx* ctx, const lvm_params* p, const uint8_t* in, int w, in
 /* Same contract on DEVICE memory for all n_streams streams at once: stream s reads
  * d_in + s*in_stream_stride and writes d_out + s*out_stream_stride (bytes).  Work is enqueued
  * on `hip_stream` (a hipStream_t; NULL = the context's own stream) and NOT synchronised:
- * *produced is decided on the host before any kernel runs.                                 */
+ * *produced is decided on the host before any kernel runs.
+ * Legal layouts: any base pointer (no alignment asked: a view into a larger image, such as a
+ * cv::Mat ROI, is fine); in_stride and out_stride >= w*channels; stream strides of any size,
+ * smaller than a frame included (two streams side by side in one mosaic frame: stride = 2*w*channels,
+ * stream stride = w*channels), but with n_streams > 1 out_stream_stride must be > 0 and the output
+ * rectangles of the streams must not overlap.  Bytes outside the w*channels x h rectangles are never
+ * written.  Dword-aligned pointers and strides with w % 4 == 0 select the vector kernels, everything
+ * else the byte kernels; in the bit-exact flavour the bytes do not depend on that choice.
+ * A row stride that cannot hold its pixels (negative ones included) or a non-positive output
+ * stream stride is refused with LVM_ERR_INVALID before any state changes or any kernel runs:
+ * the next valid frame continues the clip.                                                  */
 int  lvm_process_device(lvm_ctx* ctx, const lvm_params* p, const uint8_t* d_in, int w, int h,
                         int channels, ptrdiff_t in_stride, ptrdiff_t in_stream_stride,
                         uint8_t* d_out, ptrdiff_t out_stride, ptrdiff_t out_stream_stride,
@@ -89,7 +99,11 @@ int  lvm_process_device(lvm_ctx* ctx, const lvm_params* p, const uint8_t* d_in, 
  * temporally batched schedule (Laplace: stateless kernels take the frames as a batch dimension, the
  * IIR kernels walk over them in order with their state in registers) the frames share launches.
  * Byte for byte: for the same frames in the same memory layout every schedule (this call in any
- * lengths, per-frame calls, lvm_process, pipeline depth 1, any stream) writes the same bytes.     */
+ * lengths, per-frame calls, lvm_process, pipeline depth 1, any stream) writes the same bytes.
+ * Layouts as for lvm_process_device, frame strides of any size; the frames share launches only when
+ * they are laid out [frame][stream] (frame stride == n_streams * stream stride, in and out), every
+ * other order (such as [stream][frame]) is processed frame by frame.  A refused layout fails the call
+ * at the first frame it reaches; produced[] of the frames before it stand.                           */
 int  lvm_process_device_frames(lvm_ctx* ctx, const lvm_params* p, int n_frames, const uint8_t* d_in,
                                int w, int h, int channels, ptrdiff_t in_stride,
                                ptrdiff_t in_stream_stride, ptrdiff_t in_frame_stride, uint8_t* d_out,
@@ -377,6 +391,11 @@ int  lvm_profile_collect(lvm_ctx* ctx);
 int  lvm_profile_only(lvm_ctx* ctx, const char* name);
 int  lvm_profile_entry(lvm_ctx* ctx, int idx, char* name, size_t name_cap, double* total_ms,
                        long long* launches);
+/* Which kernels ran under entry idx's report name, comma-separated, where several share one (lap_down0, lap_final,
+ * lab_lut, rz_lab, rz_final, col_down0, col_minmax, col_out): "strips" = the wave-strip kernel, "vec4" = the tiled kernel
+ * with dword-wide frame I/O, "bytes" = the tiled kernel with byte I/O.  Empty for names with one kernel.  The frame's
+ * layout picks among them (see lvm_process_device); the tests use this to see that it picked what the launch code says. */
+int  lvm_profile_variants(lvm_ctx* ctx, int idx, char* variants, size_t cap);
 /* Algorithmic bytes per frame per stream for the current geometry/mode. */
 double lvm_algorithmic_bytes(int mode, int w, int h, int channels, int levels, double framerate);
 

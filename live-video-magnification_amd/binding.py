@@ -105,7 +105,7 @@ class LvmError(RuntimeError):
 SYMBOLS = ["lvm_create", "lvm_destroy", "lvm_reset", "lvm_process", "lvm_process_device", "lvm_process_device_frames", "lvm_set_pipeline", "lvm_flush", "lvm_synchronize",
            "lvm_last_error", "lvm_max_levels", "lvm_optimal_buffer_size", "lvm_butterworth2",
            "lvm_debug_keep_float", "lvm_debug_read_float", "lvm_debug_exact_lab", "lvm_debug_sweep_u8_steps", "lvm_debug_clock_probe_start", "lvm_debug_clock_probe_stop", "lvm_debug_lab_analytic", "lvm_get_lab_lut", "lvm_set_lab_lut", "lvm_profile_enable", "lvm_profile_collect", "lvm_profile_only",
-           "lvm_profile_entry", "lvm_algorithmic_bytes", "lvm_export_geometry", "lvm_export_frames", "lvm_export_set_overlay", "lvm_overlay_device", "lvm_tile_riesz_stage1", "lvm_tile_riesz_planes", "lvm_tile_riesz_stage2",
+           "lvm_profile_entry", "lvm_profile_variants", "lvm_algorithmic_bytes", "lvm_export_geometry", "lvm_export_frames", "lvm_export_set_overlay", "lvm_overlay_device", "lvm_tile_riesz_stage1", "lvm_tile_riesz_planes", "lvm_tile_riesz_stage2",
            "lvm_preprocess_geometry", "lvm_preprocess_device", "lvm_chain_process", "lvm_chain_process_batch",
            "lvm_set_max_frames", "lvm_host_alloc", "lvm_host_free", "lvm_compose_geometry", "lvm_compose_device", "lvm_chain_process_batch_ex",
            "lvm_chain_present", "lvm_mjpeg_bound", "lvm_mjpeg_encode_device", "lvm_export_frames_mjpeg", "lvm_mjpeg_decode_device", "lvm_export_mjpeg_frames", "lvm_mjpeg_set_restart_interval", "lvm_mjpeg_set_decoder", "lvm_mjpeg_set_samplings"]
@@ -148,6 +148,7 @@ def bind(lib):
     lib.lvm_profile_only.argtypes = [vp, C.c_char_p]
     lib.lvm_profile_entry.argtypes = [vp, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_double),
                                       C.POINTER(C.c_longlong)]
+    lib.lvm_profile_variants.argtypes = [vp, C.c_int, C.c_char_p, C.c_size_t]
     lib.lvm_algorithmic_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double]
     lib.lvm_algorithmic_bytes.restype = C.c_double
     ip = C.POINTER(C.c_int)
@@ -560,6 +561,18 @@ class Context:
             cnt = C.c_longlong()
             self.lib.lvm_profile_entry(self.h, i, name, 64, C.byref(ms), C.byref(cnt))
             out[name.value.decode()] = (ms.value, cnt.value)
+        return out
+
+    def profile_variants(self):
+        """{report name: set of kernel variants launched under it ("strips" / "vec4" / "bytes")} for the names several kernels share"""
+        n = self.lib.lvm_profile_collect(self.h)
+        out = {}
+        for i in range(max(n, 0)):
+            name, var = C.create_string_buffer(64), C.create_string_buffer(64)
+            self.lib.lvm_profile_entry(self.h, i, name, 64, None, None)
+            self._check(self.lib.lvm_profile_variants(self.h, i, var, 64))
+            if var.value:
+                out[name.value.decode()] = set(var.value.decode().split(","))
         return out
 
 

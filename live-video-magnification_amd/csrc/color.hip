@@ -1294,14 +1294,14 @@ static void col_down(Ctx* c, ColorState* st, const FrameIO& io, const ColBufs& B
         l = 2;
     } else if (vec4 && st->d0_rows_on && d0_tasks > 0) {   // wave strips with DPP halo exchange (pyramid.h)
         const dim3 gridr((unsigned)((d0_tasks + D0R_THREADS / 64 - 1) / (D0R_THREADS / 64)));
-        LVM_LAUNCH(c, "col_down0", (k_down0_rows<false, FL_LUT_EXACT>), gridr, dim3(D0R_THREADS), s, io.d_in, (long)io.in_stride, (long)io.in_sstride,
+        LVM_LAUNCH_V(c, "col_down0", "strips", (k_down0_rows<false, FL_LUT_EXACT>), gridr, dim3(D0R_THREADS), s, io.d_in, (long)io.in_stride, (long)io.in_sstride,
                    w, h, B.G[1], g1.w, g1.h, c->lab, d0_sx, (g1.h + d0_rows - 1) / d0_rows, (int)d0_tasks, d0_rows, LabPlanes{nullptr, nullptr});
     } else if (vec4) {
         auto kv = k_down0_v4<false, FL_LUT_EXACT>;
-        LVM_LAUNCH(c, "col_down0", kv, grid0, blk, s, io.d_in, (long)io.in_stride, (long)io.in_sstride, w, h, B.G[1], g1.w, g1.h, c->lab, LabPlanes{nullptr, nullptr});
+        LVM_LAUNCH_V(c, "col_down0", "vec4", kv, grid0, blk, s, io.d_in, (long)io.in_stride, (long)io.in_sstride, w, h, B.G[1], g1.w, g1.h, c->lab, LabPlanes{nullptr, nullptr});
     } else {
         auto kd0 = (C == 3) ? k_down0<3, false, FL_LUT_EXACT> : k_down0<1, false, FL_LUT_EXACT>;
-        LVM_LAUNCH(c, "col_down0", kd0, grid0, blk, s, io.d_in, (long)io.in_stride, (long)io.in_sstride, w, h, B.G[1], g1.w, g1.h, c->lab, 1.0f, LabPlanes{nullptr, nullptr});
+        LVM_LAUNCH_V(c, "col_down0", "bytes", kd0, grid0, blk, s, io.d_in, (long)io.in_stride, (long)io.in_sstride, w, h, B.G[1], g1.w, g1.h, c->lab, 1.0f, LabPlanes{nullptr, nullptr});
     }
     while (l < levels) {            // two pyramid levels per launch while possible
         if (st->g[l].w % 4 == 0 && (long)st->g[l].n * planes >= st->rows_min_elems) {
@@ -1440,18 +1440,18 @@ static void col_up_out(Ctx* c, ColorState* st, const FrameIO& io, const ColBufs&
             if (a.dbg) LVM_LAUNCH(c, "col_out_u2", (k_col_out_strips<true, true>), g2, blk, s, a, sx, sy, (int)ntasks, rows);
             else LVM_LAUNCH(c, "col_out_u2", (k_col_out_strips<true, false>), g2, blk, s, a, sx, sy, (int)ntasks, rows);
         } else {
-            LVM_LAUNCH(c, "col_minmax", (k_col_out_rows<false, false>), g2, blk, s, a, sx, sy, (int)ntasks, rows);
-            if (a.dbg) LVM_LAUNCH(c, "col_out", (k_col_out_rows<true, true>), g2, blk, s, a, sx, sy, (int)ntasks, rows);
-            else LVM_LAUNCH(c, "col_out", (k_col_out_rows<true, false>), g2, blk, s, a, sx, sy, (int)ntasks, rows);
+            LVM_LAUNCH_V(c, "col_minmax", "strips", (k_col_out_rows<false, false>), g2, blk, s, a, sx, sy, (int)ntasks, rows);
+            if (a.dbg) LVM_LAUNCH_V(c, "col_out", "strips", (k_col_out_rows<true, true>), g2, blk, s, a, sx, sy, (int)ntasks, rows);
+            else LVM_LAUNCH_V(c, "col_out", "strips", (k_col_out_rows<true, false>), g2, blk, s, a, sx, sy, (int)ntasks, rows);
         }
     } else if (vec4) {
-        LVM_LAUNCH(c, "col_minmax", k_col_out_v4<false>, grid, blk, s, a);
-        LVM_LAUNCH(c, "col_out", k_col_out_v4<true>, grid, blk, s, a);
+        LVM_LAUNCH_V(c, "col_minmax", "vec4", k_col_out_v4<false>, grid, blk, s, a);
+        LVM_LAUNCH_V(c, "col_out", "vec4", k_col_out_v4<true>, grid, blk, s, a);
     } else {
         auto k1 = (C == 3) ? k_col_out<3, false> : k_col_out<1, false>;
         auto k2 = (C == 3) ? k_col_out<3, true> : k_col_out<1, true>;
-        LVM_LAUNCH(c, "col_minmax", k1, grid, blk, s, a);
-        LVM_LAUNCH(c, "col_out", k2, grid, blk, s, a);
+        LVM_LAUNCH_V(c, "col_minmax", "bytes", k1, grid, blk, s, a);
+        LVM_LAUNCH_V(c, "col_out", "bytes", k2, grid, blk, s, a);
     }
 }
 

@@ -110,7 +110,7 @@ void lab_lut_planes(Ctx* c, const uint8_t* d_in, long in_stride, long in_sstride
     blocks = (units + per - 1) / per;
     if (blocks < 1) blocks = 1;
     auto k = vec ? (Lf ? k_lab_planes<true, true> : k_lab_planes<true, false>) : (Lf ? k_lab_planes<false, true> : k_lab_planes<false, false>);
-    LVM_LAUNCH(c, "lab_lut", k, dim3((unsigned)blocks), dim3(LC_THREADS), s, d_in, in_stride, in_sstride, w, h, nframes, c->lab_lut, iL, Lf, iab, (int)per);
+    LVM_LAUNCH_V(c, "lab_lut", vec ? "vec4" : "bytes", k, dim3((unsigned)blocks), dim3(LC_THREADS), s, d_in, in_stride, in_sstride, w, h, nframes, c->lab_lut, iL, Lf, iab, (int)per);
 }
 
 // ---- lvm_debug_sweep_u8_steps: the step table against the operations it replaces, float by float ---------------------------------

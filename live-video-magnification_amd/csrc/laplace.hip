@@ -1144,15 +1144,15 @@ static void lap_stage_b(Ctx* c, LaplaceState* st, const lvm_params& p, const Fra
     } else if (lap_vec4(io) && st->d0_rows_on && d0_tasks > 0) {
         auto kd0 = LVM_FL_PICK(fl, k_down0_rows, true);
         const dim3 gridr((unsigned)((d0_tasks + D0R_THREADS / 64 - 1) / (D0R_THREADS / 64)));
-        LVM_LAUNCH(c, "lap_down0", kd0, gridr, dim3(D0R_THREADS), s, io.d_in, (long)io.in_stride, (long)io.in_sstride, io.w, io.h,
+        LVM_LAUNCH_V(c, "lap_down0", "strips", kd0, gridr, dim3(D0R_THREADS), s, io.d_in, (long)io.in_stride, (long)io.in_sstride, io.w, io.h,
                    G[1], g1.w, g1.h, c->lab, d0_sx, (g1.h + d0_rows - 1) / d0_rows, (int)d0_tasks, d0_rows, lp);
     } else if (lap_vec4(io)) {
         auto kd0 = LVM_FL_PICK(fl, k_down0_v4, true);
-        LVM_LAUNCH(c, "lap_down0", kd0, grid0, blk, s, io.d_in, (long)io.in_stride, (long)io.in_sstride, io.w, io.h,
+        LVM_LAUNCH_V(c, "lap_down0", "vec4", kd0, grid0, blk, s, io.d_in, (long)io.in_stride, (long)io.in_sstride, io.w, io.h,
                    G[1], g1.w, g1.h, c->lab, lp);
     } else {
         auto kd0 = (C == 3) ? LVM_FL_PICK(fl, k_down0, 3, true) : k_down0<1, false, FL_LUT_EXACT>;
-        LVM_LAUNCH(c, "lap_down0", kd0, grid0, blk, s, io.d_in, (long)io.in_stride, (long)io.in_sstride, io.w, io.h,
+        LVM_LAUNCH_V(c, "lap_down0", "bytes", kd0, grid0, blk, s, io.d_in, (long)io.in_stride, (long)io.in_sstride, io.w, io.h,
                    G[1], g1.w, g1.h, c->lab, c->lab.a255, lp);
     }
     const bool use_tail = st->tailT && B.nt == 1 && !B.no_tail && !lap_split_now(st, B, first);   // batched frames: every level gets many workgroups anyway
@@ -1317,9 +1317,9 @@ static void lap_stage_a(Ctx* c, LaplaceState* st, const lvm_params& p, const Fra
         const dim3 grid4((unsigned)(groups < cap ? groups : cap)), blk4(FIN_THREADS);
         const FinArgs fa{io.d_in, (long)io.in_stride, (long)io.in_sstride, io.d_out, (long)io.out_stride, (long)io.out_sstride, io.w, io.h, cur1, w1, h1,
                          c->lab, ca, sx, sy, NS, rows, dbg, lp};
-        LVM_LAUNCH(c, "lap_final", kf4, grid4, blk4, s, fa);
+        LVM_LAUNCH_V(c, "lap_final", "strips", kf4, grid4, blk4, s, fa);
     } else {
-        LVM_LAUNCH(c, "lap_final", kf, grid, blk, s, io.d_in, (long)io.in_stride, (long)io.in_sstride, io.d_out,
+        LVM_LAUNCH_V(c, "lap_final", "bytes", kf, grid, blk, s, io.d_in, (long)io.in_stride, (long)io.in_sstride, io.d_out,
                    (long)io.out_stride, (long)io.out_sstride, io.w, io.h, cur1, w1, h1, c->lab, ca, tx, ty, NS, dbg, lp);
     }
 }

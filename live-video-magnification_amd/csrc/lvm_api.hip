@@ -27,6 +27,12 @@ void prof_begin(Ctx* c, const char* name, hipStream_t s) {
     (void)hipEventRecord(e.e0, s);
     c->prof_events.push_back(e);
 }
+void prof_variant(Ctx* c, const char* variant) {      // of the launch prof_begin has just opened
+    if (c->prof_skip) return;
+    auto& v = c->prof_totals[c->prof_events.back().name].variants;
+    for (const auto& x : v) if (x == variant) return;
+    v.emplace_back(variant);
+}
 void prof_end(Ctx* c, hipStream_t s) { if (!c->prof_skip) (void)hipEventRecord(c->prof_events.back().e1, s); }
 
 // Waits for everything this context has enqueued -- on its own two streams and on caller streams: one event PER DISTINCT
@@ -125,6 +131,16 @@ int ensure_float(Ctx* c, size_t count) {
     return LVM_OK;
 }
 
+// The layouts the device surfaces take (include/lvm_hip.h): rows that hold their pixels (compose_device's rule); stream strides are
+// free -- two streams side by side in one mosaic frame have a stream stride of one row -- except that the outputs of several
+// streams must not land on each other.  Null: fine.
+static const char* layout_error(const FrameIO& io, int nstreams) {
+    const ptrdiff_t row = (ptrdiff_t)io.w * io.channels;
+    if (io.in_stride < row || io.out_stride < row) return "frame stride too small";
+    if (nstreams > 1 && io.out_sstride <= 0) return "stream stride too small";
+    return nullptr;
+}
+
 // MagnificationProcessor::process (MagnificationProcessor.cpp:17-67) on device buffers
 static int process_device(Ctx* c, const lvm_params* p, const FrameIO& io, hipStream_t s, int* produced) {
     *produced = 0;
@@ -143,6 +159,8 @@ static int process_device(Ctx* c, const lvm_params* p, const FrameIO& io, hipStr
     if (io.d_out == nullptr) { c->err = "null output"; return LVM_ERR_INVALID; }
     const StructKey key = struct_key(*p, io.w, io.h, io.channels);                      // :32-34
     if (key.levels < 1) return LVM_OK;
+    // the kernels address rows and streams with unsigned offsets: refuse what they cannot walk before any state is touched
+    if (const char* why = layout_error(io, c->nstreams)) { c->err = why; return LVM_ERR_INVALID; }
     if (key != c->tracked) {                                                            // MagnifyCore.hpp:53-65
         // buffers of the old geometry may still be in use by queued kernels
         if (c->state) (void)c->state->flush(c, s);                       // pipelined mode: do not lose the pending frame
@@ -277,7 +295,8 @@ int lvm_process_device_frames(lvm_ctx* c, const lvm_params* p, int n_frames, con
     if (!c || !p || !produced || n_frames < 1) return LVM_ERR_INVALID;
     LVM_HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
-    if (c->keep_float && w > 0 && h > 0 && (channels == 1 || channels == 3)) {   // the batched schedules keep the first frame of a batch
+    if (c->keep_float && w > 0 && h > 0 && (channels == 1 || channels == 3) &&         // the batched schedules keep the first frame of a batch
+        !lvm::layout_error(lvm::FrameIO{d_in, in_stride, in_stream_stride, d_out, out_stride, out_stream_stride, w, h, channels}, c->nstreams)) {   // (a refused layout reserves nothing)
         const int rc = lvm::ensure_float(c, (size_t)w * h * channels);
         if (rc != LVM_OK) return rc;
     }
@@ -290,7 +309,8 @@ int lvm_process_device_frames(lvm_ctx* c, const lvm_params* p, int n_frames, con
         const int left = n_frames - f;
         const bool same = d_in && d_out && lvm::struct_key(*p, w, h, channels) == c->tracked;
         const bool layout = in_frame_stride == in_stream_stride * c->nstreams && out_frame_stride == out_stream_stride * c->nstreams;
-        const int nb = (left >= 2 && same && layout && c->state) ? c->state->batch_frames(c, *p, io, left) : 0;
+        // (a layout the per-frame path refuses is left to it: it reports the error)
+        const int nb = (left >= 2 && same && layout && c->state && !lvm::layout_error(io, c->nstreams)) ? c->state->batch_frames(c, *p, io, left) : 0;
         if (nb > 0) {
             const int rc = c->state->process_frames(c, *p, io, nb, s);
             lvm::mark_enqueued(c, s);
@@ -948,6 +968,14 @@ int lvm_profile_entry(lvm_ctx* c, int idx, char* name, size_t cap, double* total
     if (name && cap) { std::snprintf(name, cap, "%s", t.name.c_str()); }
     if (total_ms) *total_ms = t.ms;
     if (launches) *launches = t.n;
+    return LVM_OK;
+}
+
+int lvm_profile_variants(lvm_ctx* c, int idx, char* variants, size_t cap) {
+    if (!c || idx < 0 || idx >= (int)c->prof_totals.size() || !variants || !cap) return LVM_ERR_INVALID;
+    std::string all;
+    for (const auto& v : c->prof_totals[idx].variants) { if (!all.empty()) all += ','; all += v; }
+    std::snprintf(variants, cap, "%s", all.c_str());
     return LVM_OK;
 }
 

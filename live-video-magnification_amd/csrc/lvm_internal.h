@@ -429,7 +429,7 @@ __device__ __forceinline__ float pyrup_h(const float* s, int gx, int sx0, int sw
 // host-side context
 // ---------------------------------------------------------------------------------------
 struct ProfEvent { int name; hipEvent_t e0, e1; };
-struct ProfTotal { std::string name; double ms = 0; long long n = 0; };
+struct ProfTotal { std::string name; double ms = 0; long long n = 0; std::vector<std::string> variants; };   // variants: which kernels ran under the name
 
 struct LevelGeom { int w, h; size_t n; };   // n = w*h
 
@@ -548,6 +548,7 @@ void fail_state(Ctx* c, hipStream_t s);
 int ensure_float(Ctx* c, size_t count);
 void prof_begin(Ctx* c, const char* name, hipStream_t s);
 void prof_end(Ctx* c, hipStream_t s);
+void prof_variant(Ctx* c, const char* variant);
 
 #define LVM_HIP_TRY(c, expr)                                                              \
     do {                                                                                  \
@@ -631,8 +632,14 @@ struct LName {
         hipLaunchKernelGGL(kern, grid, block, 0, (stream), __VA_ARGS__);                  \
         if ((c)->profiling) lvm::prof_end((c), (stream));                                 \
     } while (0)
-
-
+// The same where several kernels share one report name (the name is what bench.py and the measurement tools key on): `var` says which
+// one ran -- "strips" (wave strips), "vec4" (tiled, dword-wide frame I/O), "bytes" (tiled, byte I/O) -- for lvm_profile_variants.
+#define LVM_LAUNCH_V(c, nm, var, kern, grid, block, stream, ...)                          \
+    do {                                                                                  \
+        if ((c)->profiling) { lvm::prof_begin((c), nm, (stream)); lvm::prof_variant((c), var); } \
+        hipLaunchKernelGGL(kern, grid, block, 0, (stream), __VA_ARGS__);                  \
+        if ((c)->profiling) lvm::prof_end((c), (stream));                                 \
+    } while (0)
 
 // labconv.hip: u8 BGR frames -> integer Lab planes (exactly one of iL / Lf is non-null)
 void lab_lut_planes(Ctx* c, const uint8_t* d_in, long in_stride, long in_sstride, int w, int h, int nframes, uint16_t* iL, float* Lf,

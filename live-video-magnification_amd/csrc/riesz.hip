@@ -1605,10 +1605,10 @@ static void rz_build(Ctx* c, RieszState* st, const FrameIO& io, const RzBufs& B,
         lab_lut_planes(c, io.d_in, (long)io.in_stride, (long)io.in_sstride, w, h, NZ, nullptr, B.oct[0], B.iab, s);
     } else if (w % 4 == 0 && io.in_stride % 4 == 0 && io.in_sstride % 4 == 0 && ((uintptr_t)io.d_in % 4) == 0) {
         const long groups = (long)(w / 4) * h;
-        LVM_LAUNCH(c, "rz_lab", k_rz_lab4, dim3((unsigned)((groups + 256 * kLabIters - 1) / (256 * kLabIters)), NZ), blk, s, io.d_in,
+        LVM_LAUNCH_V(c, "rz_lab", "vec4", k_rz_lab4, dim3((unsigned)((groups + 256 * kLabIters - 1) / (256 * kLabIters)), NZ), blk, s, io.d_in,
                    (long)io.in_stride, (long)io.in_sstride, w, h, B.oct[0], c->lab);
     } else {
-        LVM_LAUNCH(c, "rz_lab", k_rz_lab, dim3((w + 255) / 256, h, NZ), blk, s, io.d_in, (long)io.in_stride, (long)io.in_sstride, w, h, B.oct[0], c->lab);
+        LVM_LAUNCH_V(c, "rz_lab", "bytes", k_rz_lab, dim3((w + 255) / 256, h, NZ), blk, s, io.d_in, (long)io.in_stride, (long)io.in_sstride, w, h, B.oct[0], c->lab);
     }
     for (int l = 0; l < nb; ++l) {
         const LevelGeom &a = st->g[l], &b = st->g[l + 1];
@@ -1804,13 +1804,13 @@ static void rz_collapse_out(Ctx* c, RieszState* st, const lvm_params& p, const F
         strips_geom(ca, st->g[0], st->g[1]);
         auto kf = fl == FL_LUT_EXACT ? (dbg ? k_rz_collapse_strips<true, FL_LUT_EXACT, true> : k_rz_collapse_strips<true, FL_LUT_EXACT, false>)
                                      : (dbg ? k_rz_collapse_strips<true, FL_LUT_FAST, true> : k_rz_collapse_strips<true, FL_LUT_FAST, false>);
-        LVM_LAUNCH(c, "rz_final", kf, dim3((unsigned)((ca.ntasks + CS_THREADS / 64 - 1) / (CS_THREADS / 64))), dim3(CS_THREADS), s, ca);
+        LVM_LAUNCH_V(c, "rz_final", "strips", kf, dim3((unsigned)((ca.ntasks + CS_THREADS / 64 - 1) / (CS_THREADS / 64))), dim3(CS_THREADS), s, ca);
     } else if (nb >= 1)
-        LVM_LAUNCH(c, "rz_final", kfb, grid, blk, s, io.d_in, (long)io.in_stride, (long)io.in_sstride, io.d_out,
+        LVM_LAUNCH_V(c, "rz_final", vec ? "vec4" : "bytes", kfb, grid, blk, s, io.d_in, (long)io.in_stride, (long)io.in_sstride, io.d_out,
                    (long)io.out_stride, (long)io.out_sstride, w, h, (const float*)B.pf[0][F_BANDA], resn, st->g[1].w, st->g[1].h,
                    c->lab, tx, ty, NZ, dbg, (const float*)B.oct[0], (const uint32_t*)B.iab);
     else
-        LVM_LAUNCH(c, "rz_final", kfn, grid, blk, s, io.d_in, (long)io.in_stride, (long)io.in_sstride, io.d_out,
+        LVM_LAUNCH_V(c, "rz_final", vec ? "vec4" : "bytes", kfn, grid, blk, s, io.d_in, (long)io.in_stride, (long)io.in_sstride, io.d_out,
                    (long)io.out_stride, (long)io.out_sstride, w, h, (const float*)nullptr, (const float*)nullptr, 0, 0,
                    c->lab, tx, ty, NZ, dbg, (const float*)B.oct[0], (const uint32_t*)B.iab);
 }

@@ -23,61 +23,68 @@ __device__ __forceinline__ bool buf_in_range(const BufRsrc& r, uint32_t voff, ui
     if ((uint64_t)voff + soff + n > r.bytes) { std::fprintf(stderr, "hip-emu: raw buffer access with voff %u in range but voff + soff = %llu outside %u bytes: out of bounds on the GPU\n", voff, (unsigned long long)voff + soff, r.bytes); std::abort(); }
     return true;
 }
+// The vector kernels are launched only where the launch code found row strides, stream strides AND base pointers to be multiples of 4
+// (lap_vec4 and its kin): every dword-wide access they make is then dword-aligned.  Whether a misaligned one works on the GPU
+// depends on the alignment mode the driver sets, so the emulation holds the kernels to that promise and aborts on the first
+// misaligned dword access -- a launch test that lets a byte layout through to a vector kernel does not pass quietly.
+__device__ __forceinline__ void buf_aligned(const void* p) {
+    if ((uintptr_t)p % 4 != 0) { std::fprintf(stderr, "hip-emu: dword-wide access at %p, not a multiple of 4: a vector kernel was launched on a byte layout\n", p); std::abort(); }
+}
 __device__ __forceinline__ BufRsrc buf_rsrc(const void* base, uint32_t bytes) { return BufRsrc{(char*)base, bytes}; }
 __device__ __forceinline__ float buf_ld_f32(const BufRsrc& r, uint32_t voff, uint32_t soff) {
     const uint64_t o = (uint64_t)voff + soff;
     float v = 0.f;
-    if (buf_in_range(r, voff, soff, 4)) std::memcpy(&v, r.base + o, 4);
+    if (buf_in_range(r, voff, soff, 4)) { buf_aligned(r.base + o); std::memcpy(&v, r.base + o, 4); }
     return v;
 }
 __device__ __forceinline__ B96 buf_ld_b96(const BufRsrc& r, uint32_t voff, uint32_t soff) {
     const uint64_t o = (uint64_t)voff + soff;
     B96 v{0, 0, 0};
-    if (buf_in_range(r, voff, soff, 12)) std::memcpy(&v, r.base + o, 12);
+    if (buf_in_range(r, voff, soff, 12)) { buf_aligned(r.base + o); std::memcpy(&v, r.base + o, 12); }
     return v;
 }
 __device__ __forceinline__ float4 buf_ld_f32x4(const BufRsrc& r, uint32_t voff, uint32_t soff) {
     const uint64_t o = (uint64_t)voff + soff;
     float v[4] = {0.f, 0.f, 0.f, 0.f};
-    if (buf_in_range(r, voff, soff, 16)) std::memcpy(v, r.base + o, 16);
+    if (buf_in_range(r, voff, soff, 16)) { buf_aligned(r.base + o); std::memcpy(v, r.base + o, 16); }
     return make_float4(v[0], v[1], v[2], v[3]);
 }
 __device__ __forceinline__ lvm_f2 buf_ld_f32x2(const BufRsrc& r, uint32_t voff, uint32_t soff) {
     const uint64_t o = (uint64_t)voff + soff;
     lvm_f2 v = {0.f, 0.f};
-    if (buf_in_range(r, voff, soff, 8)) std::memcpy(&v, r.base + o, 8);
+    if (buf_in_range(r, voff, soff, 8)) { buf_aligned(r.base + o); std::memcpy(&v, r.base + o, 8); }
     return v;
 }
 __device__ __forceinline__ void buf_st_f32x4(float a, float b, float c, float d, const BufRsrc& r, uint32_t voff, uint32_t soff) {
     const uint64_t o = (uint64_t)voff + soff;
     const float v[4] = {a, b, c, d};
-    if (o + 16 <= r.bytes) std::memcpy(r.base + o, v, 16);       // (the product puts voff + soff into the vector register here: the SUM is range-checked)
+    if (o + 16 <= r.bytes) { buf_aligned(r.base + o); std::memcpy(r.base + o, v, 16); }       // (the product puts voff + soff into the vector register here: the SUM is range-checked)
 }
 __device__ __forceinline__ void buf_st_f32x2(float a, float b, const BufRsrc& r, uint32_t voff, uint32_t soff) {
     const uint64_t o = (uint64_t)voff + soff;
     const float v[2] = {a, b};
-    if (buf_in_range(r, voff, soff, 8)) std::memcpy(r.base + o, v, 8);
+    if (buf_in_range(r, voff, soff, 8)) { buf_aligned(r.base + o); std::memcpy(r.base + o, v, 8); }
 }
 __device__ __forceinline__ void buf_st_b96(const B96& v, const BufRsrc& r, uint32_t voff, uint32_t soff) {
     const uint64_t o = (uint64_t)voff + soff;
-    if (o + 12 <= r.bytes) std::memcpy(r.base + o, &v, 12);      // (likewise: whole offset in the vector register)
+    if (o + 12 <= r.bytes) { buf_aligned(r.base + o); std::memcpy(r.base + o, &v, 12); }      // (likewise: whole offset in the vector register)
 }
 // streaming (nontemporal) forms: a cache hint only -- the plain accesses here
-__device__ __forceinline__ float ld_stream_f32(const void* p) { float v; std::memcpy(&v, p, 4); return v; }
-__device__ __forceinline__ uint2 ld_stream_u32x2(const void* p) { uint2 v; std::memcpy(&v, p, 8); return v; }
-__device__ __forceinline__ uint4 ld_stream_u32x4(const void* p) { uint4 v; std::memcpy(&v, p, 16); return v; }
-__device__ __forceinline__ float4 ld_stream_f32x4(const void* p) { float4 v; std::memcpy(&v, p, 16); return v; }
-__device__ __forceinline__ void st_stream_b96(void* p, uint32_t a, uint32_t b, uint32_t c) { const uint32_t v[3] = {a, b, c}; std::memcpy(p, v, 12); }
-__device__ __forceinline__ void st_stream_f32x4(void* p, float a, float b, float c, float d) { const float v[4] = {a, b, c, d}; std::memcpy(p, v, 16); }
+__device__ __forceinline__ float ld_stream_f32(const void* p) { buf_aligned(p); float v; std::memcpy(&v, p, 4); return v; }
+__device__ __forceinline__ uint2 ld_stream_u32x2(const void* p) { buf_aligned(p); uint2 v; std::memcpy(&v, p, 8); return v; }
+__device__ __forceinline__ uint4 ld_stream_u32x4(const void* p) { buf_aligned(p); uint4 v; std::memcpy(&v, p, 16); return v; }
+__device__ __forceinline__ float4 ld_stream_f32x4(const void* p) { buf_aligned(p); float4 v; std::memcpy(&v, p, 16); return v; }
+__device__ __forceinline__ void st_stream_b96(void* p, uint32_t a, uint32_t b, uint32_t c) { buf_aligned(p); const uint32_t v[3] = {a, b, c}; std::memcpy(p, v, 12); }
+__device__ __forceinline__ void st_stream_f32x4(void* p, float a, float b, float c, float d) { buf_aligned(p); const float v[4] = {a, b, c, d}; std::memcpy(p, v, 16); }
 __device__ __forceinline__ float buf_lds_f32(const BufRsrc& r, uint32_t voff, uint32_t soff) { return buf_ld_f32(r, voff, soff); }
 __device__ __forceinline__ uint2 buf_lds_u32x2(const BufRsrc& r, uint32_t voff, uint32_t soff) {
     const uint64_t o = (uint64_t)voff + soff; uint2 v = make_uint2(0, 0);
-    if (buf_in_range(r, voff, soff, 8)) std::memcpy(&v, r.base + o, 8);
+    if (buf_in_range(r, voff, soff, 8)) { buf_aligned(r.base + o); std::memcpy(&v, r.base + o, 8); }
     return v;
 }
 __device__ __forceinline__ uint4 buf_lds_u32x4(const BufRsrc& r, uint32_t voff, uint32_t soff) {
     const uint64_t o = (uint64_t)voff + soff; uint4 v = make_uint4(0, 0, 0, 0);
-    if (buf_in_range(r, voff, soff, 16)) std::memcpy(&v, r.base + o, 16);
+    if (buf_in_range(r, voff, soff, 16)) { buf_aligned(r.base + o); std::memcpy(&v, r.base + o, 16); }
     return v;
 }
 __device__ __forceinline__ B96 buf_lds_b96(const BufRsrc& r, uint32_t voff, uint32_t soff) { return buf_ld_b96(r, voff, soff); }

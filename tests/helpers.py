@@ -152,6 +152,143 @@ def frames_clip(lvm, po, lib, mem, idx, w, h, levels, n_streams, calls, over=Non
             o.close()
 
 
+LAYOUT_GUARD = 64        # bytes behind the last rectangle of every allocation: part of the output's untouched area
+
+
+def _layout_geometry(w, h, n_streams, nf, layout):
+    """byte geometry of one call of nf frames in `layout` = (extra canvas columns, rx, ry, ox, oy, stream gap bytes, order):
+    (row stride, stream stride, frame stride, offset of the input view, offset of the output view, allocation size).
+    order "fs": a canvas of (w + extra) pixels by h + max(ry, oy) + 1 rows (h rows when both are 0) per (frame, stream), laid out
+                [frame][stream], gap bytes behind each;
+    order "sf": the same canvases laid out [stream][frame];
+    order "mosaic" / "mosaic_device": the streams side by side in one canvas per frame (stream stride = w * 3 bytes)."""
+    extra, rx, ry, ox, oy, gap, order = layout
+    assert max(rx, ox) <= extra
+    H = h + max(ry, oy) + (1 if max(ry, oy) else 0)
+    if order in ("mosaic", "mosaic_device"):
+        row = (n_streams * w + extra) * 3
+        ss, fs = w * 3, H * row + gap
+    else:
+        row = (w + extra) * 3
+        canvas = H * row + gap
+        ss, fs = (canvas, n_streams * canvas) if order == "fs" else (nf * canvas, canvas)
+        assert order in ("fs", "sf")
+    total = (nf - 1) * fs + (n_streams - 1) * ss + H * row + gap + LAYOUT_GUARD
+    return row, ss, fs, ry * row + rx * 3, oy * row + ox * 3, total
+
+
+def _view_index(w, h, n_streams, nf, row, ss, fs, off):
+    """flat byte indices [frame][stream][h][w * 3] of the rectangles of a call inside its allocation"""
+    f, s_, y, x = np.ogrid[:nf, :n_streams, :h, :w * 3]
+    return off + f * fs + s_ * ss + y * row + x
+
+
+def layout_clip(lvm, po, lib, mem, idx, w, h, levels, n_streams, calls, layout, env=None, over=None, clip_over=None, exact=True,
+                profile=False):
+    """lvm_process_device_frames (order "mosaic_device": lvm_process_device, frame by frame) on frames that are rectangles inside
+    larger canvases -- what a cv::Mat ROI or the export's ROI view of a decoded frame hands to the magnifier.  `layout` as in
+    _layout_geometry (tests/parity_matrix.py: LAYOUTS); input canvases are filled with 0xAB, output canvases with 0xCD, the two
+    rectangles sit at different offsets.  `env`: forcing switches, set while the contexts are created and run.
+    The context runs OpenCV-order Lab (lvm_debug_exact_lab).  Per frame and stream:
+      - the produced flags are the oracle's;
+      - exact=True: the output rectangle is the oracle's frame, bit for bit;
+        exact=False (Riesz on the GPU: device acosf / sinf / cosf): within the parity bars of the oracle (1 LSB, >= 0.999 identical)
+        AND byte-equal to a second context of the same library that gets the same frames in packed layout (w * 3, w * h * 3,
+        [frame][stream]) in the same flavour -- the arithmetic of the exact flavour does not depend on the kernel family;
+      - every other byte of the output allocation is still 0xCD (between rows, streams and frames, before the first rectangle,
+        behind the last one); a frame that was not produced leaves its rectangle untouched too.
+    Returns ([worst u8 diff, worst identical fraction] against the oracle, and with profile=True {report name launched: set of the
+    kernel variants that ran under it (lvm_profile_variants), empty for names with one kernel}, else None)."""
+    import os
+    ck, pk = lvm.synth.config(idx, (w, h, levels))
+    pk.update(over or {})
+    ck.update(clip_over or {})
+    clips = [lvm.synth.Clip(seed=1234 + s, **ck) for s in range(n_streams)]
+    P = po.make_params(**pk)
+    cp = c_params(lvm, pk)
+    order = layout[6]
+    saved = {k: os.environ.get(k) for k in (env or {})}
+    os.environ.update(env or {})
+    ctx = packed = None
+    orcs = []
+    worst, names = [0, 1.0], None
+    try:
+        ctx = lvm.Context(0, n_streams, lib)
+        ctx.exact_lab(True)
+        if profile:
+            ctx.profile(True)
+        if not exact:
+            packed = lvm.Context(0, n_streams, lib)
+            packed.exact_lab(True)
+        orcs = [po.Oracle() for _ in range(n_streams)]
+        t = 0
+        for nf in calls:
+            row, ss, fs, off_in, off_out, total = _layout_geometry(w, h, n_streams, nf, layout)
+            fin = np.stack([np.stack([c.frame(t + f) for c in clips]) for f in range(nf)])      # [frame][stream][h][w][3]
+            ii = _view_index(w, h, n_streams, nf, row, ss, fs, off_in)
+            io = _view_index(w, h, n_streams, nf, row, ss, fs, off_out)
+            assert ii.max() < total - LAYOUT_GUARD and io.max() < total - LAYOUT_GUARD and np.unique(io).size == io.size
+            buf_in = np.full(total, 0xAB, np.uint8)
+            buf_in[ii] = fin.reshape(nf, n_streams, h, w * 3)
+            d_in = mem.upload(buf_in)
+            d_out = mem.upload(np.full(total, 0xCD, np.uint8))
+            assert mem.ptr_at(d_in, 0) % 16 == 0 and mem.ptr_at(d_out, 0) % 16 == 0       # the offsets alone decide the alignment
+            p_in, p_out = mem.ptr_at(d_in, off_in), mem.ptr_at(d_out, off_out)
+            if order == "mosaic_device":
+                produced = [ctx.process_device(cp, p_in + f * fs, w, h, 3, row, ss, p_out + f * fs, row, ss, mem.stream()) for f in range(nf)]
+            else:
+                produced = ctx.process_device_frames(cp, nf, p_in, w, h, 3, row, ss, fs, p_out, row, ss, fs, mem.stream())
+            mem.sync(ctx)
+            buf_out = mem.download(d_out)
+            got = buf_out[io].reshape(nf, n_streams, h, w, 3)
+            if packed is not None:
+                fb = w * h * 3
+                q_in = mem.upload(fin)
+                q_out = mem.zeros_like(q_in)
+                prod_p = packed.process_device_frames(cp, nf, mem.ptr(q_in), w, h, 3, w * 3, fb, fb * n_streams, mem.ptr(q_out), w * 3, fb,
+                                                      fb * n_streams, mem.stream())
+                mem.sync(packed)
+                got_p = mem.download(q_out)
+                assert list(prod_p) == list(produced), (t, prod_p, produced)
+            untouched = np.ones(total, bool)
+            for f in range(nf):
+                for s_ in range(n_streams):
+                    ref, pr = orcs[s_].process(fin[f, s_], P)
+                    assert produced[f] == pr, (t + f, produced[f], pr)
+                    if not pr:
+                        continue
+                    untouched[io[f, s_].reshape(-1)] = False
+                    if exact:
+                        assert np.array_equal(ref, got[f, s_]), "frame %d stream %d: %d bytes differ from the oracle" % (
+                            t + f, s_, int((ref != got[f, s_]).sum()))
+                        continue
+                    du = np.abs(ref.astype(np.int32) - got[f, s_].astype(np.int32))
+                    worst = [max(worst[0], int(du.max())), min(worst[1], float((du == 0).mean()))]
+                    assert du.max() <= 1 and (du == 0).mean() >= 0.999, "frame %d stream %d: u8 diff %d, identical %.6f" % (
+                        t + f, s_, int(du.max()), float((du == 0).mean()))
+                    assert np.array_equal(got_p[f, s_], got[f, s_]), "frame %d stream %d: %d bytes differ from the packed layout" % (
+                        t + f, s_, int((got_p[f, s_] != got[f, s_]).sum()))
+            bad = np.flatnonzero(untouched & (buf_out != 0xCD))
+            assert bad.size == 0, "call at frame %d: %d bytes outside the output rectangles were written, first at offset %d" % (
+                t, bad.size, int(bad[0]))
+            t += nf
+        if profile:
+            variants = ctx.profile_variants()
+            names = {n: variants.get(n, set()) for n in ctx.profile_collect()}
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+        for c_ in (ctx, packed):
+            if c_ is not None:
+                c_.close()
+        for o in orcs:
+            o.close()
+    return worst, names
+
+
 def pipelined_clip(lvm, po, lib, mem, w, h, levels, nframes, ring=4):
     """lvm_process_device with pipeline depth 1 over a ring of in/out buffers + flush, OpenCV-order Lab: every frame's
     output must equal the oracle's (and therefore the depth-0 schedule's) bit for bit."""
@@ -258,6 +395,11 @@ class HostMem:
     def ptr(self, a, i=0):
         return a[i].ctypes.data
 
+    def ptr_at(self, a, byte_offset):
+        """address of byte `byte_offset` of the uint8 buffer a"""
+        assert a.dtype == np.uint8 and 0 <= byte_offset < a.size
+        return a.ctypes.data + byte_offset
+
     def write(self, a, i, v):
         a[i][...] = v
 
@@ -285,6 +427,11 @@ class TorchMem:
 
     def ptr(self, a, i=0):
         return a[i].data_ptr()
+
+    def ptr_at(self, a, byte_offset):
+        """address of byte `byte_offset` of the uint8 buffer a"""
+        assert a.dtype == self.torch.uint8 and 0 <= byte_offset < a.numel()
+        return a.data_ptr() + byte_offset
 
     def write(self, a, i, v):
         a[i].copy_(self.torch.from_numpy(np.ascontiguousarray(v)))

@@ -6,7 +6,7 @@ same name covers all three modes; the GPU module keeps the Laplace and Color one
 tests/test_gpu_exact.py)."""
 import numpy as np
 
-from helpers import frames_clip, run_pair
+from helpers import frames_clip, layout_clip, run_pair
 
 
 def _color_fps(ck, pk, fps=15.0):
@@ -220,6 +220,90 @@ def color_narrow_band_dft(lvm, po, lib, mem, monkeypatch, lo, hi, thin8):
 
 # ---- every mode: layouts, degenerate content, parameters, shapes ----------------------------------------------------------
 PADDED_STRIDES = [(0, 4, 8), (0, 1, 3), (2, 4, 4), (2, 7, 1), (3, 8, 4), (3, 5, 5)]
+
+
+# Views into larger buffers (helpers.layout_clip): (extra canvas columns, rx, ry, ox, oy, stream gap bytes, order).  The launch code
+# picks the vector kernels where w % 4 == 0 and row strides, stream strides AND both base pointers are multiples of 4, each term
+# on its own for the input and for the output; the wave-strip kernels of the production sizes size their buffer resources from the
+# row stride.  Row bytes for w = 64: 225 (A), 228 (B, C, D, G).
+LAYOUTS = {
+    "A": (11, 5, 3, 2, 1, 7, "fs"),             # odd view: rows, streams and both pointers unaligned -> byte kernels in batches
+    "B": (12, 4, 2, 8, 1, 4096, "fs"),          # aligned view: vector kernels with stride != w * 3, streams far apart
+    "C": (12, 1, 2, 8, 1, 4096, "fs"),          # odd input base only: strides are multiples of 4, the pointer term alone is false
+    "D": (12, 4, 2, 3, 1, 4096, "fs"),          # mixed: input vector-eligible, output not (its mirror image is C)
+    "E": (0, 0, 0, 0, 0, 6, "fs"),              # packed rows, stream stride h * w * 3 + 6: stream 1 unaligned, stream 0 not (two streams)
+    "F": (0, 0, 0, 0, 0, 0, "mosaic"),          # two streams side by side in one frame: stream stride w * 3 < a frame; frame by frame
+    "F_device": (0, 0, 0, 0, 0, 0, "mosaic_device"),      # the same through lvm_process_device
+    "G": (12, 4, 2, 8, 1, 0, "sf"),             # [stream][frame] order: the batch test of lvm_process_device_frames fails -> frame by frame
+}
+# per mode: call lengths, parameter overrides, clip overrides (Color: the band of COLOR_BATCH_PARAMS, 18 frames fill its window)
+LAYOUT_MODES = {0: ((1, 4, 3), None, None), 2: ((1, 4, 3), None, None),
+                3: ((18, 5, 7), {"framerate": 7.0, "coLow": 0.4, "coHigh": 2.0}, {"fps": 7.0})}
+LAYOUT_SHAPES = {0: [(64, 48, 3), (61, 45, 3)], 3: [(64, 48, 2), (61, 45, 2)], 2: [(134, 78, 2), (67, 131, 2)]}
+
+
+def _layout_streams(name):
+    return (2,) if name in ("E", "F", "F_device") else (1, 2)
+
+
+# (mode, w, h, levels, streams, layout) at the default switches: the smallest shapes of the matrix, one with w % 4 == 0 where the mode
+# has vector kernels at that size, one odd
+LAYOUT_CASES = [(idx, w, h, lv, ns, name) for idx in (0, 3, 2) for (w, h, lv) in LAYOUT_SHAPES[idx] for name in LAYOUTS for ns in _layout_streams(name)]
+
+# the production-size strip kernels forced onto small frames (switches as in FIRST_KERNEL / FUSED_TABLE / FIN_ROWS / ROWS_PYRDOWN /
+# COL_DOWN01_ROWS / COL_OUT_ROWS and the Riesz strip tests) on the views that keep them (B), break the input side through the pointer
+# term alone (C) and break the output side alone (D); LAYOUT_LAUNCHES says which kernels each mode must then pick
+LAYOUT_FORCED = {
+    "lap_rows": (0, 328, 109, 3, {"LVM_D0_MIN_TASKS": "0", "LVM_FIN_ROWS": "8", "LVM_FIN_MIN_TASKS": "0", "LVM_ROWS_MIN_ELEMS": "0"}),
+    "lap_fused": (0, 328, 109, 3, {"LVM_D0_FUSED_WAVES": "1", "LVM_FIN_ROWS": "8", "LVM_FIN_MIN_TASKS": "0"}),
+    "col_down01": (3, 264, 90, 3, {"LVM_D0_MIN_TASKS": "0", "LVM_COL_DOWN01_ROWS": "7", "LVM_COL_OUT_MIN_TASKS": "0"}),
+    "col_out_rows": (3, 264, 90, 3, {"LVM_COL_OUT_LEAN": "0", "LVM_COL_OUT_MIN_TASKS": "0"}),
+    "rz_strips": (2, 264, 150, 3, {"LVM_RZ_SPLIT_ROWS_MIN": "1", "LVM_RZ_BLUR_STRIPS_MIN": "0", "LVM_RZ_COLLAPSE_STRIPS_MIN": "1",
+                                   "LVM_RZ_PHASE4_MIN_FRAMES": "1"}),
+}
+LAYOUT_FORCED_CASES = [(force, name) for force in LAYOUT_FORCED for name in ("B", "C", "D")]
+# What the launch code must pick per forced case and layout: report names (lvm_profile_collect) with the kernel variant that ran under
+# them where several kernels share a name (lvm_profile_variants: "strips" = wave strips, "vec4" = tiled with dword-wide frame I/O,
+# "bytes" = tiled with byte I/O); None = the name must not be launched.  Read off the launch code, side by side:
+#   input side only (w % 4, in strides, d_in):   lab_lut (labconv.hip), col_down0 / col_down01 (col_down)
+#   output side only (out strides, d_out):       the Riesz strip output kernel (rz_collapse_out: out_ok) -- so C KEEPS it and D loses it
+#   both sides:                                  lap_down0, lap_down0_lut, lap_final (lap_vec4), col_out / col_minmax (col_up_out), tiled rz_final
+# so B keeps every strip kernel, C (odd input pointer) and D (odd output pointer) lose exactly the ones whose side they break.
+# The last entries of a case are kernels that read float planes only: launched in every layout, they show that the switches reached the state.
+_S, _V, _B = {"strips"}, {"vec4"}, {"bytes"}
+LAYOUT_LAUNCHES = {
+    "lap_rows": {"B": {"lab_lut": _V, "lap_down0": _S, "lap_final": _S}, "C": {"lab_lut": _B, "lap_down0": _B, "lap_final": _B},
+                 "D": {"lab_lut": _V, "lap_down0": _B, "lap_final": _B}, "*": {"pyr_down_rows_l1": set()}},      # (batched calls may take lap_down0_lut besides: its threshold counts the CUs)
+    "lap_fused": {"B": {"lap_down0_lut": set(), "lab_lut": None, "lap_down0": None, "lap_final": _S},
+                  "C": {"lap_down0_lut": None, "lab_lut": _B, "lap_down0": _B, "lap_final": _B},
+                  "D": {"lap_down0_lut": None, "lab_lut": _V, "lap_down0": _B, "lap_final": _B}, "*": {}},
+    "col_down01": {"B": {"col_down01": set(), "col_down0": None, "col_minmax_u2": set(), "col_out_u2": set(), "col_out": None},
+                   "C": {"col_down01": None, "col_down0": _B, "col_minmax_u2": None, "col_out_u2": None, "col_minmax": _B, "col_out": _B},
+                   "D": {"col_down01": set(), "col_down0": None, "col_minmax_u2": None, "col_out_u2": None, "col_minmax": _B, "col_out": _B}, "*": {}},
+    "col_out_rows": {"B": {"col_down0": _V, "col_minmax": _S, "col_out": _S}, "C": {"col_down0": _B, "col_minmax": _B, "col_out": _B},
+                     "D": {"col_down0": _V, "col_minmax": _B, "col_out": _B}, "*": {"col_out_u2": None, "col_down01": None}},
+    "rz_strips": {"B": {"lab_lut": _V, "rz_final": _S}, "C": {"lab_lut": _B, "rz_final": _S}, "D": {"lab_lut": _V, "rz_final": _B},
+                  "*": {"rz_phase": set(), "rz_phase_small": None, "rz_blur_amp": set(), "rz_blur_amp_small": None, "rz_blur_amp_tiles": None}},
+}
+
+
+def layout_case(lvm, po, lib, mem, idx, w, h, levels, n_streams, name, env=None, exact=True, profile=False):
+    calls, over, clip_over = LAYOUT_MODES[idx]
+    return layout_clip(lvm, po, lib, mem, idx, w, h, levels, n_streams, calls, LAYOUTS[name], env=env, over=over, clip_over=clip_over,
+                       exact=exact, profile=profile)
+
+
+def layout_forced_case(lvm, po, lib, mem, force, name, exact=True):
+    """one forced case: the bytes, and the kernels LAYOUT_LAUNCHES names for this layout -- a silent fall-back to another kernel family fails"""
+    idx, w, h, levels, env = LAYOUT_FORCED[force]
+    worst, names = layout_case(lvm, po, lib, mem, idx, w, h, levels, 1, name, env=env, exact=exact, profile=True)
+    want = dict(LAYOUT_LAUNCHES[force]["*"], **LAYOUT_LAUNCHES[force][name])
+    for n, variants in want.items():
+        if variants is None:
+            assert n not in names, (force, name, n, names)
+        else:
+            assert n in names and names[n] == variants, (force, name, n, variants, names)
+    return worst, {n: sorted(names[n]) for n, v in want.items() if v is not None}
 
 
 class PatchedClip:

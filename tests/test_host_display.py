@@ -80,6 +80,7 @@ def test_chain_present_gpu(lvm, po, hip):
 
     def alloc(n):
         t = torch.full((n,), 0x5A, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()        # the fill runs on torch's stream, lvm_chain_present on the context's own: without this the fill can land on a pane
         return t.data_ptr(), (lambda: t.cpu().numpy())
     _check_present(lvm, po, hip, alloc, False)
 

@@ -229,6 +229,48 @@ def _transcode_case(lvm, lib, w, h, n, split, pre_kw, q_in, q_out):
         b.close()
 
 
+ROI_MODES = {0: (6, {}), 2: (6, {}), 3: (22, {"framerate": 7.0, "coLow": 0.4, "coHigh": 2.0})}      # synth.config index -> frames, parameter overrides
+
+
+def _roi_view_case(lvm, lib, idx):
+    """The production path that hands the magnifier an unaligned view in temporal batches: a 75 x 53 source coded by libjpeg (Pillow, quality
+    90, 4:2:0), decoded on the device, ROI only (downscale 1, no gray) -- the magnifier and compose_device's `orig` read
+    d_decoded + ry * 225 + rx * 3 with rows of 225 bytes.  ROIs of 61 x 45 (odd size) and 64 x 48 (w % 4 == 0: only layout and pointer keep
+    the vector kernels away) at (5, 3); split left | right.  Both contexts run OpenCV-order Lab: the second one magnifies the cropped frame
+    from a packed upload, where it may take the vector kernels, and the bytes must not depend on that."""
+    from helpers import c_params
+    w, h = 75, 53
+    n, over = ROI_MODES[idx]
+    ck, pk = lvm.synth.config(idx, (w, h, 2))
+    pk.update(over)
+    clip = lvm.synth.Clip(seed=7, **ck)
+    jin = [pil_encode(clip.frame(t), 90, subsampling=2) for t in range(n)]
+    decoded = [pil_decode(j) for j in jin]
+    cp = c_params(lvm, pk)
+    for rw, rh in ((61, 45), (64, 48)):
+        pre = lvm.LvmPreprocessParams(1, 1, 5.2 / 75, 3.2 / 53, rw / 75, rh / 53, 0)
+        a, b = lvm.Context(0, 1, lib), lvm.Context(0, 1, lib)
+        try:
+            # (a change in the geometry's rounding must not silently re-align the view)
+            assert a.preprocess_geometry(pre, w, h, 3) == (5, 3, rw, rh, rw, rh, 3)
+            a.exact_lab(True)
+            b.exact_lab(True)
+            b.mjpeg_set_decoder(LIBJPEG)
+            canvases, prod_a = a.export_frames(decoded, pre, cp, 1)
+            jout, prod_b = b.export_mjpeg_frames(jin, w, h, pre, cp, 1, quality=85)
+            assert prod_a == prod_b and any(prod_a)
+            for k in range(n):
+                assert jout[k] == mo.encode_frame(canvases[k], 85), "ROI %d x %d, frame %d" % (rw, rh, k)
+        finally:
+            a.close()
+            b.close()
+
+
+@pytest.mark.parametrize("idx", [0, 2, 3])
+def test_libjpeg_kind_emu_export_roi_view_in_batches(lvm, emu, idx):
+    _roi_view_case(lvm, emu, idx)
+
+
 def test_libjpeg_kind_emu_export_mjpeg_to_mjpeg(lvm, emu):
     _transcode_case(lvm, emu, 66, 38, 6, 1, {}, 90, 80)
     _transcode_case(lvm, emu, 80, 60, 5, 2, dict(downscale=2, roi_enabled=1, roiX=0.1, roiY=0.2, roiW=0.7, roiH=0.6, grayscale=1), 85, 95)
@@ -282,6 +324,12 @@ def test_libjpeg_kind_gpu_1080p(lvm, hip):
 @pytest.mark.gpu
 def test_libjpeg_kind_gpu_export_mjpeg_to_mjpeg(lvm, hip):
     _transcode_case(lvm, hip, 640, 360, 9, 1, {}, 90, 85)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("idx", [0, 2, 3])
+def test_libjpeg_kind_gpu_export_roi_view_in_batches(lvm, hip, idx):
+    _roi_view_case(lvm, hip, idx)
 
 
 @pytest.mark.gpu
