@@ -115,13 +115,19 @@ def run_pair(lvm, po, lib, clip, pk, nframes, float_tol, n_streams=1, u8_max=1, 
 
 
 # ---- exact-flavour bodies shared by the emulation and the gfx950 matrices (tests/parity_matrix.py) --------------------------
-def frames_clip(lvm, po, lib, mem, idx, w, h, levels, n_streams, calls, over=None, clip_over=None):
+def _clip_of(lvm, clip_fn, ck, stream):
+    """the clip of one stream: clip_fn(ck, stream) where a case brings its own content (tests/content.py), else the synthetic
+    texture with the stream's seed"""
+    return clip_fn(ck, stream) if clip_fn else lvm.synth.Clip(seed=1234 + stream, **ck)
+
+
+def frames_clip(lvm, po, lib, mem, idx, w, h, levels, n_streams, calls, over=None, clip_over=None, clip_fn=None):
     """lvm_process_device_frames: batches of consecutive frames (sizes in `calls`) of n_streams streams, OpenCV-order Lab
     (lvm_debug_exact_lab), must give exactly the bytes the oracle produces frame by frame."""
     ck, pk = lvm.synth.config(idx, (w, h, levels))
     pk.update(over or {})
     ck.update(clip_over or {})
-    clips = [lvm.synth.Clip(seed=1234 + s, **ck) for s in range(n_streams)]
+    clips = [_clip_of(lvm, clip_fn, ck, s) for s in range(n_streams)]
     P = po.make_params(**pk)
     cp = c_params(lvm, pk)
     ctx = lvm.Context(0, n_streams, lib)
@@ -184,7 +190,7 @@ def _view_index(w, h, n_streams, nf, row, ss, fs, off):
 
 
 def layout_clip(lvm, po, lib, mem, idx, w, h, levels, n_streams, calls, layout, env=None, over=None, clip_over=None, exact=True,
-                profile=False):
+                profile=False, clip_fn=None):
     """lvm_process_device_frames (order "mosaic_device": lvm_process_device, frame by frame) on frames that are rectangles inside
     larger canvases -- what a cv::Mat ROI or the export's ROI view of a decoded frame hands to the magnifier.  `layout` as in
     _layout_geometry (tests/parity_matrix.py: LAYOUTS); input canvases are filled with 0xAB, output canvases with 0xCD, the two
@@ -203,7 +209,7 @@ def layout_clip(lvm, po, lib, mem, idx, w, h, levels, n_streams, calls, layout, 
     ck, pk = lvm.synth.config(idx, (w, h, levels))
     pk.update(over or {})
     ck.update(clip_over or {})
-    clips = [lvm.synth.Clip(seed=1234 + s, **ck) for s in range(n_streams)]
+    clips = [_clip_of(lvm, clip_fn, ck, s) for s in range(n_streams)]
     P = po.make_params(**pk)
     cp = c_params(lvm, pk)
     order = layout[6]
@@ -289,11 +295,11 @@ def layout_clip(lvm, po, lib, mem, idx, w, h, levels, n_streams, calls, layout, 
     return worst, names
 
 
-def pipelined_clip(lvm, po, lib, mem, w, h, levels, nframes, ring=4):
+def pipelined_clip(lvm, po, lib, mem, w, h, levels, nframes, ring=4, clip_fn=None):
     """lvm_process_device with pipeline depth 1 over a ring of in/out buffers + flush, OpenCV-order Lab: every frame's
     output must equal the oracle's (and therefore the depth-0 schedule's) bit for bit."""
     ck, pk = lvm.synth.config(0, (w, h, levels))
-    clip = lvm.synth.Clip(**ck)
+    clip = _clip_of(lvm, clip_fn, ck, 0)
     P = po.make_params(**pk)
     cp = c_params(lvm, pk)
     ctx = lvm.Context(0, 1, lib)
@@ -324,10 +330,10 @@ def pipelined_clip(lvm, po, lib, mem, w, h, levels, nframes, ring=4):
         orc.close()
 
 
-def two_streams_clip(lvm, po, lib, mem, w=96, h=64, levels=3, nframes=5):
+def two_streams_clip(lvm, po, lib, mem, w=96, h=64, levels=3, nframes=5, clip_fn=None):
     """A two-stream context through lvm_process_device, OpenCV-order Lab: each stream equals its own oracle bit for bit."""
     ck, pk = lvm.synth.config(0, (w, h, levels))
-    clips = [lvm.synth.Clip(seed=1234 + s, **ck) for s in range(2)]
+    clips = [_clip_of(lvm, clip_fn, ck, s) for s in range(2)]
     ctx = lvm.Context(0, 2, lib)
     ctx.exact_lab(True)
     orcs = [po.Oracle(), po.Oracle()]
@@ -351,12 +357,12 @@ def two_streams_clip(lvm, po, lib, mem, w=96, h=64, levels=3, nframes=5):
             o.close()
 
 
-def padded_strides_clip(lvm, po, lib, mem, idx, pad_in, pad_out, w=96, h=64, levels=3, nframes=6):
+def padded_strides_clip(lvm, po, lib, mem, idx, pad_in, pad_out, w=96, h=64, levels=3, nframes=6, clip_fn=None):
     """lvm_process_device on frames whose rows are padded (a cv::Mat ROI view has step > cols * channels), OpenCV-order
     Lab: dword-aligned paddings keep the vectorised kernels, odd ones select the generic byte kernels; the padding bytes
     of the output must stay untouched and the frame must equal the oracle's bit for bit."""
     ck, pk = lvm.synth.config(idx, (w, h, levels))
-    clip = lvm.synth.Clip(**ck)
+    clip = _clip_of(lvm, clip_fn, ck, 0)
     P = po.make_params(**pk)
     cp = c_params(lvm, pk)
     ctx = lvm.Context(0, 1, lib)

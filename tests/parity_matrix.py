@@ -6,12 +6,18 @@ same name covers all three modes; the GPU module keeps the Laplace and Color one
 tests/test_gpu_exact.py)."""
 import numpy as np
 
+import content
 from helpers import frames_clip, layout_clip, run_pair
 
 
 def _color_fps(ck, pk, fps=15.0):
     ck["fps"] = fps
     pk["framerate"] = fps
+
+
+def _clip(lvm, ck, kind=None):
+    """the synthetic clip, or the chromatic content `kind` of tests/content.py in its place"""
+    return lvm.synth.Clip(**ck) if kind is None else content.chroma_clip(lvm, ck, kind)
 
 
 # ---- Laplace ---------------------------------------------------------------------------------------
@@ -28,13 +34,13 @@ def laplace_shape(lvm, po, lib, w, h, levels, ch):
 ANALYTIC = [(0, 135, 77, 4), (0, 328, 109, 3), (2, 135, 77, 3), (2, 264, 150, 3)]
 
 
-def analytic_flavour(lvm, po, lib, monkeypatch, idx, w, h, levels):
+def analytic_flavour(lvm, po, lib, monkeypatch, idx, w, h, levels, kind=None, exact=True):
     """lvm_debug_lab_analytic: the cube-root forward Lab (OpenCV with its interpolation switched off) in the kernels that
     convert from the u8 frame themselves, against the oracle with lvmo_set_lab_lut(0); scalar and 4-pixel variants, strip
     first kernel forced on."""
     monkeypatch.setenv("LVM_D0_MIN_TASKS", "0")
     ck, pk = lvm.synth.config(idx, (w, h, levels))
-    return run_pair(lvm, po, lib, lvm.synth.Clip(**ck), pk, 5, 0.0, exact=True, analytic=True)
+    return run_pair(lvm, po, lib, _clip(lvm, ck, kind), pk, 5, 0.0 if exact else 1e-4, exact=exact, analytic=True)
 
 
 def laplace_param_changes_and_reset(lvm, po, lib):
@@ -63,13 +69,13 @@ def laplace_shape_3_frames(lvm, po, lib, w, h, levels):
 FIN_ROWS = [4, 8, 16]
 
 
-def laplace_final_strip_height(lvm, po, lib, monkeypatch, rows):
+def laplace_final_strip_height(lvm, po, lib, monkeypatch, rows, kind=None):
     """k_lap_final_v4 walks strips of `rows` output rows per wave (the launch code shortens them for small frames): force the
     long strips, on a height that leaves a partial last strip and a width with a partly filled last wave."""
     monkeypatch.setenv("LVM_FIN_ROWS", str(rows))
     monkeypatch.setenv("LVM_FIN_MIN_TASKS", "0")
     ck, pk = lvm.synth.config(0, (328, 90 + 2 * rows + 3, 3))
-    return run_pair(lvm, po, lib, lvm.synth.Clip(**ck), pk, 4, 0.0, exact=True)
+    return run_pair(lvm, po, lib, _clip(lvm, ck, kind), pk, 4, 0.0, exact=True)
 
 
 ROWS_PYRDOWN = [(328, 109, 3), (1000, 760, 5), (520, 77, 4)]
@@ -287,16 +293,16 @@ LAYOUT_LAUNCHES = {
 }
 
 
-def layout_case(lvm, po, lib, mem, idx, w, h, levels, n_streams, name, env=None, exact=True, profile=False):
+def layout_case(lvm, po, lib, mem, idx, w, h, levels, n_streams, name, env=None, exact=True, profile=False, clip_fn=None):
     calls, over, clip_over = LAYOUT_MODES[idx]
     return layout_clip(lvm, po, lib, mem, idx, w, h, levels, n_streams, calls, LAYOUTS[name], env=env, over=over, clip_over=clip_over,
-                       exact=exact, profile=profile)
+                       exact=exact, profile=profile, clip_fn=clip_fn)
 
 
-def layout_forced_case(lvm, po, lib, mem, force, name, exact=True):
+def layout_forced_case(lvm, po, lib, mem, force, name, exact=True, clip_fn=None):
     """one forced case: the bytes, and the kernels LAYOUT_LAUNCHES names for this layout -- a silent fall-back to another kernel family fails"""
     idx, w, h, levels, env = LAYOUT_FORCED[force]
-    worst, names = layout_case(lvm, po, lib, mem, idx, w, h, levels, 1, name, env=env, exact=exact, profile=True)
+    worst, names = layout_case(lvm, po, lib, mem, idx, w, h, levels, 1, name, env=env, exact=exact, profile=True, clip_fn=clip_fn)
     want = dict(LAYOUT_LAUNCHES[force]["*"], **LAYOUT_LAUNCHES[force][name])
     for n, variants in want.items():
         if variants is None:
@@ -363,12 +369,12 @@ EXTREME_PARAMETERS = [(3, dict(coLow=5.0, coHigh=1.0)),                # colour:
                       (2, dict(amplification=0.0, coWavelength=0.0))]  # Riesz: zero gain / zero threshold
 
 
-def extreme_parameters(lvm, po, lib, idx, over):
+def extreme_parameters(lvm, po, lib, idx, over, kind=None):
     ck, pk = lvm.synth.config(idx, (96, 64, 3))
     if idx == 3:
         _color_fps(ck, pk)
     pk.update(over)
-    return run_pair(lvm, po, lib, lvm.synth.Clip(**ck), pk, 8, 0.0, exact=True)
+    return run_pair(lvm, po, lib, _clip(lvm, ck, kind), pk, 8, 0.0, exact=True)
 
 
 class ShapeShifter:
@@ -400,3 +406,72 @@ def size_and_channel_changes(lvm, po, lib, idx):
 def no_riesz(cases):
     """the entries of a matrix list whose first element (synth.config index) is not Riesz"""
     return [c for c in cases if c[0] != 2]
+
+
+# ---- chromatic content (tests/content.py) ---------------------------------------------------------------------------------------
+# Every case above draws its pixels from synth.texture, a grey grating: B, G and R of a pixel stay within about 30 levels of each
+# other, which reads 5 % of the forward Lab table (tests/test_lab_lut.py: test_chromatic_content_reaches_the_table_off_the_grey_diagonal)
+# and one branch combination of the inverse conversion.  The cases below send saturated colours through the same kernels: the cell
+# and weight fields of the table index, its neighbours and padding plane, the mixed cubic / linear branches of Lab -> BGR, channels
+# clamped at 0 beside channels clamped at 1.
+# (mode, w, h, levels): the odd width takes the byte kernels; Color at 15 fps for 14 frames (the window fills, as in COLOR_SHAPES)
+CHROMA_SHAPES = [(0, 96, 64, 3), (0, 67, 45, 2), (2, 96, 64, 3), (2, 67, 45, 2), (3, 64, 48, 2)]
+CHROMA_CASES = [(kind, idx, w, h, levels) for kind in content.KINDS for (idx, w, h, levels) in CHROMA_SHAPES]
+CHROMA_FORCED_KINDS = ("noise", "bars")
+
+
+def chroma_shape(lvm, po, lib, kind, idx, w, h, levels, flavour_exact=True, bit_exact=None, channels=3):
+    """One kind of content through one mode.  flavour_exact: OpenCV-order Lab (lvm_debug_exact_lab), else the default flavour;
+    bit_exact (default: flavour_exact): float frames and bytes equal to the oracle's, else the project's bars (1e-4 relative, 1 LSB,
+    >= 0.999 identical bytes) -- Riesz on the GPU in either flavour (device acosf / sinf / cosf)."""
+    bit_exact = flavour_exact if bit_exact is None else bit_exact
+    assert flavour_exact or not bit_exact
+    ck, pk = lvm.synth.config(idx, (w, h, levels))
+    ck["channels"] = channels
+    if idx == 3:
+        _color_fps(ck, pk)
+    return run_pair(lvm, po, lib, content.chroma_clip(lvm, ck, kind), pk, 14 if idx == 3 else 6, 0.0 if bit_exact else 1e-4,
+                    exact=bit_exact, exact_lab=flavour_exact)
+
+
+def chroma_gray(lvm, po, lib):
+    """Laplace on one-channel frames of `noise` (the clip's channel pick): no Lab on the way, grey-exact"""
+    return chroma_shape(lvm, po, lib, "noise", 0, 96, 64, 3, channels=1)
+
+
+CHROMA_FORCED_CASES = [(kind, force) for kind in CHROMA_FORCED_KINDS for force in LAYOUT_FORCED]
+
+
+def chroma_forced(lvm, po, lib, mem, kind, force, exact=True):
+    """an entry of LAYOUT_FORCED at its own size and switches on the view that keeps every strip kernel (B): the bytes, and the
+    kernels LAYOUT_LAUNCHES names"""
+    return layout_forced_case(lvm, po, lib, mem, force, "B", exact=exact, clip_fn=content.clip_fn(lvm, kind))
+
+
+CHROMA_ANALYTIC = [(kind,) + a for kind in CHROMA_FORCED_KINDS for a in (ANALYTIC[0], ANALYTIC[2])]
+
+# temporal batches of `noise`: (mode, w, h, levels, streams, calls, parameter overrides, clip overrides)
+CHROMA_BATCHES = [(0, 160, 90, 3, 2, (1, 4, 3), None, None), (2, 96, 64, 3, 1, (2, 5, 3), None, None),
+                  (3, 64, 48, 2, 1, (18, 5, 7)) + COLOR_BATCH_PARAMS]
+PACKED = (0, 0, 0, 0, 0, 0, "fs")          # helpers.layout_clip's geometry of packed rows, [frame][stream]
+
+
+def chroma_batches(lvm, po, lib, mem, idx, w, h, levels, ns, calls, over, clip_over, exact=True):
+    """exact=False (Riesz on the GPU): the bars of helpers.layout_clip on packed frames"""
+    fn = content.clip_fn(lvm, "noise")
+    if exact:
+        return frames_clip(lvm, po, lib, mem, idx, w, h, levels, ns, calls, over, clip_over, clip_fn=fn)
+    return layout_clip(lvm, po, lib, mem, idx, w, h, levels, ns, calls, PACKED, over=over, clip_over=clip_over, exact=False, clip_fn=fn)[0]
+
+
+CHROMA_LAYOUTS = [(idx,) + LAYOUT_SHAPES[idx][0] + (name,) for idx in (0, 2) for name in ("A", "B", "D")]
+
+
+def chroma_layout(lvm, po, lib, mem, idx, w, h, levels, name, exact=True):
+    return layout_case(lvm, po, lib, mem, idx, w, h, levels, 1, name, exact=exact, clip_fn=content.clip_fn(lvm, "noise"))
+
+
+def chroma_out_of_gamut(lvm, po, lib):
+    """saturated hues amplified a thousandfold at full chroma: Lab far outside the gamut on every side of it"""
+    assert EXTREME_PARAMETERS[5] == (0, dict(amplification=1000.0, chromAttenuation=1.0))
+    return extreme_parameters(lvm, po, lib, *EXTREME_PARAMETERS[5], kind="hue")

@@ -399,3 +399,48 @@ def test_riesz_emu_strip_output_fast_flavour_equals_the_tiled_kernel(lvm, emu, m
     for (a, fa), (b, fb) in zip(*outs):
         assert np.array_equal(a, b)
         assert (fa is None and fb is None) or np.array_equal(fa, fb)
+
+
+# ---- chromatic content: saturated colours through the same kernels (tests/content.py, parity_matrix.CHROMA_*) -----------------------
+@pytest.mark.parametrize("kind,idx,w,h,levels", M.CHROMA_CASES)
+def test_emu_chroma_bit_exact(lvm, po, emu, kind, idx, w, h, levels):
+    M.chroma_shape(lvm, po, emu, kind, idx, w, h, levels)
+
+
+@pytest.mark.parametrize("kind,idx,w,h,levels", M.CHROMA_CASES)
+def test_emu_chroma_default_flavour_within_the_bars(lvm, po, emu, kind, idx, w, h, levels):
+    worst = M.chroma_shape(lvm, po, emu, kind, idx, w, h, levels, flavour_exact=False)
+    print("chroma default flavour", kind, (idx, w, h, levels), "worst rel/u8/frac, shipped u8/frac", worst)
+
+
+def test_emu_chroma_gray_frames_bit_exact(lvm, po, emu):
+    M.chroma_gray(lvm, po, emu)
+
+
+@pytest.mark.parametrize("kind,force", M.CHROMA_FORCED_CASES)
+def test_emu_chroma_forced_strip_kernels_bit_exact(lvm, po, emu, kind, force):
+    M.chroma_forced(lvm, po, emu, HOST, kind, force)
+
+
+@pytest.mark.parametrize("kind", M.CHROMA_FORCED_KINDS)
+def test_emu_chroma_final_kernel_strips_of_8_rows(lvm, po, emu, kind, monkeypatch):
+    M.laplace_final_strip_height(lvm, po, emu, monkeypatch, 8, kind=kind)
+
+
+@pytest.mark.parametrize("kind,idx,w,h,levels", M.CHROMA_ANALYTIC)
+def test_emu_chroma_analytic_flavour_bit_exact(lvm, po, emu, kind, idx, w, h, levels, monkeypatch):
+    M.analytic_flavour(lvm, po, emu, monkeypatch, idx, w, h, levels, kind=kind)
+
+
+@pytest.mark.parametrize("idx,w,h,levels,ns,calls,over,clip_over", M.CHROMA_BATCHES)
+def test_emu_chroma_temporal_batches(lvm, po, emu, idx, w, h, levels, ns, calls, over, clip_over):
+    M.chroma_batches(lvm, po, emu, HOST, idx, w, h, levels, ns, calls, over, clip_over)
+
+
+@pytest.mark.parametrize("idx,w,h,levels,name", M.CHROMA_LAYOUTS)
+def test_emu_chroma_layouts(lvm, po, emu, idx, w, h, levels, name):
+    M.chroma_layout(lvm, po, emu, HOST, idx, w, h, levels, name)
+
+
+def test_emu_chroma_far_out_of_gamut(lvm, po, emu):
+    M.chroma_out_of_gamut(lvm, po, emu)

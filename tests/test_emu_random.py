@@ -5,6 +5,7 @@ fixed-size cases of test_emu_parity.py cover the variants by construction, this 
 import numpy as np
 import pytest
 
+import content
 from helpers import run_pair
 
 MODES = (0, 2, 3)          # synth.config indices: Laplace, Riesz, Color
@@ -71,3 +72,24 @@ def test_random_configurations_gpu(lvm, po, hip, seed):
     print("random", seed, (ck["w"], ck["h"], pk["levels"], ck.get("channels", 3), pk["mode"]), "worst rel/u8/frac", worst)
     if pk["mode"] != 1:          # (mode 1: Riesz)
         run_pair(lvm, po, hip, lvm.synth.Clip(**ck), pk, 7, 0.0, exact=True, param_fn=vary)
+
+
+@pytest.mark.parametrize("seed", range(12))
+def test_random_configurations_chromatic_content_bit_exact(lvm, po, emu, seed):
+    """the draws of seeds 0 .. 11 on the chromatic content of tests/content.py, one kind per seed (every mode meets every kind)"""
+    ck, pk, vary = configure(lvm, seed)
+    run_pair(lvm, po, emu, content.chroma_clip(lvm, ck, content.KINDS[seed % 4]), pk, 7, 0.0, exact=True, param_fn=vary)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed", range(12))
+def test_random_configurations_chromatic_content_gpu(lvm, po, hip, seed):
+    """The same at four times the size on the gfx950 build: the default flavour at the parity bars, Laplace and Color draws also
+    in the exact flavour, bit for bit."""
+    ck, pk, vary = configure(lvm, seed, scale=4)
+    clip = content.chroma_clip(lvm, ck, content.KINDS[seed % 4])
+    worst = run_pair(lvm, po, hip, clip, pk, 7, 1e-4, param_fn=vary)
+    print("random chroma", seed, content.KINDS[seed % 4], (ck["w"], ck["h"], pk["levels"], ck.get("channels", 3), pk["mode"]),
+          "worst rel/u8/frac, shipped u8/frac", worst)
+    if pk["mode"] != 1:          # (mode 1: Riesz)
+        run_pair(lvm, po, hip, clip, pk, 7, 0.0, exact=True, param_fn=vary)

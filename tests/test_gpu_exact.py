@@ -15,6 +15,7 @@ exactly:
 import numpy as np
 import pytest
 
+import content
 import parity_matrix as M
 from helpers import STEPS_U8_FRAC, TorchMem, c_params, frames_clip, padded_strides_clip, pipelined_clip, run_pair, two_streams_clip
 from test_emu_random import configure, draw
@@ -205,6 +206,56 @@ def test_laplace_color_mode_switch_exact(lvm, po, hip):
     run_pair(lvm, po, hip, lvm.synth.Clip(**ck), pk0, 12, 0.0, exact=True, param_fn=lambda t, p: dict([pk0, pk3, pk0][(t // 4) % 3]))
 
 
+# chromatic content (tests/content.py): Laplace and Color bit for bit; the Riesz entries of the forced, batched and layout cases at the
+# bars of helpers.layout_clip, as tests/test_layouts.py holds them (the Riesz shapes: tests/test_gpu_parity.py)
+@pytest.mark.parametrize("kind,idx,w,h,levels", [c for c in M.CHROMA_CASES if c[1] != 2])
+def test_chroma_exact(lvm, po, hip, kind, idx, w, h, levels):
+    M.chroma_shape(lvm, po, hip, kind, idx, w, h, levels)
+
+
+def test_chroma_gray_frames_exact(lvm, po, hip):
+    M.chroma_gray(lvm, po, hip)
+
+
+@pytest.mark.parametrize("kind,force", M.CHROMA_FORCED_CASES)
+def test_chroma_forced_strip_kernels(lvm, po, hip, dev, kind, force):
+    riesz = M.LAYOUT_FORCED[force][0] == 2
+    worst, launched = M.chroma_forced(lvm, po, hip, dev, kind, force, exact=not riesz)
+    print("chroma forced", kind, force, "launched as asserted:", launched)
+    if riesz:
+        print("chroma forced", kind, force, "vs oracle: worst u8 diff %d, worst identical fraction %.6f" % tuple(worst))
+
+
+@pytest.mark.parametrize("kind", M.CHROMA_FORCED_KINDS)
+def test_chroma_final_kernel_strips_of_8_rows_exact(lvm, po, hip, kind, monkeypatch):
+    M.laplace_final_strip_height(lvm, po, hip, monkeypatch, 8, kind=kind)
+
+
+@pytest.mark.parametrize("kind,idx,w,h,levels", M.CHROMA_ANALYTIC)
+def test_chroma_analytic_flavour(lvm, po, hip, kind, idx, w, h, levels, monkeypatch):
+    worst = M.analytic_flavour(lvm, po, hip, monkeypatch, idx, w, h, levels, kind=kind, exact=idx != 2)
+    if idx == 2:
+        print("chroma analytic riesz", kind, (w, h, levels), "worst rel/u8/frac, shipped u8/frac", worst)
+
+
+@pytest.mark.parametrize("idx,w,h,levels,ns,calls,over,clip_over", M.CHROMA_BATCHES)
+def test_chroma_temporal_batches(lvm, po, hip, dev, idx, w, h, levels, ns, calls, over, clip_over):
+    worst = M.chroma_batches(lvm, po, hip, dev, idx, w, h, levels, ns, calls, over, clip_over, exact=idx != 2)
+    if idx == 2:
+        print("chroma riesz batches vs oracle: worst u8 diff %d, worst identical fraction %.6f" % tuple(worst))
+
+
+@pytest.mark.parametrize("idx,w,h,levels,name", M.CHROMA_LAYOUTS)
+def test_chroma_layouts(lvm, po, hip, dev, idx, w, h, levels, name):
+    worst, _ = M.chroma_layout(lvm, po, hip, dev, idx, w, h, levels, name, exact=idx != 2)
+    if idx == 2:
+        print("chroma riesz layout", name, "vs oracle: worst u8 diff %d, worst identical fraction %.6f" % tuple(worst))
+
+
+def test_chroma_far_out_of_gamut_exact(lvm, po, hip):
+    M.chroma_out_of_gamut(lvm, po, hip)
+
+
 LC_SEEDS = [s for s in range(24) if draw(s)[1] != 2]
 
 
@@ -280,10 +331,7 @@ SHIPPED_CASES = [(0, (640, 360, 5), {}), (0, (323, 211, 4), {}), (0, (135, 77, 4
                  (3, (264, 90, 3), {"LVM_COL_OUT_LEAN": "0", "LVM_COL_OUT_MIN_TASKS": "0"})]
 
 
-@pytest.mark.parametrize("idx,size,env", SHIPPED_CASES)
-def test_shipped_flavour_gpu_equals_emulation(lvm, hip, emu, idx, size, env, monkeypatch):
-    """Same frames through both builds in the shipped configuration (identical u8 frames) and with keep_float (identical float
-    frames and bytes); a few forced variants."""
+def _shipped_case(lvm, hip, emu, idx, size, env, monkeypatch, kind=None):
     chans = env.get("channels", 3)
     for k, v in env.items():
         if k.startswith("LVM_"):
@@ -292,10 +340,46 @@ def test_shipped_flavour_gpu_equals_emulation(lvm, hip, emu, idx, size, env, mon
     ck["channels"] = chans
     if idx == 3:
         ck["fps"] = 15.0; pk["framerate"] = 15.0
-    clip = lvm.synth.Clip(**ck)
+    clip = lvm.synth.Clip(**ck) if kind is None else content.chroma_clip(lvm, ck, kind)
     n = 14 if idx == 3 else 6
     for keep in (False, True):
         _assert_same(_run_lib(lvm, hip, clip, pk, n, keep), _run_lib(lvm, emu, clip, pk, n, keep), "keep_float=%s" % keep)
+
+
+@pytest.mark.parametrize("idx,size,env", SHIPPED_CASES)
+def test_shipped_flavour_gpu_equals_emulation(lvm, hip, emu, idx, size, env, monkeypatch):
+    """Same frames through both builds in the shipped configuration (identical u8 frames) and with keep_float (identical float
+    frames and bytes); a few forced variants."""
+    _shipped_case(lvm, hip, emu, idx, size, env, monkeypatch)
+
+
+CHROMA_SHIPPED_CASES = [SHIPPED_CASES[1], SHIPPED_CASES[5], SHIPPED_CASES[7], SHIPPED_CASES[11]]
+
+
+@pytest.mark.parametrize("kind", ["noise", "hue"])
+@pytest.mark.parametrize("idx,size,env", CHROMA_SHIPPED_CASES)
+def test_shipped_flavour_gpu_equals_emulation_on_chromatic_content(lvm, hip, emu, idx, size, env, kind, monkeypatch):
+    """The same on saturated colours: the only bit-level check the shipped flavour's colour arithmetic (reciprocal multiplies, packed
+    Lab2BGR, the gfx950 spellings of lvm_gfx950.h against the C of the emulation header) can have."""
+    _shipped_case(lvm, hip, emu, idx, size, env, monkeypatch, kind=kind)
+
+
+class _Frames:
+    def __init__(self, *frames):
+        self.frames = frames
+
+    def frame(self, t):
+        return self.frames[t]
+
+
+def test_shipped_flavour_gpu_equals_emulation_on_the_colour_cube(lvm, hip, emu):
+    """Every triple of 64 values that take every cell of the table (content.cube_values): natural, permuted, natural as three frames
+    of a Laplace clip, 3 levels."""
+    nat, per = content.cube_frames(content.cube_values(64))
+    clip = _Frames(nat, per, nat)
+    _, pk = lvm.synth.config(0, (nat.shape[1], nat.shape[0], 3))
+    for keep in (False, True):
+        _assert_same(_run_lib(lvm, hip, clip, pk, 3, keep), _run_lib(lvm, emu, clip, pk, 3, keep), "keep_float=%s" % keep)
 
 
 @pytest.mark.parametrize("idx,size,calls", [(0, (320, 180, 4), (1, 5, 3)), (0, (264, 74, 3), (1, 6, 1, 2)), (3, (80, 52, 3), (17, 16, 9))])
@@ -387,13 +471,23 @@ def _riesz_run(lvm, lib, mem, monkeypatch, frames, pk, env, keep_float, exact):
 
 @pytest.mark.parametrize("w,h,levels", RZ_SHAPES)
 def test_riesz_variants_equal_the_default_kernels(lvm, po, hip, dev, w, h, levels, monkeypatch):
+    _riesz_variants(lvm, po, hip, dev, monkeypatch, w, h, levels)
+
+
+@pytest.mark.parametrize("w,h,levels", [(264, 150, 3), (67, 131, 2)])
+def test_riesz_variants_equal_the_default_kernels_on_chromatic_content(lvm, po, hip, dev, w, h, levels, monkeypatch):
+    """the same on `noise` (tests/content.py): every variant's Lab planes and output kernels on saturated colours, both flavours"""
+    _riesz_variants(lvm, po, hip, dev, monkeypatch, w, h, levels, kind="noise")
+
+
+def _riesz_variants(lvm, po, hip, dev, monkeypatch, w, h, levels, kind=None):
     """Per shape: the default kernels and every LVM_RZ_* variant on the same frames and the same GPU, in temporal batches of 1 ... 3
     frames.  With keep_float: identical float frames (the first frame of every call) and identical bytes, in the exact and the
     default flavour.  Shipped configuration (u8 step table): identical bytes among the variants; against the float-keeping build
     of the same flavour at most 1 LSB with >= STEPS_U8_FRAC identical (the quantiser paragraph; bar of
     tests/helpers.py:3-6).  Every variant of the exact flavour also meets the oracle bars; the worst gap is printed."""
     ck, pk = lvm.synth.config(2, (w, h, levels))
-    clip = lvm.synth.Clip(**ck)
+    clip = lvm.synth.Clip(**ck) if kind is None else content.chroma_clip(lvm, ck, kind)
     n = sum(RZ_CALLS)
     frames = np.stack([clip.frame(t) for t in range(n)])
     orc = po.Oracle()
@@ -442,7 +536,7 @@ def test_riesz_variants_equal_the_default_kernels(lvm, po, hip, dev, w, h, level
                     name, ex, t, int((su8[t] != bsu8[t]).sum()))
                 dd = np.abs(su8[t].astype(np.int32) - u8[t].astype(np.int32))
                 assert dd.max() <= 1 and (dd == 0).mean() >= STEPS_U8_FRAC, (name, ex, t, int(dd.max()), float((dd == 0).mean()))
-    print("riesz", (w, h, levels), "exact flavour vs oracle (acosf / sinf / cosf of the device library): worst float rel %.3e, "
+    print("riesz", kind or "synth", (w, h, levels), "exact flavour vs oracle (acosf / sinf / cosf of the device library): worst float rel %.3e, "
           "worst identical u8 fraction %.6f" % tuple(worst))
 
 

@@ -5,6 +5,7 @@ produced flags identical frame by frame."""
 import numpy as np
 import pytest
 
+import parity_matrix as M
 from helpers import c_params, run_pair
 
 pytestmark = pytest.mark.gpu
@@ -306,6 +307,22 @@ def test_color_1080p_window_fill(lvm, po, hip):
     ck, pk = lvm.synth.config(3)
     worst = run_pair(lvm, po, hip, lvm.synth.Clip(**ck), pk, 134, FLOAT_TOL)
     print("color 1080p worst", worst)
+
+
+# ---- chromatic content (tests/content.py) ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind,idx,w,h,levels", M.CHROMA_CASES)
+def test_chroma_default_flavour(lvm, po, hip, kind, idx, w, h, levels):
+    """Saturated colours through the default flavour (float32 cube root, reciprocal multiplies, packed Lab2BGR) of every mode, and
+    through the shipped configuration's step table (run_pair's second context)."""
+    worst = M.chroma_shape(lvm, po, hip, kind, idx, w, h, levels, flavour_exact=False)
+    print("chroma default flavour", kind, (idx, w, h, levels), "worst rel/u8/frac, shipped u8/frac", worst)
+
+
+@pytest.mark.parametrize("kind,idx,w,h,levels", [c for c in M.CHROMA_CASES if c[1] == 2])
+def test_chroma_riesz_exact_flavour(lvm, po, hip, kind, idx, w, h, levels):
+    """Riesz in OpenCV's operation order: the bars, not bit-equality (device acosf / sinf / cosf; Laplace and Color: test_gpu_exact.py)"""
+    worst = M.chroma_shape(lvm, po, hip, kind, idx, w, h, levels, flavour_exact=True, bit_exact=False)
+    print("chroma riesz exact flavour", kind, (w, h, levels), "worst rel/u8/frac, shipped u8/frac", worst)
 
 
 # ---- cross-frame pipeline ----------------------------------------------------------------------------

@@ -145,3 +145,31 @@ def test_trilinear_interpolation_against_a_numpy_restatement(po):
                      acc[:, 2].astype(np.float32) * np.float32(1.0 / 16384) * np.float32(256) - np.float32(128)], -1).astype(np.float32)
     got = po.bgr2lab(s.reshape(-1, 1, 3)).reshape(-1, 3)
     assert np.array_equal(got, want)
+
+
+def _off_diagonal_nodes(dist):
+    """[r][q][p] mask of the table nodes `dist` or more grid steps off the grey diagonal (max of |p - q|, |q - r|, |p - r|)"""
+    r, q, p = np.meshgrid(np.arange(33), np.arange(33), np.arange(33), indexing="ij")
+    return np.maximum(np.maximum(np.abs(p - q), np.abs(q - r)), np.abs(p - r)) >= dist
+
+
+@pytest.mark.parametrize("idx", [0, 2])
+def test_chromatic_content_reaches_the_table_off_the_grey_diagonal(lvm, po, emu, idx):
+    """A table that is wrong at every node 5 or more grid steps off the grey diagonal (94.9 % of the nodes), in the library only:
+    each kind of tests/content.py must then fail to match the untouched oracle -- the chromatic cases of the parity matrix do read
+    that part of the table (and what the kernels make of it)."""
+    import content
+    from helpers import run_pair
+    t = _oracle_table(po).reshape(33, 33, 33, 3)
+    wrong = _off_diagonal_nodes(5)
+    assert 0.948 < wrong.mean() < 0.950
+    t2 = np.where(wrong[..., None], (t.astype(np.int32) + 4000) % 16385, t).astype(np.int16)
+    assert (t2[wrong] != t[wrong]).all() and np.array_equal(t2[~wrong], t[~wrong])
+    ck, pk = lvm.synth.config(idx, (96, 64, 3))
+    for kind in content.KINDS:
+        with pytest.raises(AssertionError):
+            run_pair(lvm, po, emu, content.chroma_clip(lvm, ck, kind), pk, 4, 0.0, exact=True, lab_lut=t2)
+    # The documented reach of the standard clip, and the reason the chromatic cases exist: synth.texture is a grey grating with
+    # +- 12 levels of per-channel noise, its pixels stay within 4 grid steps of the diagonal, and it matches the oracle bit for bit
+    # on a table of which 94.9 % is wrong.
+    run_pair(lvm, po, emu, lvm.synth.Clip(**ck), pk, 4, 0.0, exact=True, lab_lut=t2)
