@@ -323,6 +323,31 @@ int  lvm_export_frames_mjpeg(lvm_ctx* ctx, const lvm_preprocess_params* pp, cons
                              const uint8_t* const* frames, int w, int h, int channels, ptrdiff_t in_stride, int quality,
                              uint8_t* out, size_t out_capacity, size_t* offsets, int* produced);
 
+/* Which OpenCV build the arithmetic of the RIESZ mode reproduces.  cv::filter2D / cv::sepFilter2D / `Mat * double` do not round alike in
+ * every build of OpenCV, and the ill-conditioned acos(q0 / |q|) of RieszPyramid.cpp:93-97 turns their last-bit differences into ~1.2e-4 of
+ * the output.  Mask 0 -- the default: every launch, kernel and byte is what it is without this call -- is the AVX2 / AVX-512
+ * dispatch of an x86-64 build: fused taps (v_fma) and a float64 scalar product.  The bits, each the oracle's switch of the same name
+ * (oracle/lvm_oracle.h, LVMO_VAR_*):
+ *   LVM_CV_FILTER_UNFUSED  a build whose filter loops dispatch to SSE2 only (CPU_BASELINE=SSE2 without AVX2 dispatch, or a host without
+ *                          FMA3): every tap of filter2D (the 9 x 9 kernels of RieszPyramid.cpp:227-232, :314-319 and the 1 x 5 / 5 x 1
+ *                          Riesz pair of :74-76) and of sepFilter2D / GaussianBlur (the 13-tap blurs of :110, :121-126) is a multiply, then an add.
+ *   LVM_CV_FILTER_DFT      a build without SSE3 -- every ARM build, macOS on Apple silicon included: filter2D sends kernels of >= 50 elements
+ *                          through crossCorr, so the 9 x 9 kernels (:227-232, :314-319) are the float64 sum of the exact products, rounded
+ *                          once.  The 5-tap pair and the separable blurs keep the direct path (fused there, unless _UNFUSED is set as well).
+ *   LVM_CV_MUL_F32         a build whose `Mat * double` narrows the scalar to float first: the five products of each Butterworth step
+ *                          (TemporalFilter.cpp:343-350) are x * (float)s.
+ * Takes effect from the next frame of the context, for all of its streams; the temporal state is kept (as the oracle's switch keeps it)
+ * and lvm_reset keeps the kind.  Laplace, Color, preprocess, compose and the codec ignore it (they meet the parity bar under every build,
+ * DESIGN.md 5); it applies in every flavour (default, lvm_debug_exact_lab, lvm_debug_lab_analytic) and to lvm_tile_riesz_*.  A mask with
+ * other bits: LVM_ERR_INVALID, nothing changes.  INTEGRATION.md says which kind goes with which OpenCV build.                        */
+enum { LVM_CV_FILTER_UNFUSED = 1,   /* filter2D / sepFilter2D taps as multiply, then add (SSE2-only dispatch) */
+       LVM_CV_FILTER_DFT     = 2,   /* filter2D kernels of >= 50 elements through crossCorr: float64 sum of the exact
+                                       products, rounded once (builds without SSE3 = every ARM / macOS build) */
+       LVM_CV_MUL_F32        = 4,   /* Riesz IIR `Mat * double` with the scalar narrowed to float first */
+       LVM_CV_ALL            = 7 };
+int  lvm_set_opencv_build(lvm_ctx* ctx, unsigned mask);
+int  lvm_get_opencv_build(lvm_ctx* ctx, unsigned* mask);
+
 /* Cross-frame software pipeline for lvm_process_device (throughput mode, default depth 0).
  * depth 1 (implemented for the Laplace mode; other modes ignore it): a call enqueues the
  * down-sweep of ITS frame on an internal second stream concurrently with the up-sweep + output of
@@ -393,7 +418,8 @@ int  lvm_profile_entry(lvm_ctx* ctx, int idx, char* name, size_t name_cap, doubl
                        long long* launches);
 /* Which kernels ran under entry idx's report name, comma-separated, where several share one (lap_down0, lap_final,
  * lab_lut, rz_lab, rz_final, col_down0, col_minmax, col_out): "strips" = the wave-strip kernel, "vec4" = the tiled kernel
- * with dword-wide frame I/O, "bytes" = the tiled kernel with byte I/O.  Empty for names with one kernel.  The frame's
+ * with dword-wide frame I/O, "bytes" = the tiled kernel with byte I/O; under a build kind of lvm_set_opencv_build the Riesz launches it changes add "unfused", "f64", "mulf32" or
+ * "unfused+mulf32".  Empty for names with one kernel.  The frame's
  * layout picks among them (see lvm_process_device); the tests use this to see that it picked what the launch code says. */
 int  lvm_profile_variants(lvm_ctx* ctx, int idx, char* variants, size_t cap);
 /* Algorithmic bytes per frame per stream for the current geometry/mode. */

@@ -72,6 +72,7 @@ class ProcessorConfig:
 LAB_LUT_ENTRIES = 33 * 33 * 33 * 3
 MJPEG_DECODER_REPLICATE, MJPEG_DECODER_LIBJPEG = 0, 1      # lvm_mjpeg_set_decoder (include/lvm_hip.h)
 MJPEG_SAMPLING_420, MJPEG_SAMPLING_422, MJPEG_SAMPLING_444, MJPEG_SAMPLING_GRAY, MJPEG_SAMPLING_ALL = 1, 2, 4, 8, 15      # lvm_mjpeg_set_samplings
+CV_FILTER_UNFUSED, CV_FILTER_DFT, CV_MUL_F32, CV_ALL = 1, 2, 4, 7      # lvm_set_opencv_build
 
 
 class LvmParams(C.Structure):
@@ -108,7 +109,8 @@ SYMBOLS = ["lvm_create", "lvm_destroy", "lvm_reset", "lvm_process", "lvm_process
            "lvm_profile_entry", "lvm_profile_variants", "lvm_algorithmic_bytes", "lvm_export_geometry", "lvm_export_frames", "lvm_export_set_overlay", "lvm_overlay_device", "lvm_tile_riesz_stage1", "lvm_tile_riesz_planes", "lvm_tile_riesz_stage2",
            "lvm_preprocess_geometry", "lvm_preprocess_device", "lvm_chain_process", "lvm_chain_process_batch",
            "lvm_set_max_frames", "lvm_host_alloc", "lvm_host_free", "lvm_compose_geometry", "lvm_compose_device", "lvm_chain_process_batch_ex",
-           "lvm_chain_present", "lvm_mjpeg_bound", "lvm_mjpeg_encode_device", "lvm_export_frames_mjpeg", "lvm_mjpeg_decode_device", "lvm_export_mjpeg_frames", "lvm_mjpeg_set_restart_interval", "lvm_mjpeg_set_decoder", "lvm_mjpeg_set_samplings"]
+           "lvm_chain_present", "lvm_mjpeg_bound", "lvm_mjpeg_encode_device", "lvm_export_frames_mjpeg", "lvm_mjpeg_decode_device", "lvm_export_mjpeg_frames", "lvm_mjpeg_set_restart_interval", "lvm_mjpeg_set_decoder", "lvm_mjpeg_set_samplings",
+           "lvm_set_opencv_build", "lvm_get_opencv_build"]
 
 
 def bind(lib):
@@ -172,6 +174,8 @@ def bind(lib):
     lib.lvm_mjpeg_set_restart_interval.argtypes = [vp, C.c_int]
     lib.lvm_mjpeg_set_decoder.argtypes = [vp, C.c_int]
     lib.lvm_mjpeg_set_samplings.argtypes = [vp, C.c_uint]
+    lib.lvm_set_opencv_build.argtypes = [vp, C.c_uint]
+    lib.lvm_get_opencv_build.argtypes = [vp, C.POINTER(C.c_uint)]
     lib.lvm_mjpeg_decode_device.argtypes = [vp, vp, C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_int, vp, C.c_ssize_t, C.c_ssize_t]
     lib.lvm_export_mjpeg_frames.argtypes = [vp, C.POINTER(LvmPreprocessParams), C.POINTER(LvmParams), C.c_int, C.c_int, vp, C.POINTER(C.c_size_t), C.c_int, C.c_int,
                                             C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t), ip]
@@ -382,6 +386,18 @@ class Context:
         default), _422, _444 and _GRAY.  The frames of one call share one sampling; all but 4:2:0 need MJPEG_DECODER_LIBJPEG."""
         self._check(self.lib.lvm_mjpeg_set_samplings(self.h, int(mask) & 0xFFFFFFFF))
 
+    def set_opencv_build(self, mask):
+        """lvm_set_opencv_build: which OpenCV build the Riesz mode's arithmetic reproduces from the next frame on, a mask of CV_FILTER_UNFUSED (SSE2-only
+        filter dispatch), CV_FILTER_DFT (builds without SSE3: every ARM / macOS build) and CV_MUL_F32; 0 = the default (AVX2 dispatch, float64 scalar).
+        The temporal state is kept; reset() keeps the kind.  Other bits: LvmError, nothing changes."""
+        self._check(self.lib.lvm_set_opencv_build(self.h, int(mask) & 0xFFFFFFFF))
+
+    def opencv_build(self):
+        """lvm_get_opencv_build: the mask set_opencv_build installed (0 by default)."""
+        m = C.c_uint(0)
+        self._check(self.lib.lvm_get_opencv_build(self.h, C.byref(m)))
+        return int(m.value)
+
     def mjpeg_decode_device(self, jpegs, w, h, d_ptr, stride=None, frame_stride=None):
         """lvm_mjpeg_decode_device: a list of JPEG frames (bytes) -> BGR frames in device memory at d_ptr."""
         stride = w * 3 if stride is None else stride
@@ -564,7 +580,8 @@ class Context:
         return out
 
     def profile_variants(self):
-        """{report name: set of kernel variants launched under it ("strips" / "vec4" / "bytes")} for the names several kernels share"""
+        """{report name: set of kernel variants launched under it ("strips" / "vec4" / "bytes"; under set_opencv_build the kind: "unfused" / "f64" /
+        "mulf32" / "unfused+mulf32")} for the names several kernels share"""
         n = self.lib.lvm_profile_collect(self.h)
         out = {}
         for i in range(max(n, 0)):

@@ -777,6 +777,23 @@ int lvm_mjpeg_set_samplings(lvm_ctx* c, unsigned mask) {
     return LVM_OK;
 }
 
+// Kept by lvm_reset (a property of the host's OpenCV, not of the clip); read by riesz.hip at every launch, so it holds from the next frame
+// on and leaves the temporal state alone.
+int lvm_set_opencv_build(lvm_ctx* c, unsigned mask) {
+    if (!c) return LVM_ERR_INVALID;
+    if (mask & ~(unsigned)LVM_CV_ALL) {
+        c->err = "lvm_set_opencv_build: mask must be a combination of LVM_CV_FILTER_UNFUSED (1), LVM_CV_FILTER_DFT (2), LVM_CV_MUL_F32 (4)";
+        return LVM_ERR_INVALID;
+    }
+    c->opencv_build = mask;
+    return LVM_OK;
+}
+int lvm_get_opencv_build(lvm_ctx* c, unsigned* mask) {
+    if (!c || !mask) return LVM_ERR_INVALID;
+    *mask = c->opencv_build;
+    return LVM_OK;
+}
+
 size_t lvm_mjpeg_bound(int w, int h) { return (w < 1 || h < 1) ? 0 : lvm::mjpeg_bound(w, h); }
 
 int lvm_mjpeg_encode_device(lvm_ctx* c, const uint8_t* d_bgr, int w, int h, ptrdiff_t stride, ptrdiff_t frame_stride, int n_frames, int quality,

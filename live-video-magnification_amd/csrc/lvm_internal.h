@@ -535,6 +535,7 @@ struct Ctx {
     void* mjpeg_dec = nullptr;        // mjpeg_decode.hip: per-frame tables and scratch of the decoder
     int mjpeg_decoder = LVM_MJPEG_DECODER_REPLICATE;   // lvm_mjpeg_set_decoder: the arithmetic behind the entropy layer
     unsigned mjpeg_samplings = LVM_MJPEG_SAMPLING_420;  // lvm_mjpeg_set_samplings: the samplings the decoder accepts
+    unsigned opencv_build = 0;        // lvm_set_opencv_build: which OpenCV build the Riesz arithmetic reproduces (a mask of LVM_CV_*; riesz.hip)
 };
 
 inline int lab_flavour(const Ctx* c) { return c->lab_analytic ? FL_ANALYTIC : (c->exact_lab ? FL_LUT_EXACT : FL_LUT_FAST); }

@@ -56,6 +56,28 @@ __device__ const float kHp9[81] = {
     0.0003f, 0.0020f, 0.0059f, 0.0103f, 0.0123f, 0.0103f, 0.0059f, 0.0020f, 0.0003f,
     0.0000f, 0.0003f, 0.0011f, 0.0022f, 0.0027f, 0.0022f, 0.0011f, 0.0003f, 0.0000f};
 
+// ---- OpenCV build kinds (lvm_set_opencv_build, include/lvm_hip.h) -----------------------------------------------------------------
+// How one tap of a filter is accumulated.  TK_FMA is the default association (the AVX2 / AVX-512 dispatch of cv::filter2D / sepFilter2D,
+// v_fma); TK_UNFUSED rounds the product first (the SSE2-only dispatch: multiply, then add -- two operations under -ffp-contract=off);
+// TK_F64 is filter2D's crossCorr path for the 9 x 9 kernels (builds without SSE3: every ARM / macOS build): the float64 sum of the exact
+// products, rounded once -- the float64 product of two floats is exact, so fma(k, v, s) in double IS s += (double)k * (double)v.
+// Skipped zero taps stay exact in every kind: adding +-0 to a sum that started at +0 changes nothing.
+enum { TK_FMA = 0, TK_UNFUSED = 1, TK_F64 = 2 };
+template <int TK> struct TapAcc { typedef float type; };
+template <> struct TapAcc<TK_F64> { typedef double type; };
+template <int TK, class T>
+__device__ __forceinline__ T rz_tap(float k, T v, T s) {
+    if constexpr (TK == TK_F64) return __builtin_fma((double)k, v, s);
+    else if constexpr (TK == TK_UNFUSED) return s + k * v;
+    else return __builtin_fmaf(k, v, s);
+}
+// the 5-tap Riesz pair and the 13-tap separable blurs never take the float64 path (kw * kh < 50): fused or not
+template <bool UNF> __device__ __forceinline__ float tapf(float k, float v, float s) { return rz_tap<UNF ? TK_UNFUSED : TK_FMA>(k, v, s); }
+template <bool UNF> __device__ __forceinline__ lvm_f2 f2_tap(lvm_f2 k, lvm_f2 v, lvm_f2 s) {
+    if constexpr (UNF) return s + k * v;
+    else return f2_fma(k, v, s);
+}
+
 // ---- u8 BGR -> L plane (MagnifyCore.hpp:218-222) ---------------------------------------------
 // L of one pixel, ANALYTIC flavour only (lvm_debug_lab_analytic): the Y row of the matrix and cv::cubeRoot's float64
 // rational polynomial.  The default flavour takes L from OpenCV's interpolated table (labconv.hip writes the L plane).
@@ -123,34 +145,49 @@ static_assert(CSP >= CSW && CSP % 4 == 0, "pitch");
 // 4 adjacent outputs (lx..lx+3, ly), lx % 4 == 0.  Fully unrolled: the 81 coefficients become
 // immediates and zero taps vanish (measured faster than a rolled row loop with scalar coefficient
 // loads, despite the higher register count).
-__device__ __forceinline__ void conv9x4(const float (&s)[CSH][CSP], int lx, int ly, const float* k, float kscale, float (&o)[4]) {
-    o[0] = o[1] = o[2] = o[3] = 0.f;
+// TK: how a tap is accumulated (rz_tap); T = the tile's and the accumulators' type (double for TK_F64: the tile is staged as doubles,
+// so a value is converted once), P = the tile's row pitch.
+template <int TK = TK_FMA, class T, int P>
+__device__ __forceinline__ void conv9x4(const T (&s)[CSH][P], int lx, int ly, const float* k, float kscale, T (&o)[4]) {
+    o[0] = o[1] = o[2] = o[3] = 0;
 #pragma unroll
     for (int i = 0; i < 9; ++i) {
-        const float4 a = *reinterpret_cast<const float4*>(&s[ly + i][lx]);
-        const float4 b = *reinterpret_cast<const float4*>(&s[ly + i][lx + 4]);
-        const float4 c = *reinterpret_cast<const float4*>(&s[ly + i][lx + 8]);
-        const float v[12] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w};
+        T v[12];
+        if constexpr (sizeof(T) == 4) {
+            const float4 a = *reinterpret_cast<const float4*>(&s[ly + i][lx]);
+            const float4 b = *reinterpret_cast<const float4*>(&s[ly + i][lx + 4]);
+            const float4 c = *reinterpret_cast<const float4*>(&s[ly + i][lx + 8]);
+            v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+            v[8] = c.x; v[9] = c.y; v[10] = c.z; v[11] = c.w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 12; ++j) v[j] = s[ly + i][lx + j];
+        }
 #pragma unroll
         for (int j = 0; j < 9; ++j) {
             const float kv = k[i * 9 + j] * kscale;   // x2 is exact
             if (kv != 0.f) {
-                o[0] = __builtin_fmaf(kv, v[j], o[0]); o[1] = __builtin_fmaf(kv, v[j + 1], o[1]);
-                o[2] = __builtin_fmaf(kv, v[j + 2], o[2]); o[3] = __builtin_fmaf(kv, v[j + 3], o[3]);
+                o[0] = rz_tap<TK>(kv, v[j], o[0]); o[1] = rz_tap<TK>(kv, v[j + 1], o[1]);
+                o[2] = rz_tap<TK>(kv, v[j + 2], o[2]); o[3] = rz_tap<TK>(kv, v[j + 3], o[3]);
             }
         }
     }
 }
-__device__ __forceinline__ void stage_reflect(float (&s)[CSH][CSP], const float* __restrict__ src, int w, int h, int x0, int y0) {
+// row pitch of a staged 9x9 tile: doubles take the bare tile width (72 x 24 x 8 B = 13.8 KB)
+template <class T> constexpr int tile_pitch() { return sizeof(T) == 8 ? CSW : CSP; }
+template <class T, int P>
+__device__ __forceinline__ void stage_reflect(T (&s)[CSH][P], const float* __restrict__ src, int w, int h, int x0, int y0) {
     for (int i = threadIdx.x; i < CSH * CSW; i += 256) {
         const int ly = i / CSW, lx = i - ly * CSW;
         s[ly][lx] = src[(size_t)reflect101(y0 - SH + ly, h) * w + reflect101(x0 - SH + lx, w)];
     }
 }
 
+template <int TK>
 __global__ __launch_bounds__(256) void k_rz_split(const float* __restrict__ oct, int w, int h,
                                                      float* __restrict__ band, float* __restrict__ next, int nw, int nh) {
-    __shared__ __attribute__((aligned(16))) float s[CSH][CSP];
+    typedef typename TapAcc<TK>::type T;
+    __shared__ __attribute__((aligned(16))) T s[CSH][tile_pitch<T>()];
     const Bid3 bq{(int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z};
     const int x0 = bq.x * CW, y0 = bq.y * CH;
     stage_reflect(s, oct + (size_t)bq.z * w * h, w, h, x0, y0);
@@ -159,8 +196,9 @@ __global__ __launch_bounds__(256) void k_rz_split(const float* __restrict__ oct,
         const int y = threadIdx.x >> 4, x = (threadIdx.x & 15) * 4;
         const int gx = x0 + x, gy = y0 + y;
         if (gx < w && gy < h) {
-            float o[4];
-            conv9x4(s, x, y, kHp9, 1.0f, o);                                          // :227
+            T ot[4];
+            conv9x4<TK>(s, x, y, kHp9, 1.0f, ot);                                     // :227
+            const float o[4] = {(float)ot[0], (float)ot[1], (float)ot[2], (float)ot[3]};
             float* d = band + ((size_t)bq.z * h + gy) * w + gx;
             if ((w & 3) == 0) *reinterpret_cast<float4*>(d) = make_float4(o[0], o[1], o[2], o[3]);   // gx % 4 == 0, planes 256-B aligned
             else {
@@ -175,22 +213,27 @@ __global__ __launch_bounds__(256) void k_rz_split(const float* __restrict__ oct,
         const int y = 2 * v, x = 2 * q;
         const int gx = x0 + x, gy = y0 + y;
         if (gx < w && gy < h) {
-            float acc = 0.f;
+            T acc = 0;
 #pragma unroll
             for (int i = 0; i < 9; ++i) {
-                const float2 a = *reinterpret_cast<const float2*>(&s[y + i][x]);
-                const float2 b = *reinterpret_cast<const float2*>(&s[y + i][x + 2]);
-                const float2 c = *reinterpret_cast<const float2*>(&s[y + i][x + 4]);
-                const float2 d = *reinterpret_cast<const float2*>(&s[y + i][x + 6]);
-                const float e = s[y + i][x + 8];
-                const float t[9] = {a.x, a.y, b.x, b.y, c.x, c.y, d.x, d.y, e};
+                T t[9];
+                if constexpr (sizeof(T) == 4) {
+                    const float2 a = *reinterpret_cast<const float2*>(&s[y + i][x]);
+                    const float2 b = *reinterpret_cast<const float2*>(&s[y + i][x + 2]);
+                    const float2 c = *reinterpret_cast<const float2*>(&s[y + i][x + 4]);
+                    const float2 d = *reinterpret_cast<const float2*>(&s[y + i][x + 6]);
+                    t[0] = a.x; t[1] = a.y; t[2] = b.x; t[3] = b.y; t[4] = c.x; t[5] = c.y; t[6] = d.x; t[7] = d.y; t[8] = s[y + i][x + 8];
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 9; ++j) t[j] = s[y + i][x + j];
+                }
 #pragma unroll
                 for (int j = 0; j < 9; ++j) {
                     const float kv = kLp9[i * 9 + j] * 2.0f;                           // x2 is exact
-                    if (kv != 0.f) acc = __builtin_fmaf(kv, t[j], acc);               // :232-234, row-major taps
+                    if (kv != 0.f) acc = rz_tap<TK>(kv, t[j], acc);                   // :232-234, row-major taps
                 }
             }
-            next[((size_t)bq.z * nh + gy / 2) * nw + gx / 2] = acc;
+            next[((size_t)bq.z * nh + gy / 2) * nw + gx / 2] = (float)acc;
         }
     }
 }
@@ -476,12 +519,16 @@ __device__ __forceinline__ float mul_sd(float x, double s) { return (float)((dou
 // exact inside the fma, so fma(x, hi, x * lo) is the float nearest to x * s except in double-rounding ties (~2^-24 of
 // the cases, one ulp).  Three conversions / f64 operations become two f32 ones, 20 times per pixel and frame.
 __device__ __forceinline__ float mul_sd(float x, SdF s) { return __builtin_fmaf(x, s.hi, x * s.lo); }
+// LVM_CV_MUL_F32: the scalar narrowed to float before the product (s.hi = (float)s), in every flavour
+__device__ __forceinline__ float mul_sf(float x, SdF s) { return x * s.hi; }
 
 // With nt > 1 the workgroup walks over nt consecutive frames: the 13 state values of a pixel (prior
 // band + Riesz pair, accumulated phase, 8 filter registers) stay in registers and move through HBM
 // once per launch instead of once per frame; the band tile of frame t+1 is prefetched while frame t
 // is processed.
-template <bool EXACT>
+// UNF: the 5-tap Riesz pair with unfused taps (LVM_CV_FILTER_UNFUSED); MF32: `Mat * double` of the IIR step with the scalar narrowed to
+// float first (LVM_CV_MUL_F32) -- x * (float)s, in place of the exact flavour's float64 product and of the default flavour's hi / lo pair.
+template <bool EXACT, bool UNF, bool MF32>
 __global__ __launch_bounds__(256) void k_rz_phase(PhaseArgs aa) {
     __shared__ float s[PT_H + 4][PT_W + 4 + 1];
     int lvl = 0;
@@ -529,14 +576,14 @@ __global__ __launch_bounds__(256) void k_rz_phase(PhaseArgs aa) {
         const size_t fidx = (size_t)t * a.fs + idx;
         const float p = s[y + 2][x + 2];
         // filter2D with [-0.2 -0.48 0 0.48 0.2] (1x5) and its transpose: non-zero taps, fma chain
-        float r1 = __builtin_fmaf(-0.2f, s[y + 2][x], 0.f);
-        r1 = __builtin_fmaf(-0.48f, s[y + 2][x + 1], r1);
-        r1 = __builtin_fmaf(0.48f, s[y + 2][x + 3], r1);
-        r1 = __builtin_fmaf(0.2f, s[y + 2][x + 4], r1);
-        float r2 = __builtin_fmaf(-0.2f, s[y][x + 2], 0.f);
-        r2 = __builtin_fmaf(-0.48f, s[y + 1][x + 2], r2);
-        r2 = __builtin_fmaf(0.48f, s[y + 3][x + 2], r2);
-        r2 = __builtin_fmaf(0.2f, s[y + 4][x + 2], r2);
+        float r1 = tapf<UNF>(-0.2f, s[y + 2][x], 0.f);
+        r1 = tapf<UNF>(-0.48f, s[y + 2][x + 1], r1);
+        r1 = tapf<UNF>(0.48f, s[y + 2][x + 3], r1);
+        r1 = tapf<UNF>(0.2f, s[y + 2][x + 4], r1);
+        float r2 = tapf<UNF>(-0.2f, s[y][x + 2], 0.f);
+        r2 = tapf<UNF>(-0.48f, s[y + 1][x + 2], r2);
+        r2 = tapf<UNF>(0.48f, s[y + 3][x + 2], r2);
+        r2 = tapf<UNF>(0.2f, s[y + 4][x + 2], r2);
         if (aa.mode != 0) {   // seed: prior <- current (Riesz pair zeroed by RieszPyramid::init), filters cleared
             Pp = p; R1 = aa.mode == 1 ? 0.f : r1; R2 = aa.mode == 1 ? 0.f : r2;
             continue;
@@ -568,7 +615,7 @@ __global__ __launch_bounds__(256) void k_rz_phase(PhaseArgs aa) {
         // IIRTemporalFilter for the low and the high cutoff (TemporalFilter.cpp:343-350); both keep
         // their own copy of the accumulated phase in the reference, the copies are always equal.
         phc = phc + dc; phs = phs + ds;
-#define MSD(x, c) (EXACT ? mul_sd((x), aa.c) : mul_sd((x), aa.f##c))
+#define MSD(x, c) (MF32 ? mul_sf((x), aa.f##c) : (EXACT ? mul_sd((x), aa.c) : mul_sd((x), aa.f##c)))
         const float ylc = MSD(phc, lb0) + lo0c;
         const float yls = MSD(phs, lb0) + lo0s;
         lo0c = (MSD(phc, lb1) + lo1c) - MSD(ylc, la1);
@@ -601,7 +648,7 @@ __global__ __launch_bounds__(256) void k_rz_phase(PhaseArgs aa) {
 // thread and plane instead of four 4-byte ones, and a third less halo traffic than the 32 x 8 tile (1.33 x instead of
 // 1.69 x the band).  Same per-pixel arithmetic, same order: bit-identical to k_rz_phase.
 constexpr int P4_W = 64, P4_H = 16, P4_SW = P4_W + 8, P4_SH = P4_H + 4;
-template <bool EXACT>
+template <bool EXACT, bool UNF, bool MF32>
 __global__ __launch_bounds__(256) void k_rz_phase4(PhaseArgs aa) {
     __shared__ __attribute__((aligned(16))) float s[P4_SH][P4_SW];
     int lvl = 0;
@@ -682,14 +729,14 @@ __global__ __launch_bounds__(256) void k_rz_phase4(PhaseArgs aa) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const float p = hrow[4 + k];
-            float r1 = __builtin_fmaf(-0.2f, hrow[2 + k], 0.f);
-            r1 = __builtin_fmaf(-0.48f, hrow[3 + k], r1);
-            r1 = __builtin_fmaf(0.48f, hrow[5 + k], r1);
-            r1 = __builtin_fmaf(0.2f, hrow[6 + k], r1);
-            float r2 = __builtin_fmaf(-0.2f, vcol[0][k], 0.f);
-            r2 = __builtin_fmaf(-0.48f, vcol[1][k], r2);
-            r2 = __builtin_fmaf(0.48f, vcol[3][k], r2);
-            r2 = __builtin_fmaf(0.2f, vcol[4][k], r2);
+            float r1 = tapf<UNF>(-0.2f, hrow[2 + k], 0.f);
+            r1 = tapf<UNF>(-0.48f, hrow[3 + k], r1);
+            r1 = tapf<UNF>(0.48f, hrow[5 + k], r1);
+            r1 = tapf<UNF>(0.2f, hrow[6 + k], r1);
+            float r2 = tapf<UNF>(-0.2f, vcol[0][k], 0.f);
+            r2 = tapf<UNF>(-0.48f, vcol[1][k], r2);
+            r2 = tapf<UNF>(0.48f, vcol[3][k], r2);
+            r2 = tapf<UNF>(0.2f, vcol[4][k], r2);
             r1v[k] = r1; r2v[k] = r2;
             if (aa.mode != 0) {
                 Pp[k] = p; R1[k] = aa.mode == 1 ? 0.f : r1; R2[k] = aa.mode == 1 ? 0.f : r2;
@@ -716,7 +763,7 @@ __global__ __launch_bounds__(256) void k_rz_phase4(PhaseArgs aa) {
             if (ds != ds) ds = 0.f;
             const float am = EXACT ? sqrtf(ampq) : __builtin_amdgcn_sqrtf(ampq);
             phc[k] = phc[k] + dc; phs[k] = phs[k] + ds;
-#define MSD(x, c) (EXACT ? mul_sd((x), aa.c) : mul_sd((x), aa.f##c))
+#define MSD(x, c) (MF32 ? mul_sf((x), aa.f##c) : (EXACT ? mul_sd((x), aa.c) : mul_sd((x), aa.f##c)))
             const float ylc = MSD(phc[k], lb0) + lo0c[k];
             const float yls = MSD(phs[k], lb0) + lo0s[k];
             lo0c[k] = (MSD(phc[k], lb1) + lo1c[k]) - MSD(ylc, la1);
@@ -787,7 +834,8 @@ __device__ __forceinline__ float rz_amplify(float v0, float v1, float v2, float 
     return band * cp - pair * sp;
 }
 
-template <bool EXACT>
+// UNF (all three forms of this stage): the taps of the row and column passes unfused (LVM_CV_FILTER_UNFUSED, rz_tap)
+template <bool EXACT, bool UNF>
 __global__ __launch_bounds__(256) void k_rz_blur_amp(BlurArgs aa) {
     __shared__ float s[3][BSH][BS + 1];
     __shared__ float hr[3][BSH][BT + 1];
@@ -811,7 +859,7 @@ __global__ __launch_bounds__(256) void k_rz_blur_amp(BlurArgs aa) {
         const int ly = r / BT, x = r - ly * BT;
         float acc = aa.g[0] * s[f][ly][x];
 #pragma unroll
-        for (int j = 1; j < 13; ++j) acc = __builtin_fmaf(aa.g[j], s[f][ly][x + j], acc);
+        for (int j = 1; j < 13; ++j) acc = tapf<UNF>(aa.g[j], s[f][ly][x + j], acc);
         hr[f][ly][x] = acc;
     }
     __syncthreads();
@@ -824,7 +872,7 @@ __global__ __launch_bounds__(256) void k_rz_blur_amp(BlurArgs aa) {
         for (int f = 0; f < 3; ++f) {   // SymmColumnFilter: centre, then fma(kj, S[+j] + S[-j])
             float acc = aa.g[6] * hr[f][y + BH][x];
 #pragma unroll
-            for (int j = 1; j <= 6; ++j) acc = __builtin_fmaf(aa.g[6 + j], hr[f][y + BH + j][x] + hr[f][y + BH - j][x], acc);
+            for (int j = 1; j <= 6; ++j) acc = tapf<UNF>(aa.g[6 + j], hr[f][y + BH + j][x] + hr[f][y + BH - j][x], acc);
             v[f] = acc;
         }
         const size_t idx = pl + (size_t)gy * a.w + gx;
@@ -852,7 +900,7 @@ constexpr int B2W = 64, B2H = LVM_BLUR_H, B2T = 8 * B2H, B2HX = 8, B2HY = 6, B2S
 #else
 #define LVM_BLUR_BOUNDS __launch_bounds__(B2T)
 #endif
-template <bool EXACT>
+template <bool EXACT, bool UNF>
 __global__ LVM_BLUR_BOUNDS void k_rz_blur_amp4(BlurArgs aa) {
     __shared__ __attribute__((aligned(16))) float s[B2SH][B2SW];
     __shared__ __attribute__((aligned(16))) float hr[B2SH][B2W];
@@ -903,7 +951,7 @@ __global__ LVM_BLUR_BOUNDS void k_rz_blur_amp4(BlurArgs aa) {
             for (int m = 0; m < 4; ++m) {
                 float acc = aa.g[0] * v[m + 2];
 #pragma unroll
-                for (int j = 1; j < 13; ++j) acc = __builtin_fmaf(aa.g[j], v[m + 2 + j], acc);
+                for (int j = 1; j < 13; ++j) acc = tapf<UNF>(aa.g[j], v[m + 2 + j], acc);
                 o[m] = acc;
             }
             *reinterpret_cast<float4*>(&hr[ly][4 * g]) = make_float4(o[0], o[1], o[2], o[3]);
@@ -927,8 +975,8 @@ __global__ LVM_BLUR_BOUNDS void k_rz_blur_amp4(BlurArgs aa) {
             const float* u0 = &up0.x; const float* d0 = &dn0.x; const float* u1 = &up1.x; const float* d1 = &dn1.x;
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
-                acc0[m] = __builtin_fmaf(aa.g[6 + j], u0[m] + d0[m], acc0[m]);
-                acc1[m] = __builtin_fmaf(aa.g[6 + j], u1[m] + d1[m], acc1[m]);
+                acc0[m] = tapf<UNF>(aa.g[6 + j], u0[m] + d0[m], acc0[m]);
+                acc1[m] = tapf<UNF>(aa.g[6 + j], u1[m] + d1[m], acc1[m]);
             }
             up0 = up1; dn1 = dn0;          // row y+7+j is the next "up" row of output 0, row y+6-j the next "down" row of output 1
         }
@@ -961,9 +1009,10 @@ __global__ LVM_BLUR_BOUNDS void k_rz_blur_amp4(BlurArgs aa) {
 // instead of 24 x 72 with three quarters of them zero -- half the LDS bytes read by the polyphase low-pass (three 64-bit
 // reads per kernel row instead of three 128-bit ones), a fifth of the staging stores, 7 KB less LDS per workgroup.
 constexpr int CCH = CSH / 2, CCP = 40;                    // compact tile: rows, columns, row pitch (floats)
-template <bool COMPACT> struct CollapseTile { float v[COMPACT ? CCH : CSH][COMPACT ? CCP : CSP]; };
-template <bool COMPACT>
-__device__ __forceinline__ void collapse_stage(float (&sb)[CSH][CSP], CollapseTile<COMPACT>& su,
+// (T = double: the float64 kind of lvm_set_opencv_build, both tiles staged as doubles -- element by element, no vector path)
+template <bool COMPACT, class T = float> struct CollapseTile { T v[COMPACT ? CCH : CSH][COMPACT ? CCP : tile_pitch<T>()]; };
+template <bool COMPACT, class T, int P>
+__device__ __forceinline__ void collapse_stage(T (&sb)[CSH][P], CollapseTile<COMPACT, T>& su,
                                                const float* __restrict__ bandA, const float* __restrict__ resn,
                                                int w, int h, int nw, int nh, int x0, int y0) {
     // Interior tiles of planes whose width is a multiple of 4 need no reflection: the band tile is 432 aligned
@@ -971,24 +1020,26 @@ __device__ __forceinline__ void collapse_stage(float (&sb)[CSH][CSP], CollapseTi
     // (v, 0, v', 0), plus 12 rows of zeros -- about a tenth of the instructions of the per-element path below,
     // which was ~40 % of this kernel's instruction count.
     const bool interior = (w & 3) == 0 && x0 - SH >= 0 && x0 + CW + SH <= w && y0 - SH >= 0 && y0 + CH + SH <= h;
-    if (interior) {
-        for (int i = threadIdx.x; i < CSH * (CSW / 4); i += 256) {
-            const int ly = i / (CSW / 4), g = i - ly * (CSW / 4);
-            *reinterpret_cast<float4*>(&sb[ly][4 * g]) =
-                *reinterpret_cast<const float4*>(bandA + (size_t)(y0 - SH + ly) * w + (x0 - SH + 4 * g));
-        }
-        // tile origin (x0 - 4, y0 - 4) is even-even, so local parity = image parity
-        const int cx0 = (x0 - SH) >> 1, cy0 = (y0 - SH) >> 1;
-        for (int i = threadIdx.x; i < (CSH / 2) * (CSW / 4); i += 256) {
-            const int r = i / (CSW / 4), g = i - r * (CSW / 4);
-            const float2 v = *reinterpret_cast<const float2*>(resn + (size_t)(cy0 + r) * nw + (cx0 + 2 * g));   // 8-byte aligned: cx0, nw even
-            if (COMPACT) *reinterpret_cast<float2*>(&su.v[r][2 * g]) = v;
-            else {
-                *reinterpret_cast<float4*>(&su.v[2 * r][4 * g]) = make_float4(v.x, 0.f, v.y, 0.f);
-                *reinterpret_cast<float4*>(&su.v[2 * r + 1][4 * g]) = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (sizeof(T) == 4) {      // (the float64 tiles are staged element by element below)
+        if (interior) {
+            for (int i = threadIdx.x; i < CSH * (CSW / 4); i += 256) {
+                const int ly = i / (CSW / 4), g = i - ly * (CSW / 4);
+                *reinterpret_cast<float4*>(&sb[ly][4 * g]) =
+                    *reinterpret_cast<const float4*>(bandA + (size_t)(y0 - SH + ly) * w + (x0 - SH + 4 * g));
             }
+            // tile origin (x0 - 4, y0 - 4) is even-even, so local parity = image parity
+            const int cx0 = (x0 - SH) >> 1, cy0 = (y0 - SH) >> 1;
+            for (int i = threadIdx.x; i < (CSH / 2) * (CSW / 4); i += 256) {
+                const int r = i / (CSW / 4), g = i - r * (CSW / 4);
+                const float2 v = *reinterpret_cast<const float2*>(resn + (size_t)(cy0 + r) * nw + (cx0 + 2 * g));   // 8-byte aligned: cx0, nw even
+                if (COMPACT) *reinterpret_cast<float2*>(&su.v[r][2 * g]) = v;
+                else {
+                    *reinterpret_cast<float4*>(&su.v[2 * r][4 * g]) = make_float4(v.x, 0.f, v.y, 0.f);
+                    *reinterpret_cast<float4*>(&su.v[2 * r + 1][4 * g]) = make_float4(0.f, 0.f, 0.f, 0.f);
+                }
+            }
+            return;
         }
-        return;
     }
     for (int i = threadIdx.x; i < CSH * CSW; i += 256) {
         const int ly = i / CSW, lx = i - ly * CSW;
@@ -1008,14 +1059,20 @@ __device__ __forceinline__ void collapse_stage(float (&sb)[CSH][CSP], CollapseTi
 // multiples of 64), gy = image row.  Polyphase low-pass of the zero-injected image + high-pass.
 // polyphase low-pass of the zero-injected tile for the 4 outputs; ODD = parity of the image row (the kernel rows
 // i == gy (mod 2) are the only ones that meet non-zero samples: 0,2,4,6,8 or 1,3,5,7)
-template <bool ODD, bool COMPACT>
-__device__ __forceinline__ void collapse_lp4(const CollapseTile<COMPACT>& su, int lx, int ly, float (&lp)[4]) {
-    lp[0] = lp[1] = lp[2] = lp[3] = 0.f;
+template <bool ODD, bool COMPACT, int TK, class T>
+__device__ __forceinline__ void collapse_lp4(const CollapseTile<COMPACT, T>& su, int lx, int ly, T (&lp)[4]) {
+    lp[0] = lp[1] = lp[2] = lp[3] = 0;
 #pragma unroll
     for (int ii = 0; ii < (ODD ? 4 : 5); ++ii) {
         const int i = ODD ? 2 * ii + 1 : 2 * ii;
-        float v[12];
-        if (COMPACT) {               // ly + i is even (kernel rows of the output row's parity), lx a multiple of 4
+        T v[12];
+        if constexpr (sizeof(T) == 8) {
+#pragma unroll
+            for (int j = 0; j < 12; ++j) {
+                if constexpr (COMPACT) v[j] = (j & 1) ? T(0) : su.v[(ly + i) >> 1][(lx + j) >> 1];
+                else v[j] = su.v[ly + i][lx + j];
+            }
+        } else if constexpr (COMPACT) {               // ly + i is even (kernel rows of the output row's parity), lx a multiple of 4
             const float2 a = *reinterpret_cast<const float2*>(&su.v[(ly + i) >> 1][lx >> 1]);
             const float2 b = *reinterpret_cast<const float2*>(&su.v[(ly + i) >> 1][(lx >> 1) + 2]);
             const float2 c = *reinterpret_cast<const float2*>(&su.v[(ly + i) >> 1][(lx >> 1) + 4]);
@@ -1031,32 +1088,33 @@ __device__ __forceinline__ void collapse_lp4(const CollapseTile<COMPACT>& su, in
 #pragma unroll
         for (int j = 0; j < 9; ++j) {           // output m (column parity m & 1) uses taps j == m (mod 2)
             const float kv = kLp9[i * 9 + j] * 2.0f;
-            if ((j & 1) == 0) { lp[0] = __builtin_fmaf(kv, v[j], lp[0]); lp[2] = __builtin_fmaf(kv, v[j + 2], lp[2]); }
-            else { lp[1] = __builtin_fmaf(kv, v[j + 1], lp[1]); lp[3] = __builtin_fmaf(kv, v[j + 3], lp[3]); }
+            if ((j & 1) == 0) { lp[0] = rz_tap<TK>(kv, v[j], lp[0]); lp[2] = rz_tap<TK>(kv, v[j + 2], lp[2]); }
+            else { lp[1] = rz_tap<TK>(kv, v[j + 1], lp[1]); lp[3] = rz_tap<TK>(kv, v[j + 3], lp[3]); }
         }
     }
 }
 // The row parity is uniform across a wave (collapse_row() below maps waves 0-1 to the even rows of the tile
 // and waves 2-3 to the odd ones), so the parity test is a scalar branch and every tap weight an immediate.
 __device__ __forceinline__ int collapse_row() { return ((threadIdx.x >> 4) & 7) * 2 + (threadIdx.x >> 7); }
-template <bool COMPACT>
-__device__ __forceinline__ void collapse_px4(const float (&sb)[CSH][CSP], const CollapseTile<COMPACT>& su,
+template <int TK = TK_FMA, bool COMPACT, class T, int P>
+__device__ __forceinline__ void collapse_px4(const T (&sb)[CSH][P], const CollapseTile<COMPACT, T>& su,
                                              int lx, int ly, int gy, float (&o)[4]) {
-    float lp[4];
-    if (__builtin_amdgcn_readfirstlane(gy & 1)) collapse_lp4<true, COMPACT>(su, lx, ly, lp);
-    else collapse_lp4<false, COMPACT>(su, lx, ly, lp);
-    float hp[4];
-    conv9x4(sb, lx, ly, kHp9, 1.0f, hp);
+    T lp[4];
+    if (__builtin_amdgcn_readfirstlane(gy & 1)) collapse_lp4<true, COMPACT, TK>(su, lx, ly, lp);
+    else collapse_lp4<false, COMPACT, TK>(su, lx, ly, lp);
+    T hp[4];
+    conv9x4<TK>(sb, lx, ly, kHp9, 1.0f, hp);
 #pragma unroll
-    for (int m = 0; m < 4; ++m) o[m] = lp[m] + hp[m];                                 // :322
+    for (int m = 0; m < 4; ++m) o[m] = (float)lp[m] + (float)hp[m];                   // :322 (both filter2D results are float planes)
 }
 
 // (a 64 x 32 / 4 x 2 variant of this kernel, like k_rz_split2, needs 300 registers and measured 48 us against 29 us)
-template <bool COMPACT>
+template <bool COMPACT, int TK>
 __global__ __launch_bounds__(256) void k_rz_collapse(const float* __restrict__ bandA, const float* __restrict__ resn,
                                                      float* __restrict__ res, int w, int h, int nw, int nh) {
-    __shared__ __attribute__((aligned(16))) float sb[CSH][CSP];
-    __shared__ __attribute__((aligned(16))) CollapseTile<COMPACT> su;
+    typedef typename TapAcc<TK>::type T;
+    __shared__ __attribute__((aligned(16))) T sb[CSH][tile_pitch<T>()];
+    __shared__ __attribute__((aligned(16))) CollapseTile<COMPACT, T> su;
     const Bid3 bq{(int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z};      // (XCD-aware order measured: level 1 73 -> 77 us, the others equal)
     const int x0 = bq.x * CW, y0 = bq.y * CH;
     const size_t pl = (size_t)bq.z * w * h, pn = (size_t)bq.z * nw * nh;
@@ -1066,7 +1124,7 @@ __global__ __launch_bounds__(256) void k_rz_collapse(const float* __restrict__ b
     const int gx = x0 + x, gy = y0 + y;
     if (gx < w && gy < h) {
         float o[4];
-        collapse_px4(sb, su, x, y, gy, o);
+        collapse_px4<TK>(sb, su, x, y, gy, o);
         float* d = res + pl + (size_t)gy * w + gx;
         if ((w & 3) == 0) *reinterpret_cast<float4*>(d) = make_float4(o[0], o[1], o[2], o[3]);
         else {
@@ -1092,7 +1150,7 @@ __device__ __attribute__((noinline)) float rz_amplify_exact_call(float v0, float
 constexpr int BSW = 116, BS_THREADS = 256;
 struct BlurStripLv { const float *amp, *tc, *ts, *band, *R1, *R2; float* bandA; int w, h, sx, sy, rows, task0; };
 struct BlurStripArgs { BlurStripLv lv[kMaxBands]; int nlv, ntasks; float g[13]; float alpha, thr; };
-template <bool EXACT>
+template <bool EXACT, bool UNF>
 __global__ __launch_bounds__(BS_THREADS) void k_rz_blur_strips(BlurStripArgs aa) {
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
     // (launch order; the XCD-aware order of lvm_internal.h was measured here too: 550 -> 719-734 us per 32 frames)
@@ -1154,8 +1212,8 @@ __global__ __launch_bounds__(BS_THREADS) void k_rz_blur_strips(BlurStripArgs aa)
         lvm_f2 acc = f2_all(aa.g[0]) * A[0];
 #pragma unroll
         for (int k = 0; k < 6; ++k) {
-            acc = f2_fma(f2_all(aa.g[2 * k + 1]), f2_set(A[k][1], A[k + 1][0]), acc);
-            acc = f2_fma(f2_all(aa.g[2 * k + 2]), A[k + 1], acc);
+            acc = f2_tap<UNF>(f2_all(aa.g[2 * k + 1]), f2_set(A[k][1], A[k + 1][0]), acc);
+            acc = f2_tap<UNF>(f2_all(aa.g[2 * k + 2]), A[k + 1], acc);
         }
         return acc;
     };
@@ -1179,7 +1237,7 @@ __global__ __launch_bounds__(BS_THREADS) void k_rz_blur_strips(BlurStripArgs aa)
                 for (int f = 0; f < 3; ++f) {
                     lvm_f2 acc = f2_all(aa.g[6]) * H[f][(ph + 7) % 13];
 #pragma unroll
-                    for (int j = 1; j <= 6; ++j) acc = f2_fma(f2_all(aa.g[6 + j]), H[f][(ph + 7 + j) % 13] + H[f][(ph + 7 - j + 13) % 13], acc);
+                    for (int j = 1; j <= 6; ++j) acc = f2_tap<UNF>(f2_all(aa.g[6 + j]), H[f][(ph + 7 + j) % 13] + H[f][(ph + 7 - j + 13) % 13], acc);
                     v[f] = acc;
                 }
                 // Riesz pair of the band at the lane's two columns: [-0.2 -0.48 0 0.48 0.2] along the row (neighbour columns from
@@ -1189,8 +1247,8 @@ __global__ __launch_bounds__(BS_THREADS) void k_rz_blur_strips(BlurStripArgs aa)
                     const float c0v = bw[2][0], c1v = bw[2][1];
                     const float lm2 = dpp_shr1(c0v), lm1 = dpp_shr1(c1v), rp2 = dpp_shl1(c0v), rp3 = dpp_shl1(c1v);   // columns c0-2, c0-1, c0+2, c0+3
                     bd = bw[2];
-                    q1 = f2_fma(f2_all(0.2f), f2_set(rp2, rp3), f2_fma(f2_all(0.48f), f2_set(c1v, rp2), f2_fma(f2_all(-0.48f), f2_set(lm1, c0v), f2_fma(f2_all(-0.2f), f2_set(lm2, lm1), f2_all(0.f)))));
-                    q2 = f2_fma(f2_all(0.2f), bw[4], f2_fma(f2_all(0.48f), bw[3], f2_fma(f2_all(-0.48f), bw[1], f2_fma(f2_all(-0.2f), bw[0], f2_all(0.f)))));
+                    q1 = f2_tap<UNF>(f2_all(0.2f), f2_set(rp2, rp3), f2_tap<UNF>(f2_all(0.48f), f2_set(c1v, rp2), f2_tap<UNF>(f2_all(-0.48f), f2_set(lm1, c0v), f2_tap<UNF>(f2_all(-0.2f), f2_set(lm2, lm1), f2_all(0.f)))));
+                    q2 = f2_tap<UNF>(f2_all(0.2f), bw[4], f2_tap<UNF>(f2_all(0.48f), bw[3], f2_tap<UNF>(f2_all(-0.48f), bw[1], f2_tap<UNF>(f2_all(-0.2f), bw[0], f2_all(0.f)))));
                 }
                 if (owner) {
                     const size_t idx = pl + (size_t)y * w + c0;
@@ -1212,7 +1270,9 @@ __global__ __launch_bounds__(BS_THREADS) void k_rz_blur_strips(BlurStripArgs aa)
 // level-0 collapse (or plain L plane when there are no bands) + Lab2BGR + u8 (MagnifyCore.hpp:272-277).
 // 4 pixels per thread; VEC = the frame's 4-pixel groups are dword aligned (12-byte loads/stores).
 struct __attribute__((packed, aligned(4))) RzPx4 { uint32_t a, b, c; };
-template <bool BANDS, int FL, bool VEC, bool COMPACT, bool DBG>   // DBG: also store the float frame (compile time: no per-pixel branch otherwise)
+// LPLANE (without BANDS, analytic flavour): L' is the float plane `Lplane` -- level 0 collapsed by k_rz_collapse under a build kind of
+// lvm_set_opencv_build -- where the flavour would otherwise take L from the frame (the table flavours read Lplane anyway).
+template <bool BANDS, int FL, bool VEC, bool COMPACT, bool DBG, bool LPLANE = false>   // DBG: also store the float frame (compile time: no per-pixel branch otherwise)
 __global__ __launch_bounds__(256) void k_rz_final(const uint8_t* __restrict__ in, long in_stride, long in_sstride,
                                                   uint8_t* __restrict__ out, long out_stride, long out_sstride, int w, int h,
                                                   const float* __restrict__ bandA, const float* __restrict__ resn, int nw,
@@ -1279,6 +1339,11 @@ __global__ __launch_bounds__(256) void k_rz_final(const uint8_t* __restrict__ in
                 }
 #pragma unroll
                 for (int m = 0; m < 4; ++m) lin_bgr_to_lab<true>(s_gam[pb[3 * m]], s_gam[pb[3 * m + 1]], s_gam[pb[3 * m + 2]], lab.fwd, Lin[m], ain[m], bin[m]);
+                if (LPLANE) {
+                    const size_t i = ((size_t)b * h + gy) * w + gx;
+#pragma unroll
+                    for (int m = 0; m < 4; ++m) Lin[m] = (gx + m < w) ? Lplane[i + m] : 0.f;
+                }
             }
             float4 Lq = make_float4(0.f, 0.f, 0.f, 0.f);
             if (BANDS) Lq = *reinterpret_cast<const float4*>(&sb[y][x]);   // written by this very thread
@@ -1593,6 +1658,21 @@ static int strip_rows_by_work(int sx, int h, int NZ) {
     return rows;
 }
 
+// The context's build kind (lvm_set_opencv_build) as the choices the kernels are instantiated for.  9 x 9 filters: float64 sum where
+// LVM_CV_FILTER_DFT is set (with or without _UNFUSED), else unfused taps, else the default; the 5- and 13-tap filters: unfused or not.
+static int rz_tap_kind(const Ctx* c) {
+    return (c->opencv_build & LVM_CV_FILTER_DFT) ? TK_F64 : ((c->opencv_build & LVM_CV_FILTER_UNFUSED) ? TK_UNFUSED : TK_FMA);
+}
+static const char* rz_tap_name(int tk) { return tk == TK_F64 ? "f64" : "unfused"; }
+static bool rz_unfused(const Ctx* c) { return (c->opencv_build & LVM_CV_FILTER_UNFUSED) != 0; }
+static bool rz_mul_f32(const Ctx* c) { return (c->opencv_build & LVM_CV_MUL_F32) != 0; }
+// Launch under a report name that one kernel owns in the default build kind: the kind, when there is one, is the launch's variant
+#define LVM_LAUNCH_KIND(c, nm, var, kern, grid, block, stream, ...)                       \
+    do {                                                                                  \
+        if ((var) != nullptr) LVM_LAUNCH_V(c, nm, var, kern, grid, block, stream, __VA_ARGS__); \
+        else LVM_LAUNCH(c, nm, kern, grid, block, stream, __VA_ARGS__);                   \
+    } while (0)
+
 // pyramid of the nt frames: L plane + 9x9 split chain
 static void rz_build(Ctx* c, RieszState* st, const FrameIO& io, const RzBufs& B, hipStream_t s) {
     const int NZ = c->nstreams * B.nt, w = io.w, h = io.h, nb = st->levels - 1;
@@ -1610,8 +1690,16 @@ static void rz_build(Ctx* c, RieszState* st, const FrameIO& io, const RzBufs& B,
     } else {
         LVM_LAUNCH_V(c, "rz_lab", "bytes", k_rz_lab, dim3((w + 255) / 256, h, NZ), blk, s, io.d_in, (long)io.in_stride, (long)io.in_sstride, w, h, B.oct[0], c->lab);
     }
+    const int tk = rz_tap_kind(c);
     for (int l = 0; l < nb; ++l) {
         const LevelGeom &a = st->g[l], &b = st->g[l + 1];
+        if (tk != TK_FMA) {
+            // a build kind of lvm_set_opencv_build: the one kernel family of this stage that implements it, whatever the sizes and switches say
+            const dim3 grid((a.w + CW - 1) / CW, (a.h + CH - 1) / CH, NZ);
+            LVM_LAUNCH_V(c, LName("rz_split", l), rz_tap_name(tk), tk == TK_F64 ? k_rz_split<TK_F64> : k_rz_split<TK_UNFUSED>, grid, blk, s,
+                         (const float*)B.oct[l], a.w, a.h, B.pf[l][F_BAND], B.oct[l + 1], b.w, b.h);
+            continue;
+        }
         if (st->split_rows && a.w % 4 == 0 && a.w >= 8 && (long)a.n * NZ >= st->split_rows_min && (long)a.n * 4 < (1L << 31)) {   // (32-bit byte offsets inside a plane)
             // wave strips (no LDS), rows per strip by strip_rows_by_work: 32 frames of 1080p run 68-row strips -- 4096 strips of 81
             // steps, four waves on every SIMD (100 VGPRs).  LVM_RZ_SPLIT_STRIP overrides the choice.
@@ -1630,7 +1718,7 @@ static void rz_build(Ctx* c, RieszState* st, const FrameIO& io, const RzBufs& B,
             continue;
         }
         const dim3 grid((a.w + CW - 1) / CW, (a.h + CH - 1) / CH, NZ);
-        LVM_LAUNCH(c, LName("rz_split", l), k_rz_split, grid, blk, s, (const float*)B.oct[l], a.w, a.h, B.pf[l][F_BAND], B.oct[l + 1], b.w, b.h);
+        LVM_LAUNCH(c, LName("rz_split", l), k_rz_split<TK_FMA>, grid, blk, s, (const float*)B.oct[l], a.w, a.h, B.pf[l][F_BAND], B.oct[l + 1], b.w, b.h);
     }
 }
 
@@ -1666,8 +1754,21 @@ static void rz_phase(Ctx* c, RieszState* st, const RzBufs& B, int mode, hipStrea
         (vec ? blocks4 : blocks) += v.tx * v.ty * NS;
     }
     a.nlv = n1; a4.nlv = n4;
-    if (n4) LVM_LAUNCH(c, mode ? "rz_seed" : "rz_phase", (lab_flavour(c) != FL_LUT_FAST) ? k_rz_phase4<true> : k_rz_phase4<false>, dim3(blocks4), dim3(256), s, a4);
-    if (n1) LVM_LAUNCH(c, mode ? "rz_seed_small" : "rz_phase_small", (lab_flavour(c) != FL_LUT_FAST) ? k_rz_phase<true> : k_rz_phase<false>, dim3(blocks), dim3(256), s, a);
+    // (EXACT, UNF, MF32) -> instantiation
+    const bool exact = lab_flavour(c) != FL_LUT_FAST, unf = rz_unfused(c), mf32 = rz_mul_f32(c);
+    auto pick = [&](auto vec4) {
+        constexpr bool V4 = decltype(vec4)::value;
+        auto p2 = [&](auto e, auto u) {
+            constexpr bool E = decltype(e)::value, U = decltype(u)::value;
+            if constexpr (V4) return mf32 ? k_rz_phase4<E, U, true> : k_rz_phase4<E, U, false>;
+            else return mf32 ? k_rz_phase<E, U, true> : k_rz_phase<E, U, false>;
+        };
+        auto p1 = [&](auto e) { return unf ? p2(e, std::true_type{}) : p2(e, std::false_type{}); };
+        return exact ? p1(std::true_type{}) : p1(std::false_type{});
+    };
+    const char* var = unf ? (mf32 ? "unfused+mulf32" : "unfused") : (mf32 ? "mulf32" : nullptr);
+    if (n4) LVM_LAUNCH_KIND(c, mode ? "rz_seed" : "rz_phase", var, pick(std::true_type{}), dim3(blocks4), dim3(256), s, a4);
+    if (n1) LVM_LAUNCH_KIND(c, mode ? "rz_seed_small" : "rz_phase_small", var, pick(std::false_type{}), dim3(blocks), dim3(256), s, a);
 }
 
 static bool rz_level_uses_strips(const RieszState* st, int l, int NZ) {
@@ -1727,10 +1828,14 @@ static void rz_amplify(Ctx* c, RieszState* st, const lvm_params& p, const FrameI
             else { v.tx = (v.w + BT - 1) / BT; v.ty = (v.h + BTH - 1) / BTH; v.block0 = blocks; blocks += v.tx * v.ty * NZ; }
         }
         a.nlv = n1; a4.nlv = n4;
-        if (as.nlv) LVM_LAUNCH(c, "rz_blur_amp", (lab_flavour(c) != FL_LUT_FAST) ? k_rz_blur_strips<true> : k_rz_blur_strips<false>,
-                               dim3((unsigned)((as.ntasks + BS_THREADS / 64 - 1) / (BS_THREADS / 64))), dim3(BS_THREADS), s, as);
-        if (n4) LVM_LAUNCH(c, as.nlv ? "rz_blur_amp_tiles" : "rz_blur_amp", (lab_flavour(c) != FL_LUT_FAST) ? k_rz_blur_amp4<true> : k_rz_blur_amp4<false>, dim3(blocks4), dim3(B2T), s, a4);
-        if (n1) LVM_LAUNCH(c, "rz_blur_amp_small", (lab_flavour(c) != FL_LUT_FAST) ? k_rz_blur_amp<true> : k_rz_blur_amp<false>, dim3(blocks), blk, s, a);
+        const bool exact = lab_flavour(c) != FL_LUT_FAST, unf = rz_unfused(c);
+        const char* var = unf ? "unfused" : nullptr;
+#define LVM_RZ_BLUR_PICK(K) (exact ? (unf ? K<true, true> : K<true, false>) : (unf ? K<false, true> : K<false, false>))
+        if (as.nlv) LVM_LAUNCH_KIND(c, "rz_blur_amp", var, LVM_RZ_BLUR_PICK(k_rz_blur_strips),
+                                    dim3((unsigned)((as.ntasks + BS_THREADS / 64 - 1) / (BS_THREADS / 64))), dim3(BS_THREADS), s, as);
+        if (n4) LVM_LAUNCH_KIND(c, as.nlv ? "rz_blur_amp_tiles" : "rz_blur_amp", var, LVM_RZ_BLUR_PICK(k_rz_blur_amp4), dim3(blocks4), dim3(B2T), s, a4);
+        if (n1) LVM_LAUNCH_KIND(c, "rz_blur_amp_small", var, LVM_RZ_BLUR_PICK(k_rz_blur_amp), dim3(blocks), blk, s, a);
+#undef LVM_RZ_BLUR_PICK
     }
 }
 // residual = res_{L-1} (the context's own residual octave, or -- tiling -- the collapsed coarse levels of another context);
@@ -1751,10 +1856,14 @@ static void rz_collapse_out(Ctx* c, RieszState* st, const lvm_params& p, const F
         ca.strips_y = (a.h + ca.rows - 1) / ca.rows;
         ca.ntasks = ca.strips_x * ca.strips_y * NZ;
     };
-    for (int l = nb - 1; l >= (plane_out ? 0 : 1); --l) {
+    // A build kind of lvm_set_opencv_build runs every level -- level 0 included -- through the tiled k_rz_collapse, the one kernel family of
+    // this stage that implements the kinds: level 0 is collapsed into the float plane res_0 and leaves through the band-less last kernel.
+    const int tk = rz_tap_kind(c);
+    const bool kind_l0 = tk != TK_FMA && nb >= 1 && !plane_out;
+    for (int l = nb - 1; l >= ((plane_out || kind_l0) ? 0 : 1); --l) {
         const LevelGeom &a = st->g[l], &b = st->g[l + 1];
-        float* res_l = (l == 0) ? plane_out : B.res[l];
-        if (strips_ok(a, b)) {
+        float* res_l = (l == 0 && plane_out) ? plane_out : B.res[l];
+        if (tk == TK_FMA && strips_ok(a, b)) {
             CollapseStripArgs ca{};
             ca.bandA = B.pf[l][F_BANDA]; ca.resn = resn; ca.res = res_l;
             strips_geom(ca, a, b);
@@ -1765,8 +1874,11 @@ static void rz_collapse_out(Ctx* c, RieszState* st, const lvm_params& p, const F
         }
         const dim3 grid((a.w + CW - 1) / CW, (a.h + CH - 1) / CH, NZ);
         const bool compact = st->compact && a.w % 2 == 0 && a.h % 2 == 0;
-        LVM_LAUNCH(c, LName("rz_collapse", l), compact ? k_rz_collapse<true> : k_rz_collapse<false>, grid, blk, s, (const float*)B.pf[l][F_BANDA], resn,
-                   res_l, a.w, a.h, b.w, b.h);
+        auto kc = tk == TK_F64 ? (compact ? k_rz_collapse<true, TK_F64> : k_rz_collapse<false, TK_F64>)
+                               : (tk == TK_UNFUSED ? (compact ? k_rz_collapse<true, TK_UNFUSED> : k_rz_collapse<false, TK_UNFUSED>)
+                                                   : (compact ? k_rz_collapse<true, TK_FMA> : k_rz_collapse<false, TK_FMA>));
+        LVM_LAUNCH_KIND(c, LName("rz_collapse", l), tk != TK_FMA ? rz_tap_name(tk) : nullptr, kc, grid, blk, s, (const float*)B.pf[l][F_BANDA], resn,
+                        res_l, a.w, a.h, b.w, b.h);
         resn = res_l;
     }
     if (plane_out) return;
@@ -1797,7 +1909,17 @@ static void rz_collapse_out(Ctx* c, RieszState* st, const lvm_params& p, const F
     auto kfb = pick(std::true_type{});
     auto kfn = pick(std::false_type{});
     const bool out_ok = io.out_stride % 4 == 0 && io.out_sstride % 4 == 0 && ((uintptr_t)io.d_out % 4) == 0 && (long)io.out_stride * h < (1L << 31);
-    if (nb >= 1 && fl != FL_ANALYTIC && out_ok && strips_ok(st->g[0], st->g[1])) {
+    if (kind_l0) {
+        // L' = res_0 (collapsed above): the band-less last kernel, which reads the plane (analytic flavour: LPLANE)
+        auto p2 = [&](auto v) {
+            constexpr bool V = decltype(v)::value;
+            return dbg ? k_rz_final<false, FL_ANALYTIC, V, false, true, true> : k_rz_final<false, FL_ANALYTIC, V, false, false, true>;
+        };
+        auto kfp = fl == FL_ANALYTIC ? (vec ? p2(std::true_type{}) : p2(std::false_type{})) : kfn;
+        LVM_LAUNCH_V(c, "rz_final", vec ? "vec4" : "bytes", kfp, grid, blk, s, io.d_in, (long)io.in_stride, (long)io.in_sstride, io.d_out,
+                   (long)io.out_stride, (long)io.out_sstride, w, h, (const float*)nullptr, (const float*)nullptr, 0, 0,
+                   c->lab, tx, ty, NZ, dbg, resn, (const uint32_t*)B.iab);
+    } else if (nb >= 1 && fl != FL_ANALYTIC && out_ok && strips_ok(st->g[0], st->g[1])) {
         CollapseStripArgs ca{};
         ca.bandA = B.pf[0][F_BANDA]; ca.resn = resn; ca.res = nullptr;
         ca.iab = B.iab; ca.out = (uint8_t*)io.d_out; ca.out_stride = (long)io.out_stride; ca.out_sstride = (long)io.out_sstride; ca.dbg = dbg; ca.lab = c->lab;

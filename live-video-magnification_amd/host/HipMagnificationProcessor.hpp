@@ -64,6 +64,10 @@ public:
 
     void reset() override { mag_.reset(); }
 
+    // The build kind of the OpenCV this tree links (lvm_set_opencv_build; INTEGRATION.md "Which OpenCV build"): e.g. LVM_CV_FILTER_DFT where the
+    // application is built for macOS / ARM.  Explicit: nothing here probes the host's OpenCV.
+    void setOpenCvBuild(unsigned mask) { mag_.set_opencv_build(mask); }
+
 private:
     // Any value that changes iff PreprocessParams changes (operator==, IProcessor.hpp:36-39): FNV-1a
     // over the fields; the default-constructed struct maps to 0.

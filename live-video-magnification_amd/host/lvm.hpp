@@ -111,6 +111,12 @@ public:
     // LVM_MJPEG_DECODER_LIBJPEG.  Throws on an empty mask or unknown bits.
     void mjpeg_set_samplings(unsigned mask) { check(lvm_mjpeg_set_samplings(ctx_, mask)); }
 
+    // Which OpenCV build the Riesz mode's arithmetic reproduces from the next frame on: a mask of LVM_CV_FILTER_UNFUSED (filter loops dispatched
+    // to SSE2 only), LVM_CV_FILTER_DFT (no SSE3: every ARM / macOS build) and LVM_CV_MUL_F32; 0 = the default (AVX2 dispatch).  Kept across reset();
+    // the other modes ignore it.  Throws on unknown bits.  INTEGRATION.md has the rule for choosing it.
+    void set_opencv_build(unsigned mask) { check(lvm_set_opencv_build(ctx_, mask)); }
+    unsigned opencv_build() { unsigned m = 0; check(lvm_get_opencv_build(ctx_, &m)); return m; }
+
     void synchronize() { check(lvm_synchronize(ctx_)); }
     lvm_ctx* handle() const { return ctx_; }
 

@@ -1,0 +1,61 @@
+#!/usr/bin/env python3
+"""Are the default-kind Riesz kernels the code they were?  Compiles csrc/riesz.hip of a git revision (default: HEAD~1) and of the working tree to
+gfx950 assembly with the Makefile's flags and compares, kernel by kernel, the instruction streams of the kernels the revision has with their
+mask-0 instantiations here (k_rz_split -> k_rz_split<TK_FMA>, k_rz_phase<E> -> k_rz_phase<E, false, false>, ...), labels and symbol names
+stripped.  Needs hipcc, no GPU.  usage: tools/riesz_isa_vs_rev.py [REV]; exit status 1 when a kernel differs or is missing."""
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "live-video-magnification_amd", "csrc")
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize",
+         "--cuda-device-only", "-S"]
+
+
+def kernels(asm):
+    out = {}
+    for m in re.finditer(r"^(_ZN3lvm\w+):\s*; @\1\n(.*?)^\.Lfunc_end\d+:", open(asm).read(), re.S | re.M):
+        body = []
+        for line in m.group(2).split("\n"):
+            line = line.split(";")[0].strip()
+            if line and not line.startswith(".") and not line.endswith(":"):
+                body.append(re.sub(r"_ZN3lvm\w+", "SYM", re.sub(r"\.LBB\d+_\d+", "L", line)))
+        out[m.group(1)] = body
+    names = list(out)
+    plain = subprocess.run(["c++filt"] + names, capture_output=True, text=True, check=True).stdout.strip().split("\n")
+    return {re.sub(r"^void ", "", p.split("(")[0]): out[n] for n, p in zip(names, plain)}
+
+
+def default_name(name):
+    """the name a mask-0 instantiation of the working tree had before the kinds became template arguments"""
+    name = name.replace("k_rz_split<0>", "k_rz_split")
+    name = re.sub(r"(k_rz_phase4?)<(\w+), false, false>", r"\1<\2>", name)
+    name = re.sub(r"(k_rz_blur_\w+)<(\w+), false>", r"\1<\2>", name)
+    name = re.sub(r"k_rz_collapse<(\w+), 0>", r"k_rz_collapse<\1>", name)
+    return re.sub(r"(k_rz_final<.*), false>$", r"\1>", name)
+
+
+def main():
+    rev = sys.argv[1] if len(sys.argv) > 1 else "HEAD~1"
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    with tempfile.TemporaryDirectory() as tmp:
+        for rel in ("live-video-magnification_amd/csrc/riesz.hip", "live-video-magnification_amd/csrc/lvm_internal.h", "include/lvm_hip.h"):
+            with open(os.path.join(tmp, os.path.basename(rel)), "wb") as f:
+                f.write(subprocess.run(["git", "-C", ROOT, "show", "%s:%s" % (rev, rel)], capture_output=True, check=True).stdout)
+        inc = ["-I" + CSRC, "-I" + os.path.join(ROOT, "include")]
+        subprocess.check_call([hipcc] + FLAGS + ["-I" + tmp] + inc + ["-o", os.path.join(tmp, "rev.s"), os.path.join(tmp, "riesz.hip")])
+        subprocess.check_call([hipcc] + FLAGS + inc + ["-o", os.path.join(tmp, "tree.s"), os.path.join(CSRC, "riesz.hip")])
+        old, new = kernels(os.path.join(tmp, "rev.s")), kernels(os.path.join(tmp, "tree.s"))
+    new = {default_name(k): v for k, v in new.items()}
+    bad = [k for k in old if old[k] != new.get(k)]
+    for k in bad:
+        print("%s: %s" % ("MISSING" if k not in new else "DIFFERS (%d -> %d instructions)" % (len(old[k]), len(new[k])), k))
+    print("%d of %d kernels of %s have identical instruction streams in the working tree (%d kernels there)" % (len(old) - len(bad), len(old), rev, len(new)))
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
