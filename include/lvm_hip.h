@@ -77,6 +77,14 @@ int  lvm_process(lvm_ctx* ctx, const lvm_params* p, const uint8_t* in, int w, in
  * d_in + s*in_stream_stride and writes d_out + s*out_stream_stride (bytes).  Work is enqueued
  * on `hip_stream` (a hipStream_t; NULL = the context's own stream) and NOT synchronised:
  * *produced is decided on the host before any kernel runs.
+ * Call order: the calls of one context take effect in the order they are made, on whatever streams
+ * they are given -- this call, lvm_process_device_frames, lvm_flush, the preprocess / compose / overlay
+ * surfaces and the synchronous host surfaces (lvm_process, the chain, present, export and codec calls)
+ * alike.  The temporal state lives in the context, so the library orders it: a call whose stream is
+ * not the one of the context's previous call makes its stream wait for that call with an event, on
+ * the device; a call on the same stream adds nothing.  The caller orders only its own buffers: d_in
+ * is ready on `hip_stream`, and d_out is read behind the stream of the call that completes it
+ * (`hip_stream`; at pipeline depth 1 the stream of the next call or of lvm_flush).
  * Legal layouts: any base pointer (no alignment asked: a view into a larger image, such as a
  * cv::Mat ROI, is fine); in_stride and out_stride >= w*channels; stream strides of any size,
  * smaller than a frame included (two streams side by side in one mosaic frame: stride = 2*w*channels,

@@ -51,10 +51,11 @@ void sync_streams(Ctx* c) {
     if (c->caller_overflow) { (void)hipDeviceSynchronize(); c->caller_overflow = false; }
     (void)hipGetLastError();
 }
-void mark_enqueued(Ctx* c, hipStream_t s) {
-    if (s == c->own_stream) return;                       // the own stream is synchronised directly
+// Re-records the event of s's slot in caller_events behind the enqueue and leaves it in *behind; false where the stream has no slot (or the
+// record failed): sync_streams then covers it with the device-wide wait.
+static bool mark_slot(Ctx* c, hipStream_t s, hipEvent_t* behind) {
     for (auto& e : c->caller_events)
-        if (e.first == s) { if (hipEventRecord(e.second, s) != hipSuccess) { (void)hipGetLastError(); c->caller_overflow = true; } return; }
+        if (e.first == s) { if (hipEventRecord(e.second, s) != hipSuccess) { (void)hipGetLastError(); return false; } *behind = e.second; return true; }
     hipEvent_t ev = nullptr;
     if (c->caller_events.size() >= kMaxCallerStreams) {
         // full: recycle a slot whose event has completed (its stream's work is done -- the stream may not even exist any
@@ -68,20 +69,50 @@ void mark_enqueued(Ctx* c, hipStream_t s) {
                     (void)hipGetLastError();
                     (void)hipEventDestroy(e.second);
                     c->caller_events.erase(c->caller_events.begin() + (ptrdiff_t)i);
-                    c->caller_overflow = true;
-                    return;
+                    return false;
                 }
                 e.first = s;
-                return;
+                *behind = e.second;
+                return true;
             }
         }
         (void)hipGetLastError();        // hipErrorNotReady of the queries
-        c->caller_overflow = true;
-        return;
+        return false;
     }
-    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); c->caller_overflow = true; return; }
-    if (hipEventRecord(ev, s) != hipSuccess) { (void)hipGetLastError(); (void)hipEventDestroy(ev); c->caller_overflow = true; return; }
+    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); return false; }
+    if (hipEventRecord(ev, s) != hipSuccess) { (void)hipGetLastError(); (void)hipEventDestroy(ev); return false; }
     c->caller_events.emplace_back(s, ev);
+    *behind = ev;
+    return true;
+}
+void mark_enqueued(Ctx* c, hipStream_t s) {
+    c->last_stream = s;
+    if (s == c->own_stream) return;                       // the own stream is synchronised directly; it records ev_own only when a call leaves it
+    c->last_marked = mark_slot(c, s, &c->ev_last);
+    if (c->last_marked) return;
+    // no slot: the next call on another stream (order_after_previous) waits for the spare event -- or, should this record fail too, for the device
+    c->caller_overflow = true;
+    c->ev_last = c->ev_spill;
+    c->last_marked = hipEventRecord(c->ev_spill, s) == hipSuccess;
+    if (!c->last_marked) (void)hipGetLastError();
+}
+
+// Calls of one context take effect in call order on whatever streams they are given (include/lvm_hip.h): the temporal state -- IIR planes,
+// filter state, Color's ring, the parity-buffered pyramids -- lives in the context, where no caller can order it.  A call whose stream is
+// not the one of the previous enqueue makes its stream wait, ON THE DEVICE, for the event behind that enqueue before it enqueues anything;
+// waits chain, so everything older is covered too.  A call on the same stream as the previous one makes no HIP call here.
+int order_after_previous(Ctx* c, hipStream_t s) {
+    const hipStream_t prev = c->last_stream;
+    if (!prev || prev == s) return LVM_OK;
+    if (prev == c->own_stream) {
+        LVM_HIP_TRY(c, hipEventRecord(c->ev_own, prev));            // behind everything the own stream has been given so far
+        LVM_HIP_TRY(c, hipStreamWaitEvent(s, c->ev_own, 0));
+    } else if (c->last_marked) {
+        LVM_HIP_TRY(c, hipStreamWaitEvent(s, c->ev_last, 0));
+    } else {
+        LVM_HIP_TRY(c, hipDeviceSynchronize());                      // no event could be recorded behind that enqueue
+    }
+    return LVM_OK;
 }
 
 static void drop_state(Ctx* c) { delete c->state; c->state = nullptr; }
@@ -144,6 +175,7 @@ static const char* layout_error(const FrameIO& io, int nstreams) {
 // MagnificationProcessor::process (MagnificationProcessor.cpp:17-67) on device buffers
 static int process_device(Ctx* c, const lvm_params* p, const FrameIO& io, hipStream_t s, int* produced) {
     *produced = 0;
+    { const int rc = order_after_previous(c, s); if (rc != LVM_OK) return rc; }
     if (p->mode == LVM_MODE_NONE || io.d_in == nullptr || io.w <= 0 || io.h <= 0) {      // :21-29
         if (c->tracked.mode != LVM_MODE_NONE) {
             // pipelined mode: the pending frame's output is owed to its caller (same rule as on a structural change)
@@ -216,6 +248,8 @@ int lvm_create(int device, int n_streams, lvm_ctx** out) {
     ok = ok && hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&c->ev_own, hipEventDisableTiming) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&c->ev_spill, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipMalloc((void**)&c->d_gamma_u8, sizeof(g)) == hipSuccess;
     ok = ok && hipMalloc((void**)&c->d_invgamma, sizeof(ig)) == hipSuccess;
     ok = ok && hipMemcpy(c->d_gamma_u8, g, sizeof(g), hipMemcpyHostToDevice) == hipSuccess;
@@ -262,6 +296,8 @@ void lvm_destroy(lvm_ctx* c) {
     for (auto& e : c->caller_events) (void)hipEventDestroy(e.second);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
+    if (c->ev_own) (void)hipEventDestroy(c->ev_own);
+    if (c->ev_spill) (void)hipEventDestroy(c->ev_spill);
     if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;                       // (the staging buffers go with it: DevBuf)
@@ -312,7 +348,9 @@ int lvm_process_device_frames(lvm_ctx* c, const lvm_params* p, int n_frames, con
         // (a layout the per-frame path refuses is left to it: it reports the error)
         const int nb = (left >= 2 && same && layout && c->state && !lvm::layout_error(io, c->nstreams)) ? c->state->batch_frames(c, *p, io, left) : 0;
         if (nb > 0) {
-            const int rc = c->state->process_frames(c, *p, io, nb, s);
+            int rc = lvm::order_after_previous(c, s);
+            if (rc != LVM_OK) return rc;
+            rc = c->state->process_frames(c, *p, io, nb, s);
             lvm::mark_enqueued(c, s);
             if (rc != LVM_OK) { lvm::fail_state(c, s); return rc; }
             for (int k = f; k < f + nb; ++k) produced[k] = 1;
@@ -343,7 +381,9 @@ int lvm_preprocess_device(lvm_ctx* c, const lvm_preprocess_params* pp, const uin
     if (!c || !pp) return LVM_ERR_INVALID;
     LVM_HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
-    const int rc = lvm::preprocess_device(c, *pp, d_in, w, h, channels, in_stride, in_stream_stride, d_out, out_stride, out_stream_stride, s);
+    int rc = lvm::order_after_previous(c, s);          // (the area tables are the context's: preprocess.hip replaces them behind a wait for `s` alone)
+    if (rc != LVM_OK) return rc;
+    rc = lvm::preprocess_device(c, *pp, d_in, w, h, channels, in_stride, in_stream_stride, d_out, out_stride, out_stream_stride, s);
     lvm::mark_enqueued(c, s);
     return rc;
 }
@@ -364,8 +404,10 @@ int lvm_compose_device(lvm_ctx* c, int split, const uint8_t* d_orig, int ow, int
     if (!c) return LVM_ERR_INVALID;
     LVM_HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
-    const int rc = lvm::compose_device(c, split, d_orig, ow, oh, och, orig_stride, orig_stream_stride, d_proc, pw, ph, pch, proc_stride,
-                                       proc_stream_stride, d_canvas, canvas_stride, canvas_stream_stride, s);
+    int rc = lvm::order_after_previous(c, s);
+    if (rc != LVM_OK) return rc;
+    rc = lvm::compose_device(c, split, d_orig, ow, oh, och, orig_stride, orig_stream_stride, d_proc, pw, ph, pch, proc_stride,
+                             proc_stream_stride, d_canvas, canvas_stride, canvas_stream_stride, s);
     lvm::mark_enqueued(c, s);
     return rc;
 }
@@ -402,6 +444,8 @@ int lvm_tile_riesz_stage2(lvm_ctx* c, const lvm_params* p, const uint8_t* d_in, 
     LVM_HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
     lvm::FrameIO io{d_in, in_stride, in_stride * h, d_out, out_stride, out_stride * h, w, h, 3};
+    rc = lvm::order_after_previous(c, s);
+    if (rc != LVM_OK) return rc;
     rc = lvm::riesz_tile_finish(c, *p, io, d_residual_in, s);
     lvm::mark_enqueued(c, s);
     return rc;
@@ -433,7 +477,9 @@ int lvm_overlay_device(lvm_ctx* c, uint8_t* d_canvas, int canvas_w, int canvas_h
     if (!c) return LVM_ERR_INVALID;
     LVM_HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
-    const int rc = lvm::overlay_device(c, d_canvas, canvas_w, canvas_h, canvas_stride, frame_stride, n_frames, s);
+    int rc = lvm::order_after_previous(c, s);
+    if (rc != LVM_OK) return rc;
+    rc = lvm::overlay_device(c, d_canvas, canvas_w, canvas_h, canvas_stride, frame_stride, n_frames, s);
     lvm::mark_enqueued(c, s);
     return rc;
 }
@@ -508,6 +554,7 @@ int lvm_chain_process_batch_ex(lvm_ctx* c, const lvm_preprocess_params* pp, cons
     const ChainGeom g = chain_geometry(*pp, w, h, channels);
     if (out_stride < (ptrdiff_t)g.out_row) { c->err = "output stride too small"; return LVM_ERR_INVALID; }
     hipStream_t s = c->own_stream;
+    { const int orc = lvm::order_after_previous(c, s); if (orc != LVM_OK) return orc; }
     LVM_HIP_TRY(c, hipStreamSynchronize(s));      // staging buffers may be replaced below
     int rc = c->d_pre_in.reserve(c, g.roi_bytes * NS); if (rc != LVM_OK) return rc;
     rc = c->d_pre_out.reserve(c, g.out_bytes * NS); if (rc != LVM_OK) return rc;
@@ -554,6 +601,7 @@ int lvm_chain_present(lvm_ctx* c, const lvm_preprocess_params* pp, const lvm_par
     if (d_proc && proc_stride < (ptrdiff_t)g.out_row) { c->err = "proc stride too small"; return LVM_ERR_INVALID; }
     if (d_orig && orig_stride < (ptrdiff_t)g.tap_row) { c->err = "orig stride too small"; return LVM_ERR_INVALID; }      // (the tap keeps the source's channel count)
     hipStream_t s = c->own_stream;
+    { const int orc = lvm::order_after_previous(c, s); if (orc != LVM_OK) return orc; }
     LVM_HIP_TRY(c, hipStreamSynchronize(s));      // staging buffers may be replaced below
     int rc = c->d_pre_in.reserve(c, g.roi_bytes); if (rc != LVM_OK) return rc;
     rc = c->d_pre_out.reserve(c, g.out_bytes); if (rc != LVM_OK) return rc;
@@ -623,6 +671,7 @@ static int export_frames_impl(lvm_ctx* c, const lvm_preprocess_params* pp, const
     if (!mj && canvas_stride < (ptrdiff_t)cw * 3) { c->err = "canvas stride too small"; return LVM_ERR_INVALID; }
     const size_t can_row = (size_t)cw * 3, can_bytes = can_row * chh;
     hipStream_t s = c->own_stream;
+    { const int orc = lvm::order_after_previous(c, s); if (orc != LVM_OK) return orc; }
     LVM_HIP_TRY(c, hipStreamSynchronize(s));      // staging buffers may be replaced below
     // the pane Exporter::compose labels "Original" is runChainOnce's tap (ChainGeom::gray)
     const bool gray_tap = g.gray && split != LVM_SPLIT_NONE;
@@ -739,7 +788,9 @@ int lvm_mjpeg_decode_device(lvm_ctx* c, const uint8_t* jpegs, const size_t* offs
     if (!c || !jpegs || !offsets || !d_bgr || n_frames < 1) return LVM_ERR_INVALID;
     if (stride < (ptrdiff_t)w * 3 || (n_frames > 1 && frame_stride < (ptrdiff_t)h * stride)) { c->err = "bad frame arguments"; return LVM_ERR_INVALID; }
     LVM_HIP_TRY(c, hipSetDevice(c->device));
-    const int rc = lvm::mjpeg_decode_device(c, jpegs, offsets, n_frames, w, h, d_bgr, stride, frame_stride, c->own_stream);
+    int rc = lvm::order_after_previous(c, c->own_stream);
+    if (rc != LVM_OK) return rc;
+    rc = lvm::mjpeg_decode_device(c, jpegs, offsets, n_frames, w, h, d_bgr, stride, frame_stride, c->own_stream);
     if (rc == LVM_OK) lvm::mark_enqueued(c, c->own_stream);
     return rc;
 }
@@ -803,7 +854,9 @@ int lvm_mjpeg_encode_device(lvm_ctx* c, const uint8_t* d_bgr, int w, int h, ptrd
     LVM_HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->own_stream;
     const int per = n_frames < 8 ? n_frames : 8;                 // scratch (coefficients, bit buffers) for eight frames at a time
-    int rc = lvm::mjpeg_begin(c, w, h, quality, per, (size_t)n_frames, out_capacity, s);
+    int rc = lvm::order_after_previous(c, s);
+    if (rc != LVM_OK) return rc;
+    rc = lvm::mjpeg_begin(c, w, h, quality, per, (size_t)n_frames, out_capacity, s);
     if (rc != LVM_OK) return rc;
     for (int f0 = 0; f0 < n_frames; f0 += per) {
         const int nf = f0 + per <= n_frames ? per : n_frames - f0;
@@ -1011,7 +1064,12 @@ int lvm_flush(lvm_ctx* c, void* hip_stream) {
     if (!c) return LVM_ERR_INVALID;
     LVM_HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
-    return c->state ? c->state->flush(c, s) : LVM_OK;
+    if (!c->state) return LVM_OK;
+    int rc = lvm::order_after_previous(c, s);           // the owed frame's pyramid was built on the stream of the call that owes it
+    if (rc != LVM_OK) return rc;
+    rc = c->state->flush(c, s);
+    lvm::mark_enqueued(c, s);                           // (a reset or a destroy waits for the flush like for any other enqueue)
+    return rc;
 }
 
 // compulsory traffic only -- every input byte read once, every output byte

@@ -516,6 +516,11 @@ struct Ctx {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     std::vector<std::pair<hipStream_t, hipEvent_t>> caller_events;   // one event per distinct caller stream, re-recorded after every enqueue (sync_streams)
     bool caller_overflow = false;     // more caller streams than events: sync_streams synchronises the device
+    // call order across streams (order_after_previous): the stream of the latest enqueue and an event recorded behind it -- a slot of
+    // caller_events, or ev_spill when the stream got none; the own stream records ev_own only when a call leaves it for another stream
+    hipStream_t last_stream = nullptr;
+    hipEvent_t ev_last = nullptr, ev_own = nullptr, ev_spill = nullptr;
+    bool last_marked = false;         // ev_last was recorded (false: a failed record; the next stream waits for the device instead)
     int max_frames = 0;               // lvm_set_max_frames: temporal-batch buffers are sized for this many frames up front
     bool exact_lab = false;   // debug: OpenCV-order float arithmetic everywhere (bit-faithful to the oracle)
     bool lab_analytic = false;   // debug: analytic forward Lab (OpenCV with its interpolation switched off) instead of the 33^3 table
@@ -545,6 +550,7 @@ inline int lab_flavour(const Ctx* c) { return c->lab_analytic ? FL_ANALYTIC : (c
 
 void sync_streams(Ctx* c);
 void mark_enqueued(Ctx* c, hipStream_t s);
+int order_after_previous(Ctx* c, hipStream_t s);
 void fail_state(Ctx* c, hipStream_t s);
 int ensure_float(Ctx* c, size_t count);
 void prof_begin(Ctx* c, const char* name, hipStream_t s);

@@ -415,6 +415,13 @@ class HostMem:
     def stream(self):
         return None
 
+    def call_stream(self):
+        """the stream of the next device-surface call of a plan (run_plan)"""
+        return None
+
+    def quiesce(self):
+        """run_plan: the caller waits for the device (the emulation has run everything already)"""
+
     def sync(self, ctx):
         ctx.synchronize()
 
@@ -448,6 +455,13 @@ class TorchMem:
 
     def stream(self):
         return self.torch.cuda.current_stream().cuda_stream
+
+    def call_stream(self):
+        """the stream of the next device-surface call of a plan (run_plan): torch's current stream"""
+        return self.stream()
+
+    def quiesce(self):
+        self.torch.cuda.synchronize()
 
     def sync(self, ctx):
         self.torch.cuda.synchronize()
@@ -616,3 +630,310 @@ def color_shrink_in_batches(lvm, po, lib, mem, size, calls, change_at, fps_to, u
     finally:
         orc.close()
     return worst
+
+
+# ---- surface mix: ONE context through a seeded interleaving of its surfaces (tests/test_surface_mix.py) -----------------------------
+def _chain_key():
+    """What lvm_chain_process_batch_ex and lvm_export_frames put into lvm_params.preprocess_key for "preprocessing off" (csrc/lvm_api.hip
+    preprocess_key_of: FNV-1a over downscale, roi_enabled, roiX, roiY, roiW, roiH).  The device surfaces of a plan pass the same value, so
+    that every surface drives the SAME magnifier state; a wrong value here shows as a structural reset the oracle does not make."""
+    import struct
+    k = 1469598103934665603
+    for b in struct.pack("<iiffff", 1, 0, 0.0, 0.0, 1.0, 1.0):
+        k = ((k ^ b) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
+    return k
+
+
+CHAIN_KEY = _chain_key()
+# lengths of lvm_process_device_frames calls and how often each is drawn (cut to the frames that are left: the long ones end a plan)
+PLAN_BATCHES = (1, 2, 3, 4, 5, 7, 9, 16, 33)
+PLAN_BATCH_P = (0.15, 0.25, 0.2, 0.12, 0.1, 0.08, 0.05, 0.03, 0.02)
+FRAME_OPS = ("host", "device", "frames", "chain", "export")
+
+
+class StreamMem(TorchMem):
+    """TorchMem for plans whose device-surface calls go to real caller streams: `n_streams` torch.cuda.Stream() objects and, with
+    own=True, None (the context's own stream), drawn per call from `seed` (cycle=True: the streams in turn).
+
+    The caller's duties and nothing more: the chosen stream waits for the upload of its input (wait_stream), buffers live until the
+    end, results are read after torch.cuda.synchronize() (download).  Nothing orders one call of the context behind the previous one:
+    that is the library's job.  To make the order impossible to get right by luck, every other call (a "late" one) first puts a
+    device-side delay on its stream -- long enough that the stream is free DELAY_MS after every other stream, by this class's own
+    account of the delays it has issued -- and the call after it (an "early" one) goes undelayed to ANOTHER stream or to a host
+    surface: without cross-stream ordering it runs at least 20 ms before the call it follows."""
+    DELAY_MS = 25.0
+    _cycles_per_ms = None
+
+    def __init__(self, seed, n_streams=4, own=True, cycle=False):
+        super().__init__()
+        t = self.torch
+        self.pool = [t.cuda.Stream() for _ in range(n_streams)]
+        self.own, self.cycle = own, cycle
+        self.rng = np.random.default_rng(seed)
+        self.busy = [0.0] * n_streams            # ms of delay issued to each stream since the last quiesce
+        self.prev, self.late, self.turn = None, True, 0
+        self.log = []                            # (stream index or -1 for the own stream, late) per call
+        self._calibrate()
+
+    def _time_sleep(self, cycles):
+        t = self.torch
+        e0, e1 = t.cuda.Event(enable_timing=True), t.cuda.Event(enable_timing=True)
+        e0.record()
+        t.cuda._sleep(int(cycles))
+        e1.record()
+        t.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    def _calibrate(self):
+        """torch.cuda._sleep counts ticks of a clock whose rate is the device's business: measured once, and the delay the plans use
+        is measured to be the 20 ms they rely on"""
+        cls = StreamMem
+        if cls._cycles_per_ms is None:
+            self._time_sleep(1000)               # (loads the kernel)
+            n, ms = 1000000, 0.0
+            for _ in range(4):
+                ms = self._time_sleep(n)
+                if ms >= 5.0:
+                    break
+                n *= 8
+            assert ms >= 5.0, "torch.cuda._sleep(%d) took %.3f ms" % (n, ms)
+            cls._cycles_per_ms = n / ms
+            got = self._time_sleep(self.DELAY_MS * cls._cycles_per_ms)
+            assert got >= 20.0, "a delay meant to take %.0f ms took %.2f ms" % (self.DELAY_MS, got)
+
+    def handles(self):
+        return [s.cuda_stream for s in self.pool]
+
+    def call_stream(self):
+        t, n = self.torch, len(self.pool)
+        if self.cycle:
+            k = self.turn % n
+            self.turn += 1
+        else:
+            choices = [i for i in range(-1 if self.own else 0, n) if self.late or i != self.prev]
+            k = int(self.rng.choice(choices))
+        if k >= 0:
+            self.pool[k].wait_stream(t.cuda.current_stream())          # the upload of the call's input
+            if self.late:
+                target = max(self.busy) + self.DELAY_MS
+                with t.cuda.stream(self.pool[k]):
+                    t.cuda._sleep(int((target - self.busy[k]) * self._cycles_per_ms))
+                self.busy[k] = target
+        self.log.append((k, self.late))
+        self.prev, self.late = k, not self.late
+        return self.pool[k].cuda_stream if k >= 0 else 0
+
+    def quiesce(self):
+        self.torch.cuda.synchronize()
+        self.busy = [0.0] * len(self.pool)
+
+
+def draw_plan(seed, n_frames, mode, n_streams=1, warm=0, fps=30.0):
+    """A seeded interleaving of the operations one context takes, consuming n_frames consecutive frames:
+      ("host",) lvm_process    ("device",) lvm_process_device    ("frames", n) lvm_process_device_frames, n of PLAN_BATCHES
+      ("chain",) lvm_chain_process_batch_ex, preprocessing off    ("export", n) ONE lvm_export_frames segment, split None
+      ("pipeline", 0 | 1) lvm_set_pipeline    ("flush",) lvm_flush    ("max_frames", n) lvm_set_max_frames
+      ("set", {...}) an amplification or cutoff change from the next frame on    ("reset",) lvm_reset
+    The first `warm` frames go one per call (Color: the window fills before the first batch).  lvm_reset discards an owed pipelined
+    frame by contract, so a flush stands in front of every reset that could meet one, and at the end.  n_streams > 1 leaves out the
+    surfaces that take 1-stream contexts only (lvm_process, lvm_export_frames)."""
+    r = np.random.default_rng(7000 + seed)
+    kinds = ["device", "frames", "host", "chain", "export", "pipeline", "flush", "max_frames", "set", "reset"]
+    weights = np.array([0.22, 0.28, 0.12, 0.08, 0.05, 0.06, 0.05, 0.04, 0.07, 0.03])
+    if n_streams > 1:
+        weights[[2, 4]] = 0.0
+    weights = weights / weights.sum()
+    plan, t, depth, owed, exported = [], 0, 0, False, False
+    while t < n_frames:
+        k = str(r.choice(kinds, p=weights))
+        left = n_frames - t
+        if k == "device":
+            plan.append((k,)); t += 1; owed = depth == 1
+        elif k == "frames":
+            n = 1 if t < warm else min(left, int(r.choice(PLAN_BATCHES, p=PLAN_BATCH_P)))
+            plan.append((k, n)); t += n; owed = depth == 1           # (at depth 1 Laplace takes the frames one by one and owes the last)
+        elif k in ("host", "chain"):
+            plan.append((k,)); t += 1; owed = False                  # the synchronous surfaces complete what is owed
+        elif k == "export":
+            if exported or t < warm or left < 2:
+                continue
+            n = min(left, int(r.integers(2, 8)))
+            plan.append((k, n)); t += n; owed, exported = False, True
+        elif k == "pipeline":
+            depth = depth ^ int(r.random() < 0.75)                   # (mostly a change; setting the depth it has is a call too)
+            plan.append((k, depth)); owed = owed and depth == 1      # (a change flushes)
+        elif k == "flush":
+            plan.append((k,)); owed = False
+        elif k == "max_frames":
+            plan.append((k, int(r.choice([1, 2, 4, 8, 16, 33]))))
+        elif k == "set":
+            if r.random() < 0.5:
+                plan.append((k, {"amplification": float(r.uniform(1.0, 80.0))}))
+            elif mode == 0:          # Laplace: IIR blend factors
+                lo = float(r.uniform(0.01, 0.5))
+                plan.append((k, {"coLow": lo, "coHigh": float(r.uniform(lo + 0.05, 0.999))}))
+            elif mode == 1:          # Riesz: Butterworth band in Hz
+                lo = float(r.uniform(0.1, 0.3 * fps))
+                plan.append((k, {"coLow": lo, "coHigh": float(r.uniform(lo + 0.1, 0.49 * fps))}))
+            else:                    # Color: ideal band in Hz
+                lo = float(r.uniform(0.1, 0.2 * fps))
+                plan.append((k, {"coLow": lo, "coHigh": float(r.uniform(lo + 0.05, 0.45 * fps))}))
+        else:
+            if owed:
+                plan.append(("flush",))
+            plan.append((k,)); owed = False
+    if owed:
+        plan.append(("flush",))
+    return plan
+
+
+def plan_frames(plan):
+    return sum(op[1] if op[0] in ("frames", "export") else 1 for op in plan if op[0] in FRAME_OPS)
+
+
+def plan_reference(po, plan, frames, pk, key=CHAIN_KEY):
+    """The oracle over the frames of a plan ([n][stream][h][w][ch]), one oracle per stream: frame after frame with the parameters in
+    force, reset where the plan resets.  Returns (produced flags [n], frames [n][stream]...; a frame that was not produced: zeros)."""
+    n, S = frames.shape[:2]
+    assert plan_frames(plan) == n
+    orcs = [po.Oracle() for _ in range(S)]
+    prod, out = [], np.zeros_like(frames)
+    cur, t = dict(pk), 0
+    try:
+        for op in plan:
+            if op[0] == "set":
+                cur.update(op[1])
+            elif op[0] == "reset":
+                for o in orcs:
+                    o.reset()
+            elif op[0] in FRAME_OPS:
+                P = po.make_params(preprocess_key=key, **cur)
+                for _ in range(op[1] if len(op) > 1 else 1):
+                    flags = set()
+                    for s in range(S):
+                        ref, pr = orcs[s].process(frames[t, s], P)
+                        flags.add(bool(pr))
+                        if pr:
+                            out[t, s] = ref
+                    assert len(flags) == 1
+                    prod.append(flags.pop())
+                    t += 1
+    finally:
+        for o in orcs:
+            o.close()
+    return prod, out
+
+
+def run_plan(lvm, lib, mem, plan, frames, pk, key=CHAIN_KEY, exact_lab=True):
+    """One context through `plan` (draw_plan) on `frames` ([n][stream][h][w][3]); device-surface calls and flushes go to
+    mem.call_stream().  All buffers live until the end and every output is read once, after the last operation (in pipelined mode:
+    after the flush that completes it).  Before lvm_reset, before a temporal batch longer than any since the state was built (its
+    buffers grow: a free) and before the context is destroyed the caller waits for the device (mem.quiesce): whether those paths wait
+    for every caller stream by themselves is not this function's question.
+    Returns {"prod": flags [n], "out": [n][stream][h][w][3], "op": index of the operation that took frame t, "crop": {t: (rows, cols)}
+    for frames that came back as export canvases, "pass": what a frame that was not produced must hold (zeros = untouched, or the input)}."""
+    n, S, h, w, ch = frames.shape
+    assert plan_frames(plan) == n and ch == 3
+    fb = w * h * ch
+    ctx = lvm.Context(0, S, lib)
+    res = {"prod": [None] * n, "op": [None] * n, "crop": {}, "pass": np.zeros_like(frames)}
+    host_out = {}
+    pre = lvm.to_c_preprocess(lvm.PreprocessParams(), False)
+    try:
+        ctx.exact_lab(exact_lab)
+        d_in = mem.upload(frames)
+        d_out = mem.zeros_like(d_in)
+        cur, t, hint, cap = dict(pk), 0, 0, 0
+        for k, op in enumerate(plan):
+            cp = c_params(lvm, cur, key)
+            nf = (op[1] if len(op) > 1 else 1) if op[0] in FRAME_OPS else 0
+            res["op"][t:t + nf] = [k] * nf
+            if op[0] == "set":
+                cur.update(op[1])
+            elif op[0] == "reset":
+                mem.quiesce()
+                ctx.reset()
+                cap = hint
+            elif op[0] == "pipeline":
+                ctx.set_pipeline(op[1])
+            elif op[0] == "flush":
+                ctx.flush(mem.call_stream())
+            elif op[0] == "max_frames":
+                ctx.set_max_frames(op[1])
+                hint = op[1]
+            elif op[0] == "device":
+                res["prod"][t] = ctx.process_device(cp, mem.ptr(d_in, t), w, h, ch, w * ch, fb, mem.ptr(d_out, t), w * ch, fb, mem.call_stream())
+            elif op[0] == "frames":
+                if nf > cap:
+                    mem.quiesce()
+                    cap = max(nf, hint)
+                res["prod"][t:t + nf] = ctx.process_device_frames(cp, nf, mem.ptr(d_in, t), w, h, ch, w * ch, fb, fb * S, mem.ptr(d_out, t),
+                                                                  w * ch, fb, fb * S, mem.call_stream())
+            elif op[0] == "host":
+                o, p = ctx.process(frames[t, 0], cp)
+                res["prod"][t], host_out[t] = p, np.array(o, copy=True)[None]
+                res["pass"][t] = frames[t]
+            elif op[0] == "chain":
+                outs, _, p = ctx.chain_process_batch_ex(list(frames[t]), pre, cp)
+                res["prod"][t], host_out[t] = p, np.stack(outs)
+                res["pass"][t] = frames[t]                 # passthrough: the frame the magnifier saw
+            elif op[0] == "export":
+                if nf > cap:                               # (the export hands its frames on in sub-batches; the rule above, whatever their length)
+                    mem.quiesce()
+                    cap = max(nf, hint)
+                canv, prods = ctx.export_frames(list(frames[t:t + nf, 0]), pre, cp, 0)
+                for f in range(nf):
+                    res["prod"][t + f] = prods[f]
+                    hh, ww = canv[f].shape[:2]
+                    res["crop"][t + f] = (hh, ww)          # Exporter::compose crops to even sizes
+                    full = np.zeros((1, h, w, ch), np.uint8)
+                    full[0, :hh, :ww] = canv[f]
+                    host_out[t + f] = full
+                    res["pass"][t + f] = frames[t + f]
+            else:
+                raise ValueError(op)
+            t += nf
+        out = mem.download(d_out).copy()
+        for t_, o in host_out.items():
+            out[t_] = o
+        res["out"] = out
+        mem.quiesce()
+    finally:
+        ctx.close()
+    return res
+
+
+def _plan_fail(plan, res, t, msg):
+    k = res["op"][t]
+    raise AssertionError("frame %d (operation %d of %d, %r): %s\nthe operations up to it: %s" % (t, k, len(plan), plan[k], msg, plan[max(0, k - 9):k + 1]))
+
+
+def check_plan(plan, ref, res, exact=True, u8_max=1, u8_frac=0.999):
+    """Every frame of a plan's run against plan_reference: the produced flags; a produced frame byte for byte (exact) or at the
+    parity bars; a frame that was not produced is the input (host surfaces) or untouched.  A failure names the frame, the byte count
+    and the last ten operations.  Returns [worst u8 diff, worst identical fraction]."""
+    prod_r, out_r = ref
+    worst = [0, 1.0]
+    for t in range(len(prod_r)):
+        if res["prod"][t] != prod_r[t]:
+            _plan_fail(plan, res, t, "produced flag %s, the oracle's %s" % (res["prod"][t], prod_r[t]))
+        hh, ww = res["crop"].get(t, out_r.shape[2:4])
+        for s in range(out_r.shape[1]):
+            got = res["out"][t, s, :hh, :ww]
+            want = (out_r if prod_r[t] else res["pass"])[t, s, :hh, :ww]
+            du = np.abs(want.astype(np.int32) - got.astype(np.int32))
+            worst = [max(worst[0], int(du.max())), min(worst[1], float((du == 0).mean()))]
+            if (exact or not prod_r[t]) and du.max() != 0:
+                _plan_fail(plan, res, t, "stream %d: %d of %d bytes differ from the oracle (max %d)" % (s, int((du != 0).sum()), du.size, int(du.max())))
+            if du.max() > u8_max or (du == 0).mean() < u8_frac:
+                _plan_fail(plan, res, t, "stream %d: u8 diff %d, identical %.6f: outside the bars (%d bytes differ)" % (
+                    s, int(du.max()), float((du == 0).mean()), int((du != 0).sum())))
+    return worst
+
+
+def check_plans_identical(plan, res_a, res_b):
+    """two runs of one plan, byte for byte"""
+    assert res_a["prod"] == res_b["prod"], (res_a["prod"], res_b["prod"])
+    for t in range(len(res_a["prod"])):
+        if not np.array_equal(res_a["out"][t], res_b["out"][t]):
+            _plan_fail(plan, res_a, t, "%d bytes differ between the two runs" % int((res_a["out"][t] != res_b["out"][t]).sum()))

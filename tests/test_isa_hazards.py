@@ -15,7 +15,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "live-video-magnification_amd", "csrc")
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-UNITS = ["lvm_api.hip", "labconv.hip", "laplace.hip", "riesz.hip", "color.hip", "preprocess.hip", "compose.hip"]
+UNITS = ["lvm_api.hip", "labconv.hip", "laplace.hip", "riesz.hip", "color.hip", "preprocess.hip", "compose.hip", "mjpeg.hip", "mjpeg_decode.hip"]
 NOSLP = {"laplace.hip", "riesz.hip"}                      # as in csrc/Makefile
 
 
