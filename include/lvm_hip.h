@@ -47,7 +47,11 @@ typedef struct lvm_params {
     double   coLow;             /* Laplace: IIR blend in [0,1]; Phase/Color: Hz */
     double   coHigh;
     double   chromAttenuation;  /* Laplace only: gain on Lab a,b of the motion image */
-    double   framerate;         /* Color ideal filter + Riesz Butterworth */
+    double   framerate;         /* Color ideal filter + Riesz Butterworth: the true capture rate, any value (high-speed
+                                 * footage: e.g. 1000).  Color's rolling window is getOptimalBufferSize(framerate) frames:
+                                 * windows of up to 4096 frames (framerate <= 2048) run the parallel ideal filter and
+                                 * share launches in temporal batches (lvm_process_device_frames); longer windows are
+                                 * processed frame by frame by a serial kernel (one thread per window row) */
     uint64_t preprocess_key;    /* any value that changes iff PreprocessParams changes */
 } lvm_params;
 
@@ -111,7 +115,9 @@ int  lvm_process_device(lvm_ctx* ctx, const lvm_params* p, const uint8_t* d_in, 
  * Layouts as for lvm_process_device, frame strides of any size; the frames share launches only when
  * they are laid out [frame][stream] (frame stride == n_streams * stream stride, in and out), every
  * other order (such as [stream][frame]) is processed frame by frame.  A refused layout fails the call
- * at the first frame it reaches; produced[] of the frames before it stand.                           */
+ * at the first frame it reaches; produced[] of the frames before it stand.
+ * Color: the frames share launches (up to 32 at a time) once the rolling window is full, for windows
+ * of up to 4096 frames (framerate <= 2048); the frames of a longer window are processed one by one.  */
 int  lvm_process_device_frames(lvm_ctx* ctx, const lvm_params* p, int n_frames, const uint8_t* d_in,
                                int w, int h, int channels, ptrdiff_t in_stride,
                                ptrdiff_t in_stream_stride, ptrdiff_t in_frame_stride, uint8_t* d_out,

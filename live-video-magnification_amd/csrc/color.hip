@@ -16,7 +16,9 @@
 //   k_col_append                   smallest level -> window slots; resets the min/max cells
 //   k_col_dft | k_col_dft_thin     per row: packed real DFT of the needed elements (float64 sums), 0/1 mask applied
 //                                  as a packed complex spectrum (mulSpectrums), inverse transform of all T samples
-//                                  -> global min/max, keep column 1   (wave per row | thread per row, narrow bands)
+//                                  -> global min/max, keep column 1   (wave per row | thread per row, narrow bands;
+//                                  k_col_dft_long: windows of 1025..4096 frames, thread per entry and per sample over
+//                                  the 4 | 2 rows of a workgroup; k_col_dft_serial, frame by frame, beyond)
 //   k_col_norm                     min-max normalise column 1, x alpha -> up_0
 //   k_pyr_up x (L-1)               up_k -> up_{k+1}
 //   k_col_out_rows<false>          last pyrUp + bilinear resize + input add -> global min/max   (wave strips;
@@ -120,7 +122,7 @@ __global__ __launch_bounds__(256) void k_col_regrow(const float* __restrict__ ow
 // Forward: lane j owns entry j and runs the float64 sum over t = 0..n-1 in order (samples are LDS
 // broadcasts).  Inverse: lane owns output samples t, t+64, ... and sums the entries in ascending
 // bin order.  Both are the oracle's summation orders, so results are order-faithful.
-constexpr int kDftMaxN = 1024;             // window lengths above this use k_col_dft_serial
+constexpr int kDftMaxN = 1024;             // window lengths above this use k_col_dft_long (up to kLongMaxN), then k_col_dft_serial
 constexpr int kTwAllMax = 512;             // window lengths up to this get their twiddle tables built once for every warm-up length
 constexpr int kDftRows = 4;                // rows (waves) per workgroup
 struct DftEntry { short bin; short kind; };   // kind 0 = complex bin, 1 = DC, 2 = Nyquist
@@ -416,7 +418,119 @@ __global__ __launch_bounds__(256) void k_col_dft_thin8(const float* __restrict__
     block_minmax(vmin, vmax, mm[b].mn1, mm[b].mx1);
 }
 
-// Serial fallback for very long windows (n > kDftMaxN): one thread per row, same arithmetic.
+// Long windows (kDftMaxN < n <= kLongMaxN: capture rates of 513..2048 fps), any band, one frame or a temporal batch.  The arithmetic is
+// k_col_dft's, the sharing of the work is not: with 16 n bytes of float64 twiddles in LDS (64 KiB at n = 4096) a workgroup has room for
+// ROWS = 4 (n <= 2048) or 2 rows, so a twiddle read is made to serve all of them.  Forward: thread j owns entry j and runs, in ONE walk
+// over t = 0..n-1, the in-order float64 sums of that entry for every row of the workgroup (two table gathers, one broadcast read of the
+// rows' samples [t][ROWS] and 2 ROWS multiply-adds per step).  Only the passed entries are kept (s_y[entry][ROWS][re, im]), not the
+// packed spectrum.  Inverse: thread owns the samples t, t + 256, ... of every row and sums the entries in ascending bin order, the
+// Nyquist term last; the table index advances by t per bin (the passed bins are consecutive) instead of a modulo per term.
+// LDS: NMAX = 2048, ROWS = 4: 32 + 32 + 32 + 4 KiB (one workgroup per CU); NMAX = 4096, ROWS = 2: 64 + 32 + 32 + 8 KiB (one per CU).
+constexpr int kLongMaxN = 4096;            // window lengths above this use k_col_dft_serial, frame by frame
+template <int NMAX, int ROWS>
+__global__ __launch_bounds__(256) void k_col_dft_long(const float* __restrict__ win, int slot0, int n, int cap,
+                                                      int rows_per_stream, int live_per_stream, double fl, double fh,
+                                                      const double* __restrict__ tw, float* __restrict__ col1, MinMax* mm) {
+    __shared__ double s_tw[2 * NMAX];
+    __shared__ __attribute__((aligned(16))) float s_row[NMAX][ROWS];
+    __shared__ __attribute__((aligned(16))) float s_y[NMAX / 2 + 1][ROWS][2];
+    __shared__ DftEntry s_ent[NMAX / 2 + 2];
+    __shared__ int s_ne;
+    const int b = blockIdx.y, fr = blockIdx.z;              // stream, frame of the batch
+    slot0 += fr; if (slot0 >= cap) slot0 -= cap;            // frame fr sees the window shifted by fr columns
+    col1 += (size_t)fr * gridDim.y * rows_per_stream;
+    mm += fr * gridDim.y;
+    auto m = [&](int x) { return (x >= fl && x <= fh) ? 1.0f : 0.0f; };              // :70-77
+    for (int i = threadIdx.x; i < 2 * n; i += 256) s_tw[i] = tw[i];
+    if (threadIdx.x == 0) {
+        int ne = 0;
+        const int half = (n - 1) / 2;
+        if (m(0) != 0.f) { s_ent[ne].bin = 0; s_ent[ne].kind = 1; ++ne; }
+        for (int k = 1; k <= half; ++k)
+            if (m(2 * k - 1) != 0.f || m(2 * k) != 0.f) { s_ent[ne].bin = (short)k; s_ent[ne].kind = 0; ++ne; }
+        if (n % 2 == 0 && m(n - 1) != 0.f) { s_ent[ne].bin = (short)(n / 2); s_ent[ne].kind = 2; ++ne; }
+        s_ne = ne;
+    }
+    __syncthreads();
+    const int ne = s_ne;
+    const double* cs = s_tw;
+    const double* sn = s_tw + n;
+    const bool pow2 = (n & (n - 1)) == 0;            // x / 2^k == x * 2^-k exactly: skip the float64 division
+    const double inv_n = 1.0 / (double)n;
+    const bool has_dc = ne > 0 && s_ent[0].kind == 1;
+    const bool has_ny = ne > 0 && s_ent[ne - 1].kind == 2;
+    const int j0 = has_dc ? 1 : 0, j1 = has_ny ? ne - 1 : ne;
+    float vmin = INFINITY, vmax = -INFINITY;
+    const int iters = (live_per_stream + gridDim.x * ROWS - 1) / (gridDim.x * ROWS);
+    for (int it = 0; it < iters; ++it) {
+        const int r0 = (it * gridDim.x + blockIdx.x) * ROWS;
+#pragma unroll
+        for (int rr = 0; rr < ROWS; ++rr) {                                           // rows past the last live one: zeros, results unused
+            const bool live = r0 + rr < live_per_stream;
+            const float* wr = win + ((size_t)b * rows_per_stream + (live ? r0 + rr : 0)) * cap;
+            for (int t = threadIdx.x; t < n; t += 256) { int slot = slot0 + t; if (slot >= cap) slot -= cap; s_row[t][rr] = live ? wr[slot] : 0.f; }
+        }
+        __syncthreads();
+        for (int j = threadIdx.x; j < ne; j += 256) {                                 // dft + mulSpectrums
+            const int k = s_ent[j].bin, kind = s_ent[j].kind;
+            double ar[ROWS], ai[ROWS];
+#pragma unroll
+            for (int rr = 0; rr < ROWS; ++rr) ar[rr] = ai[rr] = 0;
+            int idx = 0;
+            for (int t = 0; t < n; ++t) {
+                const double c = cs[idx], s = sn[idx];
+#pragma unroll
+                for (int rr = 0; rr < ROWS; ++rr) {
+                    const double v = (double)s_row[t][rr];
+                    ar[rr] += v * c;
+                    ai[rr] += -v * s;
+                }
+                idx += k; if (idx >= n) idx -= n;
+            }
+            const float ma = kind == 0 ? m(2 * k - 1) : (kind == 1 ? m(0) : m(n - 1)), mb = kind == 0 ? m(2 * k) : 0.f;
+#pragma unroll
+            for (int rr = 0; rr < ROWS; ++rr) {
+                const float a = (float)(pow2 ? ar[rr] * inv_n : ar[rr] / n), bq = (float)(pow2 ? ai[rr] * inv_n : ai[rr] / n);
+                if (kind == 0) {
+                    s_y[j][rr][0] = a * ma - bq * mb;
+                    s_y[j][rr][1] = bq * ma + a * mb;
+                } else {
+                    s_y[j][rr][0] = a * ma;
+                    s_y[j][rr][1] = 0.f;
+                }
+            }
+        }
+        __syncthreads();
+        for (int t = threadIdx.x; t < n; t += 256) {                                  // idft, every sample
+            double acc[ROWS];
+#pragma unroll
+            for (int rr = 0; rr < ROWS; ++rr) acc[rr] = has_dc ? s_y[0][rr][0] : 0.f;
+            int idx = 0, prev = -2;
+            for (int j = j0; j < j1; ++j) {
+                const int k = s_ent[j].bin;
+                if (k == prev + 1) { idx += t; if (idx >= n) idx -= n; }
+                else idx = (int)(((unsigned)k * (unsigned)t) % (unsigned)n);
+                prev = k;
+                const double c = cs[idx], s = sn[idx];
+#pragma unroll
+                for (int rr = 0; rr < ROWS; ++rr) acc[rr] += 2.0 * ((double)s_y[j][rr][0] * c - (double)s_y[j][rr][1] * s);
+            }
+#pragma unroll
+            for (int rr = 0; rr < ROWS; ++rr) {
+                if (n % 2 == 0) acc[rr] += (t % 2 ? -1.0 : 1.0) * (double)(has_ny ? s_y[ne - 1][rr][0] : 0.f);
+                if (r0 + rr < live_per_stream) {
+                    const float v = (float)(pow2 ? acc[rr] * inv_n : acc[rr] / n);
+                    vmin = v < vmin ? v : vmin; vmax = v > vmax ? v : vmax;
+                    if (t == 1) col1[(size_t)b * rows_per_stream + r0 + rr] = v;     // MagnifyCore.hpp:190-192
+                }
+            }
+        }
+        __syncthreads();
+    }
+    block_minmax(vmin, vmax, mm[b].mn1, mm[b].mx1);
+}
+
+// Serial fallback for very long windows (n > kLongMaxN; LVM_COL_LONG_DFT=0: n > kDftMaxN): one thread per row, same arithmetic.
 __global__ __launch_bounds__(256) void k_col_dft_serial(const float* __restrict__ win, int slot0, int n, int cap,
                                                         int rows_per_stream, int live_per_stream, double fl, double fh,
                                                         const double* __restrict__ tw, float* __restrict__ Y, float* __restrict__ col1,
@@ -1163,7 +1277,10 @@ struct ColorState : ModeState {
     long rows_min_elems = 1 << 20;   // planes x pixels from which pyrDown uses k_pyr_down_rows (LVM_ROWS_MIN_ELEMS)
     double* tw = nullptr; int tw_n = 0;          // table of the current window length (points into tw_all or at tw_own)
     double* tw_all = nullptr; int tw_all_max = 0; std::vector<size_t> tw_off;   // tables of every length 2 .. tw_all_max
-    double* tw_own = nullptr;
+    double* tw_own = nullptr; size_t tw_own_cap = 0;    // one table, refilled per length (doubles it holds)
+    double* tw_stage[2] = {}; hipEvent_t tw_ev[2] = {}; int tw_turn = 0;   // pinned staging of the refills, in turns; event behind each copy
+    bool long_dft = true;            // wave-parallel filter and temporal batches for long windows (LVM_COL_LONG_DFT=0: k_col_dft_serial, frame by frame)
+    int long_from = kDftMaxN + 1;    // ... from this window length on (LVM_COL_LONG_FROM: tests hold the kernel against the oracle on small windows)
     MinMax* mm = nullptr;
     int *xofs = nullptr, *yofs = nullptr; float *xa = nullptr, *ya = nullptr; YSlot* yslot = nullptr;
     // temporal batching
@@ -1171,6 +1288,7 @@ struct ColorState : ModeState {
     ~ColorState() override {
         void* p[] = {arena, win, Y, tw_all, tw_own, mm, xofs, yofs, yslot, xa, ya, tarena, mmt};
         for (void* q : p) if (q) (void)hipFree(q);
+        for (int k = 0; k < 2; ++k) { if (tw_stage[k]) (void)hipHostFree(tw_stage[k]); if (tw_ev[k]) (void)hipEventDestroy(tw_ev[k]); }
     }
     int process(Ctx* c, const lvm_params& p, const FrameIO& io, hipStream_t s, int* produced) override;
     int batch_frames(const Ctx* c, const lvm_params& p, const FrameIO& io, int left) const override;
@@ -1331,6 +1449,13 @@ static void col_down(Ctx* c, ColorState* st, const FrameIO& io, const ColBufs& B
     }
 }
 
+// Which ideal-filter kernels a window of n frames gets: 0 = the kernels for n <= kDftMaxN (wave per row | thread per row), 1 = k_col_dft_long,
+// 2 = k_col_dft_serial (one frame per launch: no temporal batches)
+static int col_dft_kind(const ColorState* st, int n) {
+    if (n < st->long_from && n <= kDftMaxN) return 0;
+    return st->long_dft && n >= st->long_from && n <= kLongMaxN ? 1 : 2;
+}
+
 // window append (nt columns) + ideal band-pass + normalisation of column 1 for every frame of the batch;
 // slot = ring slot of the first new column, slot0 = window start seen by the first frame, n = window length
 static int col_filter(Ctx* c, ColorState* st, const lvm_params& p, const ColBufs& B, int slot, int slot0, int n, hipStream_t s) {
@@ -1356,20 +1481,32 @@ static int col_filter(Ctx* c, ColorState* st, const lvm_params& p, const ColBufs
         if (n % 2 == 0 && m(n - 1) != 0.f) push(n / 2, 2, m(n - 1), 0.f);
         eb.ne = ne;
     }
-    if (ne <= kThin8Bins && n <= kThin8MaxN && st->thin_dft && st->thin8_dft && B.nt >= st->thin_min_frames) {
+    const int kind = col_dft_kind(st, n);
+    if (kind == 1) {
+        const int rows_wg = n <= 2048 ? 4 : 2;
+        int gx = (live + rows_wg - 1) / rows_wg;
+        gx = gx < 1024 ? gx : 1024;
+        if (n <= 2048) {
+            LVM_LAUNCH_V(c, "col_dft", "long", (k_col_dft_long<2048, 4>), dim3(gx, NS, B.nt), blk, s, (const float*)st->win, slot0, n, st->cap, st->rows_ps, live,
+                         fl, fh, (const double*)st->tw, B.col1, B.mm);
+        } else {
+            LVM_LAUNCH_V(c, "col_dft", "long", (k_col_dft_long<kLongMaxN, 2>), dim3(gx, NS, B.nt), blk, s, (const float*)st->win, slot0, n, st->cap, st->rows_ps, live,
+                         fl, fh, (const double*)st->tw, B.col1, B.mm);
+        }
+    } else if (kind == 2) {   // very long windows: serial kernel, one frame per launch (batch_frames refuses them)
+        LVM_LAUNCH_V(c, "col_dft", "serial", k_col_dft_serial, dim3((live + 255) / 256, NS), blk, s, (const float*)st->win, slot0, n, st->cap,
+                     st->rows_ps, live, fl, fh, (const double*)st->tw, st->Y, B.col1, B.mm);
+    } else if (ne <= kThin8Bins && n <= kThin8MaxN && st->thin_dft && st->thin8_dft && B.nt >= st->thin_min_frames) {
         LVM_LAUNCH(c, "col_dft", n <= 128 ? k_col_dft_thin8<128> : k_col_dft_thin8<kThin8MaxN>, dim3((live + kThin8Rows - 1) / kThin8Rows, NS, B.nt), blk, s, (const float*)st->win, slot0, n, st->cap,
                    st->rows_ps, live, (const double*)st->tw, B.col1, B.mm, eb);
     } else if (ne <= kThinBins && n <= kDftMaxN && st->thin_dft && B.nt >= st->thin_min_frames) {
         LVM_LAUNCH(c, "col_dft", k_col_dft_thin, dim3((live + 255) / 256, NS, B.nt), blk, s, (const float*)st->win, slot0, n, st->cap,
                    st->rows_ps, live, (const double*)st->tw, B.col1, B.mm, eb);
-    } else if (n <= kDftMaxN) {
+    } else {
         int gx = (live + kDftRows - 1) / kDftRows;
         gx = gx < 1024 ? gx : 1024;
         LVM_LAUNCH(c, "col_dft", k_col_dft, dim3(gx, NS, B.nt), blk, s, (const float*)st->win, slot0, n, st->cap, st->rows_ps, live, fl, fh,
                    (const double*)st->tw, B.col1, B.mm);
-    } else {   // very long windows: serial kernel, one frame per launch
-        LVM_LAUNCH(c, "col_dft", k_col_dft_serial, dim3((live + 255) / 256, NS), blk, s, (const float*)st->win, slot0, n, st->cap,
-                   st->rows_ps, live, fl, fh, (const double*)st->tw, st->Y, B.col1, B.mm);
     }
     st->amp = (float)p.amplification;          // the normalisation runs at the head of col_up_out (on its own or inside the first pyrUp)
     return LVM_OK;
@@ -1469,6 +1606,8 @@ static void color_switches(ColorState* st) {
     if (env_switch("LVM_COL_OUT_MIN_TASKS", st->out_min_tasks)) st->out_min_tasks_lean = st->out_min_tasks;
     env_switch("LVM_COL_THIN_MIN_FRAMES", st->thin_min_frames);
     env_switch("LVM_ROWS_MIN_ELEMS", st->rows_min_elems);
+    env_switch("LVM_COL_LONG_DFT", st->long_dft);
+    env_switch("LVM_COL_LONG_FROM", st->long_from, [](int x) { return x >= 2; });
 }
 
 int color_create(Ctx* c, int levels, const FrameIO& io, hipStream_t s) {
@@ -1519,14 +1658,33 @@ int ColorState::process(Ctx* c, const lvm_params& p, const FrameIO& io, hipStrea
             }
             st->tw = st->tw_all + st->tw_off[(size_t)n];
         } else {
-            std::vector<double> t(2 * (size_t)n);
+            // One device table, refilled per length.  It is sized once for the longest window of this capture rate (up to kLongMaxN
+            // frames: 2 maxImages doubles), so a warm-up frame allocates nothing; longer windows grow it length by length.  The refill
+            // is a copy enqueued on `s`, behind the previous frame's kernels (every call's stream is ordered behind the previous
+            // call's: order_after_previous), from pinned staging memory used in turns: a staging buffer is rewritten only after the
+            // event behind its last copy has completed.
+            const size_t need = 2 * (size_t)n, want = maxImages <= kLongMaxN && maxImages > n ? 2 * (size_t)maxImages : need;
+            if (st->tw_own_cap < need) {
+                LVM_HIP_TRY(c, hipStreamSynchronize(s));
+                sync_streams(c);
+                if (st->tw_own) (void)hipFree(st->tw_own);
+                st->tw_own = nullptr; st->tw_own_cap = 0;
+                for (int k = 0; k < 2; ++k) {
+                    if (st->tw_stage[k]) (void)hipHostFree(st->tw_stage[k]);
+                    st->tw_stage[k] = nullptr;
+                    if (!st->tw_ev[k]) LVM_HIP_TRY(c, hipEventCreateWithFlags(&st->tw_ev[k], hipEventDisableTiming));
+                }
+                LVM_HIP_TRY(c, hipMalloc((void**)&st->tw_own, want * sizeof(double)));
+                for (int k = 0; k < 2; ++k) LVM_HIP_TRY(c, hipHostMalloc((void**)&st->tw_stage[k], want * sizeof(double)));
+                st->tw_own_cap = want;
+            } else {
+                LVM_HIP_TRY(c, hipEventSynchronize(st->tw_ev[st->tw_turn]));
+            }
+            double* t = st->tw_stage[st->tw_turn];
             for (int k = 0; k < n; ++k) { t[k] = std::cos(two_pi * k / n); t[n + k] = std::sin(two_pi * k / n); }
-            LVM_HIP_TRY(c, hipStreamSynchronize(s));
-            sync_streams(c);
-            if (st->tw_own) (void)hipFree(st->tw_own);
-            st->tw_own = nullptr;
-            LVM_HIP_TRY(c, hipMalloc((void**)&st->tw_own, t.size() * sizeof(double)));
-            LVM_HIP_TRY(c, hipMemcpy(st->tw_own, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice));
+            LVM_HIP_TRY(c, hipMemcpyAsync(st->tw_own, t, need * sizeof(double), hipMemcpyHostToDevice, s));
+            LVM_HIP_TRY(c, hipEventRecord(st->tw_ev[st->tw_turn], s));
+            st->tw_turn ^= 1;
             st->tw = st->tw_own;
         }
         st->tw_n = n;
@@ -1565,7 +1723,7 @@ static int color_reserve_frames(Ctx* c, ColorState* st, int nt, hipStream_t s) {
 int ColorState::batch_frames(const Ctx*, const lvm_params& p, const FrameIO&, int left) const {
     const int nt = left < kColorBatchMax ? left : kColorBatchMax;      // the window ring keeps that many spare slots
     const int maxImages = optimal_buffer_size((int)p.framerate);
-    const bool ok = maxImages > 0 && max_images == maxImages && n == maxImages && tw_n == n && n <= kDftMaxN && cap >= n + nt;
+    const bool ok = maxImages > 0 && max_images == maxImages && n == maxImages && tw_n == n && col_dft_kind(this, n) != 2 && cap >= n + nt;
     return ok ? nt : 0;
 }
 
