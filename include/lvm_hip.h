@@ -362,6 +362,24 @@ enum { LVM_CV_FILTER_UNFUSED = 1,   /* filter2D / sepFilter2D taps as multiply, 
 int  lvm_set_opencv_build(lvm_ctx* ctx, unsigned mask);
 int  lvm_get_opencv_build(lvm_ctx* ctx, unsigned* mask);
 
+/* Phase (Riesz) magnification of GRAY frames -- an EXTENSION beyond the reference, off by default.  The reference's magnifyRiesz returns
+ * "produced no frame" for every 1-channel frame (MagnifyCore.hpp:212), and so does LVM_MODE_PHASE here while the option is 0: every launch,
+ * byte and `produced` flag is what it is without this call.  With the option 1 a Phase context fed the gray frames g_t gives, frame by frame,
+ *     produced_t, out_t  ==  produced'_t, BGR2GRAY( Riesz( expand(g_t) ) )
+ * where expand(g) is the BGR frame with b = g = r = g, Riesz the 3-channel Phase mode with the same parameters, flavour and build kind, and
+ * BGR2GRAY the conversion of GrayscaleProcessor (GrayscaleProcessor.cpp:13: (3735 B + 19235 G + 9798 R + 16384) >> 15 on the u8 frame) --
+ * the reference chain with GrayscaleProcessor moved behind the magnifier.  The weights add up to 32768, so BGR2GRAY(expand(g)) == g and
+ * the passthrough frames (first frame, re-init on NaN coefficients, frame too small) follow the same rule; cutoff change, construction-time
+ * framerate, lvm_reset and the structural reset are unchanged.  L, a, b of a gray pixel are functions of its byte: a 256-entry table,
+ * filled on the device by the forward conversion of the context's flavour, replaces the 33^3 table kernel and the (ia, ib) plane.
+ * Every surface that processes frames takes part (lvm_process*, lvm_chain_* with grayscale = 1, lvm_chain_present, the export calls);
+ * lvm_tile_riesz_* stay BGR-only.  With lvm_debug_keep_float the kept frame is the THREE-channel BGR float frame in front of the quantiser
+ * (w*h*3 floats).  A change while the tracked state is Phase on 1-channel frames is a structural change (flush, synchronise, drop the
+ * state: the next frame is a first frame); otherwise the value is only stored.  lvm_reset keeps it.  A value other than 0 / 1:
+ * LVM_ERR_INVALID, nothing changes.                                                                                                      */
+int  lvm_set_phase_on_gray(lvm_ctx* ctx, int on);
+int  lvm_get_phase_on_gray(lvm_ctx* ctx, int* on);
+
 /* Cross-frame software pipeline for lvm_process_device (throughput mode, default depth 0).
  * depth 1 (implemented for the Laplace mode; other modes ignore it): a call enqueues the
  * down-sweep of ITS frame on an internal second stream concurrently with the up-sweep + output of
@@ -387,7 +405,8 @@ void lvm_butterworth2(double Wn, double a[3], double b[3]);
 
 /* ---- instrumentation (not part of the reference surface) -------------------------------- */
 /* Keep the pre-quantisation float frame of stream 0 (parity metric).
- * lvm_debug_read_float copies w*h*channels floats (interleaved like the u8 output).        */
+ * lvm_debug_read_float copies w*h*channels floats (interleaved like the u8 output); for a
+ * gray Phase frame under lvm_set_phase_on_gray the kept frame has three channels (w*h*3).  */
 int  lvm_debug_keep_float(lvm_ctx* ctx, int on);
 int  lvm_debug_read_float(lvm_ctx* ctx, float* dst, size_t count);
 /* Colour arithmetic.  The forward conversion is what cv::cvtColor(COLOR_BGR2Lab) on CV_32F computes in OpenCV 4
@@ -433,7 +452,8 @@ int  lvm_profile_entry(lvm_ctx* ctx, int idx, char* name, size_t name_cap, doubl
 /* Which kernels ran under entry idx's report name, comma-separated, where several share one (lap_down0, lap_final,
  * lab_lut, rz_lab, rz_final, col_down0, col_minmax, col_out): "strips" = the wave-strip kernel, "vec4" = the tiled kernel
  * with dword-wide frame I/O, "bytes" = the tiled kernel with byte I/O; under a build kind of lvm_set_opencv_build the Riesz launches it changes add "unfused", "f64", "mulf32" or
- * "unfused+mulf32".  Empty for names with one kernel.  The frame's
+ * "unfused+mulf32"; gray Phase frames (lvm_set_phase_on_gray) run "gray4" / "gray" (dword / byte frame I/O) under lab_lut, rz_lab and
+ * rz_final, and "gray-strips" under rz_final.  Empty for names with one kernel.  The frame's
  * layout picks among them (see lvm_process_device); the tests use this to see that it picked what the launch code says. */
 int  lvm_profile_variants(lvm_ctx* ctx, int idx, char* variants, size_t cap);
 /* Algorithmic bytes per frame per stream for the current geometry/mode. */

@@ -110,7 +110,7 @@ SYMBOLS = ["lvm_create", "lvm_destroy", "lvm_reset", "lvm_process", "lvm_process
            "lvm_preprocess_geometry", "lvm_preprocess_device", "lvm_chain_process", "lvm_chain_process_batch",
            "lvm_set_max_frames", "lvm_host_alloc", "lvm_host_free", "lvm_compose_geometry", "lvm_compose_device", "lvm_chain_process_batch_ex",
            "lvm_chain_present", "lvm_mjpeg_bound", "lvm_mjpeg_encode_device", "lvm_export_frames_mjpeg", "lvm_mjpeg_decode_device", "lvm_export_mjpeg_frames", "lvm_mjpeg_set_restart_interval", "lvm_mjpeg_set_decoder", "lvm_mjpeg_set_samplings",
-           "lvm_set_opencv_build", "lvm_get_opencv_build"]
+           "lvm_set_opencv_build", "lvm_get_opencv_build", "lvm_set_phase_on_gray", "lvm_get_phase_on_gray"]
 
 
 def bind(lib):
@@ -176,6 +176,8 @@ def bind(lib):
     lib.lvm_mjpeg_set_samplings.argtypes = [vp, C.c_uint]
     lib.lvm_set_opencv_build.argtypes = [vp, C.c_uint]
     lib.lvm_get_opencv_build.argtypes = [vp, C.POINTER(C.c_uint)]
+    lib.lvm_set_phase_on_gray.argtypes = [vp, C.c_int]
+    lib.lvm_get_phase_on_gray.argtypes = [vp, ip]
     lib.lvm_mjpeg_decode_device.argtypes = [vp, vp, C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_int, vp, C.c_ssize_t, C.c_ssize_t]
     lib.lvm_export_mjpeg_frames.argtypes = [vp, C.POINTER(LvmPreprocessParams), C.POINTER(LvmParams), C.c_int, C.c_int, vp, C.POINTER(C.c_size_t), C.c_int, C.c_int,
                                             C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t), ip]
@@ -397,6 +399,19 @@ class Context:
         m = C.c_uint(0)
         self._check(self.lib.lvm_get_opencv_build(self.h, C.byref(m)))
         return int(m.value)
+
+    def set_phase_on_gray(self, on):
+        """lvm_set_phase_on_gray: an extension beyond the reference, off by default.  On, MODE_PHASE magnifies 1-channel frames:
+        out == bgr2gray(Riesz(expand(g))), with expand(g) the BGR frame b = g = r = g and bgr2gray GrayscaleProcessor's conversion; off, gray Phase
+        frames produce nothing, as in the reference.  A change under a gray Phase clip restarts it; reset() keeps the value.  Anything but
+        0 / 1 (False / True): LvmError, nothing changes."""
+        self._check(self.lib.lvm_set_phase_on_gray(self.h, int(on)))
+
+    def phase_on_gray(self):
+        """lvm_get_phase_on_gray: whether MODE_PHASE magnifies gray frames (False by default)."""
+        v = C.c_int(0)
+        self._check(self.lib.lvm_get_phase_on_gray(self.h, C.byref(v)))
+        return bool(v.value)
 
     def mjpeg_decode_device(self, jpegs, w, h, d_ptr, stride=None, frame_stride=None):
         """lvm_mjpeg_decode_device: a list of JPEG frames (bytes) -> BGR frames in device memory at d_ptr."""

@@ -113,6 +113,69 @@ void lab_lut_planes(Ctx* c, const uint8_t* d_in, long in_stride, long in_sstride
     LVM_LAUNCH_V(c, "lab_lut", vec ? "vec4" : "bytes", k, dim3((unsigned)blocks), dim3(LC_THREADS), s, d_in, in_stride, in_sstride, w, h, nframes, c->lab_lut, iL, Lf, iab, (int)per);
 }
 
+// ---- gray Phase frames (lvm_set_phase_on_gray): Lab of a gray pixel is a function of its byte ---------------------------------------
+// The 256 colours (v, v, v) through the forward conversion of the flavour -- the table flavours: lut_lab_int, the very integers
+// k_lab_planes gives that pixel, as the floats the BGR kernels make of them (lut_L, lut_ab); the analytic flavour: lin_bgr_to_lab<true>
+// on the gamma table, as k_rz_lab / k_rz_final do.  tab[v] = L, tab[256 + v] = a, tab[512 + v] = b.  (The node table is read from
+// global memory here: 256 pixels do not pay for a 144 KB copy into LDS.)
+template <bool LUT>
+__global__ __launch_bounds__(256) void k_lab_gray_table(LabLut lut, LabCoef lab, float* __restrict__ tab) {
+    const uint32_t v = threadIdx.x;
+    float L, a, b;
+    if (LUT) {
+        int iL, ia, ib;
+        lut_lab_int(v, v, v, lut.ab, lut.Lcells, iL, ia, ib);
+        L = lut_L(iL); a = lut_ab(ia); b = lut_ab(ib);
+    } else {
+        const float g = lab.gamma_u8[v];
+        lin_bgr_to_lab<true>(g, g, g, lab.fwd, L, a, b);
+    }
+    tab[v] = L; tab[256 + v] = a; tab[512 + v] = b;
+}
+void lab_gray_table(Ctx* c, float* tab, hipStream_t s) {
+    auto k = fl_lut(lab_flavour(c)) ? k_lab_gray_table<true> : k_lab_gray_table<false>;
+    LVM_LAUNCH(c, "lab_gray_table", k, dim3(1), dim3(256), s, c->lab_lut, c->lab, tab);
+}
+
+// u8 gray -> float L plane through the table: a streaming kernel, 1 byte in and 4 bytes out per pixel.  VEC (w % 4 == 0, rows / streams /
+// base dword aligned): a lane takes four pixels per step -- one dword load, four LDS reads, one 16-byte store -- and a workgroup walks
+// over kGrayIters x 1024 pixels, so the table is loaded once per 4096 pixels.  Otherwise one pixel per lane, byte loads.
+constexpr int kGrayIters = 4;
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_lab_gray_plane(const uint8_t* __restrict__ in, long in_stride, long in_sstride, int w, int h,
+                                                        const float* __restrict__ tab, float* __restrict__ Lp) {
+    __shared__ float s_L[256];
+    s_L[threadIdx.x] = tab[threadIdx.x];
+    __syncthreads();
+    if (VEC) {
+        const int gpr = w >> 2, ngroups = gpr * h, b = blockIdx.y;
+#pragma unroll 1
+        for (int it = 0; it < kGrayIters; ++it) {
+            const int g = (blockIdx.x * kGrayIters + it) * 256 + threadIdx.x;
+            if (g >= ngroups) return;
+            const int y = g / gpr, x = (g - y * gpr) * 4;
+            const uint32_t v = *reinterpret_cast<const uint32_t*>(in + (size_t)b * in_sstride + (size_t)y * in_stride + (size_t)x);
+            *reinterpret_cast<float4*>(Lp + ((size_t)b * h + y) * w + x) = make_float4(s_L[v & 255u], s_L[(v >> 8) & 255u], s_L[(v >> 16) & 255u], s_L[v >> 24]);
+        }
+    } else {
+        const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, b = blockIdx.z;
+        if (x >= w) return;
+        Lp[((size_t)b * h + y) * w + x] = s_L[in[(size_t)b * in_sstride + (size_t)y * in_stride + (size_t)x]];
+    }
+}
+// under the report name of the kernel it replaces: the table kernel ("lab_lut") or, in the analytic flavour, k_rz_lab* ("rz_lab")
+void lab_gray_plane(Ctx* c, const uint8_t* d_in, long in_stride, long in_sstride, int w, int h, int nframes, const float* tab, float* Lf, hipStream_t s) {
+    const bool vec = w % 4 == 0 && in_stride % 4 == 0 && in_sstride % 4 == 0 && ((uintptr_t)d_in % 4) == 0;
+    const char* nm = fl_lut(lab_flavour(c)) ? "lab_lut" : "rz_lab";
+    if (vec) {
+        const long groups = (long)(w / 4) * h;
+        LVM_LAUNCH_V(c, nm, "gray4", k_lab_gray_plane<true>, dim3((unsigned)((groups + 256 * kGrayIters - 1) / (256 * kGrayIters)), nframes), dim3(256), s,
+                     d_in, in_stride, in_sstride, w, h, tab, Lf);
+    } else {
+        LVM_LAUNCH_V(c, nm, "gray", k_lab_gray_plane<false>, dim3((w + 255) / 256, h, nframes), dim3(256), s, d_in, in_stride, in_sstride, w, h, tab, Lf);
+    }
+}
+
 // ---- lvm_debug_sweep_u8_steps: the step table against the operations it replaces, float by float ---------------------------------
 // Thread i of the grid takes the bit patterns first + i, first + i + stride, ...: c = the float with that pattern; reference = OpenCV's
 // operations one by one (clip01, x 1024, splineInterpolate, x 255 + 1/255, cvRound + saturate -- the EXACT flavour's code); candidate =

@@ -152,6 +152,10 @@ void fail_state(Ctx* c, hipStream_t s) {
 }
 static void tracker_disable(Ctx* c) { const uint64_t pre = c->tracked.pre; c->tracked = StructKey{}; c->tracked.pre = pre; }
 
+// channels of the float frame lvm_debug_keep_float keeps: the frame's own, except that a gray Phase frame under lvm_set_phase_on_gray keeps the
+// three-channel BGR frame in front of the quantiser (what the oracle holds for the expanded frame)
+static size_t float_channels(const Ctx* c, int mode, int channels) { return (c->phase_on_gray && mode == LVM_MODE_PHASE && channels == 1) ? 3 : (size_t)channels; }
+
 int ensure_float(Ctx* c, size_t count) {
     if (count * sizeof(float) > c->d_float.cap) {
         sync_streams(c);            // kernels of earlier calls may still be writing the kept frame
@@ -202,7 +206,7 @@ static int process_device(Ctx* c, const lvm_params* p, const FrameIO& io, hipStr
         drop_state(c);                                                                  // :39-43
     }
     if (c->keep_float) {
-        const int rc = ensure_float(c, (size_t)io.w * io.h * io.channels);
+        const int rc = ensure_float(c, (size_t)io.w * io.h * float_channels(c, p->mode, io.channels));
         if (rc != LVM_OK) return rc;
     }
     int rc = c->state ? LVM_OK : create_state(c, p->mode, key.levels, io, s);
@@ -333,7 +337,7 @@ int lvm_process_device_frames(lvm_ctx* c, const lvm_params* p, int n_frames, con
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
     if (c->keep_float && w > 0 && h > 0 && (channels == 1 || channels == 3) &&         // the batched schedules keep the first frame of a batch
         !lvm::layout_error(lvm::FrameIO{d_in, in_stride, in_stream_stride, d_out, out_stride, out_stream_stride, w, h, channels}, c->nstreams)) {   // (a refused layout reserves nothing)
-        const int rc = lvm::ensure_float(c, (size_t)w * h * channels);
+        const int rc = lvm::ensure_float(c, (size_t)w * h * lvm::float_channels(c, p->mode, channels));
         if (rc != LVM_OK) return rc;
     }
     int f = 0;
@@ -440,7 +444,7 @@ int lvm_tile_riesz_stage2(lvm_ctx* c, const lvm_params* p, const uint8_t* d_in, 
     int rc = tile_check(c, p, w, h);
     if (rc != LVM_OK) return rc;
     if (!d_in || !d_out || !d_residual_in || in_stride < (ptrdiff_t)w * 3 || out_stride < (ptrdiff_t)w * 3) { c->err = "tiling: bad frame arguments"; return LVM_ERR_INVALID; }
-    if (c->tracked.mode != LVM_MODE_PHASE || c->tracked.w != w || c->tracked.h != h) { c->err = "tiling: stage 2 without a matching stage 1"; return LVM_ERR_INVALID; }
+    if (c->tracked.mode != LVM_MODE_PHASE || c->tracked.w != w || c->tracked.h != h || c->tracked.channels != 3) { c->err = "tiling: stage 2 without a matching stage 1"; return LVM_ERR_INVALID; }
     LVM_HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
     lvm::FrameIO io{d_in, in_stride, in_stride * h, d_out, out_stride, out_stride * h, w, h, 3};
@@ -845,6 +849,29 @@ int lvm_get_opencv_build(lvm_ctx* c, unsigned* mask) {
     return LVM_OK;
 }
 
+// Phase mode on gray frames, an extension beyond the reference (include/lvm_hip.h).  Kept by lvm_reset.  Whether a gray Phase key has a state at
+// all depends on it, so a change under such a key is a structural change (process_device's rule: flush, synchronise, drop; the tracker is
+// disarmed, the next frame is a first frame); under any other key the value is only stored.
+int lvm_set_phase_on_gray(lvm_ctx* c, int on) {
+    if (!c) return LVM_ERR_INVALID;
+    if (on != 0 && on != 1) { c->err = "lvm_set_phase_on_gray: the value must be 0 or 1"; return LVM_ERR_INVALID; }
+    if ((on != 0) == c->phase_on_gray) return LVM_OK;
+    if (c->tracked.mode == LVM_MODE_PHASE && c->tracked.channels == 1) {
+        LVM_HIP_TRY(c, hipSetDevice(c->device));
+        if (c->state) (void)c->state->flush(c, c->own_stream);
+        LVM_HIP_TRY(c, hipStreamSynchronize(c->own_stream));
+        lvm::sync_streams(c);
+        lvm::drop_state(c); lvm::tracker_disable(c);
+    }
+    c->phase_on_gray = on != 0;
+    return LVM_OK;
+}
+int lvm_get_phase_on_gray(lvm_ctx* c, int* on) {
+    if (!c || !on) return LVM_ERR_INVALID;
+    *on = c->phase_on_gray ? 1 : 0;
+    return LVM_OK;
+}
+
 size_t lvm_mjpeg_bound(int w, int h) { return (w < 1 || h < 1) ? 0 : lvm::mjpeg_bound(w, h); }
 
 int lvm_mjpeg_encode_device(lvm_ctx* c, const uint8_t* d_bgr, int w, int h, ptrdiff_t stride, ptrdiff_t frame_stride, int n_frames, int quality,
@@ -994,6 +1021,7 @@ int lvm_set_lab_lut(lvm_ctx* c, const int16_t* src) {
         if (src[i] < 0 || src[i] > 16384) { c->err = "lvm_set_lab_lut: entry outside [0, 16384]"; return LVM_ERR_INVALID; }
     lvm::sync_streams(c);                        // kernels in flight read the old table (this context's buffers: no device-wide wait)
     c->lab_lut_compact.assign(src, src + LVM_LAB_LUT_ENTRIES);
+    ++c->lab_lut_gen;                            // (the per-value table of a gray Riesz state is refilled from the new table at its next launch)
     return lvm::upload_lab_lut(c);
 }
 

@@ -45,6 +45,9 @@ __device__ __forceinline__ uint8_t sat_u8(float v) {
     return (uint8_t)r;
 }
 
+// cv::cvtColor(COLOR_BGR2GRAY) on u8 (GrayscaleProcessor.cpp:13): RGB2Gray<uchar>'s 15-bit fixed point
+__device__ __forceinline__ uint8_t gray15(int b, int g, int r) { return (uint8_t)((b * 3735 + g * 19235 + r * 9798 + (1 << 14)) >> 15); }
+
 // Four convertTo(CV_8U) results packed into one dword.  v_cvt_pk_u8_f32 converts with round-half-even,
 // saturates to [0, 255] and maps NaN to 0 (checked on gfx950 with tools/probe_isa.hip), i.e. it IS
 // saturate_cast<uchar>(cvRound(v)), and it writes the byte in place: 4 instructions per dword.
@@ -541,6 +544,8 @@ struct Ctx {
     int mjpeg_decoder = LVM_MJPEG_DECODER_REPLICATE;   // lvm_mjpeg_set_decoder: the arithmetic behind the entropy layer
     unsigned mjpeg_samplings = LVM_MJPEG_SAMPLING_420;  // lvm_mjpeg_set_samplings: the samplings the decoder accepts
     unsigned opencv_build = 0;        // lvm_set_opencv_build: which OpenCV build the Riesz arithmetic reproduces (a mask of LVM_CV_*; riesz.hip)
+    bool phase_on_gray = false;       // lvm_set_phase_on_gray: LVM_MODE_PHASE magnifies 1-channel frames (an extension; off = MagnifyCore.hpp:212)
+    unsigned lab_lut_gen = 0;         // counts lvm_set_lab_lut calls: the per-value Lab table of a gray Riesz state (riesz.hip) follows the forward table
 };
 
 inline int lab_flavour(const Ctx* c) { return c->lab_analytic ? FL_ANALYTIC : (c->exact_lab ? FL_LUT_EXACT : FL_LUT_FAST); }
@@ -651,6 +656,11 @@ struct LName {
 // labconv.hip: u8 BGR frames -> integer Lab planes (exactly one of iL / Lf is non-null)
 void lab_lut_planes(Ctx* c, const uint8_t* d_in, long in_stride, long in_sstride, int w, int h, int nframes, uint16_t* iL, float* Lf,
                     uint32_t* iab, hipStream_t s);
+// labconv.hip, gray Phase frames (lvm_set_phase_on_gray): Lab of the 256 colours (v, v, v) in the context's flavour -> tab[0..255] = L,
+// tab[256..511] = a, tab[512..767] = b; and u8 gray frames -> float L plane through that table
+constexpr int kGrayLabFloats = 3 * 256;
+void lab_gray_table(Ctx* c, float* tab, hipStream_t s);
+void lab_gray_plane(Ctx* c, const uint8_t* d_in, long in_stride, long in_sstride, int w, int h, int nframes, const float* tab, float* Lf, hipStream_t s);
 
 // preprocess.hip
 void preprocess_geometry(const lvm_preprocess_params& pp, int w, int h, int channels, int* rx, int* ry, int* rw, int* rh,
@@ -684,7 +694,7 @@ int compose_device(Ctx* c, int split, const uint8_t* d_orig, int ow, int oh, int
                    ptrdiff_t cstride, ptrdiff_t csstride, hipStream_t s);
 
 // The modes (laplace.hip / riesz.hip / color.hip): create the state of the tracked key and install it as c->state -- before its buffers are
-// allocated, so that a failed creation is dropped by fail_state.  riesz_create leaves c->state null for gray frames (MagnifyCore.hpp:212).
+// allocated, so that a failed creation is dropped by fail_state.  riesz_create leaves c->state null for gray frames (MagnifyCore.hpp:212) unless lvm_set_phase_on_gray is on.
 int laplace_create(Ctx* c, int levels, const FrameIO& io, hipStream_t s);
 int riesz_create(Ctx* c, int levels, const FrameIO& io, hipStream_t s);
 int color_create(Ctx* c, int levels, const FrameIO& io, hipStream_t s);

@@ -31,7 +31,7 @@ struct PreArgs {
     const AreaTab* ytab; const int* yk;
 };
 
-__device__ __forceinline__ uint8_t gray15(int b, int g, int r) { return (uint8_t)((b * 3735 + g * 19235 + r * 9798 + (1 << 14)) >> 15); }
+// (gray15: lvm_internal.h -- the gray Phase output kernels of riesz.hip apply the same weighting)
 
 // MODE 0 = crop only, 1 = integer decimation, 2 = fractional area tables.  One thread per output pixel;
 // blockIdx.z = stream.

@@ -27,6 +27,12 @@
 //   k_rz_collapse x (L-2)            res_l = lp(zero-inject(res_{l+1})) (polyphase) + hp(bandA_l)
 //   k_rz_final                       level-0 collapse + Lab2BGR(L', a, b) -> u8, (a, b) from the dword plane
 // Summation order of every filter equals the oracle's (row-major non-zero taps, fma chain).
+//
+// Gray frames (lvm_set_phase_on_gray, an extension: the reference passes them through, MagnifyCore.hpp:212) compute BGR2GRAY(Riesz(expand(g))):
+// L, a, b of a gray pixel are functions of its byte, so a 256-entry table filled by the flavour's forward conversion (labconv.hip
+// k_lab_gray_table) stands for the table kernel and the (ia, ib) plane -- k_lab_gray_plane writes oct_0, k_rz_final_gray /
+// k_rz_collapse_strips_gray read the input byte again for (a, b), run the BGR kernels' inverse conversion and quantiser and weigh the three
+// bytes into one (gray15).  Everything between the two ends is the planes and kernels above, unchanged.
 #include <cmath>
 #include <type_traits>
 
@@ -1375,6 +1381,80 @@ __global__ __launch_bounds__(256) void k_rz_final(const uint8_t* __restrict__ in
     }
 }
 
+// The same for GRAY frames (lvm_set_phase_on_gray): out = BGR2GRAY(Lab2BGR(L', a(v), b(v)) -> u8) with v the input byte of the pixel and
+// a(), b() the per-value table of the state (labconv.hip k_lab_gray_table: what the BGR kernels get for the colour (v, v, v)) in LDS.  The
+// inverse conversion, the quantiser and -- DBG -- the kept float frame (three channels) are k_rz_final's; the three bytes of a pixel meet in
+// GrayscaleProcessor's weighting (gray15) and one byte leaves.  1 byte of frame read and 1 written per pixel against 3 + 3 (+ 4 of the
+// (ia, ib) plane).  Without BANDS L' is the plane `Lplane` in every flavour (oct_0, or res_0 under a build kind).
+// VEC = rows, streams and base pointers of both frames are dword aligned and w % 4 == 0: one dword load and one dword store per thread.
+template <bool BANDS, int FL, bool VEC, bool COMPACT, bool DBG>
+__global__ __launch_bounds__(256) void k_rz_final_gray(const uint8_t* __restrict__ in, long in_stride, long in_sstride,
+                                                       uint8_t* __restrict__ out, long out_stride, long out_sstride, int w, int h,
+                                                       const float* __restrict__ bandA, const float* __restrict__ resn, int nw,
+                                                       int nh, LabCoef lab, int tiles_x, int tiles_y, int nstreams,
+                                                       float* __restrict__ dbg, const float* __restrict__ Lplane, const float* __restrict__ gtab) {
+    constexpr bool EXACT = fl_exact(FL);
+    __shared__ __attribute__((aligned(16))) float s_igt[4096];
+    __shared__ float s_a[256], s_b[256];
+    __shared__ __attribute__((aligned(16))) float sb[CSH][CSP];
+    __shared__ __attribute__((aligned(16))) CollapseTile<COMPACT> su;
+    load_invgamma(s_igt, lab.invgamma);
+    s_a[threadIdx.x] = gtab[256 + threadIdx.x]; s_b[threadIdx.x] = gtab[512 + threadIdx.x];
+    __syncthreads();
+    const int ntiles = tiles_x * tiles_y * nstreams;
+    const int y = collapse_row(), x = (threadIdx.x & 15) * 4;
+    const int tper = (ntiles + (int)gridDim.x - 1) / (int)gridDim.x;
+    const int t0 = (int)xcd_swizzle(blockIdx.x, gridDim.x) * tper, t1 = t0 + tper < ntiles ? t0 + tper : ntiles;
+    for (int t = t0; t < t1; ++t) {
+        const int b = t / (tiles_x * tiles_y);
+        const int r = t - b * (tiles_x * tiles_y);
+        const int ty = r / tiles_x, tx = r - ty * tiles_x;
+        const int x0 = tx * CW, y0 = ty * CH;
+        const int gx = x0 + x, gy = y0 + y;
+        const bool ok = gx < w && gy < h;
+        if (BANDS) {                                               // phase A of k_rz_final
+            collapse_stage(sb, su, bandA + (size_t)b * w * h, resn + (size_t)b * nw * nh, w, h, nw, nh, x0, y0);
+            __syncthreads();
+            float Lc[4] = {0.f, 0.f, 0.f, 0.f};
+            if (ok) collapse_px4(sb, su, x, y, gy, Lc);
+            __syncthreads();
+            *reinterpret_cast<float4*>(&sb[y][x]) = make_float4(Lc[0], Lc[1], Lc[2], Lc[3]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (ok) {
+            const uint8_t* p = in + (size_t)b * in_sstride + (size_t)gy * in_stride + (size_t)gx;
+            uint32_t pv[4];
+            if (VEC) { const uint32_t v = *reinterpret_cast<const uint32_t*>(p); pv[0] = v & 255u; pv[1] = (v >> 8) & 255u; pv[2] = (v >> 16) & 255u; pv[3] = v >> 24; }
+            else {
+#pragma unroll
+                for (int m = 0; m < 4; ++m) pv[m] = (gx + m < w) ? p[m] : 0;
+            }
+            float Lc[4] = {0.f, 0.f, 0.f, 0.f};
+            if (BANDS) { const float4 Lq = *reinterpret_cast<const float4*>(&sb[y][x]); Lc[0] = Lq.x; Lc[1] = Lq.y; Lc[2] = Lq.z; Lc[3] = Lq.w; }   // written by this very thread
+            else {
+                const size_t i = ((size_t)b * h + gy) * w + gx;
+#pragma unroll
+                for (int m = 0; m < 4; ++m) Lc[m] = (gx + m < w) ? Lplane[i + m] : 0.f;
+            }
+            uint32_t og[4];
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                float o0, o1, o2;
+                lab_to_bgr<EXACT>(Lc[m], s_a[pv[m]], s_b[pv[m]], EXACT ? lab.inv : lab.inv1024, s_igt, o0, o1, o2);
+                if (DBG && dbg && b == 0 && gx + m < w) { float* d = dbg + ((size_t)gy * w + gx + m) * 3; d[0] = o0; d[1] = o1; d[2] = o2; }
+                og[m] = gray15(sat_u8(o0 * 255.0f + lab.a255), sat_u8(o1 * 255.0f + lab.a255), sat_u8(o2 * 255.0f + lab.a255));
+            }
+            uint8_t* q = out + (size_t)b * out_sstride + (size_t)gy * out_stride + (size_t)gx;
+            if (VEC) *reinterpret_cast<uint32_t*>(q) = og[0] | (og[1] << 8) | (og[2] << 16) | (og[3] << 24);
+            else {
+#pragma unroll
+                for (int m = 0; m < 4; ++m) if (gx + m < w) q[m] = (uint8_t)og[m];
+            }
+        }
+        if (BANDS) __syncthreads();
+    }
+}
+
 // ---- collapse and output as WAVE STRIPS (planes with even width and height, width a multiple of 4) ---------------------------
 // The tiled kernels above read every fma operand from LDS (k_rz_final: 2.1 TB/s, neither pipe saturated).  Here a wave walks down
 // the rows of bandA_l exactly as k_rz_split_rows walks down the octave: lane i holds columns 4g .. 4g+3, the 9x9 high-pass is the
@@ -1414,6 +1494,39 @@ __device__ __forceinline__ void collapse_lp_taps(const lvm_f2 (&A)[3], const lvm
             else lp[slot][1] = f2_fma(k2, c, lp[slot][1]);                // outputs 1, 3
         }
     }
+}
+// The conversions of collapse_emit (below) with (a, b) given as floats, for the gray emit: the same calls in the same order.  (collapse_emit keeps
+// its own text: routed through these, the compiler schedules k_rz_collapse_strips<true, ...> differently, and the BGR kernels are to stay the
+// instruction streams they were.)
+// four pixels of a lane, Lab -> the three bytes each through the u8 step table (fin_steps flavours; steps = the table in LDS)
+__device__ __forceinline__ void strip_lab_to_u8(const float (&Lc)[4], const float (&av)[4], const float (&bv)[4], const LabCoef& lab, const uint2* steps, uint32_t (&u)[4][3]) {
+#pragma unroll
+    for (int m = 0; m < 4; m += 2) {
+        lvm_f2 c0, c1, c2;
+        lab_to_linear_pair(f2_set(Lc[m], Lc[m + 1]), f2_set(av[m], av[m + 1]), f2_set(bv[m], bv[m + 1]), lab.inv4096, c0, c1, c2);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) { u[m + k][0] = u8_step(c0[k], steps); u[m + k][1] = u8_step(c1[k], steps); u[m + k][2] = u8_step(c2[k], steps); }
+    }
+}
+// ... -> the float BGR frame (the other flavours; s_igt = the inverse-gamma spline in LDS)
+template <bool EXACT>
+__device__ __forceinline__ void strip_lab_to_bgr(const float (&Lc)[4], const float (&av)[4], const float (&bv)[4], const LabCoef& lab, const float* s_igt, float (&o)[4][3]) {
+    if (EXACT) {
+#pragma unroll
+        for (int m = 0; m < 4; ++m) lab_to_bgr<true>(Lc[m], av[m], bv[m], lab.inv, s_igt, o[m][0], o[m][1], o[m][2]);
+    } else {
+#pragma unroll
+        for (int m = 0; m < 4; m += 2) {
+            lvm_f2 o0, o1, o2;
+            lab_to_bgr_pair(f2_set(Lc[m], Lc[m + 1]), f2_set(av[m], av[m + 1]), f2_set(bv[m], bv[m + 1]), lab.inv1024, s_igt, o0, o1, o2);
+            o[m][0] = o0[0]; o[m][1] = o1[0]; o[m][2] = o2[0]; o[m + 1][0] = o0[1]; o[m + 1][1] = o1[1]; o[m + 1][2] = o2[1];
+        }
+    }
+}
+__device__ __forceinline__ void strip_keep_float(const float (&o)[4][3], const BufRsrc& rd, uint32_t dvoff, uint32_t dsoff) {
+    buf_st_f32x4(o[0][0], o[0][1], o[0][2], o[1][0], rd, dvoff, dsoff);
+    buf_st_f32x4(o[1][1], o[1][2], o[2][0], o[2][1], rd, dvoff, dsoff + 16u);
+    buf_st_f32x4(o[2][2], o[3][0], o[3][1], o[3][2], rd, dvoff, dsoff + 32u);
 }
 // one completed row of L' (four pixels of a lane) -> Lab2BGR with the frame's (a, b) -> u8 (and the float frame when DBG)
 template <int FL, bool DBG>
@@ -1469,6 +1582,127 @@ __device__ __forceinline__ void collapse_emit(float L0, float L1, float L2, floa
     v.b = pack_u8x4(t[1][1], t[1][2], t[2][0], t[2][1]);
     v.c = pack_u8x4(t[2][2], t[3][0], t[3][1], t[3][2]);
     buf_sts_b96(v, ro, voff, soff);                 // (the output frame is not read again on the device: streaming store)
+}
+// The same row of a GRAY frame (lvm_set_phase_on_gray): (a, b) from the per-value table in LDS (s_ab[v] = a, s_ab[256 + v] = b) at the four input
+// bytes `px`, the flavour's quantiser, GrayscaleProcessor's weighting of the three bytes, one dword of four gray bytes to `dst` (null: nothing stored).
+template <int FL, bool DBG>
+__device__ __forceinline__ void collapse_emit_gray(float L0, float L1, float L2, float L3, uint32_t px, const float* s_ab, const LabCoef& lab, const float* s_igt,
+                                                   uint8_t* dst, const BufRsrc& rd, uint32_t dvoff, uint32_t dsoff) {
+    const float Lc[4] = {L0, L1, L2, L3};
+    const uint32_t pv[4] = {px & 255u, (px >> 8) & 255u, (px >> 16) & 255u, px >> 24};
+    float av[4], bv[4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) { av[m] = s_ab[pv[m]]; bv[m] = s_ab[256 + pv[m]]; }
+    uint32_t u[4][3];
+    if (fin_steps(FL, DBG)) strip_lab_to_u8(Lc, av, bv, lab, reinterpret_cast<const uint2*>(s_igt), u);
+    else {
+        float o[4][3];
+        strip_lab_to_bgr<fl_exact(FL)>(Lc, av, bv, lab, s_igt, o);
+        if (DBG) strip_keep_float(o, rd, dvoff, dsoff);
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const uint32_t p = pack_u8x4(o[m][0] * 255.0f + lab.a255, o[m][1] * 255.0f + lab.a255, o[m][2] * 255.0f + lab.a255, 0.f);
+            u[m][0] = p & 255u; u[m][1] = (p >> 8) & 255u; u[m][2] = (p >> 16) & 255u;
+        }
+    }
+    uint32_t gq[4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) gq[m] = gray15((int)u[m][0], (int)u[m][1], (int)u[m][2]);
+    if (dst) *reinterpret_cast<uint32_t*>(dst) = gq[0] | (gq[1] << 8) | (gq[2] << 16) | (gq[3] << 24);
+}
+// the frames of a gray launch: the input bytes are read again for (a, b), the output has one byte per pixel (both dword aligned, w % 4 == 0)
+struct GrayStripIO { const uint8_t* in; long in_stride, in_sstride; const float* gtab; };
+// The strip walk of k_rz_collapse_strips<true, ...> for gray frames: the same steps, taps and order; what differs is the row of input bytes where the
+// BGR kernel fetches the (ia, ib) row, and the emit.  (It is a copy, not a function both kernels call: with the walk in a shared function the
+// compiler schedules k_rz_collapse_strips differently -- 4926 -> 4919 instructions without FINAL, 9260 -> 9258 with -- and the BGR kernels are
+// to stay the instruction streams they were, tools/riesz_isa_vs_rev.py.)  s_igt: the spline or the u8 step table in LDS.
+template <int FL, bool DBG>
+__device__ __forceinline__ void collapse_strips_walk_gray(const CollapseStripArgs& a, const GrayStripIO& gio, const float* s_igt, const float* s_ab) {
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const int task = blockIdx.x * (CS_THREADS / 64) + wave;
+    if (task >= a.ntasks) return;
+    const int w = a.w, h = a.h, nw = a.nw, nh = a.nh;
+    const int z = task / (a.strips_x * a.strips_y);
+    const int r = task - z * (a.strips_x * a.strips_y);
+    const int ty = r / a.strips_x, tx = r - ty * a.strips_x;
+    const int G = w >> 2;                                           // w % 4 == 0, G >= 2
+    const int g = tx * SR_OWN - 1 + lane;
+    const int gl = g < 0 ? 0 : (g > G - 1 ? G - 1 : g);
+    const bool owner = lane >= 1 && lane <= SR_OWN && g >= 0 && g < G;
+    const bool first = g == 0, last = g == G - 1;
+    constexpr uint32_t kDrop = 0x80000000u;
+    const uint32_t pbytes = (uint32_t)w * (uint32_t)h * 4u;
+    const BufRsrc rb = buf_rsrc(a.bandA + (size_t)z * w * h, pbytes);
+    const BufRsrc rc = buf_rsrc(a.resn + (size_t)z * nw * nh, (uint32_t)nw * (uint32_t)nh * 4u);
+    // the lane's four bytes of a row of the input / output frame (gl is clamped and an output row is only written by its owner inside the strip:
+    // every address lies inside the w x h rectangle of the frame)
+    const uint8_t* gin = gio.in + (size_t)z * gio.in_sstride + 4u * (uint32_t)gl;
+    uint8_t* gout = owner ? a.out + (size_t)z * a.out_sstride + 4u * (uint32_t)gl : nullptr;
+    const BufRsrc rd = buf_rsrc(a.dbg, (DBG && a.dbg && z == 0) ? pbytes * 3u : 0u);   // float frame of stream 0 (three channels)
+    const uint32_t lband = 16u * (uint32_t)gl, lcoarse = 8u * (uint32_t)gl;
+    const uint32_t ldbg = owner ? 48u * (uint32_t)gl : kDrop;
+    const int y0 = ty * a.rows;                                     // rows is even
+    const int yend = y0 + a.rows < h ? y0 + a.rows : h;
+    const int nq = yend - y0 + 8;                                   // input rows y0 - 4 .. yend + 3
+    lvm_f2 hp[9][2], lp[9][2];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { hp[k][0] = hp[k][1] = f2_all(0.f); lp[k][0] = lp[k][1] = f2_all(0.f); }
+    int ry = reflect101(y0 - 4, h), rdir = reflect101(y0 - 3, h) - ry;
+    auto advance_row = [&]() __attribute__((always_inline)) {
+        const int t = ry + rdir;
+        const bool lo = t < 0, hi = t > h - 1;
+        ry = lo ? (h > 1 ? 1 : 0) : (hi ? (h > 1 ? h - 2 : 0) : t);
+        rdir = lo ? 1 : (hi ? -1 : rdir);
+    };
+    // in flight per wave: the band row of the next step, the coarse row of the next even step, the (a, b) row of the next output row
+    float4 nxt = buf_ld_f32x4(rb, lband, (uint32_t)ry * (uint32_t)w * 4u);
+    float2 nxtc;
+    { const lvm_f2 c = buf_ld_f32x2(rc, lcoarse, (uint32_t)(ry >> 1) * (uint32_t)nw * 4u); nxtc = make_float2(c[0], c[1]); }
+    uint32_t nxti = 0u;
+    int q = 0;
+#define LVM_COLLAPSE_STEP(P18)                                                                                     \
+    {                                                                                                               \
+        if ((P18) % 9 == 0 && q >= nq) break;                                                                       \
+        constexpr int P = (P18) % 9;                                                                                \
+        constexpr bool EVEN = ((P18) & 1) == 0;                     /* input row y0 - 4 + q and output row y0 - 8 + q, y0 even */ \
+        const float4 cur = nxt;                                                                                     \
+        const float2 curc = nxtc;                                                                                   \
+        const uint32_t curi = nxti;                                                                                 \
+        advance_row();                                              /* row y0 - 3 + q, reflected */                 \
+        nxt = buf_ld_f32x4(rb, lband, (uint32_t)ry * (uint32_t)w * 4u);                                             \
+        if (!EVEN) { const lvm_f2 c = buf_ld_f32x2(rc, lcoarse, (uint32_t)(ry >> 1) * (uint32_t)nw * 4u); nxtc = make_float2(c[0], c[1]); }   /* that row is even */ \
+        {                                                           /* input bytes of output row y0 - 7 + q: complete one step from now */ \
+            const int orow = y0 - 7 + q;                                                                            \
+            nxti = *reinterpret_cast<const uint32_t*>(gin + (size_t)(orow < 0 ? 0 : (orow > h - 1 ? h - 1 : orow)) * gio.in_stride);   \
+        }                                                                                                           \
+        lvm_issue_fence();                                                                                        \
+        lvm_f2 V[6], W[5];                                                                                          \
+        row12(cur, first, last, V, W);                                                                              \
+        hp_row_taps<P>(V, W, hp);                                                                                   \
+        if (EVEN) {                                                                                                 \
+            lvm_f2 A[3], B[2];                                                                                      \
+            coarse6(curc, first, last, A, B);                                                                       \
+            collapse_lp_taps<P>(A, B, lp);                                                                          \
+        }                                                                                                           \
+        constexpr int E = (P + 1) % 9;                              /* output row o = y0 - 8 + q is complete */     \
+        const bool inside = q >= 8 && q < nq;                                                                       \
+        const uint32_t o = inside ? (uint32_t)(y0 - 8 + q) : 0u;                                                    \
+        const float L0 = lp[E][0][0] + hp[E][0][0], L1 = lp[E][1][0] + hp[E][0][1];   /* RieszPyramid.cpp:322 */    \
+        const float L2 = lp[E][0][1] + hp[E][1][0], L3 = lp[E][1][1] + hp[E][1][1];                                 \
+        collapse_emit_gray<FL, DBG>(L0, L1, L2, L3, curi, s_ab, a.lab, s_igt, (inside && gout) ? gout + (size_t)o * a.out_stride : nullptr, rd, inside ? ldbg : kDrop, o * (uint32_t)w * 12u); \
+        hp[E][0] = hp[E][1] = f2_all(0.f); lp[E][0] = lp[E][1] = f2_all(0.f);                                      \
+        ++q;                                                                                                        \
+        _Pragma("unroll") for (int d = 1; d < 9; ++d) {                                                             \
+            lvm_pin(hp[(E + d) % 9][0], hp[(E + d) % 9][1]);                                                        \
+            lvm_pin(lp[(E + d) % 9][0], lp[(E + d) % 9][1]);                                                        \
+        }                                                                                                           \
+    }
+    for (;;) {
+        LVM_COLLAPSE_STEP(0) LVM_COLLAPSE_STEP(1) LVM_COLLAPSE_STEP(2) LVM_COLLAPSE_STEP(3) LVM_COLLAPSE_STEP(4) LVM_COLLAPSE_STEP(5)
+        LVM_COLLAPSE_STEP(6) LVM_COLLAPSE_STEP(7) LVM_COLLAPSE_STEP(8) LVM_COLLAPSE_STEP(9) LVM_COLLAPSE_STEP(10) LVM_COLLAPSE_STEP(11)
+        LVM_COLLAPSE_STEP(12) LVM_COLLAPSE_STEP(13) LVM_COLLAPSE_STEP(14) LVM_COLLAPSE_STEP(15) LVM_COLLAPSE_STEP(16) LVM_COLLAPSE_STEP(17)
+    }
+#undef LVM_COLLAPSE_STEP
 }
 template <bool FINAL, int FL, bool DBG>
 __global__ __launch_bounds__(CS_THREADS, 3) void k_rz_collapse_strips(CollapseStripArgs a) {
@@ -1565,6 +1799,18 @@ __global__ __launch_bounds__(CS_THREADS, 3) void k_rz_collapse_strips(CollapseSt
     }
 #undef LVM_COLLAPSE_STEP
 }
+// level-0 collapse + output of GRAY frames (lvm_set_phase_on_gray): a.out is the 1-channel output frame, a.iab is not used.
+// (The float-keeping builds hold the twelve floats of a lane's four pixels across the stores on top of the two frame pointers: at three
+// waves per SIMD they spill 20-32 bytes into the loop, at two they do not.  The shipped build, DBG = false, keeps the BGR kernel's bound.)
+template <int FL, bool DBG>
+__global__ __launch_bounds__(CS_THREADS, DBG ? 2 : 3) void k_rz_collapse_strips_gray(CollapseStripArgs a, GrayStripIO gio) {
+    __shared__ __attribute__((aligned(16))) float s_igt[fin_steps(FL, DBG) ? 2 * kU8StepSlices : 4096];
+    __shared__ float s_ab[512];
+    if (fin_steps(FL, DBG)) load_u8steps(reinterpret_cast<uint2*>(s_igt), a.lab.u8steps); else load_invgamma(s_igt, a.lab.invgamma);
+    for (int i = threadIdx.x; i < 512; i += CS_THREADS) s_ab[i] = gio.gtab[256 + i];
+    __syncthreads();
+    collapse_strips_walk_gray<FL, DBG>(a, gio, s_igt, s_ab);
+}
 
 // ------------------------------------------------------------------------------------------
 // host side
@@ -1579,6 +1825,9 @@ struct RieszState : ModeState {
     float* f[kMaxLevels + 1][F_ALL_N] = {};
     // temporal batching: per-frame fields (band, amp, tc, ts, bandA, R1c, R2c), octaves and collapse results of tcap frames
     uint32_t* iab = nullptr; uint32_t* iab_t = nullptr;      // (ia | ib << 16) planes of the input frames (labconv.hip)
+    // gray frames (lvm_set_phase_on_gray): no (ia, ib) planes; L, a, b of the 256 byte values instead (labconv.hip lab_gray_table), refilled on the
+    // launch stream whenever the flavour or the forward table it was filled from has changed
+    bool gray = false; float* gray_tab = nullptr; int tab_flavour = -1; unsigned tab_lut_gen = 0;
     int tcap = 0; float* tarena = nullptr;
     float* ft[kMaxLevels + 1][F_ALL_N] = {}; float* oct_t[kMaxLevels + 1] = {}; float* res_t[kMaxLevels + 1] = {};   // per band level: band,P,R1p,R2p,phc,phs,lo0c,lo0s,lo1c,lo1s,hi0c,hi0s,hi1c,hi1s,amp,tc,ts,bandA
     bool inited = false;
@@ -1608,7 +1857,7 @@ struct RieszState : ModeState {
     }
     ~RieszState() override { if (arena) (void)hipFree(arena); if (tarena) (void)hipFree(tarena); }
     int process(Ctx* c, const lvm_params& p, const FrameIO& io, hipStream_t s, int* produced) override;
-    int batch_frames(const Ctx*, const lvm_params& p, const FrameIO& io, int left) const override { return io.channels >= 3 && steady(p) ? left : 0; }
+    int batch_frames(const Ctx*, const lvm_params& p, const FrameIO& io, int left) const override { return (io.channels >= 3 || gray) && steady(p) ? left : 0; }
     int process_frames(Ctx* c, const lvm_params& p, const FrameIO& io, int nt, hipStream_t s) override;
 };
 enum { F_BAND, F_P, F_R1, F_R2, F_PHC, F_PHS, F_LO0C, F_LO0S, F_LO1C, F_LO1S, F_HI0C, F_HI0S, F_HI1C, F_HI1S, F_AMP, F_TC, F_TS, F_BANDA, F_COUNT,
@@ -1629,7 +1878,8 @@ static int riesz_alloc(Ctx* c, RieszState* st, int w, int h, int levels) {
             for (int k = 0; k < F_COUNT; ++k) st->f[l][k] = a.take(st->g[l].n * NS);
             st->f[l][F_R1C] = st->f[l][F_R1]; st->f[l][F_R2C] = st->f[l][F_R2];
         }
-        st->iab = a.take<uint32_t>(st->g[0].n * NS);
+        if (st->gray) st->gray_tab = a.take(kGrayLabFloats);
+        else st->iab = a.take<uint32_t>(st->g[0].n * NS);
     });
 }
 
@@ -1639,7 +1889,7 @@ static void riesz_coeffs(double frq, double fps, double a[3], double b[3]) {   /
 }
 
 // One buffer set = where the per-frame arrays of nt frames live ([frame][stream] planes).
-struct RzBufs { float** oct; float** res; float* (*pf)[F_ALL_N]; int nt; uint32_t* iab; };
+struct RzBufs { float** oct; float** res; float* (*pf)[F_ALL_N]; int nt; uint32_t* iab; };   // (iab: null for gray frames)
 struct RieszState;
 static bool rz_level_uses_strips(const RieszState* st, int l, int NZ);
 // Rows per strip of a 9x9 strip kernel (k_rz_split_rows, k_rz_collapse_strips).  A strip of r rows runs r + 8 steps rounded up to groups
@@ -1680,6 +1930,13 @@ static void rz_build(Ctx* c, RieszState* st, const FrameIO& io, const RzBufs& B,
     if (c->tile_mode == 2) {
         // spatial tiling, the gathered coarse levels (lvm_tile_riesz_planes): the "frame" IS an octave of another context's pyramid
         (void)hipMemcpyAsync(B.oct[0], c->tile_plane_in, (size_t)w * h * sizeof(float), hipMemcpyDeviceToDevice, s);
+    } else if (st->gray) {
+        // gray frames (lvm_set_phase_on_gray): L through the per-value table, in place of the table kernel / k_rz_lab*
+        if (st->tab_flavour != lab_flavour(c) || st->tab_lut_gen != c->lab_lut_gen) {
+            lab_gray_table(c, st->gray_tab, s);
+            st->tab_flavour = lab_flavour(c); st->tab_lut_gen = c->lab_lut_gen;
+        }
+        lab_gray_plane(c, io.d_in, (long)io.in_stride, (long)io.in_sstride, w, h, NZ, st->gray_tab, B.oct[0], s);
     } else if (fl_lut(lab_flavour(c))) {
         // OpenCV's forward table, once per frame: the float L plane for the pyramid and (ia, ib) for the output kernel
         lab_lut_planes(c, io.d_in, (long)io.in_stride, (long)io.in_sstride, w, h, NZ, nullptr, B.oct[0], B.iab, s);
@@ -1909,7 +2166,38 @@ static void rz_collapse_out(Ctx* c, RieszState* st, const lvm_params& p, const F
     auto kfb = pick(std::true_type{});
     auto kfn = pick(std::false_type{});
     const bool out_ok = io.out_stride % 4 == 0 && io.out_sstride % 4 == 0 && ((uintptr_t)io.d_out % 4) == 0 && (long)io.out_stride * h < (1L << 31);
-    if (kind_l0) {
+    if (st->gray) {
+        // gray frames (lvm_set_phase_on_gray): the same choice among the same three routes, the gray forms of their kernels
+        auto pickg = [&](auto bands) {
+            constexpr bool BN = decltype(bands)::value;
+            auto p3 = [&](auto e, auto v, auto cp) {
+                constexpr int E = decltype(e)::value; constexpr bool V = decltype(v)::value, CP = decltype(cp)::value;
+                return dbg ? k_rz_final_gray<BN, E, V, CP, true> : k_rz_final_gray<BN, E, V, CP, false>;
+            };
+            auto p2 = [&](auto e, auto v) { return (compact && BN) ? p3(e, v, std::true_type{}) : p3(e, v, std::false_type{}); };
+            auto p1 = [&](auto e) { return vec ? p2(e, std::true_type{}) : p2(e, std::false_type{}); };
+            return fl == FL_ANALYTIC ? p1(std::integral_constant<int, FL_ANALYTIC>{})
+                                     : (fl == FL_LUT_EXACT ? p1(std::integral_constant<int, FL_LUT_EXACT>{}) : p1(std::integral_constant<int, FL_LUT_FAST>{}));
+        };
+        const bool bands = nb >= 1 && !kind_l0;
+        if (bands && fl != FL_ANALYTIC && out_ok && vec && strips_ok(st->g[0], st->g[1])) {       // (vec: the strip kernel reads the input frame dword-wide as well)
+            CollapseStripArgs ca{};
+            ca.bandA = B.pf[0][F_BANDA]; ca.resn = resn; ca.res = nullptr;
+            ca.iab = nullptr; ca.out = (uint8_t*)io.d_out; ca.out_stride = (long)io.out_stride; ca.out_sstride = (long)io.out_sstride; ca.dbg = dbg; ca.lab = c->lab;
+            strips_geom(ca, st->g[0], st->g[1]);
+            const GrayStripIO gio{io.d_in, (long)io.in_stride, (long)io.in_sstride, st->gray_tab};
+            auto kf = fl == FL_LUT_EXACT ? (dbg ? k_rz_collapse_strips_gray<FL_LUT_EXACT, true> : k_rz_collapse_strips_gray<FL_LUT_EXACT, false>)
+                                         : (dbg ? k_rz_collapse_strips_gray<FL_LUT_FAST, true> : k_rz_collapse_strips_gray<FL_LUT_FAST, false>);
+            LVM_LAUNCH_V(c, "rz_final", "gray-strips", kf, dim3((unsigned)((ca.ntasks + CS_THREADS / 64 - 1) / (CS_THREADS / 64))), dim3(CS_THREADS), s, ca, gio);
+        } else if (bands)
+            LVM_LAUNCH_V(c, "rz_final", vec ? "gray4" : "gray", pickg(std::true_type{}), grid, blk, s, io.d_in, (long)io.in_stride, (long)io.in_sstride, io.d_out,
+                       (long)io.out_stride, (long)io.out_sstride, w, h, (const float*)B.pf[0][F_BANDA], resn, st->g[1].w, st->g[1].h,
+                       c->lab, tx, ty, NZ, dbg, (const float*)B.oct[0], (const float*)st->gray_tab);
+        else       // no bands, or level 0 collapsed into res_0 by a build kind: L' is that plane
+            LVM_LAUNCH_V(c, "rz_final", vec ? "gray4" : "gray", pickg(std::false_type{}), grid, blk, s, io.d_in, (long)io.in_stride, (long)io.in_sstride, io.d_out,
+                       (long)io.out_stride, (long)io.out_sstride, w, h, (const float*)nullptr, (const float*)nullptr, 0, 0,
+                       c->lab, tx, ty, NZ, dbg, kind_l0 ? resn : (const float*)B.oct[0], (const float*)st->gray_tab);
+    } else if (kind_l0) {
         // L' = res_0 (collapsed above): the band-less last kernel, which reads the plane (analytic flavour: LPLANE)
         auto p2 = [&](auto v) {
             constexpr bool V = decltype(v)::value;
@@ -1957,8 +2245,9 @@ static void riesz_switches(RieszState* st) {
 }
 
 int riesz_create(Ctx* c, int levels, const FrameIO& io, hipStream_t s) {
-    if (io.channels < 3) return LVM_OK;                                          // MagnifyCore.hpp:212: gray frames pass through, nothing is allocated
+    if (io.channels < 3 && !c->phase_on_gray) return LVM_OK;                     // MagnifyCore.hpp:212: gray frames pass through, nothing is allocated
     RieszState* st = new RieszState();
+    st->gray = io.channels < 3;                                                  // lvm_set_phase_on_gray: an extension beyond the reference (include/lvm_hip.h)
     riesz_switches(st);
     c->state = st;
     int rc = riesz_alloc(c, st, io.w, io.h, levels);
@@ -2007,7 +2296,7 @@ int riesz_tile_residual(Ctx* c, float* d_dst, int* rw, int* rh, hipStream_t s) {
 // stage 2 of a stripe context: collapse from `d_residual` (the coarse context's result, rows of this stripe) + Lab2BGR + u8
 int riesz_tile_finish(Ctx* c, const lvm_params& p, const FrameIO& io, const float* d_residual, hipStream_t s) {
     RieszState* st = dynamic_cast<RieszState*>(c->state);
-    if (!st || !st->inited || io.w != st->g[0].w || io.h != st->g[0].h) { c->err = "tiling: stage 2 without a matching stage 1"; return LVM_ERR_INVALID; }
+    if (!st || st->gray || !st->inited || io.w != st->g[0].w || io.h != st->g[0].h) { c->err = "tiling: stage 2 without a matching stage 1"; return LVM_ERR_INVALID; }
     const RzBufs B{st->oct, st->res, st->f, 1, st->iab};
     rz_collapse_out(c, st, p, io, B, s, d_residual, nullptr);
     LVM_HIP_TRY(c, hipGetLastError());
@@ -2038,7 +2327,7 @@ static int riesz_reserve_frames(Ctx* c, RieszState* st, int nt, hipStream_t s) {
                 st->ft[l][k] = a.take(st->g[l].n * NS * nt);
             }
         }
-        st->iab_t = a.take<uint32_t>(st->g[0].n * NS * nt);
+        if (!st->gray) st->iab_t = a.take<uint32_t>(st->g[0].n * NS * nt);
     });
     if (rc != LVM_OK) return rc;
     st->tcap = nt;

@@ -68,6 +68,10 @@ public:
     // application is built for macOS / ARM.  Explicit: nothing here probes the host's OpenCV.
     void setOpenCvBuild(unsigned mask) { mag_.set_opencv_build(mask); }
 
+    // Phase mode with the Grayscale toggle -- an extension beyond the reference, off by default (lvm_set_phase_on_gray; INTEGRATION.md "Phase mode
+    // with the Grayscale toggle"): gray frames are magnified as BGR2GRAY(Riesz(expand(g))) instead of passing through unchanged.
+    void setPhaseOnGray(bool on) { mag_.set_phase_on_gray(on); }
+
 private:
     // Any value that changes iff PreprocessParams changes (operator==, IProcessor.hpp:36-39): FNV-1a
     // over the fields; the default-constructed struct maps to 0.

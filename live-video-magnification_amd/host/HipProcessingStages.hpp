@@ -69,6 +69,11 @@ public:
 
     void reset() override { mag_.reset(); }
 
+    // Phase mode with the Grayscale toggle (PreprocessParams::grayscale) -- an extension beyond the reference, off by default
+    // (lvm_set_phase_on_gray; INTEGRATION.md "Phase mode with the Grayscale toggle"): the gray frames behind GrayscaleProcessor are
+    // magnified as BGR2GRAY(Riesz(expand(g))) instead of passing through unchanged (MagnifyCore.hpp:212).
+    void setPhaseOnGray(bool on) { mag_.set_phase_on_gray(on); }
+
 private:
     struct PinnedFrame : Frame { explicit PinnedFrame(const Frame& f) : Frame(f) {} std::shared_ptr<std::uint8_t> keep; };
     lvm::Magnifier mag_;

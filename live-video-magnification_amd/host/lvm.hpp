@@ -117,6 +117,12 @@ public:
     void set_opencv_build(unsigned mask) { check(lvm_set_opencv_build(ctx_, mask)); }
     unsigned opencv_build() { unsigned m = 0; check(lvm_get_opencv_build(ctx_, &m)); return m; }
 
+    // Phase mode on gray frames -- an extension beyond the reference (whose magnifyRiesz produces nothing for them, MagnifyCore.hpp:212), off by
+    // default: out == BGR2GRAY(Riesz(expand(g))), expand(g) the BGR frame b = g = r = g, BGR2GRAY GrayscaleProcessor's conversion
+    // (include/lvm_hip.h lvm_set_phase_on_gray).  A change under a gray Phase clip restarts it; kept across reset().
+    void set_phase_on_gray(bool on) { check(lvm_set_phase_on_gray(ctx_, on ? 1 : 0)); }
+    bool phase_on_gray() { int v = 0; check(lvm_get_phase_on_gray(ctx_, &v)); return v != 0; }
+
     void synchronize() { check(lvm_synchronize(ctx_)); }
     lvm_ctx* handle() const { return ctx_; }
 
