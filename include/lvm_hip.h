@@ -380,6 +380,46 @@ int  lvm_get_opencv_build(lvm_ctx* ctx, unsigned* mask);
 int  lvm_set_phase_on_gray(lvm_ctx* ctx, int on);
 int  lvm_get_phase_on_gray(lvm_ctx* ctx, int* on);
 
+/* Chain input in RAW CAMERA FORMATS -- an opt-in extension; with LVM_PIX_BGR (the default) every launch, byte, error message and `produced`
+ * flag is what it is without this call.  The reference opens cameras with cv::CAP_V4L2 (source/CameraSource.cpp:36,53), whose backend prefers
+ * the raw formats: every cap_.read() ends in cv::cvtColor(COLOR_YUV2BGR_*) on the grab thread.  With format F != LVM_PIX_BGR the frames given
+ * to the surfaces below are in F and the result is, frame by frame and byte for byte, what the same call gives on
+ * cvtColor(frame, COLOR_YUV2BGR_F) -- the reference chain behind a cv::VideoCapture that converted the frame itself.
+ * Per pixel (OpenCV 4 color_yuv: ITU-R BT.601, limited range, 20-bit fixed point; int32, nothing overflows; `>>` arithmetic: negative
+ * sums floor; sat_u8 clamps to 0..255):
+ *     y = max(0, Y - 16) * 1220542
+ *     R = sat_u8((y + (1 << 19) + 1673527 * (V - 128)) >> 20)
+ *     G = sat_u8((y + (1 << 19) -  852492 * (V - 128) - 409993 * (U - 128)) >> 20)
+ *     B = sat_u8((y + (1 << 19) + 2116026 * (U - 128)) >> 20)
+ * Chroma is replicated, never interpolated: pixels 2k and 2k + 1 of a row share (U, V) in the 4:2:2 formats, a 2 x 2 block shares the pair at
+ * UV row y >> 1, byte pair x >> 1 in NV12 / NV21 -- by ABSOLUTE frame coordinates: an ROI that starts at an odd x or y keeps the chroma of the
+ * pair / block it cuts through.  Order: convert, crop, INTER_AREA, BGR2GRAY -- block sums add converted B, G, R bytes and the gray frame is
+ * gray15(B, G, R) of the converted, decimated pixel, not Y.  The stage is never the identity: crop-only at full size is the plain conversion.
+ * Arguments with F != LVM_PIX_BGR (anything else: LVM_ERR_INVALID with a message that names the rule, refused before any state changes):
+ *   channels   must be 3: it describes the frame the chain sees (also for lvm_preprocess_geometry / lvm_export_geometry, which are unchanged);
+ *   w          must be even; h too for NV12 / NV21 (OpenCV's own preconditions);
+ *   in_stride  >= 2 * w for the packed formats, >= w for NV12 / NV21;
+ *   NV12 / NV21 frames are ONE buffer: the UV plane starts at row h with the same stride (OpenCV's (3h/2) x w single-channel layout, what V4L2
+ *   hands out); a stream stride covers the whole buffer.
+ * Surfaces that take part: lvm_preprocess_device (device frames, all streams), lvm_chain_process / _batch / _batch_ex (the tap / `original` is
+ * the converted colour frame), lvm_chain_present, lvm_export_frames, lvm_export_frames_mjpeg.  Only the ROI's raw bytes cross PCIe: 2 B / pixel
+ * (4:2:2) or 1.5 B / pixel (NV12 / NV21) instead of 3.  Surfaces that do NOT: lvm_process* (IProcessor::process: a processor input is BGR / gray,
+ * core/Frame.hpp:12), lvm_export_mjpeg_frames and lvm_mjpeg_decode_device (JPEG in), lvm_tile_riesz_*.  An FFmpeg-backed VideoCapture converts
+ * with swscale, which is other arithmetic and NOT what this restates (INTEGRATION.md 3b').
+ * The setter only stores the value -- it is read by the next call that takes frames, in call order like everything else of the context: the
+ * magnifier sees BGR / gray frames of the same geometry either way, so its temporal state, the tracked structural key and preprocess_key are
+ * untouched.  lvm_reset keeps the format.  An unknown format: LVM_ERR_INVALID, nothing changes.  lvm_profile_variants reports the kernel that
+ * ran under "preprocess": "yuv4" (four pixels per thread, dword-wide frame I/O: crop-only, colour out, dword-aligned pointers and strides, an
+ * ROI that starts at an even x, a width that is a multiple of 4) or "yuv" (byte I/O, everything else); both give identical bytes.       */
+enum lvm_pixel_format { LVM_PIX_BGR = 0,      /* BGR8 or Gray8 by `channels`: today's behaviour */
+                        LVM_PIX_YUYV = 1,     /* Y0 U Y1 V   (V4L2 YUYV / YUY2) */
+                        LVM_PIX_UYVY = 2,     /* U Y0 V Y1 */
+                        LVM_PIX_YVYU = 3,     /* Y0 V Y1 U */
+                        LVM_PIX_NV12 = 4,     /* h rows of Y, then h/2 rows of interleaved U V, same row stride */
+                        LVM_PIX_NV21 = 5 };   /* ... of interleaved V U */
+int  lvm_set_source_format(lvm_ctx* ctx, int fmt);
+int  lvm_get_source_format(lvm_ctx* ctx, int* fmt);
+
 /* Cross-frame software pipeline for lvm_process_device (throughput mode, default depth 0).
  * depth 1 (implemented for the Laplace mode; other modes ignore it): a call enqueues the
  * down-sweep of ITS frame on an internal second stream concurrently with the up-sweep + output of

@@ -73,6 +73,7 @@ LAB_LUT_ENTRIES = 33 * 33 * 33 * 3
 MJPEG_DECODER_REPLICATE, MJPEG_DECODER_LIBJPEG = 0, 1      # lvm_mjpeg_set_decoder (include/lvm_hip.h)
 MJPEG_SAMPLING_420, MJPEG_SAMPLING_422, MJPEG_SAMPLING_444, MJPEG_SAMPLING_GRAY, MJPEG_SAMPLING_ALL = 1, 2, 4, 8, 15      # lvm_mjpeg_set_samplings
 CV_FILTER_UNFUSED, CV_FILTER_DFT, CV_MUL_F32, CV_ALL = 1, 2, 4, 7      # lvm_set_opencv_build
+PIX_BGR, PIX_YUYV, PIX_UYVY, PIX_YVYU, PIX_NV12, PIX_NV21 = 0, 1, 2, 3, 4, 5      # lvm_set_source_format (enum lvm_pixel_format)
 
 
 class LvmParams(C.Structure):
@@ -110,7 +111,8 @@ SYMBOLS = ["lvm_create", "lvm_destroy", "lvm_reset", "lvm_process", "lvm_process
            "lvm_preprocess_geometry", "lvm_preprocess_device", "lvm_chain_process", "lvm_chain_process_batch",
            "lvm_set_max_frames", "lvm_host_alloc", "lvm_host_free", "lvm_compose_geometry", "lvm_compose_device", "lvm_chain_process_batch_ex",
            "lvm_chain_present", "lvm_mjpeg_bound", "lvm_mjpeg_encode_device", "lvm_export_frames_mjpeg", "lvm_mjpeg_decode_device", "lvm_export_mjpeg_frames", "lvm_mjpeg_set_restart_interval", "lvm_mjpeg_set_decoder", "lvm_mjpeg_set_samplings",
-           "lvm_set_opencv_build", "lvm_get_opencv_build", "lvm_set_phase_on_gray", "lvm_get_phase_on_gray"]
+           "lvm_set_opencv_build", "lvm_get_opencv_build", "lvm_set_phase_on_gray", "lvm_get_phase_on_gray",
+           "lvm_set_source_format", "lvm_get_source_format"]
 
 
 def bind(lib):
@@ -178,6 +180,8 @@ def bind(lib):
     lib.lvm_get_opencv_build.argtypes = [vp, C.POINTER(C.c_uint)]
     lib.lvm_set_phase_on_gray.argtypes = [vp, C.c_int]
     lib.lvm_get_phase_on_gray.argtypes = [vp, ip]
+    lib.lvm_set_source_format.argtypes = [vp, C.c_int]
+    lib.lvm_get_source_format.argtypes = [vp, ip]
     lib.lvm_mjpeg_decode_device.argtypes = [vp, vp, C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_int, vp, C.c_ssize_t, C.c_ssize_t]
     lib.lvm_export_mjpeg_frames.argtypes = [vp, C.POINTER(LvmPreprocessParams), C.POINTER(LvmParams), C.c_int, C.c_int, vp, C.POINTER(C.c_size_t), C.c_int, C.c_int,
                                             C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t), ip]
@@ -247,6 +251,20 @@ class Context:
     def reset(self):
         self._check(self.lib.lvm_reset(self.h))
 
+    def _frame_dims(self, f):
+        """(w, h, channels, row bytes) of a host frame: HxWx3 / HxW arrays as BGR / gray frames; under a raw source format
+        (set_source_format) 2-D uint8 arrays of (h, 2w) bytes (YUYV / UYVY / YVYU) or (3h/2, w) bytes (NV12 / NV21), channels = 3."""
+        fmt = self.source_format()
+        if fmt == PIX_BGR:
+            return f.shape[1], f.shape[0], (1 if f.ndim == 2 else f.shape[2]), f.shape[1] * (1 if f.ndim == 2 else f.shape[2])
+        if f.ndim != 2:
+            raise LvmError("a raw frame is a 2-D uint8 array: (h, 2w) for the packed formats, (3h/2, w) for NV12 / NV21")
+        if fmt in (PIX_NV12, PIX_NV21):
+            if f.shape[0] % 3:
+                raise LvmError("an NV12 / NV21 frame has 3h/2 rows")
+            return f.shape[1], f.shape[0] // 3 * 2, 3, f.shape[1]
+        return f.shape[1] // 2, f.shape[0], 3, f.shape[1]
+
     def preprocess_geometry(self, cpre, w, h, ch):
         """(roi_x, roi_y, roi_w, roi_h, out_w, out_h, out_channels) of the two stages in front of the magnifier."""
         v = [C.c_int() for _ in range(7)]
@@ -264,14 +282,13 @@ class Context:
         frames = [np.ascontiguousarray(f, dtype=np.uint8) for f in frames]
         if len(frames) != self.n_streams:
             raise LvmError("chain_process_batch needs one frame per stream")
-        h, w = frames[0].shape[:2]
-        ch = 1 if frames[0].ndim == 2 else frames[0].shape[2]
+        w, h, ch, row = self._frame_dims(frames[0])
         _, _, _, _, ow, oh, och = self.preprocess_geometry(cpre, w, h, ch)
         outs = [np.empty((oh, ow) if och == 1 else (oh, ow, och), dtype=np.uint8) for _ in frames]
         pin = (C.c_void_p * len(frames))(*[f.ctypes.data for f in frames])
         pout = (C.c_void_p * len(frames))(*[o.ctypes.data for o in outs])
         produced = C.c_int(0)
-        self._check(self.lib.lvm_chain_process_batch(self.h, C.byref(cpre), C.byref(cparams), pin, w, h, ch, w * ch, pout, ow * och,
+        self._check(self.lib.lvm_chain_process_batch(self.h, C.byref(cpre), C.byref(cparams), pin, w, h, ch, row, pout, ow * och,
                                                      C.byref(produced)))
         return outs, bool(produced.value)
 
@@ -281,8 +298,7 @@ class Context:
         frames = [np.ascontiguousarray(f, dtype=np.uint8) for f in frames]
         if len(frames) != self.n_streams:
             raise LvmError("chain_process_batch_ex needs one frame per stream")
-        h, w = frames[0].shape[:2]
-        ch = 1 if frames[0].ndim == 2 else frames[0].shape[2]
+        w, h, ch, row = self._frame_dims(frames[0])
         _, _, _, _, ow, oh, och = self.preprocess_geometry(cpre, w, h, ch)
         outs = [np.empty((oh, ow) if och == 1 else (oh, ow, och), dtype=np.uint8) for _ in frames]
         taps = [np.empty((oh, ow) if ch == 1 else (oh, ow, ch), dtype=np.uint8) for _ in frames]
@@ -290,17 +306,16 @@ class Context:
         pout = (C.c_void_p * len(frames))(*[o.ctypes.data for o in outs])
         ptap = (C.c_void_p * len(frames))(*[o.ctypes.data for o in taps])
         produced = C.c_int(0)
-        self._check(self.lib.lvm_chain_process_batch_ex(self.h, C.byref(cpre), C.byref(cparams), pin, w, h, ch, w * ch, pout, ow * och,
+        self._check(self.lib.lvm_chain_process_batch_ex(self.h, C.byref(cpre), C.byref(cparams), pin, w, h, ch, row, pout, ow * och,
                                                         ptap, ow * ch, C.byref(produced)))
         return outs, taps, bool(produced.value)
 
     def chain_present(self, frame, cpre, cparams, d_proc, proc_stride, d_orig, orig_stride):
         """lvm_chain_present: host frame in, processed frame and `original` tap left in DEVICE buffers (addresses).  Returns produced."""
         frame = np.ascontiguousarray(frame, dtype=np.uint8)
-        h, w = frame.shape[:2]
-        ch = 1 if frame.ndim == 2 else frame.shape[2]
+        w, h, ch, row = self._frame_dims(frame)
         produced = C.c_int(0)
-        self._check(self.lib.lvm_chain_present(self.h, C.byref(cpre), C.byref(cparams), frame.ctypes.data, w, h, ch, w * ch,
+        self._check(self.lib.lvm_chain_present(self.h, C.byref(cpre), C.byref(cparams), frame.ctypes.data, w, h, ch, row,
                                                d_proc, proc_stride, d_orig, orig_stride, C.byref(produced)))
         return bool(produced.value)
 
@@ -332,8 +347,7 @@ class Context:
         """lvm_export_frames: Exporter::run's loop body (runChainOnce + Exporter::compose) for consecutive host frames of a 1-stream
         context.  Returns (canvases, produced flags)."""
         frames = [np.ascontiguousarray(f, dtype=np.uint8) for f in frames]
-        h, w = frames[0].shape[:2]
-        ch = 1 if frames[0].ndim == 2 else frames[0].shape[2]
+        w, h, ch, row = self._frame_dims(frames[0])
         cw, chh = C.c_int(0), C.c_int(0)
         self._check(self.lib.lvm_export_geometry(C.byref(cpre), int(split), w, h, ch, C.byref(cw), C.byref(chh)))
         if cw.value <= 0 or chh.value <= 0:
@@ -342,7 +356,7 @@ class Context:
         pin = (C.c_void_p * len(frames))(*[f.ctypes.data for f in frames])
         pout = (C.c_void_p * len(frames))(*[o.ctypes.data for o in canvases])
         produced = (C.c_int * len(frames))()
-        self._check(self.lib.lvm_export_frames(self.h, C.byref(cpre), C.byref(cparams), int(split), len(frames), pin, w, h, ch, w * ch,
+        self._check(self.lib.lvm_export_frames(self.h, C.byref(cpre), C.byref(cparams), int(split), len(frames), pin, w, h, ch, row,
                                                pout, cw.value * 3, produced))
         return canvases, [bool(x) for x in produced]
 
@@ -413,6 +427,20 @@ class Context:
         self._check(self.lib.lvm_get_phase_on_gray(self.h, C.byref(v)))
         return bool(v.value)
 
+    def set_source_format(self, fmt):
+        """lvm_set_source_format: what the frames given to chain_process*, chain_present, export_frames, export_frames_mjpeg and
+        preprocess_device hold from the next call on: PIX_BGR (the default: BGR / gray frames) or a raw camera format, PIX_YUYV / PIX_UYVY /
+        PIX_YVYU ((h, 2w) uint8 arrays) / PIX_NV12 / PIX_NV21 ((3h/2, w) uint8 arrays), converted on the device with OpenCV's fixed-point BT.601
+        arithmetic (cvtColor(COLOR_YUV2BGR_*)) in the kernel that crops and decimates.  The temporal state is kept; reset() keeps the format.
+        process() and the JPEG surfaces do not take part.  An unknown format: LvmError, nothing changes."""
+        self._check(self.lib.lvm_set_source_format(self.h, int(fmt)))
+
+    def source_format(self):
+        """lvm_get_source_format: the format set_source_format installed (PIX_BGR by default)."""
+        v = C.c_int(0)
+        self._check(self.lib.lvm_get_source_format(self.h, C.byref(v)))
+        return int(v.value)
+
     def mjpeg_decode_device(self, jpegs, w, h, d_ptr, stride=None, frame_stride=None):
         """lvm_mjpeg_decode_device: a list of JPEG frames (bytes) -> BGR frames in device memory at d_ptr."""
         stride = w * 3 if stride is None else stride
@@ -441,8 +469,7 @@ class Context:
     def export_frames_mjpeg(self, frames, cpre, cparams, split, quality=75, capacity=None):
         """lvm_export_frames_mjpeg: Exporter::run's loop body with the canvases encoded on the device.  Returns (JPEG frames, produced flags)."""
         frames = [np.ascontiguousarray(f, dtype=np.uint8) for f in frames]
-        h, w = frames[0].shape[:2]
-        ch = 1 if frames[0].ndim == 2 else frames[0].shape[2]
+        w, h, ch, row = self._frame_dims(frames[0])
         cw, chh = C.c_int(0), C.c_int(0)
         self._check(self.lib.lvm_export_geometry(C.byref(cpre), int(split), w, h, ch, C.byref(cw), C.byref(chh)))
         if cw.value <= 0 or chh.value <= 0:
@@ -453,7 +480,7 @@ class Context:
         offs = (C.c_size_t * (n + 1))()
         pin = (C.c_void_p * n)(*[f.ctypes.data for f in frames])
         produced = (C.c_int * n)()
-        self._check(self.lib.lvm_export_frames_mjpeg(self.h, C.byref(cpre), C.byref(cparams), int(split), n, pin, w, h, ch, w * ch, int(quality),
+        self._check(self.lib.lvm_export_frames_mjpeg(self.h, C.byref(cpre), C.byref(cparams), int(split), n, pin, w, h, ch, row, int(quality),
                                                      out.ctypes.data, cap, offs, produced))
         return [out[offs[i]:offs[i + 1]].tobytes() for i in range(n)], [bool(x) for x in produced]
 
@@ -461,12 +488,11 @@ class Context:
         """Preprocess -> Grayscale -> Magnification on a host frame (lvm_chain_process).  Returns (out, produced);
         `out` is the magnified frame, or the preprocessed frame on passthrough."""
         frame = np.ascontiguousarray(frame, dtype=np.uint8)
-        h, w = frame.shape[:2]
-        ch = 1 if frame.ndim == 2 else frame.shape[2]
+        w, h, ch, row = self._frame_dims(frame)
         _, _, _, _, ow, oh, och = self.preprocess_geometry(cpre, w, h, ch)
         out = np.empty((oh, ow) if och == 1 else (oh, ow, och), dtype=np.uint8)
         produced = C.c_int(0)
-        self._check(self.lib.lvm_chain_process(self.h, C.byref(cpre), C.byref(cparams), frame.ctypes.data, w, h, ch, w * ch,
+        self._check(self.lib.lvm_chain_process(self.h, C.byref(cpre), C.byref(cparams), frame.ctypes.data, w, h, ch, row,
                                                out.ctypes.data, ow * och, C.byref(produced)))
         return out, bool(produced.value)
 
@@ -595,7 +621,7 @@ class Context:
         return out
 
     def profile_variants(self):
-        """{report name: set of kernel variants launched under it ("strips" / "vec4" / "bytes"; under set_opencv_build the kind: "unfused" / "f64" /
+        """{report name: set of kernel variants launched under it ("strips" / "vec4" / "bytes"; "yuv4" / "yuv" under a raw source format; under set_opencv_build the kind: "unfused" / "f64" /
         "mulf32" / "unfused+mulf32")} for the names several kernels share"""
         n = self.lib.lvm_profile_collect(self.h)
         out = {}

@@ -176,6 +176,17 @@ static const char* layout_error(const FrameIO& io, int nstreams) {
     return nullptr;
 }
 
+// Frames in a raw camera format (lvm_set_source_format): the rules of include/lvm_hip.h, checked before any state changes.  Null: fine.
+static const char* raw_frame_error(int fmt, int w, int h, int channels, ptrdiff_t in_stride) {
+    const bool nv = fmt == LVM_PIX_NV12 || fmt == LVM_PIX_NV21;
+    if (channels != 3) return "raw source format: channels must be 3 (it describes the frame the chain sees)";
+    if (w <= 0 || h <= 0) return "bad frame arguments";
+    if (w % 2) return "raw source format: w must be even";
+    if (nv && h % 2) return "raw source format: h must be even for NV12 / NV21";
+    if (in_stride < (ptrdiff_t)w * (nv ? 1 : 2)) return nv ? "raw source format: in_stride must be >= w for NV12 / NV21" : "raw source format: in_stride must be >= 2 * w for the packed formats";
+    return nullptr;
+}
+
 // MagnificationProcessor::process (MagnificationProcessor.cpp:17-67) on device buffers
 static int process_device(Ctx* c, const lvm_params* p, const FrameIO& io, hipStream_t s, int* produced) {
     *produced = 0;
@@ -383,11 +394,18 @@ int lvm_preprocess_device(lvm_ctx* c, const lvm_preprocess_params* pp, const uin
                           ptrdiff_t in_stride, ptrdiff_t in_stream_stride, uint8_t* d_out, ptrdiff_t out_stride,
                           ptrdiff_t out_stream_stride, void* hip_stream) {
     if (!c || !pp) return LVM_ERR_INVALID;
+    const int fmt = c->source_format;
+    if (fmt != LVM_PIX_BGR) {
+        if (const char* why = lvm::raw_frame_error(fmt, w, h, channels, in_stride)) { c->err = why; return LVM_ERR_INVALID; }
+    }
+    // the whole raw frame is on the device: its pixel (0, 0) starts a chroma pair / block, the UV plane starts at row h (NV12 / NV21)
+    const lvm::RawSource raw{fmt, 0, 0, (ptrdiff_t)h * in_stride};
     LVM_HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
     int rc = lvm::order_after_previous(c, s);          // (the area tables are the context's: preprocess.hip replaces them behind a wait for `s` alone)
     if (rc != LVM_OK) return rc;
-    rc = lvm::preprocess_device(c, *pp, d_in, w, h, channels, in_stride, in_stream_stride, d_out, out_stride, out_stream_stride, s);
+    rc = lvm::preprocess_device(c, *pp, d_in, w, h, channels, in_stride, in_stream_stride, d_out, out_stride, out_stream_stride, s, nullptr, 0, 0,
+                                fmt != LVM_PIX_BGR ? &raw : nullptr);
     lvm::mark_enqueued(c, s);
     return rc;
 }
@@ -502,6 +520,10 @@ static uint64_t preprocess_key_of(const lvm_preprocess_params& pp) {
 struct ChainGeom {
     int channels, rx, ry, rw, rh, ow, oh, och;
     size_t roi_row, roi_bytes;      // the cropped source frame
+    // raw source formats: the staged frame is the ROI widened to whole chroma pairs -- pixel columns [rx & ~1, (rx + rw - 1) | 1] of the ROI's
+    // rows (2 bytes each: packed formats), or that many Y bytes per ROI row followed by the UV rows (ry >> 1) .. ((ry + rh - 1) >> 1) (NV12 / NV21)
+    int fmt, h, uv_rows;
+    lvm::RawSource raw;             // what the kernel needs to know about it: the parities of the ROI's origin, where the UV rows start
     size_t out_row, out_bytes;      // the frame the magnifier sees and the one it writes
     bool identity;                  // nothing to do in front of the magnifier (PreprocessProcessor.cpp:15, GrayscaleProcessor.cpp:8-9)
     // runChainOnce's `original` is chain[0]'s output (ChainBuilder.cpp:25: the tap sits BEFORE GrayscaleProcessor): with grayscale on
@@ -509,19 +531,34 @@ struct ChainGeom {
     bool gray;
     size_t tap_row, tap_bytes;      // a frame of the tap: 3 channels with `gray`, the magnifier's input frame otherwise
 };
-static ChainGeom chain_geometry(const lvm_preprocess_params& pp, int w, int h, int channels) {
+static ChainGeom chain_geometry(const lvm_preprocess_params& pp, int w, int h, int channels, int fmt = LVM_PIX_BGR) {
     ChainGeom g{};
-    g.channels = channels;
+    g.channels = channels; g.fmt = fmt; g.h = h;
     lvm::preprocess_geometry(pp, w, h, channels, &g.rx, &g.ry, &g.rw, &g.rh, &g.ow, &g.oh, &g.och);
     g.roi_row = (size_t)g.rw * channels; g.roi_bytes = g.roi_row * g.rh;
     g.out_row = (size_t)g.ow * g.och; g.out_bytes = g.out_row * g.oh;
     g.identity = g.ow == g.rw && g.oh == g.rh && g.och == channels;
     g.gray = g.och == 1 && channels == 3;
     g.tap_row = g.gray ? (size_t)g.ow * 3 : g.out_row; g.tap_bytes = g.tap_row * g.oh;
+    if (fmt != LVM_PIX_BGR) {
+        const size_t cols = (size_t)(((g.rx + g.rw - 1) | 1) + 1 - (g.rx & ~1));
+        const bool nv = fmt == LVM_PIX_NV12 || fmt == LVM_PIX_NV21;
+        g.uv_rows = nv ? ((g.ry + g.rh - 1) >> 1) - (g.ry >> 1) + 1 : 0;
+        g.roi_row = nv ? cols : cols * 2; g.roi_bytes = g.roi_row * ((size_t)g.rh + g.uv_rows);
+        g.raw = lvm::RawSource{fmt, g.rx & 1, nv ? (g.ry & 1) : 0, (ptrdiff_t)(g.roi_row * g.rh)};
+        g.identity = false;         // crop-only at full size is the plain conversion: it writes the BGR frame the magnifier reads
+    }
     return g;
 }
 // only the ROI rows cross PCIe (the crop is the pitch of the 2-D copy)
 static hipError_t chain_upload(const ChainGeom& g, uint8_t* d_dst, const uint8_t* frame, ptrdiff_t in_stride, hipStream_t s) {
+    if (g.fmt != LVM_PIX_BGR) {     // the ROI's raw bytes: whole chroma pairs; NV12 / NV21: two 2-D copies
+        const size_t x0 = (size_t)(g.rx & ~1) * (g.uv_rows ? 1 : 2);
+        const hipError_t e = hipMemcpy2DAsync(d_dst, g.roi_row, frame + (size_t)g.ry * in_stride + x0, (size_t)in_stride, g.roi_row, (size_t)g.rh, hipMemcpyHostToDevice, s);
+        if (e != hipSuccess || !g.uv_rows) return e;
+        return hipMemcpy2DAsync(d_dst + g.raw.uv_offset, g.roi_row, frame + ((size_t)g.h + (size_t)(g.ry >> 1)) * in_stride + x0, (size_t)in_stride, g.roi_row,
+                                (size_t)g.uv_rows, hipMemcpyHostToDevice, s);
+    }
     return hipMemcpy2DAsync(d_dst, g.roi_row, frame + (size_t)g.ry * in_stride + (size_t)g.rx * g.channels, (size_t)in_stride, g.roi_row, (size_t)g.rh,
                             hipMemcpyHostToDevice, s);
 }
@@ -531,7 +568,7 @@ static int chain_preprocess(Ctx* c, const lvm_preprocess_params& pp, const Chain
     lvm_preprocess_params q = pp;
     q.roi_enabled = 0;
     return lvm::preprocess_device(c, q, d_src, g.rw, g.rh, g.channels, (ptrdiff_t)src_row, (ptrdiff_t)src_fbytes, d_dst, (ptrdiff_t)g.out_row, (ptrdiff_t)g.out_bytes, s,
-                                  d_tap, tap_stride, tap_sstride);
+                                  d_tap, tap_stride, tap_sstride, g.fmt != LVM_PIX_BGR ? &g.raw : nullptr);
 }
 static lvm_params chain_params(const lvm_params& p, const lvm_preprocess_params& pp) {
     lvm_params mp = p;
@@ -550,12 +587,15 @@ int lvm_chain_process_batch_ex(lvm_ctx* c, const lvm_preprocess_params* pp, cons
     if (!c || !pp || !p || !produced || !in || !out) return LVM_ERR_INVALID;
     *produced = 0;
     const int NS = c->nstreams;
-    if (w <= 0 || h <= 0 || (channels != 1 && channels != 3) || in_stride < (ptrdiff_t)w * channels) {
+    const int fmt = c->source_format;
+    if (fmt != LVM_PIX_BGR) {
+        if (const char* why = lvm::raw_frame_error(fmt, w, h, channels, in_stride)) { c->err = why; return LVM_ERR_INVALID; }
+    } else if (w <= 0 || h <= 0 || (channels != 1 && channels != 3) || in_stride < (ptrdiff_t)w * channels) {
         c->err = "bad frame arguments"; return LVM_ERR_INVALID;
     }
     for (int s = 0; s < NS; ++s) if (!in[s] || !out[s]) { c->err = "null frame pointer"; return LVM_ERR_INVALID; }
     LVM_HIP_TRY(c, hipSetDevice(c->device));
-    const ChainGeom g = chain_geometry(*pp, w, h, channels);
+    const ChainGeom g = chain_geometry(*pp, w, h, channels, fmt);
     if (out_stride < (ptrdiff_t)g.out_row) { c->err = "output stride too small"; return LVM_ERR_INVALID; }
     hipStream_t s = c->own_stream;
     { const int orc = lvm::order_after_previous(c, s); if (orc != LVM_OK) return orc; }
@@ -599,9 +639,12 @@ int lvm_chain_present(lvm_ctx* c, const lvm_preprocess_params* pp, const lvm_par
     if (!c || !pp || !p || !produced || !in) return LVM_ERR_INVALID;
     *produced = 0;
     if (c->nstreams != 1) { c->err = "lvm_chain_present needs a 1-stream context"; return LVM_ERR_INVALID; }
-    if (w <= 0 || h <= 0 || (channels != 1 && channels != 3) || in_stride < (ptrdiff_t)w * channels) { c->err = "bad frame arguments"; return LVM_ERR_INVALID; }
+    const int fmt = c->source_format;
+    if (fmt != LVM_PIX_BGR) {
+        if (const char* why = lvm::raw_frame_error(fmt, w, h, channels, in_stride)) { c->err = why; return LVM_ERR_INVALID; }
+    } else if (w <= 0 || h <= 0 || (channels != 1 && channels != 3) || in_stride < (ptrdiff_t)w * channels) { c->err = "bad frame arguments"; return LVM_ERR_INVALID; }
     LVM_HIP_TRY(c, hipSetDevice(c->device));
-    const ChainGeom g = chain_geometry(*pp, w, h, channels);
+    const ChainGeom g = chain_geometry(*pp, w, h, channels, fmt);
     if (d_proc && proc_stride < (ptrdiff_t)g.out_row) { c->err = "proc stride too small"; return LVM_ERR_INVALID; }
     if (d_orig && orig_stride < (ptrdiff_t)g.tap_row) { c->err = "orig stride too small"; return LVM_ERR_INVALID; }      // (the tap keeps the source's channel count)
     hipStream_t s = c->own_stream;
@@ -663,10 +706,13 @@ static int export_frames_impl(lvm_ctx* c, const lvm_preprocess_params* pp, const
     if (js && (!js->bytes || !js->offsets || channels != 3)) return LVM_ERR_INVALID;
     if (js) in_stride = (ptrdiff_t)w * 3;
     if (c->nstreams != 1) { c->err = "lvm_export_frames needs a 1-stream context"; return LVM_ERR_INVALID; }
-    if (w <= 0 || h <= 0 || (channels != 1 && channels != 3) || in_stride < (ptrdiff_t)w * channels) { c->err = "bad frame arguments"; return LVM_ERR_INVALID; }
+    const int fmt = js ? LVM_PIX_BGR : c->source_format;        // (JPEG frames decode to BGR: lvm_export_mjpeg_frames does not take part)
+    if (fmt != LVM_PIX_BGR) {
+        if (const char* why = lvm::raw_frame_error(fmt, w, h, channels, in_stride)) { c->err = why; return LVM_ERR_INVALID; }
+    } else if (w <= 0 || h <= 0 || (channels != 1 && channels != 3) || in_stride < (ptrdiff_t)w * channels) { c->err = "bad frame arguments"; return LVM_ERR_INVALID; }
     for (int k = 0; k < n_frames; ++k) { produced[k] = 0; if ((!js && !frames[k]) || (!mj && !canvases[k])) { c->err = "null frame pointer"; return LVM_ERR_INVALID; } }
     LVM_HIP_TRY(c, hipSetDevice(c->device));
-    const ChainGeom g = chain_geometry(*pp, w, h, channels);
+    const ChainGeom g = chain_geometry(*pp, w, h, channels, fmt);
     int pw, ph, cw, chh;
     if (split < LVM_SPLIT_NONE || split > LVM_SPLIT_TOP_BOTTOM) { c->err = "invalid split mode"; return LVM_ERR_INVALID; }
     if (!lvm::compose_geometry(split, g.ow, g.oh, g.ow, g.oh, &pw, &ph, &cw, &chh) || cw <= 0 || chh <= 0) {
@@ -869,6 +915,23 @@ int lvm_set_phase_on_gray(lvm_ctx* c, int on) {
 int lvm_get_phase_on_gray(lvm_ctx* c, int* on) {
     if (!c || !on) return LVM_ERR_INVALID;
     *on = c->phase_on_gray ? 1 : 0;
+    return LVM_OK;
+}
+
+// Raw camera formats in front of the chain, an extension beyond the reference (include/lvm_hip.h).  Only stored: the surfaces that take frames read
+// it when they are called, and the magnifier sees the same BGR / gray frames either way.  Kept by lvm_reset.
+int lvm_set_source_format(lvm_ctx* c, int fmt) {
+    if (!c) return LVM_ERR_INVALID;
+    if (fmt < LVM_PIX_BGR || fmt > LVM_PIX_NV21) {
+        c->err = "lvm_set_source_format: the format must be LVM_PIX_BGR (0), _YUYV (1), _UYVY (2), _YVYU (3), _NV12 (4) or _NV21 (5)";
+        return LVM_ERR_INVALID;
+    }
+    c->source_format = fmt;
+    return LVM_OK;
+}
+int lvm_get_source_format(lvm_ctx* c, int* fmt) {
+    if (!c || !fmt) return LVM_ERR_INVALID;
+    *fmt = c->source_format;
     return LVM_OK;
 }
 

@@ -545,7 +545,8 @@ struct Ctx {
     unsigned mjpeg_samplings = LVM_MJPEG_SAMPLING_420;  // lvm_mjpeg_set_samplings: the samplings the decoder accepts
     unsigned opencv_build = 0;        // lvm_set_opencv_build: which OpenCV build the Riesz arithmetic reproduces (a mask of LVM_CV_*; riesz.hip)
     bool phase_on_gray = false;       // lvm_set_phase_on_gray: LVM_MODE_PHASE magnifies 1-channel frames (an extension; off = MagnifyCore.hpp:212)
-    unsigned lab_lut_gen = 0;         // counts lvm_set_lab_lut calls: the per-value Lab table of a gray Riesz state (riesz.hip) follows the forward table
+    int source_format = LVM_PIX_BGR;  // lvm_set_source_format: what the frames given to the chain / export / preprocess surfaces hold (preprocess.hip converts)
+    unsigned lab_lut_gen = 0;        // counts lvm_set_lab_lut calls: the per-value Lab table of a gray Riesz state (riesz.hip) follows the forward table
 };
 
 inline int lab_flavour(const Ctx* c) { return c->lab_analytic ? FL_ANALYTIC : (c->exact_lab ? FL_LUT_EXACT : FL_LUT_FAST); }
@@ -667,7 +668,11 @@ void preprocess_geometry(const lvm_preprocess_params& pp, int w, int h, int chan
                          int* ow, int* oh, int* och);
 int preprocess_device(Ctx* c, const lvm_preprocess_params& pp, const uint8_t* d_in, int w, int h, int channels, ptrdiff_t in_stride,
                       ptrdiff_t in_sstride, uint8_t* d_out, ptrdiff_t out_stride, ptrdiff_t out_sstride, hipStream_t s,
-                      uint8_t* d_tap = nullptr, ptrdiff_t tap_stride = 0, ptrdiff_t tap_sstride = 0);
+                      uint8_t* d_tap = nullptr, ptrdiff_t tap_stride = 0, ptrdiff_t tap_sstride = 0, const struct RawSource* raw = nullptr);
+// A frame in a raw camera format (lvm_set_source_format): d_in points at a buffer that holds the w x h frame -- or, behind the chain's
+// upload, the part of it that covers the ROI -- whose pixel (0, 0) sits at (px, py) in {0, 1}^2 of the chroma pair / 2x2 block it belongs
+// to; uv_offset = bytes from d_in to the UV row of pixel row 0 (NV12 / NV21).  Without one, preprocess_device reads BGR / gray frames.
+struct RawSource { int fmt; int px, py; ptrdiff_t uv_offset; };
 void preprocess_release(Ctx* c);
 
 // compose.hip

@@ -11,6 +11,10 @@
 //   * gray: 15-bit fixed point (b*3735 + g*19235 + r*9798 + 2^14) >> 15, applied to the decimated bytes
 //     exactly as the reference's stage order does.
 // Byte/integer work: results are bit-exact against the oracle (tests/test_preprocess_*.py).
+//
+// Opt-in (lvm_set_source_format): the source frame in a raw camera format -- YUYV, UYVY, YVYU, NV12, NV21 -- converted by the same launch with the
+// arithmetic of cv::cvtColor(COLOR_YUV2BGR_*), i.e. the reference chain behind a cv::VideoCapture that converted the frame itself: the fetch of a
+// source pixel becomes "load the raw bytes, convert", everything behind it is the code of the BGR kernels (tests/test_yuv_source.py).
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -33,28 +37,27 @@ struct PreArgs {
 
 // (gray15: lvm_internal.h -- the gray Phase output kernels of riesz.hip apply the same weighting)
 
-// MODE 0 = crop only, 1 = integer decimation, 2 = fractional area tables.  One thread per output pixel;
-// blockIdx.z = stream.
-template <int MODE, int CN>
-__global__ __launch_bounds__(256) void k_preprocess(PreArgs a) {
-    const int dx = blockIdx.x * 64 + (threadIdx.x & 63), dy = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (dx >= a.ow || dy >= a.oh) return;
-    const uint8_t* src = a.in + (size_t)blockIdx.z * a.in_sstride;
-    uint8_t* q = a.out + (size_t)blockIdx.z * a.out_sstride + (size_t)dy * a.out_stride + (size_t)dx * a.ocn;
-    int v[CN];
+// The arithmetic of one output pixel, shared by every kernel of this file: `fetch.at(x, y)` is a cursor at source pixel (x, y) of the ROI and
+// `cursor(i, v)` delivers the CN bytes of the pixel i columns to its right -- a load for BGR / gray frames, a load + conversion for the raw
+// camera formats below -- and everything behind it (block sums, (sum + 2) >> 2, saturate_cast<uchar>(sum * (1.f / area)), the fractional AreaTab
+// sums in table order) is the same code for all of them.  The byte cursor spells the address arithmetic the BGR kernels always had (row pointer,
+// 64-bit column offset), and they form their output pointer before the loads: their instruction streams stay those of the kernels without it.
+// MODE 0 = crop only, 1 = integer decimation, 2 = fractional area tables.
+template <int MODE, int CN, class Fetch>
+__device__ __forceinline__ void pre_pixel(const PreArgs& a, const Fetch& fetch, int dx, int dy, int (&v)[CN]) {
     if (MODE == 0) {
-        const uint8_t* p = src + (size_t)dy * a.in_stride + (size_t)dx * CN;
-#pragma unroll
-        for (int c = 0; c < CN; ++c) v[c] = p[c];
+        fetch.at(dx, dy)(0, v);
     } else if (MODE == 1) {
         int sum[CN];
 #pragma unroll
         for (int c = 0; c < CN; ++c) sum[c] = 0;
         for (int yy = 0; yy < a.sy; ++yy) {
-            const uint8_t* p = src + (size_t)(dy * a.sy + yy) * a.in_stride + (size_t)(dx * a.sx) * CN;
+            const auto row = fetch.at(dx * a.sx, dy * a.sy + yy);
             for (int xx = 0; xx < a.sx; ++xx) {
+                int p[CN];
+                row(xx, p);
 #pragma unroll
-                for (int c = 0; c < CN; ++c) sum[c] += p[xx * CN + c];
+                for (int c = 0; c < CN; ++c) sum[c] += p[c];
             }
         }
         const bool fast2 = a.sx == 2 && a.sy == 2;
@@ -66,13 +69,14 @@ __global__ __launch_bounds__(256) void k_preprocess(PreArgs a) {
         const int x0 = a.xk[dx], x1 = a.xk[dx + 1], y0 = a.yk[dy], y1 = a.yk[dy + 1];
         for (int j = y0; j < y1; ++j) {
             const float beta = a.ytab[j].alpha;
-            const uint8_t* S = src + (size_t)a.ytab[j].si * a.in_stride;
+            const auto row = fetch.at(0, a.ytab[j].si);
             float buf[CN];
 #pragma unroll
             for (int c = 0; c < CN; ++c) buf[c] = 0.f;
             for (int k = x0; k < x1; ++k) {
                 const float alpha = a.xtab[k].alpha;
-                const uint8_t* p = S + (size_t)a.xtab[k].si * CN;
+                int p[CN];
+                row(a.xtab[k].si, p);
 #pragma unroll
                 for (int c = 0; c < CN; ++c) buf[c] = buf[c] + (float)p[c] * alpha;
             }
@@ -82,15 +86,163 @@ __global__ __launch_bounds__(256) void k_preprocess(PreArgs a) {
 #pragma unroll
         for (int c = 0; c < CN; ++c) v[c] = (int)sat_u8(sum[c]);
     }
+}
+
+// ... and where it goes: the frame the magnifier sees (gray15 of the decimated bytes with grayscale on) and the optional colour tap
+__device__ __forceinline__ uint8_t* pre_out(const PreArgs& a, size_t z, int dx, int dy) {
+    return a.out + z * a.out_sstride + (size_t)dy * a.out_stride + (size_t)dx * a.ocn;
+}
+template <int CN>
+__device__ __forceinline__ void pre_store(const PreArgs& a, uint8_t* q, size_t z, int dx, int dy, const int (&v)[CN]) {
     if (CN == 3 && a.ocn == 1) {
         q[0] = gray15(v[0], v[1], v[2]);
         if (a.tap) {        // PreprocessProcessor's own output: what the chain hands on as `original` before GrayscaleProcessor runs
-            uint8_t* t = a.tap + (size_t)blockIdx.z * a.tap_sstride + (size_t)dy * a.tap_stride + (size_t)dx * 3;
+            uint8_t* t = a.tap + z * a.tap_sstride + (size_t)dy * a.tap_stride + (size_t)dx * 3;
             t[0] = (uint8_t)v[0]; t[1] = (uint8_t)v[1]; t[2] = (uint8_t)v[2];
         }
     } else {
 #pragma unroll
         for (int c = 0; c < CN; ++c) q[c] = (uint8_t)v[c];
+    }
+}
+
+template <int CN>
+struct FetchBytes {
+    const uint8_t* src; long stride;
+    struct Cursor {
+        const uint8_t* p;
+        __device__ __forceinline__ void operator()(int i, int (&v)[CN]) const {
+            const uint8_t* q = p + (size_t)i * CN;
+#pragma unroll
+            for (int c = 0; c < CN; ++c) v[c] = q[c];
+        }
+    };
+    __device__ __forceinline__ Cursor at(int x, int y) const { return Cursor{src + (size_t)y * stride + (size_t)x * CN}; }
+};
+
+// One thread per output pixel; blockIdx.z = stream.
+template <int MODE, int CN>
+__global__ __launch_bounds__(256) void k_preprocess(PreArgs a) {
+    const int dx = blockIdx.x * 64 + (threadIdx.x & 63), dy = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (dx >= a.ow || dy >= a.oh) return;
+    const FetchBytes<CN> fetch{a.in + (size_t)blockIdx.z * a.in_sstride, a.in_stride};
+    uint8_t* q = pre_out(a, blockIdx.z, dx, dy);
+    int v[CN];
+    pre_pixel<MODE, CN>(a, fetch, dx, dy, v);
+    pre_store<CN>(a, q, blockIdx.z, dx, dy, v);
+}
+
+// ---- raw camera formats (lvm_set_source_format, include/lvm_hip.h) -----------------------------------------------------------------
+// cv::cvtColor(COLOR_YUV2BGR_*) in front of PreprocessProcessor: OpenCV 4's color_yuv, ITU-R BT.601 limited range in 20-bit fixed point.
+// All int32 (|sum| < 2^30), `>>` arithmetic: negative sums floor before the clamp.
+__device__ __forceinline__ int yuv_sat(int s) { s >>= 20; return s < 0 ? 0 : (s > 255 ? 255 : s); }
+__device__ __forceinline__ void yuv2bgr(int Y, int U, int V, int (&v)[3]) {
+    const int y = (Y > 16 ? Y - 16 : 0) * 1220542 + (1 << 19), u = U - 128, w = V - 128;
+    v[0] = yuv_sat(y + 2116026 * u);
+    v[1] = yuv_sat(y - 852492 * w - 409993 * u);
+    v[2] = yuv_sat(y + 1673527 * w);
+}
+
+// Where the bytes of a 4:2:2 pair sit (Y of pixel 2k at yo, of pixel 2k + 1 at yo + 2) and the order of an NV chroma pair.
+template <int FMT> struct YuvLayout {
+    static constexpr bool packed = FMT == LVM_PIX_YUYV || FMT == LVM_PIX_UYVY || FMT == LVM_PIX_YVYU;
+    static constexpr int yo = FMT == LVM_PIX_UYVY ? 1 : 0;
+    static constexpr int uo = FMT == LVM_PIX_YUYV ? 1 : (FMT == LVM_PIX_UYVY ? 0 : (FMT == LVM_PIX_YVYU ? 3 : (FMT == LVM_PIX_NV12 ? 0 : 1)));
+    static constexpr int vo = FMT == LVM_PIX_YUYV ? 3 : (FMT == LVM_PIX_UYVY ? 2 : (FMT == LVM_PIX_YVYU ? 1 : (FMT == LVM_PIX_NV12 ? 1 : 0)));
+};
+
+// The source of the raw kernels.  PreArgs::in points at the 4:2:2 pair (packed) / the Y byte (NV12, NV21) that holds pixel (-x0, 0) of the
+// ROI, `uv` at the chroma pair of pixel (-x0, -y0): x0, y0 in {0, 1} are the parities of the ROI's origin in the frame, so that pairs and
+// 2x2 blocks are shared by ABSOLUTE frame coordinates.
+struct YuvSrc { const uint8_t* uv; int x0, y0; };
+
+template <int FMT>
+struct FetchYuv {
+    const uint8_t* src; const uint8_t* uv; long stride; int x0, y0;
+    struct Cursor {
+        const uint8_t* py; const uint8_t* pc; int X;        // the Y row (packed: the row of pairs), the chroma row, the column in them
+        __device__ __forceinline__ void operator()(int i, int (&v)[3]) const {
+            typedef YuvLayout<FMT> L;
+            const int x = X + i;
+            int Y, U, V;
+            if (L::packed) {
+                const uint8_t* p = py + (size_t)(x >> 1) * 4;
+                Y = p[L::yo + (x & 1) * 2]; U = p[L::uo]; V = p[L::vo];
+            } else {
+                Y = py[x];
+                const uint8_t* q = pc + (size_t)(x & ~1);
+                U = q[L::uo]; V = q[L::vo];
+            }
+            yuv2bgr(Y, U, V, v);
+        }
+    };
+    __device__ __forceinline__ Cursor at(int x, int y) const {
+        return Cursor{src + (size_t)y * stride, YuvLayout<FMT>::packed ? nullptr : uv + (size_t)((y + y0) >> 1) * stride, x + x0};
+    }
+};
+
+// Byte variant ("yuv"): any geometry, any alignment.  One thread per output pixel like k_preprocess; block sums add converted bytes.
+template <int MODE, int FMT>
+__global__ __launch_bounds__(256) void k_preprocess_yuv(PreArgs a, YuvSrc y) {
+    const int dx = blockIdx.x * 64 + (threadIdx.x & 63), dy = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (dx >= a.ow || dy >= a.oh) return;
+    const size_t so = (size_t)blockIdx.z * a.in_sstride;
+    const FetchYuv<FMT> fetch{a.in + so, y.uv ? y.uv + so : nullptr, a.in_stride, y.x0, y.y0};
+    uint8_t* q = pre_out(a, blockIdx.z, dx, dy);
+    int v[3];
+    pre_pixel<MODE, 3>(a, fetch, dx, dy, v);
+    pre_store<3>(a, q, blockIdx.z, dx, dy, v);
+}
+
+// Vector variant ("yuv4") of the conversion-only case, colour out: a live camera at full frame into the magnifier.  A thread takes four
+// pixels -- two 4:2:2 pairs as one 8-byte load, or a dword of Y and a dword of UV -- and writes their 12 bytes as three dwords.  The
+// launch code selects it where every base pointer and stride is a multiple of 4, x0 = 0 and the width a multiple of 4.  The raw rows
+// are read once, by this kernel alone, and the BGR frame is written for a later launch: streaming loads and stores (lvm_gfx950.h).
+template <int FMT>
+__global__ __launch_bounds__(256) void k_yuv_vec4(PreArgs a, YuvSrc y) {
+    typedef YuvLayout<FMT> L;
+    const int g = blockIdx.x * 64 + (threadIdx.x & 63), dy = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (g >= (a.ow >> 2) || dy >= a.oh) return;
+    const size_t so = (size_t)blockIdx.z * a.in_sstride;
+    uint32_t yy, uv;                   // yy: Y of the four pixels, byte k = pixel k; uv: byte 0 = U, 1 = V of pixels 0-1, bytes 2, 3 of pixels 2-3
+    if (L::packed) {
+        const uint2 d = ld_stream_u32x2(a.in + so + (size_t)dy * a.in_stride + (size_t)g * 8);
+        const uint32_t ys = L::yo * 8, us = L::uo * 8, vs = L::vo * 8;
+        yy = ((d.x >> ys) & 255u) | (((d.x >> (ys + 16)) & 255u) << 8) | (((d.y >> ys) & 255u) << 16) | (((d.y >> (ys + 16)) & 255u) << 24);
+        uv = ((d.x >> us) & 255u) | (((d.x >> vs) & 255u) << 8) | (((d.y >> us) & 255u) << 16) | (((d.y >> vs) & 255u) << 24);
+    } else {
+        yy = __float_as_uint(ld_stream_f32(a.in + so + (size_t)dy * a.in_stride + (size_t)g * 4));
+        const uint32_t q = __float_as_uint(ld_stream_f32(y.uv + so + (size_t)((dy + y.y0) >> 1) * a.in_stride + (size_t)g * 4));
+        uv = L::uo == 0 ? q : (((q >> 8) & 0x00ff00ffu) | ((q & 0x00ff00ffu) << 8));
+    }
+    int p[4][3];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int sh = (k >> 1) * 16;
+        yuv2bgr((int)((yy >> (8 * k)) & 255u), (int)((uv >> sh) & 255u), (int)((uv >> (sh + 8)) & 255u), p[k]);
+    }
+    uint8_t* q = a.out + (size_t)blockIdx.z * a.out_sstride + (size_t)dy * a.out_stride + (size_t)g * 12;
+    st_stream_b96(q, lvm_pack_b4(p[0][0], p[0][1], p[0][2], p[1][0]), lvm_pack_b4(p[1][1], p[1][2], p[2][0], p[2][1]),
+                  lvm_pack_b4(p[2][2], p[3][0], p[3][1], p[3][2]));
+}
+
+typedef void (*YuvKernel)(PreArgs, YuvSrc);
+template <int MODE> static YuvKernel yuv_kernel(int fmt) {
+    switch (fmt) {
+    case LVM_PIX_YUYV: return k_preprocess_yuv<MODE, LVM_PIX_YUYV>;
+    case LVM_PIX_UYVY: return k_preprocess_yuv<MODE, LVM_PIX_UYVY>;
+    case LVM_PIX_YVYU: return k_preprocess_yuv<MODE, LVM_PIX_YVYU>;
+    case LVM_PIX_NV12: return k_preprocess_yuv<MODE, LVM_PIX_NV12>;
+    default:           return k_preprocess_yuv<MODE, LVM_PIX_NV21>;
+    }
+}
+static YuvKernel yuv_vec4_kernel(int fmt) {
+    switch (fmt) {
+    case LVM_PIX_YUYV: return k_yuv_vec4<LVM_PIX_YUYV>;
+    case LVM_PIX_UYVY: return k_yuv_vec4<LVM_PIX_UYVY>;
+    case LVM_PIX_YVYU: return k_yuv_vec4<LVM_PIX_YVYU>;
+    case LVM_PIX_NV12: return k_yuv_vec4<LVM_PIX_NV12>;
+    default:           return k_yuv_vec4<LVM_PIX_NV21>;
     }
 }
 
@@ -145,8 +297,10 @@ void preprocess_release(Ctx* c) {
 
 int preprocess_device(Ctx* c, const lvm_preprocess_params& pp, const uint8_t* d_in, int w, int h, int channels, ptrdiff_t in_stride,
                       ptrdiff_t in_sstride, uint8_t* d_out, ptrdiff_t out_stride, ptrdiff_t out_sstride, hipStream_t s,
-                      uint8_t* d_tap, ptrdiff_t tap_stride, ptrdiff_t tap_sstride) {
+                      uint8_t* d_tap, ptrdiff_t tap_stride, ptrdiff_t tap_sstride, const RawSource* raw) {
     if (!d_in || !d_out || w <= 0 || h <= 0 || (channels != 1 && channels != 3)) { c->err = "preprocess: bad frame arguments"; return LVM_ERR_INVALID; }
+    const int fmt = raw ? raw->fmt : LVM_PIX_BGR;
+    if (fmt != LVM_PIX_BGR && (fmt < LVM_PIX_YUYV || fmt > LVM_PIX_NV21 || channels != 3)) { c->err = "preprocess: bad source format"; return LVM_ERR_INVALID; }
     int rx, ry, rw, rh, ow, oh, och;
     preprocess_geometry(pp, w, h, channels, &rx, &ry, &rw, &rh, &ow, &oh, &och);
     if (out_stride < (ptrdiff_t)ow * och) { c->err = "preprocess: output stride too small"; return LVM_ERR_INVALID; }
@@ -187,7 +341,29 @@ int preprocess_device(Ctx* c, const lvm_preprocess_params& pp, const uint8_t* d_
         }
     }
     const dim3 grid((ow + 63) / 64, (oh + 3) / 4, c->nstreams), blk(256);
-    if (channels == 3) {
+    if (fmt != LVM_PIX_BGR) {
+        // the frame is raw: the ROI's origin in it, (X0, Y0), decides which pair / 2x2 block a pixel shares its chroma with
+        const bool packed = fmt <= LVM_PIX_YVYU;
+        const int X0 = rx + raw->px, Y0 = ry + raw->py;
+        YuvSrc y{};
+        y.x0 = X0 & 1; y.y0 = packed ? 0 : (Y0 & 1);
+        if (packed) {
+            a.in = d_in + (size_t)ry * in_stride + (size_t)(X0 >> 1) * 4;
+        } else {
+            a.in = d_in + (size_t)ry * in_stride + (size_t)(X0 & ~1);
+            y.uv = d_in + raw->uv_offset + (size_t)(Y0 >> 1) * in_stride + (size_t)(X0 & ~1);
+        }
+        auto dword = [](const void* p, ptrdiff_t s0, ptrdiff_t s1) { return ((uintptr_t)p | (uintptr_t)s0 | (uintptr_t)s1) % 4 == 0; };
+        const ptrdiff_t iss = c->nstreams > 1 ? in_sstride : 0, oss = c->nstreams > 1 ? out_sstride : 0;
+        const bool vec = mode == 0 && och == 3 && y.x0 == 0 && ow % 4 == 0 && dword(a.in, in_stride, iss) && dword(y.uv, 0, 0) && dword(d_out, out_stride, oss);
+if (vec) {
+            const dim3 grid4((ow / 4 + 63) / 64, (oh + 3) / 4, c->nstreams);
+            LVM_LAUNCH_V(c, "preprocess", "yuv4", yuv_vec4_kernel(fmt), grid4, blk, s, a, y);
+        } else {
+            auto k = mode == 0 ? yuv_kernel<0>(fmt) : (mode == 1 ? yuv_kernel<1>(fmt) : yuv_kernel<2>(fmt));
+            LVM_LAUNCH_V(c, "preprocess", "yuv", k, grid, blk, s, a, y);
+        }
+    } else if (channels == 3) {
         auto k = mode == 0 ? k_preprocess<0, 3> : (mode == 1 ? k_preprocess<1, 3> : k_preprocess<2, 3>);
         LVM_LAUNCH(c, "preprocess", k, grid, blk, s, a);
     } else {

@@ -123,6 +123,13 @@ public:
     void set_phase_on_gray(bool on) { check(lvm_set_phase_on_gray(ctx_, on ? 1 : 0)); }
     bool phase_on_gray() { int v = 0; check(lvm_get_phase_on_gray(ctx_, &v)); return v != 0; }
 
+    // Frames of the chain / export calls in a raw camera format (LVM_PIX_YUYV, _UYVY, _YVYU, _NV12, _NV21; LVM_PIX_BGR = the default) -- an
+    // extension beyond the reference: the device converts with the arithmetic of cv::cvtColor(COLOR_YUV2BGR_*) in the kernel that crops and
+    // decimates, so a raw V4L2 capture uploads 2 or 1.5 bytes per pixel instead of 3 (include/lvm_hip.h lvm_set_source_format; `channels` of
+    // those calls is then 3, `w` x `h` the picture's size).  process() does not take part.  Keeps the temporal state; kept across reset().
+    void set_source_format(int fmt) { check(lvm_set_source_format(ctx_, fmt)); }
+    int source_format() { int v = 0; check(lvm_get_source_format(ctx_, &v)); return v; }
+
     void synchronize() { check(lvm_synchronize(ctx_)); }
     lvm_ctx* handle() const { return ctx_; }
 
