@@ -1272,7 +1272,7 @@ struct ColorState : ModeState {
     int out_rows = 16;               // rows per wave strip of k_col_out_rows (LVM_COL_OUT_ROWS; 0 = tiled k_col_out_v4)
     int out_rows_lean = 36;          // ... of k_col_out_strips (strip start-up = 3 V rows + 3 U2 rows: longer strips; 1080 = 30 x 36)
     bool out_lean = true;            // k_col_out_strips (both pyrUps inside, packed FP32, loads an iteration ahead); LVM_COL_OUT_LEAN=0: k_col_out_rows
-    int thin_min_frames = 1;         // ... from this many frames per launch (LVM_COL_THIN_MIN_FRAMES).  Round 5: 4 -> 1 -- the eight-lanes-per-row kernel of round 4 also wins
+    int thin_min_frames = 1;         // ... from this many frames per launch (LVM_COL_THIN_MIN_FRAMES, >= 1).  Round 5: 4 -> 1 -- the eight-lanes-per-row kernel of round 4 also wins
                                      // for ONE frame per launch (24 -> 16 us per 1080p frame; the wave-per-row kernel remains for wide bands)
     long rows_min_elems = 1 << 20;   // planes x pixels from which pyrDown uses k_pyr_down_rows (LVM_ROWS_MIN_ELEMS)
     double* tw = nullptr; int tw_n = 0;          // table of the current window length (points into tw_all or at tw_own)
@@ -1497,15 +1497,15 @@ static int col_filter(Ctx* c, ColorState* st, const lvm_params& p, const ColBufs
         LVM_LAUNCH_V(c, "col_dft", "serial", k_col_dft_serial, dim3((live + 255) / 256, NS), blk, s, (const float*)st->win, slot0, n, st->cap,
                      st->rows_ps, live, fl, fh, (const double*)st->tw, st->Y, B.col1, B.mm);
     } else if (ne <= kThin8Bins && n <= kThin8MaxN && st->thin_dft && st->thin8_dft && B.nt >= st->thin_min_frames) {
-        LVM_LAUNCH(c, "col_dft", n <= 128 ? k_col_dft_thin8<128> : k_col_dft_thin8<kThin8MaxN>, dim3((live + kThin8Rows - 1) / kThin8Rows, NS, B.nt), blk, s, (const float*)st->win, slot0, n, st->cap,
+        LVM_LAUNCH_V(c, "col_dft", n <= 128 ? "thin8-128" : "thin8", n <= 128 ? k_col_dft_thin8<128> : k_col_dft_thin8<kThin8MaxN>, dim3((live + kThin8Rows - 1) / kThin8Rows, NS, B.nt), blk, s, (const float*)st->win, slot0, n, st->cap,
                    st->rows_ps, live, (const double*)st->tw, B.col1, B.mm, eb);
     } else if (ne <= kThinBins && n <= kDftMaxN && st->thin_dft && B.nt >= st->thin_min_frames) {
-        LVM_LAUNCH(c, "col_dft", k_col_dft_thin, dim3((live + 255) / 256, NS, B.nt), blk, s, (const float*)st->win, slot0, n, st->cap,
+        LVM_LAUNCH_V(c, "col_dft", "thin", k_col_dft_thin, dim3((live + 255) / 256, NS, B.nt), blk, s, (const float*)st->win, slot0, n, st->cap,
                    st->rows_ps, live, (const double*)st->tw, B.col1, B.mm, eb);
     } else {
         int gx = (live + kDftRows - 1) / kDftRows;
         gx = gx < 1024 ? gx : 1024;
-        LVM_LAUNCH(c, "col_dft", k_col_dft, dim3(gx, NS, B.nt), blk, s, (const float*)st->win, slot0, n, st->cap, st->rows_ps, live, fl, fh,
+        LVM_LAUNCH_V(c, "col_dft", "wave", k_col_dft, dim3(gx, NS, B.nt), blk, s, (const float*)st->win, slot0, n, st->cap, st->rows_ps, live, fl, fh,
                    (const double*)st->tw, B.col1, B.mm);
     }
     st->amp = (float)p.amplification;          // the normalisation runs at the head of col_up_out (on its own or inside the first pyrUp)
@@ -1539,15 +1539,15 @@ static void col_up_out(Ctx* c, ColorState* st, const FrameIO& io, const ColBufs&
     for (int k = 0; k + 1 < levels - (fuse2 ? 1 : 0); ++k) {      // L-1 generic pyrUps, the last one is fused into k_col_out (k_col_out_strips: the last two)
         if (k == 0 && norm_in_up) {
             const long ngroups = (long)(2 * uw / 4) * uh;
-            LVM_LAUNCH(c, "pyr_up_l0", k_pyr_up_rows_norm, dim3((unsigned)((ngroups + 255) / 256), planes), blk, s, (const float*)B.col1, st->rows_ps, C, uw, uh,
+            LVM_LAUNCH_V(c, "pyr_up_l0", "rows-norm", k_pyr_up_rows_norm, dim3((unsigned)((ngroups + 255) / 256), planes), blk, s, (const float*)B.col1, st->rows_ps, C, uw, uh,
                        B.up[1], (int)ngroups, (const MinMax*)B.mm, st->amp);
         } else if (st->up_rows && (2 * uw) % 4 == 0) {      // barrier-free blocks of 4 x 2 outputs per lane (pyramid.h)
             const long ngroups = (long)(2 * uw / 4) * uh;
-            LVM_LAUNCH(c, LName("pyr_up", k), k_pyr_up_rows<1>, dim3((unsigned)((ngroups + 255) / 256), planes), blk, s, (const float*)B.up[k], uw, uh,
+            LVM_LAUNCH_V(c, LName("pyr_up", k), "rows", k_pyr_up_rows<1>, dim3((unsigned)((ngroups + 255) / 256), planes), blk, s, (const float*)B.up[k], uw, uh,
                        B.up[k + 1], (int)ngroups);
         } else {
             const dim3 grid((2 * uw + 63) / 64, (2 * uh + 15) / 16, planes);
-            LVM_LAUNCH(c, LName("pyr_up", k), k_pyr_up<1>, grid, blk, s, (const float*)B.up[k], uw, uh, B.up[k + 1], 2 * uw, 2 * uh);
+            LVM_LAUNCH_V(c, LName("pyr_up", k), "tiled", k_pyr_up<1>, grid, blk, s, (const float*)B.up[k], uw, uh, B.up[k + 1], 2 * uw, 2 * uh);
         }
         uw *= 2; uh *= 2;
     }
@@ -1604,7 +1604,7 @@ static void color_switches(ColorState* st) {
     env_switch("LVM_COL_DOWN01", st->d01_on);
     env_switch("LVM_COL_DOWN01_ROWS", st->d01_rows_forced);
     if (env_switch("LVM_COL_OUT_MIN_TASKS", st->out_min_tasks)) st->out_min_tasks_lean = st->out_min_tasks;
-    env_switch("LVM_COL_THIN_MIN_FRAMES", st->thin_min_frames);
+    env_switch("LVM_COL_THIN_MIN_FRAMES", st->thin_min_frames, [](int v) { return v >= 1; });
     env_switch("LVM_ROWS_MIN_ELEMS", st->rows_min_elems);
     env_switch("LVM_COL_LONG_DFT", st->long_dft);
     env_switch("LVM_COL_LONG_FROM", st->long_from, [](int x) { return x >= 2; });

@@ -962,7 +962,7 @@ struct LaplaceState : ModeState {
     // integer Lab planes of the input frames (labconv.hip; 3-channel frames): per frame parity and for temporal batches
     uint16_t* iLp[2] = {}; uint32_t* iabp[2] = {};
     uint16_t* iLt = nullptr; uint32_t* iabt = nullptr;
-    int split_min_nt = 1;                 // frames per launch from which levels >= 2 run as IIR + collapse launches (LVM_LAP_SPLIT_MIN_NT)
+    int split_min_nt = 1;                 // frames per launch from which levels >= 2 run as IIR + collapse launches (LVM_LAP_SPLIT_MIN_NT, >= 1)
     long fin_min_tasks = 4096;            // strips are shortened until a launch has this many of them (LVM_FIN_MIN_TASKS)
     long rows_min_elems = 2000000;        // planes x pixels from which pyrDown uses k_pyr_down_rows (LVM_ROWS_MIN_ELEMS): 32-frame batches keep the strips on
                                           // levels 1-3 (3.1 M at level 3), four streams per per-frame call take the two-level kernel from level 2 (one launch less)
@@ -970,19 +970,19 @@ struct LaplaceState : ModeState {
                                           // written nor read back (34 + 41 -> 20 + 14 + 34 us per 32 frames at 1080p); LVM_LAP_SPLIT_FROM=2: levels 2 .. L-1 decoupled
     int split_levels = 1;                 // temporal batches: levels >= 2 as one IIR launch + one collapse launch (LVM_LAP_SPLIT=0: level-by-level chain)
     int up_rows = 1;                      // barrier-free k_lap_up_rows for the steady state (LVM_UP_ROWS=0: tiled k_lap_up)
-    long up_rows_max_blocks = 1024;       // launches with fewer tiled workgroups than this use k_lap_up_rows (LVM_UP_ROWS_MAX_BLOCKS)
+    long up_rows_max_blocks = 1024;       // launches with fewer tiled workgroups than this use k_lap_up_rows (LVM_UP_ROWS_MAX_BLOCKS, >= 0)
     bool d0_rows_on = true;               // wave-strip first kernel (LVM_D0_ROWS=0: LDS-tiled k_down0_v4 always)
     bool d0_fused = true;                 // table conversion fused into the first kernel on large launches (LVM_D0_FUSED=0: separate kernels)
-    int d0_fused_rows = 0;                // force the fused first kernel with strips of this many rows (LVM_D0_FUSED_ROWS; measurement only)
-    long d0_fused_groups = 0;             // persistent workgroups of the fused first kernel (LVM_D0_FUSED_GROUPS; 0 = one per CU)
+    int d0_fused_rows = 0;                // force the fused first kernel with strips of this many rows (LVM_D0_FUSED_ROWS, >= 0; 0 = off; measurement only)
+    long d0_fused_groups = 0;             // persistent workgroups of the fused first kernel (LVM_D0_FUSED_GROUPS, >= 0; 0 = one per CU)
     long d0_fused_waves = 0;              // ... = launches with at least this many strips (LVM_D0_FUSED_WAVES; 0 = one per resident wave)
     long d0_min_tasks = 4096;             // ... for launches with at least this many strips (LVM_D0_MIN_TASKS)
-    long fin_groups = 0;                  // workgroups of the persistent last kernel (LVM_FIN_GROUPS; 0 = 1024)
+    long fin_groups = 0;                  // workgroups of the persistent last kernel (LVM_FIN_GROUPS, >= 0; 0 = 1024)
     int fin_rows = 8;                     // rows per wave strip of k_lap_final_v4 (LVM_FIN_ROWS, power of two)
-    int up_depth_big = 1;                 // ... at the levels with >= 1024 workgroups (LVM_UP_DEPTH_BIG)
-    int up_depth = 8;                     // frame-loop prefetch depth of k_lap_up at the coarse levels (LVM_UP_DEPTH=1|2|4|8)
-    int pd_rows = 16;                     // output rows per wave strip of k_pyr_down_rows (LVM_PD_ROWS)
-    int fuse_down = 2;                    // pyramid levels per pyrDown launch (LVM_FUSE_DOWN=2|3 selects the fused kernels)
+    int up_depth_big = 1;                 // ... at the levels with >= 1024 workgroups (LVM_UP_DEPTH_BIG=1|2|4|8)
+    int up_depth = 8;                     // frame-loop prefetch depth of k_lap_up at the coarse levels (LVM_UP_DEPTH=1|2|4|8: the kernel has these four instantiations)
+    int pd_rows = 16;                     // output rows per wave strip of k_pyr_down_rows (LVM_PD_ROWS, >= 1; launches halve it while > 4 and short of strips)
+    int fuse_down = 2;                    // pyramid levels per pyrDown launch (LVM_FUSE_DOWN=1|2|3: 2 and 3 select the fused kernels)
     int tailT = 0;                       // first level handled by k_lap_tail (0 = tail disabled)
     TailArgs tail{};
     ~LaplaceState() override {
@@ -1241,7 +1241,7 @@ static void lap_stage_a(Ctx* c, LaplaceState* st, const lvm_params& p, const Fra
         int depth = 8;
         while (depth > 1 && B.nt % depth != 0) depth >>= 1;
         auto ki = depth == 8 ? k_lap_iir_levels<8> : (depth == 4 ? k_lap_iir_levels<4> : (depth == 2 ? k_lap_iir_levels<2> : k_lap_iir_levels<1>));
-        LVM_LAUNCH(c, "lap_iir", ki, dim3((unsigned)blocks, (unsigned)st->planes), blk, s, ia);
+        LVM_LAUNCH_V(c, "lap_iir", LVar("d", depth), ki, dim3((unsigned)blocks, (unsigned)st->planes), blk, s, ia);
         if (levels >= F + 2) {
             CollapseArgs ca;
             ca.nlv = levels - F;
@@ -1253,7 +1253,7 @@ static void lap_stage_a(Ctx* c, LaplaceState* st, const lvm_params& p, const Fra
             case 5: kc = k_lap_collapse<5>; break; case 6: kc = k_lap_collapse<6>; break; case 7: kc = k_lap_collapse<7>; break;
             case 8: kc = k_lap_collapse<8>; break; case 9: kc = k_lap_collapse<9>; break; default: kc = k_lap_collapse<10>; break;
             }
-            LVM_LAUNCH(c, "lap_collapse", kc, gridc, blk, s, ca);
+            LVM_LAUNCH_V(c, "lap_collapse", LVar("n", ca.nlv < 10 ? ca.nlv : 10), kc, gridc, blk, s, ca);
         }
         up_start = F - 1;
     }
@@ -1281,16 +1281,17 @@ static void lap_stage_a(Ctx* c, LaplaceState* st, const lvm_params& p, const Fra
             auto kr = depth == 4 ? (hc ? k_lap_up_rows<2, 4, true> : k_lap_up_rows<2, 4, false>)
                                  : (depth == 2 ? (hc ? k_lap_up_rows<2, 2, true> : k_lap_up_rows<2, 2, false>)
                                                : (hc ? k_lap_up_rows<2, 1, true> : k_lap_up_rows<2, 1, false>));
-            LVM_LAUNCH(c, LName("lap_up", l), kr, g2, blk, s, a, gw, (int)ngroups);
+            LVM_LAUNCH_V(c, LName("lap_up", l), LVar("rows d", depth, hc ? " curn" : ""), kr, g2, blk, s, a, gw, (int)ngroups);
             continue;
         }
-        int depth = (blocks >= 1024) ? st->up_depth_big : st->up_depth;   // frame ring of the tiled kernel
-        while (depth > 1 && a.nt % depth != 0) depth >>= 1;           // the ring depth must divide the frame count
+        int depth = (blocks >= 1024) ? st->up_depth_big : st->up_depth;   // frame ring of the tiled kernel: 1, 2, 4 or 8 (laplace_switches)
+        while (depth > 1 && a.nt % depth != 0) depth >>= 1;           // the ring depth must divide the frame count (a power of two stays one)
+        const char* hcv = a.curn ? " curn" : "";                      // (the variant: which ring depth, and whether cur_{l+1} is added)
         if (first) LVM_LAUNCH(c, LName("lap_seed", l), (k_lap_up<true, 1>), grid, blk, s, a);
-        else if (depth == 1) LVM_LAUNCH(c, LName("lap_up", l), (k_lap_up<false, 1>), grid, blk, s, a);
-        else if (depth == 2) LVM_LAUNCH(c, LName("lap_up", l), (k_lap_up<false, 2>), grid, blk, s, a);
-        else if (depth <= 4) LVM_LAUNCH(c, LName("lap_up", l), (k_lap_up<false, 4>), grid, blk, s, a);
-        else LVM_LAUNCH(c, LName("lap_up", l), (k_lap_up<false, 8>), grid, blk, s, a);
+        else if (depth == 1) LVM_LAUNCH_V(c, LName("lap_up", l), LVar("tiled d", 1, hcv), (k_lap_up<false, 1>), grid, blk, s, a);
+        else if (depth == 2) LVM_LAUNCH_V(c, LName("lap_up", l), LVar("tiled d", 2, hcv), (k_lap_up<false, 2>), grid, blk, s, a);
+        else if (depth == 4) LVM_LAUNCH_V(c, LName("lap_up", l), LVar("tiled d", 4, hcv), (k_lap_up<false, 4>), grid, blk, s, a);
+        else LVM_LAUNCH_V(c, LName("lap_up", l), LVar("tiled d", 8, hcv), (k_lap_up<false, 8>), grid, blk, s, a);
     }
     const int fl = lab_flavour(c);
     float* dbg = (c->keep_float && B.dbg_frame) ? c->d_float.as<float>() : nullptr;   // (the float frame kept is the first one of the batch)
@@ -1380,24 +1381,27 @@ int LaplaceState::process_frames(Ctx* c, const lvm_params& p, const FrameIO& io,
 }
 
 static void laplace_switches(LaplaceState* st) {
-    env_switch("LVM_FUSE_DOWN", st->fuse_down);
-    env_switch("LVM_UP_DEPTH", st->up_depth);
-    env_switch("LVM_UP_DEPTH_BIG", st->up_depth_big);
-    env_switch("LVM_PD_ROWS", st->pd_rows);
+    // a refused value keeps the default: it never reaches a launch
+    const auto ring_depth = [](int v) { return v == 1 || v == 2 || v == 4 || v == 8; };
+    const auto not_negative = [](long v) { return v >= 0; };
+    env_switch("LVM_FUSE_DOWN", st->fuse_down, [](int v) { return v >= 1 && v <= 3; });
+    env_switch("LVM_UP_DEPTH", st->up_depth, ring_depth);
+    env_switch("LVM_UP_DEPTH_BIG", st->up_depth_big, ring_depth);
+    env_switch("LVM_PD_ROWS", st->pd_rows, [](int v) { return v >= 1; });    // (0: a division by zero in the strip count)
     env_switch("LVM_D0_ROWS", st->d0_rows_on);
     env_switch("LVM_D0_FUSED", st->d0_fused);
     env_switch("LVM_D0_FUSED_WAVES", st->d0_fused_waves);
-    env_switch("LVM_D0_FUSED_GROUPS", st->d0_fused_groups);
-    env_switch("LVM_D0_FUSED_ROWS", st->d0_fused_rows);
+    env_switch("LVM_D0_FUSED_GROUPS", st->d0_fused_groups, not_negative);
+    env_switch("LVM_D0_FUSED_ROWS", st->d0_fused_rows, [](int v) { return v >= 0; });   // (any height >= 1 walks: the strip keeps a 5-row window)
     env_switch("LVM_D0_MIN_TASKS", st->d0_min_tasks);
     env_switch("LVM_LAP_SPLIT", st->split_levels);
-    env_switch("LVM_LAP_SPLIT_MIN_NT", st->split_min_nt);
+    env_switch("LVM_LAP_SPLIT_MIN_NT", st->split_min_nt, [](int v) { return v >= 1; });
     env_switch("LVM_UP_ROWS", st->up_rows);
-    env_switch("LVM_UP_ROWS_MAX_BLOCKS", st->up_rows_max_blocks);
+    env_switch("LVM_UP_ROWS_MAX_BLOCKS", st->up_rows_max_blocks, not_negative);
     env_switch("LVM_ROWS_MIN_ELEMS", st->rows_min_elems);
     env_switch("LVM_LAP_SPLIT_FROM", st->split_from, [](int v) { return v == 2 || v == 3; });
     env_switch("LVM_FIN_MIN_TASKS", st->fin_min_tasks);
-    env_switch("LVM_FIN_GROUPS", st->fin_groups);
+    env_switch("LVM_FIN_GROUPS", st->fin_groups, not_negative);
     env_switch("LVM_FIN_ROWS", st->fin_rows, [](int v) { return v == 2 || v == 4 || v == 8 || v == 16 || v == 32; });
 }
 

@@ -637,6 +637,14 @@ struct LName {
     operator const char*() const { return s; }
 };
 
+// Variant of a launch whose kernel or template argument is picked at run time ("tiled d8", "n5"): head, number, tail.  Like LName
+// only built while profiling (LVM_LAUNCH_V evaluates its variant argument inside the profiling branch).
+struct LVar {
+    char s[32];
+    LVar(const char* head, int v, const char* tail = "") { std::snprintf(s, sizeof(s), "%s%d%s", head, v, tail); }
+    operator const char*() const { return s; }
+};
+
 // Launch with optional event bracketing.  `nm` is the kernel's report name; template kernels
 // with several arguments are passed through a function-pointer variable.
 #define LVM_LAUNCH(c, nm, kern, grid, block, stream, ...)                                 \
@@ -646,7 +654,8 @@ struct LName {
         if ((c)->profiling) lvm::prof_end((c), (stream));                                 \
     } while (0)
 // The same where several kernels share one report name (the name is what bench.py and the measurement tools key on): `var` says which
-// one ran -- "strips" (wave strips), "vec4" (tiled, dword-wide frame I/O), "bytes" (tiled, byte I/O) -- for lvm_profile_variants.
+// one ran -- "strips" (wave strips), "vec4" (tiled, dword-wide frame I/O), "bytes" (tiled, byte I/O) -- for lvm_profile_variants; where the
+// launch code picks a template argument at run time, the pick ("rows d4", "tiled d8 curn", "d2", "n5", "thin8-128": LVar).
 #define LVM_LAUNCH_V(c, nm, var, kern, grid, block, stream, ...)                          \
     do {                                                                                  \
         if ((c)->profiling) { lvm::prof_begin((c), nm, (stream)); lvm::prof_variant((c), var); } \

@@ -1836,7 +1836,7 @@ struct RieszState : ModeState {
     bool phase4 = true;              // 4-pixels-per-thread phase kernel on levels whose width is a multiple of 4 (LVM_RZ_PHASE4=0: scalar kernel)
     int phase4_min_frames = 2;       // ... from this many frames x streams per launch (LVM_RZ_PHASE4_MIN_FRAMES): ONE frame of one stream has too few 4-pixel threads to
                                      // hide the state loads -- the one-pixel kernel runs it in 58 us against 64 (round 5)
-    int fin_groups = 0;              // workgroups of the persistent last kernel (LVM_RZ_FIN_GROUPS; 0 = a sixth of the tiles, at least 2048)
+    int fin_groups = 0;              // workgroups of the persistent last kernel (LVM_RZ_FIN_GROUPS, >= 0; 0 = a sixth of the tiles, at least 2048)
     int split_strip = 0;             // rows per strip of k_rz_split_rows (LVM_RZ_SPLIT_STRIP; 0 = chosen per launch)
     bool collapse_strips = true;     // collapse / output as wave strips (LVM_RZ_COLLAPSE_STRIPS=0: the tiled kernels) ...
     long collapse_strips_min = 10000000;   // ... for launches of at least this many plane-pixels (LVM_RZ_COLLAPSE_STRIPS_MIN)
@@ -1965,17 +1965,17 @@ static void rz_build(Ctx* c, RieszState* st, const FrameIO& io, const RzBufs& B,
             if (rows <= 0) rows = strip_rows_by_work(sx, a.h, NZ);
             const int sy = (a.h + rows - 1) / rows;
             const long ntasks = (long)sx * sy * NZ;
-            LVM_LAUNCH(c, LName("rz_split", l), k_rz_split_rows, dim3((unsigned)((ntasks + SR_THREADS / 64 - 1) / (SR_THREADS / 64))), dim3(SR_THREADS), s,
+            LVM_LAUNCH_V(c, LName("rz_split", l), "strips", k_rz_split_rows, dim3((unsigned)((ntasks + SR_THREADS / 64 - 1) / (SR_THREADS / 64))), dim3(SR_THREADS), s,
                        (const float*)B.oct[l], a.w, a.h, B.pf[l][F_BAND], B.oct[l + 1], b.w, b.h, sx, sy, (int)ntasks, rows);
             continue;
         }
         if (st->split2 && a.w % 4 == 0 && (long)a.n * NZ >= st->split2_min) {
             const dim3 grid2((a.w + CW - 1) / CW, (a.h + C2H - 1) / C2H, NZ);
-            LVM_LAUNCH(c, LName("rz_split", l), k_rz_split2, grid2, blk, s, (const float*)B.oct[l], a.w, a.h, B.pf[l][F_BAND], B.oct[l + 1], b.w, b.h);
+            LVM_LAUNCH_V(c, LName("rz_split", l), "4x2", k_rz_split2, grid2, blk, s, (const float*)B.oct[l], a.w, a.h, B.pf[l][F_BAND], B.oct[l + 1], b.w, b.h);
             continue;
         }
         const dim3 grid((a.w + CW - 1) / CW, (a.h + CH - 1) / CH, NZ);
-        LVM_LAUNCH(c, LName("rz_split", l), k_rz_split<TK_FMA>, grid, blk, s, (const float*)B.oct[l], a.w, a.h, B.pf[l][F_BAND], B.oct[l + 1], b.w, b.h);
+        LVM_LAUNCH_V(c, LName("rz_split", l), "tile", k_rz_split<TK_FMA>, grid, blk, s, (const float*)B.oct[l], a.w, a.h, B.pf[l][F_BAND], B.oct[l + 1], b.w, b.h);
     }
 }
 
@@ -2235,7 +2235,7 @@ static void riesz_switches(RieszState* st) {
     env_switch("LVM_RZ_PHASE4_MIN_FRAMES", st->phase4_min_frames);
     env_switch("LVM_RZ_COMPACT", st->compact);
     env_switch("LVM_RZ_PHASE4", st->phase4);
-    env_switch("LVM_RZ_FIN_GROUPS", st->fin_groups);
+    env_switch("LVM_RZ_FIN_GROUPS", st->fin_groups, [](int v) { return v >= 0; });
     env_switch("LVM_RZ_SPLIT_STRIP", st->split_strip, [](int v) { return v >= 2 && v % 2 == 0; });
     env_switch("LVM_RZ_SPLIT_ROWS", st->split_rows);
     env_switch("LVM_RZ_COLLAPSE_STRIPS", st->collapse_strips);

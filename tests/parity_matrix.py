@@ -4,6 +4,9 @@ and on the gfx950 build by tests/test_gpu_exact.py.  Each body takes the library
 device pointers, a memory adaptor (helpers.HostMem / helpers.TorchMem).  Lists hold Riesz entries where the emulation test of the
 same name covers all three modes; the GPU module keeps the Laplace and Color ones (Riesz calls acosf / sinf / cosf, see
 tests/test_gpu_exact.py)."""
+import os
+import re
+
 import numpy as np
 
 import content
@@ -475,3 +478,310 @@ def chroma_out_of_gamut(lvm, po, lib):
     """saturated hues amplified a thousandfold at full chroma: Lab far outside the gamut on every side of it"""
     assert EXTREME_PARAMETERS[5] == (0, dict(amplification=1000.0, chromAttenuation=1.0))
     return extreme_parameters(lvm, po, lib, *EXTREME_PARAMETERS[5], kind="hue")
+
+
+# ---- launch switches and run-time instantiations (tests/test_emu_switches.py, tests/test_gpu_switches.py) ----------------------------
+# Every LVM_* switch the launch code reads and no other test sets, and every kernel instantiation the launch code picks from a frame
+# or level count.  A case is (mode, (w, h, levels), streams, call lengths, switches, check): the clip goes through
+# lvm_process_device_frames in those calls, OpenCV-order Lab, with profiling on; the bytes of every frame and the float frame of every
+# call's first frame (1-stream cases; Color: of 1-frame calls) must be the oracle's bit for bit -- Riesz on the GPU: the default kernels' on the same GPU -- and
+# `check` gets, per call, {report name: variants} (lvm_profile_variants) and asserts the kernel the case is there for: a case that
+# silently ran the default kernels fails.
+_CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "live-video-magnification_amd", "csrc")
+
+
+def up_tile():
+    """(UT_W, UT_H): the tile of the LDS-tiled k_lap_up, read from csrc/pyramid.h"""
+    text = open(os.path.join(_CSRC, "pyramid.h"), encoding="utf-8").read()
+    return tuple(int(re.search(r"#define LVM_UT_%s (\d+)" % k, text).group(1)) for k in "WH")
+
+
+def tiled_up_blocks(w, h, ns):
+    """workgroups of the tiled k_lap_up at level 1 of w x h BGR frames of ns streams (laplace.hip, lap_stage_a: grid.z = planes)"""
+    tw, th = up_tile()
+    w1, h1 = (w + 1) // 2, (h + 1) // 2
+    return -(-w1 // tw) * -(-h1 // th) * 3 * ns
+
+
+def _pow2_dividing(nt, cap):
+    d = cap
+    while d > 1 and nt % d:
+        d //= 2
+    return d
+
+
+def _present(name, variants=None, calls=None):
+    """`name` launched in every call (of `calls`: indices; default: all but the seeding first call), with exactly these variants"""
+    def check(prof, nts):
+        for k in (range(1, len(prof)) if calls is None else calls):
+            assert name in prof[k], (name, k, nts[k], sorted(prof[k]))
+            if variants is not None:
+                assert prof[k][name] == set(variants), (name, k, nts[k], prof[k][name], variants)
+    return check
+
+
+def _absent(*names, calls=None):
+    def check(prof, nts):
+        for k in (range(len(prof)) if calls is None else calls):
+            for name in names:
+                assert not any(re.fullmatch(name, n) for n in prof[k]), (name, k, nts[k], sorted(prof[k]))
+    return check
+
+
+def _by_frames(name, fn):
+    """per call after the first: `name` ran as exactly the variant fn(frames of the call)"""
+    def check(prof, nts):
+        for k in range(1, len(prof)):
+            assert prof[k].get(name) == {fn(nts[k])}, (name, k, nts[k], prof[k].get(name), fn(nts[k]))
+    return check
+
+
+def _all(*checks):
+    def check(prof, nts):
+        for c in checks:
+            c(prof, nts)
+    return check
+
+
+UP_CALLS = (1, 8, 4, 6, 3)         # every ring depth on a frame count it divides and on one it does not
+_FIN = {"LVM_FIN_ROWS": "8", "LVM_FIN_MIN_TASKS": "0"}
+_FPS7 = ({"framerate": 7.0}, {"fps": 7.0})            # Color: a window of 16 columns
+_FPS15 = ({"framerate": 15.0}, {"fps": 15.0})
+# level 1 of 132 x 1346 (66 x 673: two tile columns, the right one 2 pixels wide; 43 tile rows, the last one 1 pixel high) on four streams:
+# 2 x 43 tiles x 12 planes = 1032 tiled workgroups, of the frames that reach the 1024 from which the launch code reads LVM_UP_DEPTH_BIG
+# about the fewest pixels (tests assert the count from UT_W / UT_H: tiled_up_blocks)
+BIG_UP = (132, 1346, 3, 4)
+
+SWITCH_CASES = {}
+
+
+def _case(key, idx, size, calls, env, check, ns=1, over=None, clip_over=None):
+    assert key not in SWITCH_CASES, key
+    SWITCH_CASES[key] = dict(idx=idx, size=size, ns=ns, calls=tuple(calls), env=env, check=check, over=over, clip_over=clip_over)
+
+
+# odd intermediate sizes, a coarsest tile that is no multiple of 8, several tiles.  Per-frame calls, then one call of two frames: at the two
+# small sizes the LDS-resident tail kernel builds the coarse levels of a per-frame call itself and leaves pyrDown fewer than three levels,
+# so k_pyr_down_multi<3> runs there in the batch only (a batch has no tail kernel); at 1001 x 763 in every call.  (At 135 x 77 the tail kernel
+# starts at level 1: a per-frame call has no pyrDown launch at all.)
+for _s, _pf, _pf1 in [((330, 200, 6), (), (0, 1, 2)), ((135, 77, 4), (), ()), ((1001, 763, 5), (0, 1, 2), (0, 1, 2))]:
+    _case("fuse_down3-%dx%d" % _s[:2], 0, _s, (1, 1, 1, 2), {"LVM_FUSE_DOWN": "3"}, _present("pyr_down3_l1", calls=_pf + (3,)))
+    _case("fuse_down1-%dx%d" % _s[:2], 0, _s, (1, 1, 1, 2), {"LVM_FUSE_DOWN": "1"},
+          _all(_present("pyr_down_l1", calls=_pf1 + (3,)), _absent(r"pyr_down[23]_l\d+")))
+for _d in (1, 2, 4, 8):
+    _case("up_depth%d" % _d, 0, (328, 109, 3), UP_CALLS, {"LVM_UP_ROWS": "0", "LVM_UP_DEPTH": str(_d)},
+          _all(_by_frames("lap_up_l1", lambda nt, d=_d: "tiled d%d curn" % _pow2_dividing(nt, d)),
+               _by_frames("lap_iir", lambda nt: "d%d" % _pow2_dividing(nt, 8))))
+for _d in (2, 4, 8):
+    _case("up_depth_big%d" % _d, 0, BIG_UP[:3], (1, 8, 4), {"LVM_UP_DEPTH_BIG": str(_d)},
+          _by_frames("lap_up_l1", lambda nt, d=_d: "tiled d%d curn" % _pow2_dividing(nt, d)), ns=BIG_UP[3])
+_case("up_rows_max_blocks", 0, BIG_UP[:3], (1, 8, 4), {"LVM_UP_ROWS_MAX_BLOCKS": "1000000"},
+      _by_frames("lap_up_l1", lambda nt: "rows d4 curn"), ns=BIG_UP[3])
+for _r in (1, 3, 4, 16):          # 16 is halved to <= 4 at these sizes, 3 to 3: the halving loop from a start that is no power of two
+    for _s in ROWS_PYRDOWN:
+        _case("pd_rows%d-%dx%d" % ((_r,) + _s[:2]), 0, _s, (1, 1, 1), {"LVM_ROWS_MIN_ELEMS": "0", "LVM_PD_ROWS": str(_r)},
+              _present("pyr_down_rows_l1", calls=(0, 1, 2)))
+_case("d0_rows0-laplace", 0, (328, 109, 3), (1, 1, 1), {"LVM_D0_ROWS": "0", "LVM_D0_MIN_TASKS": "0"}, _present("lap_down0", {"vec4"}, calls=(0, 1, 2)))
+_case("d0_rows0-color", 3, (264, 90, 3), (7, 5, 1), {"LVM_D0_ROWS": "0", "LVM_D0_MIN_TASKS": "0", "LVM_COL_DOWN01": "0"},
+      _all(_present("col_down0", {"vec4"}, calls=(0, 1)), _absent("col_down01")), over=_FPS15[0], clip_over=_FPS15[1])
+for _r in (5, 16):                # a height below the launch code's own choices (6 .. 48) and one of them
+    for _s in [t[:3] for t in FUSED_TABLE if t[3]]:
+        _case("d0_fused_rows%d-%dx%d" % ((_r,) + _s[:2]), 0, _s, (1, 1, 1), {"LVM_D0_FUSED_WAVES": "1", "LVM_D0_FUSED_ROWS": str(_r)},
+              _all(_present("lap_down0_lut", calls=(0, 1, 2)), _absent("lap_down0", "lab_lut")))
+# persistent kernels: one workgroup (or a few) walks every strip of every frame -- the state carried from task to task
+for _g in (1, 3):
+    _case("d0_fused_groups%d" % _g, 0, (328, 109, 3), (1, 4, 3), dict(_FIN, LVM_D0_FUSED_WAVES="1", LVM_D0_FUSED_GROUPS=str(_g)),
+          _all(_present("lap_down0_lut", calls=(0, 1, 2)), _present("lap_final", {"strips"}, calls=(0, 1, 2))))
+for _g in (1, 7):
+    _case("fin_groups%d" % _g, 0, (328, 109, 3), (1, 4, 3), dict(_FIN, LVM_FIN_GROUPS=str(_g)), _present("lap_final", {"strips"}, calls=(0, 1, 2)))
+for _g in (1, 5):                 # (the tiled last kernel is the persistent one: the strip form of level 0 switched off)
+    _case("rz_fin_groups%d" % _g, 2, (264, 150, 3), (1, 4, 3), {"LVM_RZ_FIN_GROUPS": str(_g), "LVM_RZ_COLLAPSE_STRIPS": "0"},
+          _present("rz_final", {"vec4"}))
+_case("rz_phase4_0", 2, (264, 150, 3), (1, 4, 3), {"LVM_RZ_PHASE4": "0"}, _all(_present("rz_phase_small"), _absent("rz_phase")))
+_RZ_TILES = {"LVM_RZ_SPLIT_ROWS": "0", "LVM_RZ_SPLIT2_MIN": "0"}          # the 9 x 9 split as tiles: 4 x 2 outputs per thread, or (LVM_RZ_SPLIT2=0) one
+_case("rz_split2_default", 2, (264, 150, 3), (1, 4, 3), _RZ_TILES, _present("rz_split_l0", {"4x2"}, calls=(0, 1, 2)))
+_case("rz_split2_0", 2, (264, 150, 3), (1, 4, 3), dict(_RZ_TILES, LVM_RZ_SPLIT2="0"), _present("rz_split_l0", {"tile"}, calls=(0, 1, 2)))
+_SPLIT_CALLS = (1, 4, 1, 5, 2, 8)
+_case("lap_split_min_nt4", 0, (320, 182, 5), _SPLIT_CALLS, {"LVM_LAP_SPLIT_MIN_NT": "4"},
+      _all(_present("lap_iir", calls=[k for k, n in enumerate(_SPLIT_CALLS) if n >= 4]), _present("lap_collapse", calls=[k for k, n in enumerate(_SPLIT_CALLS) if n >= 4]),
+           _absent("lap_iir", "lap_collapse", calls=[k for k, n in enumerate(_SPLIT_CALLS) if n < 4])))
+for _k, (_lo, _hi) in enumerate(NARROW_DFT_BANDS):
+    _case("col_thin_dft0-band%d" % _k, 3, (64, 48, 2), (18, 5, 7, 9), {"LVM_COL_THIN_DFT": "0"}, _present("col_dft", {"wave"}, calls=(0, 1, 2, 3)),
+          over=dict(_FPS7[0], coLow=_lo, coHigh=_hi), clip_over=_FPS7[1])
+# the window (16 columns) is full after the first call: from then on 1- and 2-frame calls take the wave-per-row kernel, the others the thin one
+_THIN_CALLS = (18, 1, 5, 2, 4, 1)
+_case("col_thin_min_frames4", 3, (64, 48, 2), _THIN_CALLS, {"LVM_COL_THIN_MIN_FRAMES": "4"},
+      _all(_present("col_dft", {"wave"}, calls=(1, 3, 5)), _present("col_dft", {"thin8-128"}, calls=(2, 4))),
+      over=dict(_FPS7[0], coLow=0.8, coHigh=1.6), clip_over=_FPS7[1])
+# The first pyrUp of the up chain is a k_pyr_up_rows launch where the top level's width is even, and then the default normalises inside it.
+# 96 x 64 and 528 x 90 (top levels 12 and 66 wide) are such: the switches move them to the other path.  264 x 90 (top level 33 wide) takes
+# the tiled pyrUp and k_col_norm whatever the switches say.
+for _s, _even in [((96, 64, 3), True), ((264, 90, 3), False), ((528, 90, 3), True)]:
+    _on = _all(_present("col_norm", calls=(0, 1, 2)), _present("pyr_up_l0", {"rows" if _even else "tiled"}, calls=(0, 1, 2)))
+    _case("col_up_default-%dx%d" % _s[:2], 3, _s, (7, 5, 1), {},
+          _all(_absent("col_norm"), _present("pyr_up_l0", {"rows-norm"}, calls=(0, 1, 2))) if _even else _on, over=_FPS15[0], clip_over=_FPS15[1])
+    _case("col_norm_in_up0-%dx%d" % _s[:2], 3, _s, (7, 5, 1), {"LVM_COL_NORM_IN_UP": "0"}, _on, over=_FPS15[0], clip_over=_FPS15[1])
+    _case("col_up_rows0-%dx%d" % _s[:2], 3, _s, (7, 5, 1), {"LVM_COL_UP_ROWS": "0"},
+          _all(_present("col_norm", calls=(0, 1, 2)), _present("pyr_up_l0", {"tiled"}, calls=(0, 1, 2))), over=_FPS15[0], clip_over=_FPS15[1])
+# k_lap_collapse<N>, N = levels - F: F = 3 in calls of >= 4 frames (from 5 levels on), else 2.  N = 7 needs 9 levels, N = 8 ten.
+# N = 9 and N = 10 need frames of at least 5121 x 5121 and 10241 x 10241 (lvm_max_levels = 11, 12): compiled, not tested.
+DEEP = {4: (320, 180), 6: (256, 256), 7: (512, 384), 8: (1024, 768), 9: (1536, 1284), 10: (3072, 2564)}
+
+
+def _collapse_n(levels):
+    return lambda nt: "n%d" % (levels - (3 if nt >= 4 and levels >= 5 else 2))
+
+
+for _lv, _wh in DEEP.items():
+    _case("deep%d" % _lv, 0, _wh + (_lv,), (1, 2) if _lv in (4, 10) else (1, 4, 2), {}, _by_frames("lap_collapse", _collapse_n(_lv)))
+# the defaults and the two-level pyramid (level 1 is the top live level: no cur_2 to add) for the ledger of instantiations
+_case("up_default", 0, (328, 109, 3), UP_CALLS, {}, _by_frames("lap_up_l1", lambda nt: "rows d%d curn" % _pow2_dividing(nt, 4)))
+_case("up_default-2levels", 0, (320, 180, 2), UP_CALLS, {}, _by_frames("lap_up_l1", lambda nt: "rows d%d" % _pow2_dividing(nt, 4)))
+_case("up_tiled-2levels", 0, (320, 180, 2), UP_CALLS, {"LVM_UP_ROWS": "0"}, _by_frames("lap_up_l1", lambda nt: "tiled d%d" % _pow2_dividing(nt, 8)))
+_NARROW = dict(_FPS7[0], coLow=0.8, coHigh=1.6)
+_case("col_dft_thin8", 3, (64, 48, 2), (18, 5, 1), {}, _present("col_dft", {"thin8-128"}, calls=(0, 1)), over=_NARROW, clip_over=_FPS7[1])
+_case("col_dft_thin", 3, (64, 48, 2), (18, 5, 1), {"LVM_COL_THIN8_DFT": "0"}, _present("col_dft", {"thin"}, calls=(0, 1)), over=_NARROW, clip_over=_FPS7[1])
+_case("col_dft_long", 3, (64, 48, 2), (18, 5, 1), {"LVM_COL_LONG_FROM": "2"}, _present("col_dft", {"long"}, calls=(0, 1)), over=_NARROW, clip_over=_FPS7[1])
+_case("col_dft_serial", 3, (64, 48, 2), (18, 5, 1), {"LVM_COL_LONG_FROM": "2", "LVM_COL_LONG_DFT": "0"}, _present("col_dft", {"serial"}, calls=(0, 1)),
+      over=_NARROW, clip_over=_FPS7[1])
+# a window of 129 .. 256 columns (120 fps: 256): k_col_dft_thin8<kThin8MaxN> once 129 frames are in
+_case("col_dft_thin8_256", 3, (40, 30, 1), (120, 12, 8), {}, _all(_present("col_dft", {"thin8-128"}, calls=(0,)), _present("col_dft", {"thin8"}, calls=(2,))),
+      over={"framerate": 120.0, "coLow": 0.8, "coHigh": 1.6}, clip_over={"fps": 120.0})
+
+# What the launch code can pick at run time, as (report name without its level, variant): the ledger tests assert that the cases above reach
+# every one.  k_lap_collapse<9> and <10> are left out (unreachable below 5121 x 5121 and 10241 x 10241, see DEEP).
+REQUIRED = ({("lap_up", "%s d%d%s" % (k, d, c)) for k, ds in (("rows", (1, 2, 4)), ("tiled", (1, 2, 4, 8))) for d in ds for c in ("", " curn")}
+            | {("lap_iir", "d%d" % d) for d in (1, 2, 4, 8)} | {("lap_collapse", "n%d" % n) for n in range(2, 9)}
+            | {("col_dft", v) for v in ("thin8-128", "thin8", "thin", "wave", "long", "serial")})
+
+
+# Values the validators of the switches refuse (csrc: laplace_switches): the default must run.  Emulation only -- the point of the validators is
+# that such a value never reaches a kernel, so these are kept apart from SWITCH_CASES and no GPU test runs them.
+_ROWS_ON = {"LVM_ROWS_MIN_ELEMS": "0"}
+REFUSED_CASES = {
+    # a ring of 3 (6) would launch k_lap_up<false, 4> (<8>) on 3 (6) frames: a frame past the batch.  Refused: the default 8, halved to fit
+    "refused-up_depth3": (0, (328, 109, 3), (1, 3, 3), {"LVM_UP_ROWS": "0", "LVM_UP_DEPTH": "3"}, _present("lap_up_l1", {"tiled d1 curn"})),
+    "refused-up_depth6": (0, (328, 109, 3), (1, 6), {"LVM_UP_ROWS": "0", "LVM_UP_DEPTH": "6"}, _present("lap_up_l1", {"tiled d2 curn"})),
+    "refused-pd_rows0": (0, (328, 109, 3), (1, 1, 1), dict(_ROWS_ON, LVM_PD_ROWS="0"), _present("pyr_down_rows_l1", calls=(0, 1, 2))),
+    "refused-pd_rows-4": (0, (328, 109, 3), (1, 1, 1), dict(_ROWS_ON, LVM_PD_ROWS="-4"), _present("pyr_down_rows_l1", calls=(0, 1, 2))),
+    "refused-fin_groups-1": (0, (328, 109, 3), (1, 4, 3), dict(_FIN, LVM_FIN_GROUPS="-1"), _present("lap_final", {"strips"}, calls=(0, 1, 2))),
+    # 7 would read as ">= 3", the three-level kernel.  Refused: the default, two levels per launch
+    "refused-fuse_down7": (0, (330, 200, 6), (1, 1, 2), {"LVM_FUSE_DOWN": "7"},
+                           _all(_present("pyr_down2_l1", calls=(2,)), _absent(r"pyr_down3_l\d+"))),
+}
+REFUSED_SWITCH = {"refused-up_depth3": "LVM_UP_DEPTH", "refused-up_depth6": "LVM_UP_DEPTH", "refused-pd_rows0": "LVM_PD_ROWS",
+                  "refused-pd_rows-4": "LVM_PD_ROWS", "refused-fin_groups-1": "LVM_FIN_GROUPS", "refused-fuse_down7": "LVM_FUSE_DOWN"}
+
+
+def _lookup(key):
+    if key in SWITCH_CASES:
+        return SWITCH_CASES[key]
+    idx, size, calls, env, check = REFUSED_CASES[key]
+    return dict(idx=idx, size=size, ns=1, calls=calls, env=env, check=check, over=None, clip_over=None)
+
+
+def switch_run(lvm, lib, mem, key, env=None):
+    """the library's side of SWITCH_CASES[key] (env: the switches, default the case's): per call (input frames, produced flags, output
+    frames, float frame of the call's first frame or None, {report name: variants})"""
+    c = _lookup(key)
+    w, h, levels = c["size"]
+    ns = c["ns"]
+    ck, pk = lvm.synth.config(c["idx"], c["size"])
+    pk.update(c["over"] or {})
+    ck.update(c["clip_over"] or {})
+    clips = [lvm.synth.Clip(seed=1234 + s, **ck) for s in range(ns)]
+    env = c["env"] if env is None else env
+    saved = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    ctx, res, t, fb = None, [], 0, w * h * 3
+    try:
+        ctx = lvm.Context(0, ns, lib)
+        ctx.exact_lab(True)
+        ctx.keep_float(ns == 1)
+        ctx.profile(True)
+        cp = lvm.LvmParams(pk["mode"], pk["levels"], pk["amplification"], pk["coWavelength"], pk["coLow"], pk["coHigh"], pk["chromAttenuation"],
+                           pk["framerate"], 0)
+        for nf in c["calls"]:
+            fin = np.stack([np.stack([cl.frame(t + f) for cl in clips]) for f in range(nf)])      # [frame][stream][h][w][3]
+            d_in = mem.upload(fin)
+            d_out = mem.zeros_like(d_in)
+            prod = ctx.process_device_frames(cp, nf, mem.ptr(d_in), w, h, 3, w * 3, fb, fb * ns, mem.ptr(d_out), w * 3, fb, fb * ns, mem.stream())
+            mem.sync(ctx)
+            out = np.array(mem.download(d_out), copy=True)
+            # (Laplace and Riesz keep the float frame of a call's first frame, Color of its last: read after 1-frame calls)
+            fl = ctx.read_float((h, w, 3)).copy() if ns == 1 and prod[0] and (nf == 1 or c["idx"] != 3) else None
+            variants = ctx.profile_variants()
+            names = {n: variants.get(n, set()) for n in ctx.profile_collect()}
+            ctx.profile_only(None)                     # clears the report: the next call's launches on their own
+            res.append((fin, list(prod), out, fl, names))
+            t += nf
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+        if ctx is not None:
+            ctx.close()
+    return pk, res
+
+
+_LAUNCHED = {}          # (build, case) -> per call {report name: variants}, of the cases that have passed in this process
+
+
+def switch_case(lvm, po, lib, mem, build, key, reference="oracle"):
+    """One case of SWITCH_CASES on the library `lib` (`build`: "emu" / "gpu", the ledger's key): bytes and float frames against the
+    oracle, or (reference="default": Riesz on the GPU, device acosf / sinf / cosf) against the same library without the case's switches;
+    then the case's check of what was launched.  Returns the launches per call; a case that has passed is not run again."""
+    if (build, key) in _LAUNCHED:
+        return _LAUNCHED[(build, key)]
+    c = _lookup(key)
+    pk, res = switch_run(lvm, lib, mem, key)
+    if reference == "default":
+        _, base = switch_run(lvm, lib, mem, key, env={})
+        for k, ((_, prod, out, fl, _n), (_, bprod, bout, bfl, _m)) in enumerate(zip(res, base)):
+            assert prod == bprod, (key, k, prod, bprod)          # (a frame that was not produced leaves its zeros in both)
+            assert np.array_equal(out, bout), "%s call %d: %d bytes differ from the default kernels" % (key, k, int((out != bout).sum()))
+            assert (fl is None) == (bfl is None) and (fl is None or np.array_equal(fl, bfl)), "%s call %d: float frames differ from the default kernels" % (key, k)
+        assert any(p for r in res for p in r[1]), key
+    else:
+        P = po.make_params(**pk)
+        orcs = [po.Oracle() for _ in range(c["ns"])]
+        try:
+            t = 0
+            for k, (fin, prod, out, fl, _n) in enumerate(res):
+                for f in range(len(prod)):
+                    for s in range(c["ns"]):
+                        ref, pr = orcs[s].process(fin[f, s], P)
+                        assert prod[f] == pr, (key, t + f, prod[f], pr)
+                        if not pr:
+                            continue
+                        assert np.array_equal(ref, out[f, s]), "%s frame %d stream %d: %d bytes differ from the oracle" % (
+                            key, t + f, s, int((ref != out[f, s]).sum()))
+                        if fl is not None and f == 0:
+                            fr = orcs[s].last_float()
+                            assert np.array_equal(fr, fl), "%s frame %d: %d float values differ from the oracle" % (key, t + f, int((fr != fl).sum()))
+                t += len(prod)
+        finally:
+            for o in orcs:
+                o.close()
+    prof = [r[4] for r in res]
+    c["check"](prof, list(c["calls"]))
+    _LAUNCHED[(build, key)] = prof
+    return prof
+
+
+# the cases that between them launch all of REQUIRED ("deep10" where the build runs it)
+LEDGER_KEYS = (["up_depth%d" % d for d in (1, 2, 4, 8)] + ["up_default", "up_default-2levels", "up_tiled-2levels", "col_thin_dft0-band0"]
+               + ["deep%d" % lv for lv in DEEP] + ["col_dft_thin8", "col_dft_thin", "col_dft_long", "col_dft_serial", "col_dft_thin8_256"])
+
+
+def ledger(lvm, po, lib, mem, build, keys, reference=None):
+    """(report name without its level, variant) of everything the cases `keys` launch on this build (cases that have not run yet run now)"""
+    seen = set()
+    for key in keys:
+        ref = (reference or {}).get(key, "oracle")
+        for call in switch_case(lvm, po, lib, mem, build, key, ref):
+            for name, variants in call.items():
+                seen |= {(re.sub(r"_l\d+$", "", name), v) for v in variants}
+    return seen

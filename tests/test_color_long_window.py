@@ -272,7 +272,7 @@ def _b_check(lvm, lib, mem, name, beyond="long", stop=None):
     want = g[name + "_frames"][:len(got)]
     bad = [(clip["keep_from"] + k, int((got[k] != want[k]).sum())) for k in range(len(want)) if not np.array_equal(got[k], want[k])]
     assert not bad, "%d frames differ from the oracle's, (frame, bytes) %s" % (len(bad), bad[:8])
-    assert short == set(), short                                    # windows up to 1024 frames: the kernels that report no variant
+    assert short and short <= {"thin8-128", "thin8", "thin", "wave"}, short     # windows up to 1024 frames: their own kernels, never "long" / "serial"
     assert variants == {beyond}, variants
     return batches
 
