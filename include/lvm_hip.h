@@ -470,6 +470,10 @@ int  lvm_debug_clock_probe_start(lvm_ctx* ctx, double max_seconds);
 int  lvm_debug_clock_probe_stop(lvm_ctx* ctx, double* mhz, double* seconds);
 int  lvm_debug_sweep_u8_steps(lvm_ctx* ctx, uint32_t first_bits, uint64_t count, uint64_t* mismatches, uint32_t* first_bad_bits);
 int  lvm_debug_lab_analytic(lvm_ctx* ctx, int on);
+/* The portable transcendental functions of the Riesz mode (csrc/rz_trig.h: what the exact flavour calls under LVM_RZ_PORTABLE_TRIG=1 and
+ * the oracle under LVMO_VAR_PORTABLE_TRIG) ON THE DEVICE: d_y[i] = fn(d_x[i]) for n floats in device memory, fn 0 = rz_acosf, 1 = rz_sinf,
+ * 2 = rz_cosf.  Asynchronous on `stream` (null: the context's own).                                                                   */
+int  lvm_debug_trig_eval(lvm_ctx* ctx, int fn, const float* d_x, float* d_y, size_t n, void* stream);
 /* The forward table: LVM_LAB_LUT_ENTRIES int16 values in OpenCV's RGB2Labprev order, index 3 (p + 33 q + 1089 r) + channel
  * with p, q, r the R, G, B grid indices and entries L / 100 * 16384, (a + 128) / 256 * 16384, (b + 128) / 256 * 16384.
  * lvm_create builds it by restating initLabTabs (color_lab.cpp); lvm_set_lab_lut installs another one, e.g. the table of

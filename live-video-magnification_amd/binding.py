@@ -106,7 +106,7 @@ class LvmError(RuntimeError):
 
 SYMBOLS = ["lvm_create", "lvm_destroy", "lvm_reset", "lvm_process", "lvm_process_device", "lvm_process_device_frames", "lvm_set_pipeline", "lvm_flush", "lvm_synchronize",
            "lvm_last_error", "lvm_max_levels", "lvm_optimal_buffer_size", "lvm_butterworth2",
-           "lvm_debug_keep_float", "lvm_debug_read_float", "lvm_debug_exact_lab", "lvm_debug_sweep_u8_steps", "lvm_debug_clock_probe_start", "lvm_debug_clock_probe_stop", "lvm_debug_lab_analytic", "lvm_get_lab_lut", "lvm_set_lab_lut", "lvm_profile_enable", "lvm_profile_collect", "lvm_profile_only",
+           "lvm_debug_keep_float", "lvm_debug_read_float", "lvm_debug_exact_lab", "lvm_debug_sweep_u8_steps", "lvm_debug_clock_probe_start", "lvm_debug_clock_probe_stop", "lvm_debug_lab_analytic", "lvm_debug_trig_eval", "lvm_get_lab_lut", "lvm_set_lab_lut", "lvm_profile_enable", "lvm_profile_collect", "lvm_profile_only",
            "lvm_profile_entry", "lvm_profile_variants", "lvm_algorithmic_bytes", "lvm_export_geometry", "lvm_export_frames", "lvm_export_set_overlay", "lvm_overlay_device", "lvm_tile_riesz_stage1", "lvm_tile_riesz_planes", "lvm_tile_riesz_stage2",
            "lvm_preprocess_geometry", "lvm_preprocess_device", "lvm_chain_process", "lvm_chain_process_batch",
            "lvm_set_max_frames", "lvm_host_alloc", "lvm_host_free", "lvm_compose_geometry", "lvm_compose_device", "lvm_chain_process_batch_ex",
@@ -145,6 +145,7 @@ def bind(lib):
     lib.lvm_debug_clock_probe_start.argtypes = [vp, C.c_double]
     lib.lvm_debug_clock_probe_stop.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.lvm_debug_sweep_u8_steps.argtypes = [vp, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+    lib.lvm_debug_trig_eval.argtypes = [vp, C.c_int, vp, vp, C.c_size_t, vp]
     lib.lvm_get_lab_lut.argtypes = [vp, vp]
     lib.lvm_set_lab_lut.argtypes = [vp, vp]
     lib.lvm_profile_enable.argtypes = [vp, C.c_int]
@@ -590,6 +591,11 @@ class Context:
     def lab_analytic(self, on=True):
         """Analytic forward Lab (OpenCV with its interpolation switched off) instead of the 33^3 table."""
         self._check(self.lib.lvm_debug_lab_analytic(self.h, int(on)))
+
+    def trig_eval(self, fn, d_x, d_y, n, stream=None):
+        """d_y[i] = fn(d_x[i]) on the device for n floats (device pointers); fn 0 = rz_acosf, 1 = rz_sinf, 2 = rz_cosf of csrc/rz_trig.h
+        (lvm_debug_trig_eval).  Asynchronous on `stream`."""
+        self._check(self.lib.lvm_debug_trig_eval(self.h, int(fn), d_x, d_y, int(n), stream))
 
     def lab_lut(self):
         """The forward table in use: int16 [33*33*33*3], index 3 (p + 33 q + 1089 r) + channel."""

@@ -1071,6 +1071,17 @@ int lvm_debug_clock_probe_stop(lvm_ctx* c, double* mhz, double* seconds) {
 
 int lvm_debug_lab_analytic(lvm_ctx* c, int on) { if (!c) return LVM_ERR_INVALID; c->lab_analytic = on != 0; return LVM_OK; }
 
+int lvm_debug_trig_eval(lvm_ctx* c, int fn, const float* d_x, float* d_y, size_t n, void* hip_stream) {
+    if (!c || fn < 0 || fn > 2 || (n && (!d_x || !d_y))) return LVM_ERR_INVALID;
+    LVM_HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
+    int rc = lvm::order_after_previous(c, s);
+    if (rc != LVM_OK) return rc;
+    rc = lvm::riesz_trig_eval(c, fn, d_x, d_y, n, s);
+    lvm::mark_enqueued(c, s);
+    return rc;
+}
+
 int lvm_get_lab_lut(lvm_ctx* c, int16_t* dst) {
     if (!c || !dst) return LVM_ERR_INVALID;
     std::memcpy(dst, c->lab_lut_compact.data(), c->lab_lut_compact.size() * sizeof(int16_t));

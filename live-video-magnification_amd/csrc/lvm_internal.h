@@ -714,6 +714,7 @@ int riesz_create(Ctx* c, int levels, const FrameIO& io, hipStream_t s);
 int color_create(Ctx* c, int levels, const FrameIO& io, hipStream_t s);
 int riesz_tile_residual(Ctx* c, float* d_dst, int* rw, int* rh, hipStream_t s);
 int riesz_tile_finish(Ctx* c, const lvm_params& p, const FrameIO& io, const float* d_residual, hipStream_t s);
+int riesz_trig_eval(Ctx* c, int fn, const float* d_x, float* d_y, size_t n, hipStream_t s);   // rz_trig.h on the device: fn 0 = rz_acosf, 1 = rz_sinf, 2 = rz_cosf
 
 // host tables (lab_tables.cpp)
 void build_lab_tables(float gamma_u8[256], float invgamma[4096], float fwd[9], float inv[9]);

@@ -37,6 +37,8 @@
 #include <type_traits>
 
 #include "lvm_internal.h"
+#define RZ_TRIG_FN __host__ __device__ __forceinline__
+#include "rz_trig.h"
 
 namespace lvm {
 
@@ -515,10 +517,12 @@ struct PhaseArgs {
 constexpr int PT_W = 32, PT_H = 8;
 
 // arcCos (RieszPyramid.cpp:8-23): out-of-range input returns -1 / +1, not pi / 0
+// PT (LVM_RZ_PORTABLE_TRIG, exact flavour only): rz_acosf of rz_trig.h -- the bits of the oracle under LVMO_VAR_PORTABLE_TRIG -- in place of the device libm's acosf
+template <bool PT>
 __device__ __forceinline__ float arc_cos(float x) {
     if (x < -1.0f) return -1.0f;
     if (x > 1.0f) return 1.0f;
-    return acosf(x);
+    return PT ? rz_acosf(x) : acosf(x);
 }
 __device__ __forceinline__ float mul_sd(float x, double s) { return (float)((double)x * s); }
 // The same product for the default flavour without the float64 unit: s = hi + lo (two floats, exact to 2^-48), x * hi is
@@ -534,8 +538,9 @@ __device__ __forceinline__ float mul_sf(float x, SdF s) { return x * s.hi; }
 // is processed.
 // UNF: the 5-tap Riesz pair with unfused taps (LVM_CV_FILTER_UNFUSED); MF32: `Mat * double` of the IIR step with the scalar narrowed to
 // float first (LVM_CV_MUL_F32) -- x * (float)s, in place of the exact flavour's float64 product and of the default flavour's hi / lo pair.
-template <bool EXACT, bool UNF, bool MF32>
+template <bool EXACT, bool UNF, bool MF32, bool PT = false>
 __global__ __launch_bounds__(256) void k_rz_phase(PhaseArgs aa) {
+    static_assert(EXACT || !PT, "the portable functions belong to the exact flavour");
     __shared__ float s[PT_H + 4][PT_W + 4 + 1];
     int lvl = 0;
     const int bid = (int)blockIdx.x;       // (the XCD-aware order of lvm_internal.h was measured here: blur 730 -> 875 us per 32 frames, phase unchanged)
@@ -600,7 +605,7 @@ __global__ __launch_bounds__(256) void k_rz_phase(PhaseArgs aa) {
         const float q2 = R2 * np + r2 * Pp;
         const float xy = q1 * q1 + q2 * q2;                                // :89
         const float ampq = sqrtf(q0 * q0 + xy);                            // :91
-        const float phi = arc_cos(q0 / ampq);                              // :93-97
+        const float phi = arc_cos<PT>(q0 / ampq);                          // :93-97
         // The acos argument above keeps IEEE sqrt and division in every flavour (it is the ill-conditioned step);
         // the direction q/|q| and the amplitude are well-conditioned: the default flavour uses v_rsq / v_sqrt there.
         float dc, ds;
@@ -654,8 +659,9 @@ __global__ __launch_bounds__(256) void k_rz_phase(PhaseArgs aa) {
 // thread and plane instead of four 4-byte ones, and a third less halo traffic than the 32 x 8 tile (1.33 x instead of
 // 1.69 x the band).  Same per-pixel arithmetic, same order: bit-identical to k_rz_phase.
 constexpr int P4_W = 64, P4_H = 16, P4_SW = P4_W + 8, P4_SH = P4_H + 4;
-template <bool EXACT, bool UNF, bool MF32>
+template <bool EXACT, bool UNF, bool MF32, bool PT = false>
 __global__ __launch_bounds__(256) void k_rz_phase4(PhaseArgs aa) {
+    static_assert(EXACT || !PT, "the portable functions belong to the exact flavour");
     __shared__ __attribute__((aligned(16))) float s[P4_SH][P4_SW];
     int lvl = 0;
     const int bid = (int)blockIdx.x;       // (the XCD-aware order of lvm_internal.h was measured here: blur 730 -> 875 us per 32 frames, phase unchanged)
@@ -754,7 +760,7 @@ __global__ __launch_bounds__(256) void k_rz_phase4(PhaseArgs aa) {
             const float q2 = R2[k] * np + r2 * Pp[k];
             const float xy = q1 * q1 + q2 * q2;
             const float ampq = sqrtf(q0 * q0 + xy);
-            const float phi = arc_cos(q0 / ampq);
+            const float phi = arc_cos<PT>(q0 / ampq);
             float dc, ds;
             if (EXACT) {
                 const float sxy = sqrtf(xy);
@@ -815,14 +821,16 @@ struct BlurArgs {                      // all band levels in one launch (indepen
 // in [0, pi], absolute error ~1e-6): the phase-shifted band moves by ~1e-6 of its amplitude, and nothing
 // downstream feeds back into the temporal state.  The precise sinf/cosf pair alone is ~200 instructions
 // per pixel, more than the three 13-tap Gaussians together.
-template <bool EXACT>
+// PT (LVM_RZ_PORTABLE_TRIG, with EXACT): rz_cosf / rz_sinf of rz_trig.h in place of the device libm's pair.
+template <bool EXACT, bool PT = false>
 __device__ __forceinline__ float rz_amplify(float v0, float v1, float v2, float r1, float r2, float band, float alpha, float thr) {
+    static_assert(EXACT || !PT, "the portable functions belong to the exact flavour");
     if (EXACT) {
         const float c = v1 / v0, sn = v2 / v0;                         // :125-126
         const float magV = sqrtf(c * c + sn * sn);                     // :133-134
         float magV2 = magV * alpha;                                     // :135
         magV2 = magV2 < thr ? magV2 : thr;                               // :136 THRESH_TRUNC = v_min(src, thr): NaN -> thr (minps)
-        const float cp = cosf(magV2), sp = sinf(magV2);                // :138
+        const float cp = PT ? rz_cosf(magV2) : cosf(magV2), sp = PT ? rz_sinf(magV2) : sinf(magV2);   // :138
         float pair = (r1 * c + r2 * sn) / magV;                        // :139-140
         if (pair != pair) pair = 0.f;                                  // :141
         return band * cp - pair * sp;                                  // :143
@@ -841,7 +849,7 @@ __device__ __forceinline__ float rz_amplify(float v0, float v1, float v2, float 
 }
 
 // UNF (all three forms of this stage): the taps of the row and column passes unfused (LVM_CV_FILTER_UNFUSED, rz_tap)
-template <bool EXACT, bool UNF>
+template <bool EXACT, bool UNF, bool PT = false>
 __global__ __launch_bounds__(256) void k_rz_blur_amp(BlurArgs aa) {
     __shared__ float s[3][BSH][BS + 1];
     __shared__ float hr[3][BSH][BT + 1];
@@ -882,7 +890,7 @@ __global__ __launch_bounds__(256) void k_rz_blur_amp(BlurArgs aa) {
             v[f] = acc;
         }
         const size_t idx = pl + (size_t)gy * a.w + gx;
-        a.bandA[idx] = rz_amplify<EXACT>(v[0], v[1], v[2], a.R1[idx], a.R2[idx], a.band[idx], aa.alpha, aa.thr);
+        a.bandA[idx] = rz_amplify<EXACT, PT>(v[0], v[1], v[2], a.R1[idx], a.R2[idx], a.band[idx], aa.alpha, aa.thr);
     }
 }
 
@@ -906,7 +914,7 @@ constexpr int B2W = 64, B2H = LVM_BLUR_H, B2T = 8 * B2H, B2HX = 8, B2HY = 6, B2S
 #else
 #define LVM_BLUR_BOUNDS __launch_bounds__(B2T)
 #endif
-template <bool EXACT, bool UNF>
+template <bool EXACT, bool UNF, bool PT = false>
 __global__ LVM_BLUR_BOUNDS void k_rz_blur_amp4(BlurArgs aa) {
     __shared__ __attribute__((aligned(16))) float s[B2SH][B2SW];
     __shared__ __attribute__((aligned(16))) float hr[B2SH][B2W];
@@ -1001,7 +1009,7 @@ __global__ LVM_BLUR_BOUNDS void k_rz_blur_amp4(BlurArgs aa) {
         float o[4];
 #pragma unroll
         for (int m = 0; m < 4; ++m)
-            o[m] = rz_amplify<EXACT>(bl[0][d][m], bl[1][d][m], bl[2][d][m], R1[m], R2[m], Bd[m], aa.alpha, aa.thr);
+            o[m] = rz_amplify<EXACT, PT>(bl[0][d][m], bl[1][d][m], bl[2][d][m], R1[m], R2[m], Bd[m], aa.alpha, aa.thr);
         *reinterpret_cast<float4*>(a.bandA + idx) = make_float4(o[0], o[1], o[2], o[3]);
     }
 }
@@ -1153,11 +1161,15 @@ __global__ __launch_bounds__(256) void k_rz_collapse(const float* __restrict__ b
 __device__ __attribute__((noinline)) float rz_amplify_exact_call(float v0, float v1, float v2, float r1, float r2, float band, float alpha, float thr) {
     return rz_amplify<true>(v0, v1, v2, r1, r2, band, alpha, thr);
 }
+__device__ __attribute__((noinline)) float rz_amplify_ptrig_call(float v0, float v1, float v2, float r1, float r2, float band, float alpha, float thr) {
+    return rz_amplify<true, true>(v0, v1, v2, r1, r2, band, alpha, thr);      // (LVM_RZ_PORTABLE_TRIG; out of line for the same reason)
+}
 constexpr int BSW = 116, BS_THREADS = 256;
 struct BlurStripLv { const float *amp, *tc, *ts, *band, *R1, *R2; float* bandA; int w, h, sx, sy, rows, task0; };
 struct BlurStripArgs { BlurStripLv lv[kMaxBands]; int nlv, ntasks; float g[13]; float alpha, thr; };
-template <bool EXACT, bool UNF>
+template <bool EXACT, bool UNF, bool PT = false>
 __global__ __launch_bounds__(BS_THREADS) void k_rz_blur_strips(BlurStripArgs aa) {
+    static_assert(EXACT || !PT, "the portable functions belong to the exact flavour");
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
     // (launch order; the XCD-aware order of lvm_internal.h was measured here too: 550 -> 719-734 us per 32 frames)
     const int task = blockIdx.x * (BS_THREADS / 64) + wave;
@@ -1259,7 +1271,10 @@ __global__ __launch_bounds__(BS_THREADS) void k_rz_blur_strips(BlurStripArgs aa)
                 if (owner) {
                     const size_t idx = pl + (size_t)y * w + c0;
                     float2 o;
-                    if (EXACT) {      // the libm sine / cosine of the exact flavour is large: out of line, or the 13-phase loop does not unroll
+                    if (PT) {
+                        o.x = rz_amplify_ptrig_call(v[0][0], v[1][0], v[2][0], q1[0], q2[0], bd[0], aa.alpha, aa.thr);
+                        o.y = rz_amplify_ptrig_call(v[0][1], v[1][1], v[2][1], q1[1], q2[1], bd[1], aa.alpha, aa.thr);
+                    } else if (EXACT) {      // the libm sine / cosine of the exact flavour is large: out of line, or the 13-phase loop does not unroll
                         o.x = rz_amplify_exact_call(v[0][0], v[1][0], v[2][0], q1[0], q2[0], bd[0], aa.alpha, aa.thr);
                         o.y = rz_amplify_exact_call(v[0][1], v[1][1], v[2][1], q1[1], q2[1], bd[1], aa.alpha, aa.thr);
                     } else {
@@ -1850,6 +1865,8 @@ struct RieszState : ModeState {
     long blur_strips_min = 2000;     // ... for levels of at least this many plane-pixels per launch (LVM_RZ_BLUR_STRIPS_MIN).  Round 5: 2^19 -> 2000 -- per-frame calls used to
                                      // send level 1 (518 400 px) to the tiled kernel and the small levels to a third launch: 242 -> 205 us per 1080p frame with every even-width level in the ONE strip launch
     int blur_strip_rows = 64;        // rows per strip (LVM_RZ_BLUR_STRIP_ROWS), halved until a level has 4096 strips
+    bool portable_trig = false;      // LVM_RZ_PORTABLE_TRIG=1: the EXACT instantiations of the phase and blur / amplify kernels call rz_trig.h (the oracle's bits under
+                                     // LVMO_VAR_PORTABLE_TRIG, variant "ptrig") in place of the device libm; the default flavour ignores it
     double lo_freq = 0, hi_freq = 0, fps = 0;
     double la[3] = {}, lb[3] = {}, ha[3] = {}, hb[3] = {};
     bool steady(const lvm_params& p) const {
@@ -2012,18 +2029,19 @@ static void rz_phase(Ctx* c, RieszState* st, const RzBufs& B, int mode, hipStrea
     }
     a.nlv = n1; a4.nlv = n4;
     // (EXACT, UNF, MF32) -> instantiation
-    const bool exact = lab_flavour(c) != FL_LUT_FAST, unf = rz_unfused(c), mf32 = rz_mul_f32(c);
+    const bool exact = lab_flavour(c) != FL_LUT_FAST, unf = rz_unfused(c), mf32 = rz_mul_f32(c), ptrig = exact && st->portable_trig;
     auto pick = [&](auto vec4) {
         constexpr bool V4 = decltype(vec4)::value;
-        auto p2 = [&](auto e, auto u) {
-            constexpr bool E = decltype(e)::value, U = decltype(u)::value;
-            if constexpr (V4) return mf32 ? k_rz_phase4<E, U, true> : k_rz_phase4<E, U, false>;
-            else return mf32 ? k_rz_phase<E, U, true> : k_rz_phase<E, U, false>;
+        auto p2 = [&](auto e, auto u, auto pt) {
+            constexpr bool E = decltype(e)::value, U = decltype(u)::value, PT = decltype(pt)::value;
+            if constexpr (V4) return mf32 ? k_rz_phase4<E, U, true, PT> : k_rz_phase4<E, U, false, PT>;
+            else return mf32 ? k_rz_phase<E, U, true, PT> : k_rz_phase<E, U, false, PT>;
         };
-        auto p1 = [&](auto e) { return unf ? p2(e, std::true_type{}) : p2(e, std::false_type{}); };
-        return exact ? p1(std::true_type{}) : p1(std::false_type{});
+        auto p1 = [&](auto e, auto pt) { return unf ? p2(e, std::true_type{}, pt) : p2(e, std::false_type{}, pt); };
+        return exact ? (ptrig ? p1(std::true_type{}, std::true_type{}) : p1(std::true_type{}, std::false_type{})) : p1(std::false_type{}, std::false_type{});
     };
-    const char* var = unf ? (mf32 ? "unfused+mulf32" : "unfused") : (mf32 ? "mulf32" : nullptr);
+    const char* var = ptrig ? (unf ? (mf32 ? "unfused+mulf32+ptrig" : "unfused+ptrig") : (mf32 ? "mulf32+ptrig" : "ptrig"))
+                            : (unf ? (mf32 ? "unfused+mulf32" : "unfused") : (mf32 ? "mulf32" : nullptr));
     if (n4) LVM_LAUNCH_KIND(c, mode ? "rz_seed" : "rz_phase", var, pick(std::true_type{}), dim3(blocks4), dim3(256), s, a4);
     if (n1) LVM_LAUNCH_KIND(c, mode ? "rz_seed_small" : "rz_phase_small", var, pick(std::false_type{}), dim3(blocks), dim3(256), s, a);
 }
@@ -2085,9 +2103,10 @@ static void rz_amplify(Ctx* c, RieszState* st, const lvm_params& p, const FrameI
             else { v.tx = (v.w + BT - 1) / BT; v.ty = (v.h + BTH - 1) / BTH; v.block0 = blocks; blocks += v.tx * v.ty * NZ; }
         }
         a.nlv = n1; a4.nlv = n4;
-        const bool exact = lab_flavour(c) != FL_LUT_FAST, unf = rz_unfused(c);
-        const char* var = unf ? "unfused" : nullptr;
-#define LVM_RZ_BLUR_PICK(K) (exact ? (unf ? K<true, true> : K<true, false>) : (unf ? K<false, true> : K<false, false>))
+        const bool exact = lab_flavour(c) != FL_LUT_FAST, unf = rz_unfused(c), ptrig = exact && st->portable_trig;
+        const char* var = ptrig ? (unf ? "unfused+ptrig" : "ptrig") : (unf ? "unfused" : nullptr);
+#define LVM_RZ_BLUR_PICK(K) (exact ? (ptrig ? (unf ? K<true, true, true> : K<true, false, true>) : (unf ? K<true, true> : K<true, false>)) \
+                                   : (unf ? K<false, true> : K<false, false>))
         if (as.nlv) LVM_LAUNCH_KIND(c, "rz_blur_amp", var, LVM_RZ_BLUR_PICK(k_rz_blur_strips),
                                     dim3((unsigned)((as.ntasks + BS_THREADS / 64 - 1) / (BS_THREADS / 64))), dim3(BS_THREADS), s, as);
         if (n4) LVM_LAUNCH_KIND(c, as.nlv ? "rz_blur_amp_tiles" : "rz_blur_amp", var, LVM_RZ_BLUR_PICK(k_rz_blur_amp4), dim3(blocks4), dim3(B2T), s, a4);
@@ -2225,6 +2244,22 @@ static void rz_collapse_out(Ctx* c, RieszState* st, const lvm_params& p, const F
                    c->lab, tx, ty, NZ, dbg, (const float*)B.oct[0], (const uint32_t*)B.iab);
 }
 
+// ---- lvm_debug_trig_eval: rz_trig.h on the device, value by value (tests hold it against the oracle's lvmo_trig_eval bit for bit) ----
+__global__ __launch_bounds__(256) void k_rz_trig_eval(int fn, const float* x, float* y, size_t n) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+        y[i] = fn == 0 ? rz_acosf(x[i]) : (fn == 1 ? rz_sinf(x[i]) : rz_cosf(x[i]));
+}
+int riesz_trig_eval(Ctx* c, int fn, const float* d_x, float* d_y, size_t n, hipStream_t s) {
+    if (n == 0) return LVM_OK;
+    size_t blocks = (n + 255) / 256;
+    if (blocks > 8 * (size_t)c->num_cus) blocks = 8 * (size_t)c->num_cus;
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(k_rz_trig_eval, dim3((unsigned)blocks), dim3(256), 0, s, fn, d_x, d_y, n);
+    LVM_HIP_TRY(c, hipGetLastError());
+    return LVM_OK;
+}
+
 static void riesz_switches(RieszState* st) {
     env_switch("LVM_RZ_BLUR4", st->blur4);
     env_switch("LVM_RZ_BLUR_STRIPS", st->blur_strips);
@@ -2242,6 +2277,7 @@ static void riesz_switches(RieszState* st) {
     env_switch("LVM_RZ_COLLAPSE_STRIPS_MIN", st->collapse_strips_min);
     env_switch("LVM_RZ_COLLAPSE_STRIP", st->collapse_strip, [](int v) { return v >= 2 && v % 2 == 0; });
     env_switch("LVM_RZ_SPLIT_ROWS_MIN", st->split_rows_min);
+    env_switch("LVM_RZ_PORTABLE_TRIG", st->portable_trig);
 }
 
 int riesz_create(Ctx* c, int levels, const FrameIO& io, hipStream_t s) {

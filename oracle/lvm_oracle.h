@@ -123,11 +123,15 @@ enum {
     LVMO_VAR_SPLINE_CV3      = 128,  /* gamma / inverse-gamma splines in the OpenCV 3.x form of splineBuild (forward sweep to n-2, x 0.3333333333333333f) instead of
                                         OpenCV 4's (sweep to n-1, / 3): what rounds 1-4 restated */
     LVMO_VAR_DFT_F32         = 256,  /* Color band-pass: both transforms in binary32 (radix-2 FFT for power-of-two windows) instead of float64 direct sums */
-    LVMO_VAR_FILTER_DFT      = 512   /* filter2D with kw * kh >= 50 through its DFT path (crossCorr; builds without SSE3 = every ARM build): the 9 x 9 Riesz kernels as
+    LVMO_VAR_FILTER_DFT      = 512,  /* filter2D with kw * kh >= 50 through its DFT path (crossCorr; builds without SSE3 = every ARM build): the 9 x 9 Riesz kernels as
                                         float64 sums rounded once instead of binary32 fma chains */
+    LVMO_VAR_PORTABLE_TRIG   = 1024  /* Riesz acosf / cosf / sinf through csrc/rz_trig.h (float64 evaluation rounded once, no libm call) instead of the C library's: the
+                                        same bits as the kernels under LVM_RZ_PORTABLE_TRIG, on any host and on the GPU */
 };
 void     lvmo_set_variant(unsigned mask);
 unsigned lvmo_get_variant(void);
+/* rz_trig.h on arrays: fn 0 = rz_acosf, 1 = rz_sinf, 2 = rz_cosf; returns 0, or -1 for another fn */
+int      lvmo_trig_eval(int fn, const float* x, float* y, size_t n);
 
 /* Exporter::compose (export/Exporter.cpp:53-88) without the text overlay */
 int lvmo_compose_geometry(int split, int ow, int oh, int pw, int ph, int* cw, int* ch);

@@ -97,6 +97,7 @@ def lib():
         L.lvmo_set_variant.argtypes = [C.c_uint]
         L.lvmo_set_variant.restype = None
         L.lvmo_get_variant.restype = C.c_uint
+        L.lvmo_trig_eval.argtypes = [C.c_int, _f32p, _f32p, C.c_size_t]
         L.lvmo_compose_geometry.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip]
         L.lvmo_compose.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_ssize_t, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                    C.c_ssize_t, C.c_void_p, C.c_ssize_t]
@@ -108,11 +109,21 @@ def lib():
 
 # lvm_oracle.h LVMO_VAR_*: the unpinned OpenCV build choices as switches (0 = the restatement the parity tests use)
 VARIANTS = {"pyr_simd": 1, "filter_unfused": 2, "addw_fused": 4, "mul_f32": 8, "gamma_f32": 16, "lut_nudge_up": 32,
-            "lut_nudge_down": 64, "spline_cv3": 128, "dft_f32": 256, "filter_dft": 512}
+            "lut_nudge_down": 64, "spline_cv3": 128, "dft_f32": 256, "filter_dft": 512, "portable_trig": 1024}
+TRIG_FNS = {"acos": 0, "sin": 1, "cos": 2}          # csrc/rz_trig.h: rz_acosf, rz_sinf, rz_cosf (lvmo_trig_eval, lvm_debug_trig_eval)
 
 
 def set_variant(mask):
     lib().lvmo_set_variant(int(mask))
+
+
+def trig_eval(fn, x):
+    """rz_acosf / rz_sinf / rz_cosf of csrc/rz_trig.h (fn: "acos" / "sin" / "cos", or 0 / 1 / 2) on a float32 array"""
+    x = np.ascontiguousarray(x, np.float32)
+    y = np.empty_like(x)
+    rc = lib().lvmo_trig_eval(int(TRIG_FNS.get(fn, fn)), x, y, x.size)
+    assert rc == 0, fn
+    return y
 
 
 def gamma_tab(inverse):

@@ -227,8 +227,167 @@ def color_narrow_band_dft(lvm, po, lib, mem, monkeypatch, lo, hi, thin8):
                 clip_over={"fps": 7.0})
 
 
+# ---- Riesz (phase) ---------------------------------------------------------------------------------
+# Run on the CPU emulation build by tests/test_emu_parity.py (host libm on both sides) and on the gfx950 build by
+# tests/test_gpu_riesz_exact.py under portable_trig() below: csrc/rz_trig.h on both sides, so the GPU owes the oracle's bits too.
+def portable_trig(monkeypatch, po, oracle_bits=()):
+    """LVM_RZ_PORTABLE_TRIG=1 for the contexts created from here on (monkeypatch restores it) and LVMO_VAR_PORTABLE_TRIG, plus
+    `oracle_bits` (names of po.VARIANTS), for the oracle: the caller -- a fixture -- sets the oracle's mask back to 0 when the test ends"""
+    monkeypatch.setenv("LVM_RZ_PORTABLE_TRIG", "1")
+    mask = po.VARIANTS["portable_trig"] | sum(po.VARIANTS[b] for b in oracle_bits)
+    po.set_variant(mask)
+    return mask
+
+
+PTRIG_NAMES = ("rz_phase", "rz_phase_small", "rz_blur_amp", "rz_blur_amp_small", "rz_blur_amp_tiles")
+
+
+def ptrig_launches(names):
+    """of {report name: variants}: the phase and blur / amplify launches, each of which must have run as a `ptrig` variant and nothing else"""
+    got = {n: v for n, v in names.items() if n in PTRIG_NAMES}
+    assert any(n.startswith("rz_phase") for n in got) and any(n.startswith("rz_blur_amp") for n in got), names
+    for n, v in got.items():
+        assert v and all("ptrig" in x.split("+") for x in v), (n, v)
+    return got
+
+
+def no_ptrig_launches(names):
+    assert not any("ptrig" in x for v in names.values() for x in v), names
+
+
+def profiled_call(lvm, lib, mem, w, h, levels, env=None, kind=0, nframes=3, exact_lab=True):
+    """one profiled lvm_process_device_frames call of `nframes` frames behind two seeding per-frame calls, exact flavour:
+    ({report name: variants} of that call, its output frames, its input frames)"""
+    import os
+    ck, pk = lvm.synth.config(2, (w, h, levels))
+    clip = lvm.synth.Clip(**ck)
+    env = env or {}
+    saved = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    ctx = None
+    fb = w * h * 3
+    try:
+        ctx = lvm.Context(0, 1, lib)
+        ctx.exact_lab(exact_lab)
+        if kind:
+            ctx.set_opencv_build(kind)
+        cp = lvm.LvmParams(pk["mode"], pk["levels"], pk["amplification"], pk["coWavelength"], pk["coLow"], pk["coHigh"], pk["chromAttenuation"],
+                           pk["framerate"], 0)
+        fin = np.stack([clip.frame(t) for t in range(2 + nframes)])
+        d_in = mem.upload(fin)
+        d_out = mem.zeros_like(d_in)
+        for t in range(2):
+            ctx.process_device_frames(cp, 1, mem.ptr(d_in, t), w, h, 3, w * 3, fb, fb, mem.ptr(d_out, t), w * 3, fb, fb, mem.stream())
+        mem.sync(ctx)
+        ctx.profile(True)
+        prod = ctx.process_device_frames(cp, nframes, mem.ptr(d_in, 2), w, h, 3, w * 3, fb, fb, mem.ptr(d_out, 2), w * 3, fb, fb, mem.stream())
+        mem.sync(ctx)
+        assert all(prod), prod
+        variants = ctx.profile_variants()
+        names = {n: variants.get(n, set()) for n in ctx.profile_collect()}
+        return names, np.array(mem.download(d_out), copy=True), fin
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+        if ctx is not None:
+            ctx.close()
+
+
+RIESZ_SHAPES = [(96, 64, 3), (135, 77, 4), (64, 48, 1), (67, 131, 2), (160, 90, 5), (134, 78, 2)]
+
+
+def riesz_shape(lvm, po, lib, w, h, levels):
+    ck, pk = lvm.synth.config(2, (w, h, levels))
+    return run_pair(lvm, po, lib, lvm.synth.Clip(**ck), pk, 6, 0.0, exact=True)
+
+
+RIESZ_TILE_KERNELS = [(264, 150, 3, (2, 1, 2)), (160, 90, 5, (2, 3)), (96, 64, 3, (2, 1, 1))]
+
+
+def riesz_wide_and_narrow_tile_kernels(lvm, po, lib, mem, monkeypatch, w, h, levels, calls, wide):
+    """k_rz_split2 / k_rz_phase4 (wide = "1") or k_rz_split / k_rz_phase ("0") forced onto small frames, per-frame calls between
+    temporal batches"""
+    monkeypatch.setenv("LVM_RZ_SPLIT2_MIN", "0" if wide == "1" else "1000000000")
+    monkeypatch.setenv("LVM_RZ_PHASE4_MIN_FRAMES", "1" if wide == "1" else "2")
+    monkeypatch.setenv("LVM_RZ_SPLIT_ROWS", "0")
+    frames_clip(lvm, po, lib, mem, 2, w, h, levels, 1, calls)
+
+
+def riesz_register_blocked_blur(lvm, po, lib, monkeypatch, blur4):
+    monkeypatch.setenv("LVM_RZ_BLUR4", blur4)
+    monkeypatch.setenv("LVM_RZ_BLUR_STRIPS", "0")         # (the strip form is the default for every even-width level since round 5)
+    ck, pk = lvm.synth.config(2, (264, 150, 3))
+    return run_pair(lvm, po, lib, lvm.synth.Clip(**ck), pk, 4, 0.0, exact=True)
+
+
+RIESZ_STRIP_BLUR = [(264, 150, 3, "16", True), (134, 78, 2, "64", True), (520, 70, 3, "32", True), (264, 150, 3, "16", False)]
+
+
+def riesz_strip_blur(lvm, po, lib, monkeypatch, w, h, levels, rows, exact):
+    monkeypatch.setenv("LVM_RZ_BLUR_STRIPS_MIN", "0")
+    monkeypatch.setenv("LVM_RZ_BLUR_STRIP_ROWS", rows)
+    ck, pk = lvm.synth.config(2, (w, h, levels))
+    return run_pair(lvm, po, lib, lvm.synth.Clip(**ck), pk, 4, 0.0 if exact else 1e-4, exact=exact)
+
+
+def riesz_strip_blur_in_temporal_batches(lvm, po, lib, mem, monkeypatch):
+    monkeypatch.setenv("LVM_RZ_BLUR_STRIPS_MIN", "0")
+    monkeypatch.setenv("LVM_RZ_BLUR_STRIP_ROWS", "32")
+    frames_clip(lvm, po, lib, mem, 2, 264, 150, 3, 2, (2, 4, 1))
+
+
+def riesz_tiled_blur(lvm, po, lib, monkeypatch):
+    monkeypatch.setenv("LVM_RZ_BLUR_STRIPS", "0")
+    ck, pk = lvm.synth.config(2, (264, 150, 3))
+    return run_pair(lvm, po, lib, lvm.synth.Clip(**ck), pk, 3, 0.0, exact=True)
+
+
+def riesz_collapse_tile_variants(lvm, po, lib, monkeypatch, compact):
+    monkeypatch.setenv("LVM_RZ_COMPACT", compact)
+    ck, pk = lvm.synth.config(2, (264, 150, 3))
+    return run_pair(lvm, po, lib, lvm.synth.Clip(**ck), pk, 3, 0.0, exact=True)
+
+
+def riesz_cutoff_change_gray_and_reset(lvm, po, lib):
+    ck, pk = lvm.synth.config(2, (96, 64, 3))
+
+    def vary(t, p):
+        if t >= 3:
+            p["coLow"] = 1.0            # MagnifyCore.hpp:243-248: new coefficients, filters cleared, prior rebuilt
+        if t >= 5:
+            p["coHigh"] = 5.0
+        if t >= 7:
+            p["levels"] = 2             # structural change: re-init => passthrough frame
+        return p
+    run_pair(lvm, po, lib, lvm.synth.Clip(**ck), pk, 10, 0.0, exact=True, param_fn=vary)
+    gray = lvm.synth.Clip(96, 64, channels=1)
+    run_pair(lvm, po, lib, gray, pk, 3, 0.0, exact=True)    # < 3 channels: always passthrough (:212)
+
+
+RIESZ_BATCHES = [(96, 64, 3, 1, (2, 5, 3)), (135, 77, 4, 2, (3, 4)), (160, 90, 5, 1, (6, 2)), (64, 48, 1, 1, (4,))]
+RIESZ_SPLIT_STRIPS = (["0", "10", "54"], [(520, 70, 3), (256, 41, 2), (1000, 24, 2), (128, 5, 2)])            # (strip heights, sizes)
+RIESZ_COLLAPSE_STRIPS = (["0", "10", "64"], [(512, 64, 4), (520, 70, 2), (1000, 24, 2), (8, 4, 2)])
+
+
+def riesz_wave_strip_stencils(lvm, po, lib, monkeypatch, w, h, levels, strip):
+    monkeypatch.setenv("LVM_RZ_SPLIT_ROWS_MIN", "1")
+    monkeypatch.setenv("LVM_RZ_SPLIT_STRIP", strip)
+    ck, pk = lvm.synth.config(2, (w, h, levels))
+    return run_pair(lvm, po, lib, lvm.synth.Clip(**ck), pk, 4, 0.0, exact=True)
+
+
+def riesz_wave_strip_collapse_and_output(lvm, po, lib, monkeypatch, w, h, levels, strip):
+    monkeypatch.setenv("LVM_RZ_COLLAPSE_STRIPS_MIN", "1")
+    monkeypatch.setenv("LVM_RZ_COLLAPSE_STRIP", strip)
+    ck, pk = lvm.synth.config(2, (w, h, levels))
+    return run_pair(lvm, po, lib, lvm.synth.Clip(**ck), pk, 4, 0.0, exact=True)
+
+
 # ---- every mode: layouts, degenerate content, parameters, shapes ----------------------------------------------------------
-PADDED_STRIDES = [(0, 4, 8), (0, 1, 3), (2, 4, 4), (2, 7, 1), (3, 8, 4), (3, 5, 5)]
+PADDED_STRIDES =[(0, 4, 8), (0, 1, 3), (2, 4, 4), (2, 7, 1), (3, 8, 4), (3, 5, 5)]
 
 
 # Views into larger buffers (helpers.layout_clip): (extra canvas columns, rx, ry, ox, oy, stream gap bytes, order).  The launch code
@@ -302,11 +461,14 @@ def layout_case(lvm, po, lib, mem, idx, w, h, levels, n_streams, name, env=None,
                        exact=exact, profile=profile, clip_fn=clip_fn)
 
 
-def layout_forced_case(lvm, po, lib, mem, force, name, exact=True, clip_fn=None):
-    """one forced case: the bytes, and the kernels LAYOUT_LAUNCHES names for this layout -- a silent fall-back to another kernel family fails"""
+def layout_forced_case(lvm, po, lib, mem, force, name, exact=True, clip_fn=None, ptrig=False):
+    """one forced case: the bytes, and the kernels LAYOUT_LAUNCHES names for this layout -- a silent fall-back to another kernel family fails.
+    ptrig (under portable_trig()): the phase and blur / amplify launches LAYOUT_LAUNCHES expects run as their `ptrig` variant"""
     idx, w, h, levels, env = LAYOUT_FORCED[force]
     worst, names = layout_case(lvm, po, lib, mem, idx, w, h, levels, 1, name, env=env, exact=exact, profile=True, clip_fn=clip_fn)
     want = dict(LAYOUT_LAUNCHES[force]["*"], **LAYOUT_LAUNCHES[force][name])
+    if ptrig:
+        want = {n: ({"ptrig"} if n in PTRIG_NAMES and v == set() else v) for n, v in want.items()}
     for n, variants in want.items():
         if variants is None:
             assert n not in names, (force, name, n, names)
@@ -445,10 +607,10 @@ def chroma_gray(lvm, po, lib):
 CHROMA_FORCED_CASES = [(kind, force) for kind in CHROMA_FORCED_KINDS for force in LAYOUT_FORCED]
 
 
-def chroma_forced(lvm, po, lib, mem, kind, force, exact=True):
+def chroma_forced(lvm, po, lib, mem, kind, force, exact=True, ptrig=False):
     """an entry of LAYOUT_FORCED at its own size and switches on the view that keeps every strip kernel (B): the bytes, and the
     kernels LAYOUT_LAUNCHES names"""
-    return layout_forced_case(lvm, po, lib, mem, force, "B", exact=exact, clip_fn=content.clip_fn(lvm, kind))
+    return layout_forced_case(lvm, po, lib, mem, force, "B", exact=exact, clip_fn=content.clip_fn(lvm, kind), ptrig=ptrig)
 
 
 CHROMA_ANALYTIC = [(kind,) + a for kind in CHROMA_FORCED_KINDS for a in (ANALYTIC[0], ANALYTIC[2])]
@@ -673,9 +835,57 @@ REFUSED_SWITCH = {"refused-up_depth3": "LVM_UP_DEPTH", "refused-up_depth6": "LVM
                   "refused-pd_rows-4": "LVM_PD_ROWS", "refused-fin_groups-1": "LVM_FIN_GROUPS", "refused-fuse_down7": "LVM_FUSE_DOWN"}
 
 
+# ---- the portable functions (LVM_RZ_PORTABLE_TRIG + LVMO_VAR_PORTABLE_TRIG): one case per instantiation that calls them --------------
+# k_rz_phase / k_rz_phase4 <true, UNF, MF32, true> under every build kind of (UNF, MF32), and the three forms of the blur / amplify stage --
+# wave strips (with the out-of-line rz_amplify_ptrig_call), register-blocked tiles, scalar tiles -- <true, UNF, true>.  Run by
+# tests/test_emu_portable_trig.py and tests/test_gpu_riesz_exact.py through switch_case under portable_trig(): bytes and float frames
+# equal to the oracle's, and every phase and blur / amplify launch reported as the `ptrig` variant of its kind.  Sizes: 264 x 150 L3
+# (levels 264 and 132 wide: four pixels per thread, register-blocked tiles) and 134 x 78 L2 (2 mod 4: the scalar kernels, strips).
+PTRIG_CASES = {}
+_CV_UNFUSED, _CV_MUL_F32 = 1, 4                               # LVM_CV_* (include/lvm_hip.h)
+_KIND_BITS = {0: (), _CV_UNFUSED: ("filter_unfused",), _CV_MUL_F32: ("mul_f32",), _CV_UNFUSED | _CV_MUL_F32: ("filter_unfused", "mul_f32")}
+_KIND_PHASE = {0: "ptrig", _CV_UNFUSED: "unfused+ptrig", _CV_MUL_F32: "mulf32+ptrig", _CV_UNFUSED | _CV_MUL_F32: "unfused+mulf32+ptrig"}
+
+
+def _ptrig_check(want, absent=()):
+    def check(prof, nts):
+        for k in range(1, len(prof)):
+            got = ptrig_launches(prof[k])
+            assert got == {n: {v} for n, v in want.items()}, (k, nts[k], got, want)
+            assert not any(n in prof[k] for n in absent), (k, absent, sorted(prof[k]))
+    return check
+
+
+def _ptrig_case(key, size, env, want, kind=0):
+    assert key not in PTRIG_CASES and key not in SWITCH_CASES, key
+    PTRIG_CASES[key] = dict(idx=2, size=size, ns=1, calls=(1, 1, 3, 2), env=env, check=_ptrig_check(want), over=None, clip_over=None, kind=kind,
+                            oracle_bits=_KIND_BITS[kind])
+
+
+for _kind in _KIND_BITS:
+    _blur = "unfused+ptrig" if _kind & _CV_UNFUSED else "ptrig"
+    _case_tail = "" if not _kind else "-" + _KIND_PHASE[_kind].replace("+ptrig", "")
+    _ptrig_case("ptrig-phase" + _case_tail, (134, 78, 2), {}, {"rz_phase_small": _KIND_PHASE[_kind], "rz_blur_amp": _blur}, _kind)
+    _ptrig_case("ptrig-phase4" + _case_tail, (264, 150, 3), {"LVM_RZ_PHASE4_MIN_FRAMES": "1"}, {"rz_phase": _KIND_PHASE[_kind], "rz_blur_amp": _blur}, _kind)
+for _kind in (0, _CV_UNFUSED):
+    _blur = "unfused+ptrig" if _kind else "ptrig"
+    _case_tail = "-unfused" if _kind else ""
+    _tiles = {"LVM_RZ_BLUR_STRIPS": "0", "LVM_RZ_PHASE4_MIN_FRAMES": "1"}
+    _ptrig_case("ptrig-blur-blocked" + _case_tail, (264, 150, 3), dict(_tiles, LVM_RZ_BLUR4="1"), {"rz_phase": _KIND_PHASE[_kind], "rz_blur_amp": _blur}, _kind)
+    _ptrig_case("ptrig-blur-tiled" + _case_tail, (264, 150, 3), dict(_tiles, LVM_RZ_BLUR4="0"), {"rz_phase": _KIND_PHASE[_kind], "rz_blur_amp_small": _blur}, _kind)
+# the smallest shape of tests/test_gpu_opencv_build.py (odd sizes: byte I/O, the scalar tile kernels) under the two kinds the header meets
+for _kind in (_CV_UNFUSED, _CV_MUL_F32):
+    _ptrig_case("ptrig-67x131-" + _KIND_PHASE[_kind].replace("+ptrig", ""), (67, 131, 2), {},
+                {"rz_phase_small": _KIND_PHASE[_kind], "rz_blur_amp_small": "unfused+ptrig" if _kind & _CV_UNFUSED else "ptrig"}, _kind)
+_ptrig_case("ptrig-blur-strips16", (264, 150, 3), {"LVM_RZ_BLUR_STRIPS_MIN": "0", "LVM_RZ_BLUR_STRIP_ROWS": "16", "LVM_RZ_PHASE4_MIN_FRAMES": "1"},
+            {"rz_phase": "ptrig", "rz_blur_amp": "ptrig"})
+
+
 def _lookup(key):
     if key in SWITCH_CASES:
         return SWITCH_CASES[key]
+    if key in PTRIG_CASES:
+        return PTRIG_CASES[key]
     idx, size, calls, env, check = REFUSED_CASES[key]
     return dict(idx=idx, size=size, ns=1, calls=calls, env=env, check=check, over=None, clip_over=None)
 
@@ -698,6 +908,8 @@ def switch_run(lvm, lib, mem, key, env=None):
         ctx = lvm.Context(0, ns, lib)
         ctx.exact_lab(True)
         ctx.keep_float(ns == 1)
+        if c.get("kind"):
+            ctx.set_opencv_build(c["kind"])
         ctx.profile(True)
         cp = lvm.LvmParams(pk["mode"], pk["levels"], pk["amplification"], pk["coWavelength"], pk["coLow"], pk["coHigh"], pk["chromAttenuation"],
                            pk["framerate"], 0)

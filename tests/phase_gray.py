@@ -35,15 +35,18 @@ def params(lvm, w, h, levels):
     return lvm.synth.config(2, (w, h, levels))[1]
 
 
-def reference(po, frames, pks, kind=0, analytic=False):
+def reference(po, frames, pks, kind=0, analytic=False, portable_trig=False):
     """[(produced, gray u8 frame, BGR float frame or None)] of the gray frames: the oracle on expand(g) with the parameters pks[t]
-    (a dict: the same for every frame), under the build kind `kind` and the forward Lab flavour, then BGR2GRAY"""
+    (a dict: the same for every frame), under the build kind `kind` and the forward Lab flavour, then BGR2GRAY.  portable_trig: the
+    oracle's LVMO_VAR_PORTABLE_TRIG besides (csrc/rz_trig.h: what the library computes under LVM_RZ_PORTABLE_TRIG).  The oracle's
+    variant mask is put back to what it was."""
     if isinstance(pks, dict):
         pks = [pks] * len(frames)
     orc = po.Oracle()
     out = []
     po.lib().lvmo_set_lab_lut(0 if analytic else 1)
-    po.set_variant(sum(po.VARIANTS[name] for bit, name in _ORACLE_BIT.items() if kind & bit))
+    before = int(po.lib().lvmo_get_variant())
+    po.set_variant(sum(po.VARIANTS[name] for bit, name in _ORACLE_BIT.items() if kind & bit) | (po.VARIANTS["portable_trig"] if portable_trig else 0))
     try:
         for g, pk in zip(frames, pks):
             u8, pr = orc.process(expand(g), po.make_params(**pk))
@@ -54,16 +57,16 @@ def reference(po, frames, pks, kind=0, analytic=False):
                     a.setflags(write=False)
             out.append((bool(pr), gray, fl))
     finally:
-        po.set_variant(0)
+        po.set_variant(before)
         po.lib().lvmo_set_lab_lut(1)
         orc.close()
     return out
 
 
 @functools.lru_cache(maxsize=None)
-def clip_reference(lvm, po, w, h, levels, kind=0, analytic=False, n=NFRAMES, seed=None):
+def clip_reference(lvm, po, w, h, levels, kind=0, analytic=False, n=NFRAMES, seed=None, portable_trig=False):
     """reference() of gray_clip(), computed once per case and shared (read-only arrays)"""
-    return tuple(reference(po, gray_clip(lvm, po, w, h, levels, n, seed), params(lvm, w, h, levels), kind, analytic))
+    return tuple(reference(po, gray_clip(lvm, po, w, h, levels, n, seed), params(lvm, w, h, levels), kind, analytic, portable_trig))
 
 
 def assert_not_vacuous(frames, refs):

@@ -32,84 +32,56 @@ def test_laplace_emu_two_streams_are_independent(lvm, po, emu):
 
 
 # ---- Riesz (phase) ---------------------------------------------------------------------------------
-@pytest.mark.parametrize("w,h,levels", [(96, 64, 3), (135, 77, 4), (64, 48, 1), (67, 131, 2), (160, 90, 5), (134, 78, 2)])
+@pytest.mark.parametrize("w,h,levels", M.RIESZ_SHAPES)
 def test_riesz_emu_bit_exact(lvm, po, emu, w, h, levels):
-    ck, pk = lvm.synth.config(2, (w, h, levels))
-    run_pair(lvm, po, emu, lvm.synth.Clip(**ck), pk, 6, 0.0, exact=True)
+    M.riesz_shape(lvm, po, emu, w, h, levels)
 
 
-@pytest.mark.parametrize("w,h,levels,calls", [(264, 150, 3, (2, 1, 2)), (160, 90, 5, (2, 3)), (96, 64, 3, (2, 1, 1))])
+@pytest.mark.parametrize("w,h,levels,calls", M.RIESZ_TILE_KERNELS)
 @pytest.mark.parametrize("wide", ["1", "0"])
 def test_riesz_emu_wide_and_narrow_tile_kernels(lvm, po, emu, w, h, levels, calls, wide, monkeypatch):
     """Round 5 picks the tile kernels by launch size: k_rz_split2 (4 x 2 outputs per thread) from 600 000 plane-pixels per launch, else
     k_rz_split (one output per thread); k_rz_phase4 (four pixels per thread) from two frames x streams per launch, else k_rz_phase.  Both
     choices forced onto small frames -- per-frame calls between temporal batches, so that the state written by one phase kernel is read
     by the other."""
-    monkeypatch.setenv("LVM_RZ_SPLIT2_MIN", "0" if wide == "1" else "1000000000")
-    monkeypatch.setenv("LVM_RZ_PHASE4_MIN_FRAMES", "1" if wide == "1" else "2")
-    monkeypatch.setenv("LVM_RZ_SPLIT_ROWS", "0")
-    frames_clip(lvm, po, emu, HOST, 2, w, h, levels, 1, calls)
+    M.riesz_wide_and_narrow_tile_kernels(lvm, po, emu, HOST, monkeypatch, w, h, levels, calls, wide)
 
 
 @pytest.mark.parametrize("blur4", ["1", "0"])
 def test_riesz_emu_register_blocked_blur(lvm, po, emu, blur4, monkeypatch):
     """k_rz_blur_amp4 (64 x 32 tiles, vector staging of interior tiles, 4 x 2 outputs per thread) against the
     scalar kernel's arithmetic: a frame with interior, edge and partial tiles on two levels."""
-    monkeypatch.setenv("LVM_RZ_BLUR4", blur4)
-    monkeypatch.setenv("LVM_RZ_BLUR_STRIPS", "0")         # (the strip form is the default for every even-width level since round 5)
-    ck, pk = lvm.synth.config(2, (264, 150, 3))
-    run_pair(lvm, po, emu, lvm.synth.Clip(**ck), pk, 4, 0.0, exact=True)
+    M.riesz_register_blocked_blur(lvm, po, emu, monkeypatch, blur4)
 
 
-@pytest.mark.parametrize("w,h,levels,rows,exact", [(264, 150, 3, "16", True), (134, 78, 2, "64", True), (520, 70, 3, "32", True), (264, 150, 3, "16", False)])
+@pytest.mark.parametrize("w,h,levels,rows,exact", M.RIESZ_STRIP_BLUR)
 def test_riesz_emu_strip_blur(lvm, po, emu, w, h, levels, rows, exact, monkeypatch):
     """k_rz_blur_strips (three 13-tap Gaussians + amplify as wave strips: DPP halo exchange over three lanes either side, a
     13-row register window per plane) forced onto small levels: several strips per row with mirrored edge columns, a last
     strip ending short of the wave, strips shorter than the 12 halo rows, odd heights, level widths 2 mod 4.
     exact=False: the default flavour (hardware sine / cosine) against the parity bars."""
-    monkeypatch.setenv("LVM_RZ_BLUR_STRIPS_MIN", "0")
-    monkeypatch.setenv("LVM_RZ_BLUR_STRIP_ROWS", rows)
-    ck, pk = lvm.synth.config(2, (w, h, levels))
-    run_pair(lvm, po, emu, lvm.synth.Clip(**ck), pk, 4, 0.0 if exact else 1e-4, exact=exact)
+    M.riesz_strip_blur(lvm, po, emu, monkeypatch, w, h, levels, rows, exact)
 
 
 def test_riesz_emu_strip_blur_in_temporal_batches(lvm, po, emu, monkeypatch):
     """Batched frames with the strip form forced onto every level: the phase kernel then stores no per-frame Riesz pair for
     those levels and the amplify stage recomputes it from the band (two streams, calls of several lengths)."""
-    monkeypatch.setenv("LVM_RZ_BLUR_STRIPS_MIN", "0")
-    monkeypatch.setenv("LVM_RZ_BLUR_STRIP_ROWS", "32")
-    frames_clip(lvm, po, emu, HOST, 2, 264, 150, 3, 2, (2, 4, 1))
+    M.riesz_strip_blur_in_temporal_batches(lvm, po, emu, HOST, monkeypatch)
 
 
 def test_riesz_emu_tiled_blur_still_matches(lvm, po, emu, monkeypatch):
-    monkeypatch.setenv("LVM_RZ_BLUR_STRIPS", "0")
-    ck, pk = lvm.synth.config(2, (264, 150, 3))
-    run_pair(lvm, po, emu, lvm.synth.Clip(**ck), pk, 3, 0.0, exact=True)
+    M.riesz_tiled_blur(lvm, po, emu, monkeypatch)
 
 
 @pytest.mark.parametrize("compact", ["1", "0"])
 def test_riesz_emu_collapse_tile_variants(lvm, po, emu, compact, monkeypatch):
     """The collapse kernels' zero-injected tile, compact (even rows / columns only; planes with even width and height) and
     full: interior (vector-staged) and border tiles on level 0, a plane with an odd height on level 1."""
-    monkeypatch.setenv("LVM_RZ_COMPACT", compact)
-    ck, pk = lvm.synth.config(2, (264, 150, 3))
-    run_pair(lvm, po, emu, lvm.synth.Clip(**ck), pk, 3, 0.0, exact=True)
+    M.riesz_collapse_tile_variants(lvm, po, emu, monkeypatch, compact)
 
 
 def test_riesz_emu_cutoff_change_gray_and_reset(lvm, po, emu):
-    ck, pk = lvm.synth.config(2, (96, 64, 3))
-
-    def vary(t, p):
-        if t >= 3:
-            p["coLow"] = 1.0            # MagnifyCore.hpp:243-248: new coefficients, filters cleared, prior rebuilt
-        if t >= 5:
-            p["coHigh"] = 5.0
-        if t >= 7:
-            p["levels"] = 2             # structural change: re-init => passthrough frame
-        return p
-    run_pair(lvm, po, emu, lvm.synth.Clip(**ck), pk, 10, 0.0, exact=True, param_fn=vary)
-    gray = lvm.synth.Clip(96, 64, channels=1)
-    run_pair(lvm, po, emu, gray, pk, 3, 0.0, exact=True)    # < 3 channels: always passthrough (:212)
+    M.riesz_cutoff_change_gray_and_reset(lvm, po, emu)
 
 
 # ---- Colour ----------------------------------------------------------------------------------------
@@ -278,7 +250,7 @@ def test_frames_api_other_modes_fall_back_frame_by_frame(lvm, po, emu):
     frames_clip(lvm, po, emu, HOST, 3, 96, 64, 3, 1, (4, 3))
 
 
-@pytest.mark.parametrize("w,h,levels,ns,calls", [(96, 64, 3, 1, (2, 5, 3)), (135, 77, 4, 2, (3, 4)), (160, 90, 5, 1, (6, 2)), (64, 48, 1, 1, (4,))])
+@pytest.mark.parametrize("w,h,levels,ns,calls", M.RIESZ_BATCHES)
 def test_riesz_emu_temporal_batches(lvm, po, emu, w, h, levels, ns, calls):
     frames_clip(lvm, po, emu, HOST, 2, w, h, levels, ns, calls)
 
@@ -350,30 +322,24 @@ def test_fast_final_kernel_strips_and_shortcut_paths(lvm, po, emu, w, h, levels)
     print("fast final kernel", (w, h, levels), worst)
 
 
-@pytest.mark.parametrize("strip", ["0", "10", "54"])
-@pytest.mark.parametrize("w,h,levels", [(520, 70, 3), (256, 41, 2), (1000, 24, 2), (128, 5, 2)])
+@pytest.mark.parametrize("strip", M.RIESZ_SPLIT_STRIPS[0])
+@pytest.mark.parametrize("w,h,levels", M.RIESZ_SPLIT_STRIPS[1])
 def test_riesz_emu_wave_strip_stencils(lvm, po, emu, w, h, levels, strip, monkeypatch):
     """The LDS-free 9x9 strip kernels (forced onto these small planes): several 248-column strips per row (a full one, a
     partial one, a strip whose last lane owns the image's last column group), strips cut by the image height, odd heights,
     the strip height chosen by the launch code (0) or forced (10 rows: several strips per column; 54: the 1080p choice), a
     plane of five rows (the row index of the loads bounces off both edges inside one group of steps), bit-exact against the oracle."""
-    monkeypatch.setenv("LVM_RZ_SPLIT_ROWS_MIN", "1")
-    monkeypatch.setenv("LVM_RZ_SPLIT_STRIP", strip)
-    ck, pk = lvm.synth.config(2, (w, h, levels))
-    run_pair(lvm, po, emu, lvm.synth.Clip(**ck), pk, 4, 0.0, exact=True)
+    M.riesz_wave_strip_stencils(lvm, po, emu, monkeypatch, w, h, levels, strip)
 
 
-@pytest.mark.parametrize("strip", ["0", "10", "64"])
-@pytest.mark.parametrize("w,h,levels", [(512, 64, 4), (520, 70, 2), (1000, 24, 2), (8, 4, 2)])
+@pytest.mark.parametrize("strip", M.RIESZ_COLLAPSE_STRIPS[0])
+@pytest.mark.parametrize("w,h,levels", M.RIESZ_COLLAPSE_STRIPS[1])
 def test_riesz_emu_wave_strip_collapse_and_output(lvm, po, emu, w, h, levels, strip, monkeypatch):
     """k_rz_collapse_strips forced onto small planes with even sizes: the collapse of levels 1 and 2 and the output kernel of a
     512 x 64 frame, several 248-column strips per row, strips cut by the image height, the smallest plane the kernel accepts
     (two column groups, four rows: every row index is a reflection), strip height chosen by the launch code or forced;
     OpenCV-order Lab arithmetic: bit-exact against the oracle."""
-    monkeypatch.setenv("LVM_RZ_COLLAPSE_STRIPS_MIN", "1")
-    monkeypatch.setenv("LVM_RZ_COLLAPSE_STRIP", strip)
-    ck, pk = lvm.synth.config(2, (w, h, levels))
-    run_pair(lvm, po, emu, lvm.synth.Clip(**ck), pk, 4, 0.0, exact=True)
+    M.riesz_wave_strip_collapse_and_output(lvm, po, emu, monkeypatch, w, h, levels, strip)
 
 
 def test_riesz_emu_strip_output_fast_flavour_equals_the_tiled_kernel(lvm, emu, monkeypatch):

@@ -31,14 +31,14 @@ def _per_frame(lvm, ctx, frames, pk, refs):
         assert np.array_equal(gray, out), "frame %d: %d bytes differ from the reference" % (t, int((gray != out).sum()))
 
 
-def _batched(lvm, emu, streams, pk, refs, flavour="exact", kind=0):
+def _batched(lvm, emu, streams, pk, refs, flavour="exact", kind=0, mem=HOST):
     """lvm_process_device_frames in calls of (1, 2, 1, 3): every stream's bytes, stream 0's float frame at the head of each call"""
     ctx = pg.context(lvm, emu, len(streams), flavour, kind=kind)
 
     def check_float(t, fg):
         assert np.array_equal(refs[0][t][2], fg), "frame %d: %d float values differ from the reference" % (t, int((refs[0][t][2] != fg).sum()))
     try:
-        prod, outs = pg.run_frames(lvm, ctx, HOST, streams, pk, check_float=check_float)
+        prod, outs = pg.run_frames(lvm, ctx, mem, streams, pk, check_float=check_float)
         for s, r in enumerate(refs):
             pg.assert_equals_reference(prod, outs[:, s], r, "stream %d" % s)
     finally:

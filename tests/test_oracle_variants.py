@@ -113,6 +113,30 @@ def test_riesz_envelope(base):
         assert rel <= 5e-3 and du <= 3 and same >= 0.99, (name, rows[name])
 
 
+def test_portable_trig_is_inside_the_parity_bars(base):
+    """LVMO_VAR_PORTABLE_TRIG (acosf / cosf / sinf through csrc/rz_trig.h instead of the C library's) on Riesz cfg2, 64 frames, against
+    the default oracle: inside the project's parity bars -- 1e-4 relative on the float frame, 1 LSB, >= 0.999 identical bytes: the
+    bars a libm of another make is held to, which is what the header is.  The figures go into DESIGN.md 5 (-s prints them)."""
+    got = run_clip(2, po.VARIANTS["portable_trig"])
+    rel, du, same = distance(base[2], got)
+    nfl = sum(int((fa != fb).sum()) for fa, fb in zip(base[2][0], got[0]) if fa is not None)
+    tot = sum(fa.size for fa in base[2][0] if fa is not None)
+    nu8 = sum(int((ua != ub).sum()) for ua, ub in zip(base[2][1], got[1]) if ua is not None)
+    print("cfg2 %-18s float %.2e  u8 max %d  identical %.5f  (%d of %d float values differ at all, %d bytes)" % ("portable_trig", rel, du, same, nfl, tot, nu8))
+    assert rel <= 1e-4 and du <= 1 and same >= 0.999, (rel, du, same)
+    assert po.lib().lvmo_get_variant() == 0
+
+
+@pytest.mark.parametrize("cfg", [0, 3])
+def test_portable_trig_leaves_laplace_and_color_alone(cfg, base):
+    """they call none of the three functions: bit-identical float frames and bytes under the bit"""
+    got = run_clip(cfg, po.VARIANTS["portable_trig"])
+    for t, (fa, fb, ua, ub) in enumerate(zip(base[cfg][0], got[0], base[cfg][1], got[1])):
+        assert (fa is None) == (fb is None), t
+        if fa is not None:
+            assert np.array_equal(fa, fb) and np.array_equal(ua, ub), (cfg, t)
+
+
 def test_variant_switches_change_the_primitives():
     """every switch reaches the code it names (a dead switch would make the envelope vacuous)"""
     rng = np.random.default_rng(5)

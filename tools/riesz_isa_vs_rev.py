@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Are the default-kind Riesz kernels the code they were?  Compiles csrc/riesz.hip of a git revision (default: HEAD~1) and of the working tree to
 gfx950 assembly with the Makefile's flags and compares, kernel by kernel, the instruction streams of the kernels the revision has with their
-mask-0 instantiations here (k_rz_split -> k_rz_split<TK_FMA>, k_rz_phase<E> -> k_rz_phase<E, false, false>, ...), labels and symbol names
-stripped.  Needs hipcc, no GPU.  usage: tools/riesz_isa_vs_rev.py [REV]; exit status 1 when a kernel differs or is missing."""
+mask-0 instantiations here (k_rz_split -> k_rz_split<TK_FMA>, k_rz_phase<E> -> k_rz_phase<E, false, false>, ...; the instantiations without the
+portable functions of LVM_RZ_PORTABLE_TRIG -- last template argument false -- stand for the kernels of a revision from before that argument), labels
+and symbol names stripped.  Needs hipcc, no GPU.  usage: tools/riesz_isa_vs_rev.py [REV]; exit status 1 when a kernel differs or is missing."""
 import os
 import re
 import subprocess
@@ -29,9 +30,16 @@ def kernels(asm):
     return {re.sub(r"^void ", "", p.split("(")[0]): out[n] for n, p in zip(names, plain)}
 
 
+def portable_off(name):
+    """the name an instantiation without the portable functions (LVM_RZ_PORTABLE_TRIG: the last template argument, false) had before that argument existed"""
+    name = re.sub(r"(k_rz_phase4?)<(\w+), (\w+), (\w+), false>", r"\1<\2, \3, \4>", name)
+    return re.sub(r"(k_rz_blur_\w+)<(\w+), (\w+), false>", r"\1<\2, \3>", name)
+
+
 def default_name(name):
     """the name a mask-0 instantiation of the working tree had before the kinds became template arguments"""
     name = name.replace("k_rz_split<0>", "k_rz_split")
+    name = portable_off(name)
     name = re.sub(r"(k_rz_phase4?)<(\w+), false, false>", r"\1<\2>", name)
     name = re.sub(r"(k_rz_blur_\w+)<(\w+), false>", r"\1<\2>", name)
     name = re.sub(r"k_rz_collapse<(\w+), 0>", r"k_rz_collapse<\1>", name)
@@ -49,7 +57,8 @@ def main():
         subprocess.check_call([hipcc] + FLAGS + ["-I" + tmp] + inc + ["-o", os.path.join(tmp, "rev.s"), os.path.join(tmp, "riesz.hip")])
         subprocess.check_call([hipcc] + FLAGS + inc + ["-o", os.path.join(tmp, "tree.s"), os.path.join(CSRC, "riesz.hip")])
         old, new = kernels(os.path.join(tmp, "rev.s")), kernels(os.path.join(tmp, "tree.s"))
-    new = {**{default_name(k): v for k, v in new.items()}, **new}   # (a revision that already has the kinds as template arguments: the names as they are)
+    # (a revision that already has the kinds as template arguments: the names as they are, or without the portable-functions argument)
+    new = {**{default_name(k): v for k, v in new.items()}, **{portable_off(k): v for k, v in new.items()}, **new}
     bad = [k for k in old if old[k] != new.get(k)]
     for k in bad:
         print("%s: %s" % ("MISSING" if k not in new else "DIFFERS (%d -> %d instructions)" % (len(old[k]), len(new[k])), k))
