@@ -632,13 +632,15 @@ __global__ __launch_bounds__(256) void k_lap_final(const uint8_t* __restrict__ i
 constexpr int FIN_THREADS = LVM_FIN_THREADS;
 struct Row3 { float4 c[3]; };            // horizontal-pass results of one source row, 3 channels x 4 columns
 #ifndef LVM_FIN_WAVES
-#define LVM_FIN_WAVES 0          // minimum waves per SIMD asked of the register allocator (0: none; 121 VGPRs = 4 waves)
+#define LVM_FIN_WAVES 0          // minimum waves per SIMD asked of the register allocator for EVERY instance (measurements; 0: fin_waves' own choice)
 #endif
-#if LVM_FIN_WAVES
-#define LVM_FIN_BOUNDS __launch_bounds__(FIN_THREADS, LVM_FIN_WAVES)
-#else
-#define LVM_FIN_BOUNDS __launch_bounds__(FIN_THREADS)
-#endif
+// The default instance (motion, no float frame, table flavour) fits 80 VGPRs without scratch -- six waves per SIMD, three 512-thread
+// workgroups per CU -- but only when the register allocator is told to aim there: left alone it settles at five waves (82 VGPRs),
+// which two workgroups of eight waves cannot use.  The other instances keep the budget they had (some would spill at 80).
+constexpr int fin_waves(bool motion, bool dbg, int fl) {
+    return LVM_FIN_WAVES ? LVM_FIN_WAVES : ((motion && !dbg && fl == FL_LUT_FAST && LVM_FIN_THREADS == 512) ? 6 : 1);
+}
+#define LVM_FIN_BOUNDS __launch_bounds__(FIN_THREADS, fin_waves(MOTION, DBG, FL))
 struct FinArgs {
     const uint8_t* in; long in_stride, in_sstride;
     uint8_t* out; long out_stride, out_sstride;
@@ -648,10 +650,11 @@ struct FinArgs {
 };
 // One output row of 4 pixels: Lab(in) + [1, ca, ca] * motion -> Lab2BGR -> u8 (MagnifyCore.hpp:143-153).  m = the motion image of the
 // row (EXACT: scaled by 1/64 as pyrUp does; otherwise the unscaled vertical sum, whose power-of-two scale `msc` is folded into the
-// add -- fma(m, 2^-k, L) rounds exactly like L + m * 2^-k).  dbg_px: where the float pixels go (lvm_debug_keep_float) or null.
+// add -- fma(m, 2^-k, L) rounds exactly like L + m * 2^-k; mca = msc * ca, the same for the chroma planes).  dbg_px: where the float
+// pixels go (lvm_debug_keep_float) or null.
 // STEPS (the default flavour without the float frame): s_igt points at the u8 step table instead of the spline (lab_to_u8)
 template <bool MOTION, bool DBG, int FL>
-__device__ __forceinline__ B96 lap_emit_row(const Raw4 pin, const float (&m)[3][4], const float msc, const float ca, const LabCoef& lab,
+__device__ __forceinline__ B96 lap_emit_row(const Raw4 pin, const float (&m)[3][4], const float msc, const float mca, const float ca, const LabCoef& lab,
                                             const float* s_igt, const float* s_gam, float* dbg_px) {
     constexpr bool EXACT = fl_exact(FL);
     constexpr bool STEPS = fin_steps(FL, DBG);
@@ -664,7 +667,7 @@ __device__ __forceinline__ B96 lap_emit_row(const Raw4 pin, const float (&m)[3][
             float L = L4[k], a = a4[k], bb = b4[k];
             if (MOTION) {
                 L = __builtin_fmaf(m[0][k], msc, L);
-                a = __builtin_fmaf(m[1][k], msc * ca, a); bb = __builtin_fmaf(m[2][k], msc * ca, bb);
+                a = __builtin_fmaf(m[1][k], mca, a); bb = __builtin_fmaf(m[2][k], mca, bb);
             }
             lab_to_u8(L, a, bb, lab.inv4096, reinterpret_cast<const uint2*>(s_igt), u[3 * k], u[3 * k + 1], u[3 * k + 2]);
         }
@@ -679,7 +682,7 @@ __device__ __forceinline__ B96 lap_emit_row(const Raw4 pin, const float (&m)[3][
             if (EXACT) { L = L + m[0][k]; a = a + m[1][k] * ca; bb = bb + m[2][k] * ca; }
             else {
                 L = __builtin_fmaf(m[0][k], msc, L);
-                a = __builtin_fmaf(m[1][k], msc * ca, a); bb = __builtin_fmaf(m[2][k], msc * ca, bb);
+                a = __builtin_fmaf(m[1][k], mca, a); bb = __builtin_fmaf(m[2][k], mca, bb);
             }
         }
         lab_to_bgr<EXACT>(L, a, bb, EXACT ? lab.inv : lab.inv1024, s_igt, o0, o1, o2);
@@ -695,7 +698,7 @@ __device__ __forceinline__ B96 lap_emit_row(const Raw4 pin, const float (&m)[3][
 }
 // one wave strip (task) of the last kernel; s_igt = inverse-gamma spline in LDS, s_gam = gamma table (analytic flavour)
 template <bool MOTION, bool DBG, int FL>     // DBG: also store the float frame (lvm_debug_keep_float); a per-pixel branch
-__device__ __forceinline__ void lap_final_strip(const FinArgs& q, int task, int lane, const float* s_igt, const float* s_gam) {
+__device__ __forceinline__ void lap_final_strip(const FinArgs& q, int task, int lane, const float ca64, const float ca16, const float* s_igt, const float* s_gam) {
     constexpr bool EXACT = fl_exact(FL);
     constexpr bool PLANES = fl_lut(FL);
     const uint8_t* __restrict__ in = q.in; const long in_stride = q.in_stride, in_sstride = q.in_sstride;
@@ -705,7 +708,9 @@ __device__ __forceinline__ void lap_final_strip(const FinArgs& q, int task, int 
     float* __restrict__ dbg = q.dbg; const LabPlanes lp = q.lp;
     const int b = task / (strips_x * strips_y);
     const int r = task - b * (strips_x * strips_y);
-    const int ty = r / strips_x, tx = r - ty * strips_x;
+    // (tx passes through a scalar read: as plain arithmetic of `task` the column offsets below become induction variables of the
+    // task loop, two VGPRs that live for the whole kernel on top of `lane`)
+    const int ty = r / strips_x, tx = __builtin_amdgcn_readfirstlane(r - ty * strips_x);
     const int gx = tx * 256 + 4 * lane, y0 = ty * rows;        // rows is even: y0 is even
     if (gx >= w) return;
     // uniform (scalar) bases + 32-bit lane offsets
@@ -719,7 +724,9 @@ __device__ __forceinline__ void lap_final_strip(const FinArgs& q, int task, int 
     // column w1 reads column w1 - 1) and every lane runs the interior formulas -- s1 + 6 s0 + s1 = 6 s0 + 2 s1,
     // s0 + 6 s1 + s1 = s0 + 7 s1, (s1 + s1) 4 = 8 s1: equal up to the rounding of one addition at the two border
     // columns, 16 selects / border variants less per lane and source row.
-    const unsigned cm1 = 4u * (i0 > 0 ? i0 - 1 : (EXACT ? 0 : 1)), c00 = 4u * i0, cp1 = 4u * (i0 + 1 < w1 ? i0 + 1 : w1 - 1), cp2 = 4u * (i0 + 2 < w1 ? i0 + 2 : w1 - 1);
+    // (w is a multiple of 4 and gx < w: i0 <= w1 - 2, so column i0 + 1 always exists -- it is c00 plus the load's immediate offset,
+    // not a register of its own; only the lane at each end of a row needs cm1 / cp2 to differ from c00 -+ 4 / 8)
+    const unsigned cm1 = 4u * (i0 > 0 ? i0 - 1 : (EXACT ? 0 : 1)), c00 = 4u * i0, cp2 = 4u * (i0 + 2 < w1 ? i0 + 2 : w1 - 1);
     const size_t pstride = (size_t)w1 * h1;
     // Round 5: every access of the strip goes through a buffer resource (base + size in SGPRs, a 32-bit lane offset, a wave-uniform row
     // offset): no 64-bit address arithmetic in vector registers (the generic form cost ~55 v_lshl_add_u64 per three steps and 24
@@ -733,7 +740,8 @@ __device__ __forceinline__ void lap_final_strip(const FinArgs& q, int task, int 
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const uint32_t rb = (uint32_t)(((size_t)sy * w1 + c * pstride) * sizeof(float));
-            const float sm1 = buf_ld_f32(rcur, cm1, rb), s0 = buf_ld_f32(rcur, c00, rb), s1 = buf_ld_f32(rcur, cp1, rb), s2 = buf_ld_f32(rcur, cp2, rb);
+            const uint32_t cr = c00 + rb;      // (formed per row, so that the + 4 of column i0 + 1 stays next to its load and becomes its immediate offset)
+            const float sm1 = buf_ld_f32(rcur, cm1, rb), s0 = buf_ld_f32(rcur, cr, 0u), s1 = buf_ld_f32(rcur, cr + 4u, 0u), s2 = buf_ld_f32(rcur, cp2, rb);
             if (EXACT) o.c[c] = pyrup_h4(sm1, s0, s1, s2, i0, w1);
             else if (LVM_FAST_FMA) {   // one rounding less per even column (fma), a few 1e-8 of the motion image
                 o.c[c].x = __builtin_fmaf(s0, 6.f, sm1 + s1); o.c[c].y = (s0 + s1) * 4.f; o.c[c].z = __builtin_fmaf(s1, 6.f, s0 + s2); o.c[c].w = (s1 + s2) * 4.f;
@@ -750,13 +758,16 @@ __device__ __forceinline__ void lap_final_strip(const FinArgs& q, int task, int 
     auto ld_in = [&](int y) __attribute__((always_inline)) {
         if (!PLANES) return load_raw4<false>(src, in_stride, lp, poff, w, y, (unsigned)gx);
         Raw4 r{};
-        const uint2 l = buf_lds_u32x2(rL, (uint32_t)gx * 2u, (uint32_t)y * (uint32_t)w * 2u);
-        const uint4 ab = buf_lds_u32x4(rAB, (uint32_t)gx * 4u, (uint32_t)y * (uint32_t)w * 4u);
+        // (gx * 2 is c00; the a/b offset is formed per load as (c00 + row) << 1 -- one v_add_lshl_u32 -- instead of a third per-lane
+        // column offset kept in a register for the whole strip)
+        const uint32_t rowL = (uint32_t)y * (uint32_t)w * 2u;
+        const uint2 l = buf_lds_u32x2(rL, c00, rowL);
+        const uint4 ab = buf_lds_u32x4(rAB, (c00 + rowL) << 1, 0u);
         r.d[0] = l.x; r.d[1] = l.y; r.d[2] = ab.x; r.d[3] = ab.y; r.d[4] = ab.z; r.d[5] = ab.w;
         return r;
     };
-    auto emit = [&](const Raw4 pin, const float (&m)[3][4], const float msc) __attribute__((always_inline)) {
-        const B96 o = lap_emit_row<MOTION, DBG, FL>(pin, m, msc, ca, lab, s_igt, s_gam, (DBG && dbg && b == 0) ? dbg + ((size_t)gy * w + gx) * 3 : nullptr);
+    auto emit = [&](const Raw4 pin, const float (&m)[3][4], const float msc, const float mca) __attribute__((always_inline)) {
+        const B96 o = lap_emit_row<MOTION, DBG, FL>(pin, m, msc, mca, ca, lab, s_igt, s_gam, (DBG && dbg && b == 0) ? dbg + ((size_t)gy * w + gx) * 3 : nullptr);
         buf_sts_b96(o, rout, xoff, (uint32_t)gy * (uint32_t)out_stride);      // (the output frame is not read again on the device: streaming store)
     };
     // two output rows (2j, 2j+1) from the window rows A = j-1, B = j, C = j+1; afterwards A holds row
@@ -783,10 +794,14 @@ __device__ __forceinline__ void lap_final_strip(const FinArgs& q, int task, int 
             }
         }
         const bool more = gy + 2 < yend;
-        if (MOTION && more) A = hrow(j + 2);                 // in flight during the colour math of both rows
-        emit(pe, m, 1.f / 64.f);
+        emit(pe, m, 1.f / 64.f, ca64);
         ++gy;
         if (!has_odd) return false;
+        // The next window row is fetched BETWEEN the two rows' colour math, not before the first: the compiler finishes the horizontal
+        // pass as soon as its loads are issued (one wait either way, and `po` -- issued before the first row's math -- has landed by
+        // then), so fetched earlier its twelve results are only carried through the first row's math, where the kernel's register
+        // peak is.  Six VGPRs less; at <= 80 a SIMD holds six of these waves instead of five (three workgroups per CU, not two).
+        if (MOTION && more) A = hrow(j + 2);
         if (MOTION) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
@@ -798,7 +813,7 @@ __device__ __forceinline__ void lap_final_strip(const FinArgs& q, int task, int 
                 }
             }
         }
-        emit(po, m, 1.f / 16.f);
+        emit(po, m, 1.f / 16.f, ca16);
         ++gy; ++j;
         return more;
     };
@@ -825,10 +840,14 @@ __global__ LVM_FIN_BOUNDS void k_lap_final_v4(FinArgs q) {
     constexpr int WAVES = FIN_THREADS / 64;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
     const int ntasks = q.strips_x * q.strips_y * q.nstreams;
+    // the chroma scales of the two row parities (ca / 64, ca / 16): wave-uniform products, moved to scalar registers once -- the fma
+    // takes one as an operand; left to a vector multiply they occupy two VGPRs for the whole kernel
+    const float ca64 = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint((1.f / 64.f) * q.ca)));
+    const float ca16 = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint((1.f / 16.f) * q.ca)));
     // (strip groups handed out round-robin: a contiguous run per workgroup in XCD-aware order -- the next group is the row of
     // strips below, whose first cur_1 rows the CU has just read -- measured 194-203 -> 222-226 us per 32 frames)
     for (int task = blockIdx.x * WAVES + wave; task < ntasks; task += gridDim.x * WAVES)
-        lap_final_strip<MOTION, DBG, FL>(q, task, lane, s_igt, s_gam);
+        lap_final_strip<MOTION, DBG, FL>(q, task, lane, ca64, ca16, s_igt, s_gam);
 }
 
 
@@ -977,7 +996,7 @@ struct LaplaceState : ModeState {
     long d0_fused_groups = 0;             // persistent workgroups of the fused first kernel (LVM_D0_FUSED_GROUPS, >= 0; 0 = one per CU)
     long d0_fused_waves = 0;              // ... = launches with at least this many strips (LVM_D0_FUSED_WAVES; 0 = one per resident wave)
     long d0_min_tasks = 4096;             // ... for launches with at least this many strips (LVM_D0_MIN_TASKS)
-    long fin_groups = 0;                  // workgroups of the persistent last kernel (LVM_FIN_GROUPS, >= 0; 0 = 1024)
+    long fin_groups = 0;                  // workgroups of the persistent last kernel (LVM_FIN_GROUPS, >= 0; 0 = kFinRounds x the resident ones)
     int fin_rows = 8;                     // rows per wave strip of k_lap_final_v4 (LVM_FIN_ROWS, power of two)
     int up_depth_big = 1;                 // ... at the levels with >= 1024 workgroups (LVM_UP_DEPTH_BIG=1|2|4|8)
     int up_depth = 8;                     // frame-loop prefetch depth of k_lap_up at the coarse levels (LVM_UP_DEPTH=1|2|4|8: the kernel has these four instantiations)
@@ -1208,6 +1227,24 @@ static void lap_stage_b(Ctx* c, LaplaceState* st, const lvm_params& p, const Fra
     }
 }
 
+// The persistent grid of k_lap_final_v4 is kFinRounds x the workgroups the device really holds at a time.  That number follows from the
+// launched instance's registers and LDS (the default one: 80 VGPRs = 6 waves per SIMD = three 512-thread workgroups per CU; the exact and
+// analytic flavours two), so the runtime is asked, once per instance; the answer is kept in the context beside num_cus.  A host
+// compiler without the occupancy query, or a refused query, assumes two workgroups per CU.
+constexpr int kFinRounds = 2;
+template <class K>
+static int lap_fin_resident(Ctx* c, K kern) {
+    const void* id = reinterpret_cast<const void*>(kern);
+    if (c->fin_occ_kernel != id) {
+        int n = 0;
+#ifdef __HIPCC__
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, FIN_THREADS, 0) != hipSuccess) { n = 0; (void)hipGetLastError(); }
+#endif
+        c->fin_occ_kernel = id; c->fin_occ_groups = n > 0 ? n : 2;
+    }
+    return c->fin_occ_groups;
+}
+
 // Stage A of a frame: the fused band/IIR/collapse steps of the levels below T and the final kernel.
 static void lap_stage_a(Ctx* c, LaplaceState* st, const lvm_params& p, const FrameIO& io, const LapBufs& B, bool first, hipStream_t s) {
     const int C = io.channels, levels = st->levels;
@@ -1314,7 +1351,7 @@ static void lap_stage_a(Ctx* c, LaplaceState* st, const lvm_params& p, const Fra
         const int sy = (io.h + rows - 1) / rows;
         const int waves = FIN_THREADS / 64;
         const long groups = ((long)sx * sy * NS + waves - 1) / waves;
-        const long cap = st->fin_groups > 0 ? st->fin_groups : 1024;
+        const long cap = st->fin_groups > 0 ? st->fin_groups : (long)kFinRounds * lap_fin_resident(c, kf4) * c->num_cus;
         const dim3 grid4((unsigned)(groups < cap ? groups : cap)), blk4(FIN_THREADS);
         const FinArgs fa{io.d_in, (long)io.in_stride, (long)io.in_sstride, io.d_out, (long)io.out_stride, (long)io.out_sstride, io.w, io.h, cur1, w1, h1,
                          c->lab, ca, sx, sy, NS, rows, dbg, lp};

@@ -530,6 +530,7 @@ struct Ctx {
     uint32_t* d_lab_ab = nullptr; uint4* d_lab_Lcells = nullptr;   // the forward table in its device layouts (lab_lut.h)
     LabLut lab_lut{};
     int num_cus = 256;
+    const void* fin_occ_kernel = nullptr; int fin_occ_groups = 0;   // last Laplace kernel: the instance asked about and the workgroups of it one CU holds (lap_fin_resident)
     std::vector<int16_t> lab_lut_compact;   // the same table, [r][q][p][3] (lvm_get_lab_lut)
     // preprocess stage (preprocess.hip): area tables of the current geometry, staging of the host chain
     void* pre_tables = nullptr;
