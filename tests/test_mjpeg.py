@@ -168,7 +168,7 @@ def test_mjpeg_emu_restart_intervals_of_any_length(lvm, emu, restart):
 
 
 def test_mjpeg_emu_noise_at_quality_100_long_codes_and_stuffing(lvm, emu):
-    """white noise at quality 100: 16-bit codes with 8-10 amplitude bits, words straddled by almost every code, FF bytes to stuff"""
+    """white noise at quality 100: 16-bit codes with 8-9 amplitude bits (categories 10 and 11: tests/test_mjpeg_extremes.py), words straddled by almost every code, FF bytes to stuff"""
     _encode_and_compare(lvm, emu, _numpy_dev(), [(96, 32, 100, 1), (40, 40, 97, 2)], noise=200.0)
 
 
