@@ -420,6 +420,57 @@ enum lvm_pixel_format { LVM_PIX_BGR = 0,      /* BGR8 or Gray8 by `channels`: to
 int  lvm_set_source_format(lvm_ctx* ctx, int fmt);
 int  lvm_get_source_format(lvm_ctx* ctx, int* fmt);
 
+/* Export canvases as 4:2:0 SURFACES -- NV12 / NV21 / I420 / YV12, converted on the device; an opt-in extension, with LVM_PIX_BGR (the default)
+ * every launch, byte, error message and `produced` flag is what it is without this call.  The reference's default export format is
+ * ExportFormat::Mp4H264 (export/ExportTypes.hpp:23), and every H.264 / HEVC / AV1 encoder behind this library (VCN through VA-API or AMF, an FFmpeg
+ * rawvideo pipe) takes 4:2:0 surfaces: 1.5 B / pixel come down instead of 3, or the surface stays on the device.  With canvas format F != LVM_PIX_BGR
+ * a participating surface gives cvtColor(canvas, COLOR_BGR2YUV_I420) (OpenCV 4 color_yuv) of the BGR canvas it gives under LVM_PIX_BGR, byte for
+ * byte, in the layout of F; the text overlay of lvm_export_set_overlay is applied to the BGR pixels FIRST.  Per pixel (ITU-R BT.601, limited range,
+ * 20-bit fixed point, int32: every sum is positive and below 2^31 and every result lies in 0..255, so no saturation or sign rule is exercised):
+ *     Y = ( 269484 R + 528482 G + 102760 B + (1 << 19) + ( 16 << 20)) >> 20
+ *     U = (-155188 R - 305135 G + 460324 B + (1 << 19) + (128 << 20)) >> 20
+ *     V = ( 460324 R - 385875 G -  74448 B + (1 << 19) + (128 << 20)) >> 20
+ * Y at every pixel; U and V from the TOP-LEFT pixel (even x, even y, canvas coordinates) of each 2 x 2 block -- OpenCV subsamples, it does not
+ * average.  The U and V rows each sum to 1: OpenCV's quirk, kept.  OpenCV 4 has no COLOR_BGR2YUV_NV12: NV12 / NV21 are the I420 samples interleaved.
+ * An FFmpeg-backed cv::VideoWriter converts BGR to yuv420p with swscale, which is other arithmetic and NOT what this restates (INTEGRATION.md 3d'').
+ * Layouts (canvas_w and canvas_h are even: lvm_compose_geometry crops the panes to even sizes; canvas_stride is the Y row stride):
+ *   LVM_PIX_NV12 / LVM_PIX_NV21   canvas_h rows of Y; the interleaved U V (V U) plane starts at row canvas_h with the same stride: canvas_h / 2 rows of
+ *                                 canvas_w bytes -- ONE buffer, the convention of the source formats.  canvas_stride >= canvas_w.
+ *   LVM_PIX_I420 / LVM_PIX_YV12   canvas_h rows of Y; the first chroma plane (U for I420, V for YV12) starts at byte canvas_stride * canvas_h, the
+ *                                 second at canvas_stride * canvas_h * 5 / 4; each has canvas_h / 2 rows of canvas_w / 2 bytes, row stride
+ *                                 canvas_stride / 2.  canvas_stride even and >= canvas_w; with canvas_stride == canvas_w this is OpenCV's
+ *                                 (3h/2) x w single-channel Mat and FFmpeg's contiguous yuv420p.
+ *   The packed 4:2:2 formats (1..3) are refused as canvas formats.
+ * lvm_set_canvas_format   only stores the value: the next participating call reads it, in call order.  lvm_reset keeps it; the temporal state, the
+ *                         tracked structural key and the overlay tables are left alone.  Any value other than 0, 4, 5, 6, 7: LVM_ERR_INVALID with a
+ *                         message that names the allowed values, nothing changes.
+ * lvm_canvas_layout       a pure function of the rules above: the bytes of one canvas, the offsets of the chroma planes and their row stride.  BGR:
+ *                         bytes = canvas_stride * canvas_h (canvas_stride >= 3 * canvas_w), no chroma planes (0, 0, 0).  NV12 / NV21: plane2_offset = 0.
+ *                         Outputs may be NULL.  A refused format, size or stride: LVM_ERR_INVALID.
+ * lvm_canvas_convert_device   n_frames device-resident BGR canvases (w x h, row stride bgr_stride >= 3 * w, frame i at d_bgr + i * bgr_frame_stride) ->
+ *                         format fmt (one of the four YUV formats, whatever lvm_set_canvas_format says) at d_out + i * out_frame_stride, Y row stride
+ *                         out_stride.  Enqueued on hip_stream, not synchronised; it takes its place in the context's call order like
+ *                         lvm_overlay_device.  Any base pointers are legal.  w or h odd or < 2, short strides, overlapping output frames
+ *                         (out_frame_stride smaller than the layout's bytes when n_frames > 1): LVM_ERR_INVALID before anything runs.  The surface for
+ *                         callers that compose on the device (lvm_compose_device, lvm_overlay_device) and encode there.
+ * lvm_export_frames       with F != LVM_PIX_BGR canvases[k] receives format F; canvas_stride obeys F's rule (>= canvas_w; 3 * canvas_w is no longer
+ *                         required).  produced[], batching, sub-batches and the three-queue pipeline stay as they are; stage 3 downloads 1.5 B / pixel.
+ *                         lvm_export_geometry is unchanged.
+ * Surfaces that do NOT take part: lvm_export_frames_mjpeg, lvm_export_mjpeg_frames, lvm_mjpeg_encode_device (BGR in, JPEG out), lvm_chain_* and
+ * lvm_chain_present (frames, not canvases), lvm_compose_device (always BGR), lvm_overlay_device (BGR canvases).
+ * Work unit: 2 rows x 8 pixels per thread.  lvm_profile_variants reports under "canvas_yuv" the kernel that ran: "vec8" (dword-wide loads and stores:
+ * every pointer, stride and plane offset involved dword-aligned, w a multiple of 8 -- and, reading panes, a pane-1 column that is a multiple of 8) or
+ * "bytes" (everything else); both give identical bytes.  lvm_export_frames without labels reads the panes directly and never writes the BGR canvas:
+ * that route reports "fused" as well (LVM_CANVAS_FUSED=0 forces compose, then convert); with labels it composes, overlays, then converts.      */
+enum { LVM_PIX_I420 = 6,      /* canvas formats only: h rows of Y, h/2 rows of U, h/2 rows of V (FFmpeg yuv420p) */
+       LVM_PIX_YV12 = 7 };    /* ... V before U */
+int  lvm_set_canvas_format(lvm_ctx* ctx, int fmt);
+int  lvm_get_canvas_format(lvm_ctx* ctx, int* fmt);
+int  lvm_canvas_layout(int fmt, int canvas_w, int canvas_h, ptrdiff_t canvas_stride, size_t* bytes, size_t* plane1_offset, size_t* plane2_offset,
+                       ptrdiff_t* chroma_stride);
+int  lvm_canvas_convert_device(lvm_ctx* ctx, int fmt, const uint8_t* d_bgr, int w, int h, ptrdiff_t bgr_stride, ptrdiff_t bgr_frame_stride, int n_frames,
+                               uint8_t* d_out, ptrdiff_t out_stride, ptrdiff_t out_frame_stride, void* hip_stream);
+
 /* Cross-frame software pipeline for lvm_process_device (throughput mode, default depth 0).
  * depth 1 (implemented for the Laplace mode; other modes ignore it): a call enqueues the
  * down-sweep of ITS frame on an internal second stream concurrently with the up-sweep + output of

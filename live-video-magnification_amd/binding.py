@@ -74,6 +74,7 @@ MJPEG_DECODER_REPLICATE, MJPEG_DECODER_LIBJPEG = 0, 1      # lvm_mjpeg_set_decod
 MJPEG_SAMPLING_420, MJPEG_SAMPLING_422, MJPEG_SAMPLING_444, MJPEG_SAMPLING_GRAY, MJPEG_SAMPLING_ALL = 1, 2, 4, 8, 15      # lvm_mjpeg_set_samplings
 CV_FILTER_UNFUSED, CV_FILTER_DFT, CV_MUL_F32, CV_ALL = 1, 2, 4, 7      # lvm_set_opencv_build
 PIX_BGR, PIX_YUYV, PIX_UYVY, PIX_YVYU, PIX_NV12, PIX_NV21 = 0, 1, 2, 3, 4, 5      # lvm_set_source_format (enum lvm_pixel_format)
+PIX_I420, PIX_YV12 = 6, 7                                                          # lvm_set_canvas_format only (with PIX_BGR, PIX_NV12, PIX_NV21)
 
 
 class LvmParams(C.Structure):
@@ -112,7 +113,8 @@ SYMBOLS = ["lvm_create", "lvm_destroy", "lvm_reset", "lvm_process", "lvm_process
            "lvm_set_max_frames", "lvm_host_alloc", "lvm_host_free", "lvm_compose_geometry", "lvm_compose_device", "lvm_chain_process_batch_ex",
            "lvm_chain_present", "lvm_mjpeg_bound", "lvm_mjpeg_encode_device", "lvm_export_frames_mjpeg", "lvm_mjpeg_decode_device", "lvm_export_mjpeg_frames", "lvm_mjpeg_set_restart_interval", "lvm_mjpeg_set_decoder", "lvm_mjpeg_set_samplings",
            "lvm_set_opencv_build", "lvm_get_opencv_build", "lvm_set_phase_on_gray", "lvm_get_phase_on_gray",
-           "lvm_set_source_format", "lvm_get_source_format"]
+           "lvm_set_source_format", "lvm_get_source_format",
+           "lvm_set_canvas_format", "lvm_get_canvas_format", "lvm_canvas_layout", "lvm_canvas_convert_device"]
 
 
 def bind(lib):
@@ -183,6 +185,10 @@ def bind(lib):
     lib.lvm_get_phase_on_gray.argtypes = [vp, ip]
     lib.lvm_set_source_format.argtypes = [vp, C.c_int]
     lib.lvm_get_source_format.argtypes = [vp, ip]
+    lib.lvm_set_canvas_format.argtypes = [vp, C.c_int]
+    lib.lvm_get_canvas_format.argtypes = [vp, ip]
+    lib.lvm_canvas_layout.argtypes = [C.c_int, C.c_int, C.c_int, C.c_ssize_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_ssize_t)]
+    lib.lvm_canvas_convert_device.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_ssize_t, C.c_ssize_t, C.c_int, vp, C.c_ssize_t, C.c_ssize_t, vp]
     lib.lvm_mjpeg_decode_device.argtypes = [vp, vp, C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_int, vp, C.c_ssize_t, C.c_ssize_t]
     lib.lvm_export_mjpeg_frames.argtypes = [vp, C.POINTER(LvmPreprocessParams), C.POINTER(LvmParams), C.c_int, C.c_int, vp, C.POINTER(C.c_size_t), C.c_int, C.c_int,
                                             C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t), ip]
@@ -353,12 +359,13 @@ class Context:
         self._check(self.lib.lvm_export_geometry(C.byref(cpre), int(split), w, h, ch, C.byref(cw), C.byref(chh)))
         if cw.value <= 0 or chh.value <= 0:
             raise LvmError("export_frames: empty canvas for this geometry (Exporter::compose returns an empty Mat)")
-        canvases = [np.empty((chh.value, cw.value, 3), dtype=np.uint8) for _ in frames]
+        yuv = self.canvas_format() != PIX_BGR         # (3h/2, w) uint8 arrays with rows packed: OpenCV's single-channel Mat of a 4:2:0 frame
+        canvases = [np.empty((chh.value * 3 // 2, cw.value) if yuv else (chh.value, cw.value, 3), dtype=np.uint8) for _ in frames]
         pin = (C.c_void_p * len(frames))(*[f.ctypes.data for f in frames])
         pout = (C.c_void_p * len(frames))(*[o.ctypes.data for o in canvases])
         produced = (C.c_int * len(frames))()
         self._check(self.lib.lvm_export_frames(self.h, C.byref(cpre), C.byref(cparams), int(split), len(frames), pin, w, h, ch, row,
-                                               pout, cw.value * 3, produced))
+                                               pout, cw.value * (1 if yuv else 3), produced))
         return canvases, [bool(x) for x in produced]
 
     def export_set_overlay(self, labels):
@@ -441,6 +448,33 @@ class Context:
         v = C.c_int(0)
         self._check(self.lib.lvm_get_source_format(self.h, C.byref(v)))
         return int(v.value)
+
+    def set_canvas_format(self, fmt):
+        """lvm_set_canvas_format: what export_frames hands out from the next call on: PIX_BGR (the default: (h, w, 3) canvases) or a 4:2:0 surface,
+        PIX_NV12 / PIX_NV21 / PIX_I420 / PIX_YV12 ((3h/2, w) uint8 arrays) -- cvtColor(canvas, COLOR_BGR2YUV_I420) of the BGR canvas (BT.601, limited
+        range, OpenCV's fixed point; chroma of the top-left pixel of each 2 x 2 block), the text overlay applied first, converted on the device.  The
+        temporal state and the overlay tables are kept; reset() keeps the format.  The JPEG, chain and compose surfaces do not take part.  Any other
+        format: LvmError, nothing changes."""
+        self._check(self.lib.lvm_set_canvas_format(self.h, int(fmt)))
+
+    def canvas_format(self):
+        """lvm_get_canvas_format: the format set_canvas_format installed (PIX_BGR by default)."""
+        v = C.c_int(0)
+        self._check(self.lib.lvm_get_canvas_format(self.h, C.byref(v)))
+        return int(v.value)
+
+    def canvas_layout(self, fmt, cw, chh, stride):
+        """lvm_canvas_layout: (bytes, plane1_offset, plane2_offset, chroma_stride) of one canvas of cw x chh with Y row stride `stride` (BGR: the row
+        stride) in format fmt; LvmError where the format, the size or the stride breaks the format's rule."""
+        b, p1, p2, cs = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_ssize_t(0)
+        if self.lib.lvm_canvas_layout(int(fmt), cw, chh, stride, C.byref(b), C.byref(p1), C.byref(p2), C.byref(cs)) != 0:
+            raise LvmError("lvm_canvas_layout: format, size or stride refused")
+        return int(b.value), int(p1.value), int(p2.value), int(cs.value)
+
+    def canvas_convert_device(self, fmt, d_bgr, w, h, bgr_stride, bgr_frame_stride, n_frames, d_out, out_stride, out_frame_stride, stream=None):
+        """lvm_canvas_convert_device: n_frames device-resident BGR canvases (address) -> 4:2:0 surfaces of format fmt at d_out.  Asynchronous on `stream`."""
+        self._check(self.lib.lvm_canvas_convert_device(self.h, int(fmt), d_bgr, w, h, bgr_stride, bgr_frame_stride, n_frames, d_out, out_stride,
+                                                       out_frame_stride, stream))
 
     def mjpeg_decode_device(self, jpegs, w, h, d_ptr, stride=None, frame_stride=None):
         """lvm_mjpeg_decode_device: a list of JPEG frames (bytes) -> BGR frames in device memory at d_ptr."""
@@ -627,7 +661,7 @@ class Context:
         return out
 
     def profile_variants(self):
-        """{report name: set of kernel variants launched under it ("strips" / "vec4" / "bytes"; "yuv4" / "yuv" under a raw source format; under set_opencv_build the kind: "unfused" / "f64" /
+        """{report name: set of kernel variants launched under it ("strips" / "vec4" / "bytes"; "yuv4" / "yuv" under a raw source format; "vec8" / "bytes" and "fused" under "canvas_yuv"; under set_opencv_build the kind: "unfused" / "f64" /
         "mulf32" / "unfused+mulf32")} for the names several kernels share"""
         n = self.lib.lvm_profile_collect(self.h)
         out = {}

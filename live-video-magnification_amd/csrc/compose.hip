@@ -170,4 +170,206 @@ int compose_device(Ctx* c, int split, const uint8_t* d_orig, int ow, int oh, int
     return LVM_OK;
 }
 
+// ---- canvases as 4:2:0 surfaces (lvm_set_canvas_format, include/lvm_hip.h) -------------------------------------------------------------
+// cvtColor(canvas, COLOR_BGR2YUV_I420) of OpenCV 4 (color_yuv: ITU-R BT.601, limited range, 20-bit fixed point) in the layouts NV12 / NV21 /
+// I420 / YV12.  Every sum is positive and below 2^31 (the extreme ones: tests/test_yuv_canvas.py), every result lies in 0..255: plain int32, a
+// shift, no clamp.  Chroma is the top-left pixel's of each 2 x 2 block.  Pure streaming: 3 (or 1) bytes in, 1.5 bytes out per pixel.
+__device__ __forceinline__ uint32_t yuv_y(int b, int g, int r) { return (uint32_t)((269484 * r + 528482 * g + 102760 * b + (1 << 19) + (16 << 20)) >> 20); }
+__device__ __forceinline__ uint32_t yuv_u(int b, int g, int r) { return (uint32_t)((-155188 * r - 305135 * g + 460324 * b + (1 << 19) + (128 << 20)) >> 20); }
+__device__ __forceinline__ uint32_t yuv_v(int b, int g, int r) { return (uint32_t)((460324 * r - 385875 * g - 74448 * b + (1 << 19) + (128 << 20)) >> 20); }
+
+struct CanvasYuvArgs {
+    // the source: a BGR canvas in memory (src[1], cn 3, one pane at the origin: frame f at + f * fstride), or the panes compose_device would
+    // write into it ([0] original, [1] processed; BGR or gray, gray as b = g = r)
+    const uint8_t* src[2]; long stride[2]; int cn[2];
+    long src_fstride;
+    int pane_w, pane_h, npanes, dx1, dy1;
+    uint8_t* dst; long ystride, cstride, dst_fstride, plane1, plane2;   // plane1 / plane2: where U / V go (planar), or plane1 = the interleaved plane
+    int w, h;                 // canvas size (even)
+    int interleaved, v_first; // NV12 / NV21: byte pairs (U, V) / (V, U) in one plane of row stride cstride = ystride
+};
+
+// One thread per block of 2 rows x 8 pixels of the canvas: 2 x 24 BGR bytes (2 x 8 of a gray pane) in, 2 x 8 Y bytes and 4 U + 4 V bytes out;
+// blockIdx.z = frame.  VEC: dword-wide loads and stores (every pointer, stride and offset dword-aligned, w % 8 == 0, the block inside ONE pane);
+// otherwise bytes, a block of 2, 4 or 6 pixels at the right edge (w is even) and a pane per pixel.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_canvas_yuv(CanvasYuvArgs a) {
+    const int x0 = (blockIdx.x * 64 + (threadIdx.x & 63)) * 8, y0 = (blockIdx.y * 4 + (threadIdx.x >> 6)) * 2;
+    if (x0 >= a.w || y0 >= a.h) return;
+    const size_t f = blockIdx.z;
+    const int n = a.w - x0 < 8 ? a.w - x0 : 8;
+    uint32_t Y[2][8], U[4], V[4];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int y = y0 + r;
+        // (a block of two rows lies in one pane vertically: pane heights are even)
+        const int py = (a.npanes == 2 && y >= a.pane_h && a.dy1) ? 1 : 0;
+        uint8_t px[24];
+        if (VEC) {
+            const int pane = a.npanes == 2 ? ((a.dx1 && x0 >= a.dx1) || py ? 1 : 0) : 1;
+            const int lx = x0 - (pane && a.npanes == 2 ? a.dx1 : 0), ly = y - (py ? a.dy1 : 0);
+            const uint8_t* p = a.src[pane] + f * a.src_fstride + (size_t)ly * a.stride[pane];
+            if (a.cn[pane] == 3) {
+                const uint32_t* p4 = reinterpret_cast<const uint32_t*>(p + (size_t)lx * 3);
+#pragma unroll
+                for (int k = 0; k < 6; ++k) { const uint32_t v = p4[k]; px[4 * k] = (uint8_t)v; px[4 * k + 1] = (uint8_t)(v >> 8); px[4 * k + 2] = (uint8_t)(v >> 16); px[4 * k + 3] = (uint8_t)(v >> 24); }
+            } else {
+                const uint32_t* p4 = reinterpret_cast<const uint32_t*>(p + lx);
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    const uint32_t v = p4[k];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) { const uint8_t g = (uint8_t)(v >> (8 * j)); px[12 * k + 3 * j] = g; px[12 * k + 3 * j + 1] = g; px[12 * k + 3 * j + 2] = g; }
+                }
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const int x = x0 + k;
+                const int pane = a.npanes == 2 ? ((a.dx1 && x >= a.dx1) || py ? 1 : 0) : 1;
+                const int lx = x - (pane && a.npanes == 2 ? a.dx1 : 0), ly = y - (py ? a.dy1 : 0);
+                const uint8_t* p = a.src[pane] + f * a.src_fstride + (size_t)ly * a.stride[pane];
+                if (k < n) {
+                    if (a.cn[pane] == 3) { px[3 * k] = p[(size_t)lx * 3]; px[3 * k + 1] = p[(size_t)lx * 3 + 1]; px[3 * k + 2] = p[(size_t)lx * 3 + 2]; }
+                    else { const uint8_t g = p[lx]; px[3 * k] = g; px[3 * k + 1] = g; px[3 * k + 2] = g; }      // COLOR_GRAY2BGR
+                } else { px[3 * k] = 0; px[3 * k + 1] = 0; px[3 * k + 2] = 0; }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) Y[r][k] = yuv_y(px[3 * k], px[3 * k + 1], px[3 * k + 2]);
+        if (r == 0) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { U[k] = yuv_u(px[6 * k], px[6 * k + 1], px[6 * k + 2]); V[k] = yuv_v(px[6 * k], px[6 * k + 1], px[6 * k + 2]); }
+        }
+    }
+    uint8_t* q = a.dst + f * a.dst_fstride;
+    uint8_t* qy = q + (size_t)y0 * a.ystride + x0;
+    const size_t crow = (size_t)(y0 >> 1) * a.cstride;
+    if (a.v_first && a.interleaved) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { const uint32_t t = U[k]; U[k] = V[k]; V[k] = t; }
+    }
+    if (VEC) {
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            uint32_t* q4 = reinterpret_cast<uint32_t*>(qy + (size_t)r * a.ystride);
+            q4[0] = Y[r][0] | (Y[r][1] << 8) | (Y[r][2] << 16) | (Y[r][3] << 24);
+            q4[1] = Y[r][4] | (Y[r][5] << 8) | (Y[r][6] << 16) | (Y[r][7] << 24);
+        }
+        if (a.interleaved) {
+            uint32_t* c4 = reinterpret_cast<uint32_t*>(q + a.plane1 + crow + x0);
+            c4[0] = U[0] | (V[0] << 8) | (U[1] << 16) | (V[1] << 24);
+            c4[1] = U[2] | (V[2] << 8) | (U[3] << 16) | (V[3] << 24);
+        } else {
+            *reinterpret_cast<uint32_t*>(q + a.plane1 + crow + (x0 >> 1)) = U[0] | (U[1] << 8) | (U[2] << 16) | (U[3] << 24);
+            *reinterpret_cast<uint32_t*>(q + a.plane2 + crow + (x0 >> 1)) = V[0] | (V[1] << 8) | (V[2] << 16) | (V[3] << 24);
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int k = 0; k < 8; ++k) if (k < n) qy[(size_t)r * a.ystride + k] = (uint8_t)Y[r][k];
+        if (a.interleaved) {
+            uint8_t* cq = q + a.plane1 + crow + x0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) if (2 * k < n) { cq[2 * k] = (uint8_t)U[k]; cq[2 * k + 1] = (uint8_t)V[k]; }
+        } else {
+            uint8_t* uq = q + a.plane1 + crow + (x0 >> 1);
+            uint8_t* vq = q + a.plane2 + crow + (x0 >> 1);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) if (2 * k < n) { uq[k] = (uint8_t)U[k]; vq[k] = (uint8_t)V[k]; }
+        }
+    }
+}
+
+const char* canvas_layout(int fmt, int w, int h, ptrdiff_t stride, CanvasLayout* out) {
+    CanvasLayout L{};
+    if (fmt == LVM_PIX_BGR) {
+        if (w < 1 || h < 1) return "canvas format: bad canvas size";
+        if (stride < (ptrdiff_t)w * 3) return "canvas stride too small";
+        L.bytes = (size_t)stride * h;
+    } else if (fmt == LVM_PIX_NV12 || fmt == LVM_PIX_NV21 || fmt == LVM_PIX_I420 || fmt == LVM_PIX_YV12) {
+        const bool nv = fmt == LVM_PIX_NV12 || fmt == LVM_PIX_NV21;
+        if (w < 2 || h < 2 || w % 2 || h % 2) return "canvas format: w and h must be even and >= 2";
+        if (nv && stride < (ptrdiff_t)w) return "canvas format: canvas_stride must be >= canvas_w for NV12 / NV21";
+        if (!nv && (stride < (ptrdiff_t)w || stride % 2)) return "canvas format: canvas_stride must be even and >= canvas_w for I420 / YV12";
+        L.plane1 = (size_t)stride * h;
+        L.plane2 = nv ? 0 : L.plane1 + L.plane1 / 4;
+        L.bytes = L.plane1 + L.plane1 / 2;
+        L.cstride = nv ? stride : stride / 2;
+    } else {
+        return "canvas format: the format must be LVM_PIX_BGR (0), _NV12 (4), _NV21 (5), _I420 (6) or _YV12 (7)";
+    }
+    if (out) *out = L;
+    return nullptr;
+}
+
+// the destination half of the arguments, and whether it allows dword stores
+static bool canvas_yuv_dst(CanvasYuvArgs& a, int fmt, int w, int h, uint8_t* d_out, ptrdiff_t out_stride, ptrdiff_t out_fstride, int n_frames, const CanvasLayout& L) {
+    a.w = w; a.h = h;
+    a.dst = d_out; a.ystride = (long)out_stride; a.cstride = (long)L.cstride; a.dst_fstride = n_frames > 1 ? (long)out_fstride : 0;
+    a.interleaved = fmt == LVM_PIX_NV12 || fmt == LVM_PIX_NV21;
+    a.v_first = fmt == LVM_PIX_NV21 || fmt == LVM_PIX_YV12;
+    a.plane1 = (long)L.plane1; a.plane2 = (long)L.plane2;
+    if (!a.interleaved && a.v_first) { a.plane1 = (long)L.plane2; a.plane2 = (long)L.plane1; }      // YV12: the V plane comes first
+    return w % 8 == 0 && (uintptr_t)d_out % 4 == 0 && out_stride % 4 == 0 && a.dst_fstride % 4 == 0 && L.cstride % 4 == 0 && L.plane1 % 4 == 0 && L.plane2 % 4 == 0;
+}
+
+static int canvas_yuv_launch(Ctx* c, const CanvasYuvArgs& a, bool vec, bool fused, int n_frames, hipStream_t s) {
+    const dim3 grid(((a.w + 7) / 8 + 63) / 64, (a.h / 2 + 3) / 4, (unsigned)n_frames), blk(256);
+    if (vec) LVM_LAUNCH_V(c, "canvas_yuv", "vec8", k_canvas_yuv<true>, grid, blk, s, a);
+    else LVM_LAUNCH_V(c, "canvas_yuv", "bytes", k_canvas_yuv<false>, grid, blk, s, a);
+    if (fused && c->profiling) prof_variant(c, "fused");
+    LVM_HIP_TRY(c, hipGetLastError());
+    return LVM_OK;
+}
+
+int canvas_yuv_device(Ctx* c, int fmt, const uint8_t* d_bgr, int w, int h, ptrdiff_t bgr_stride, ptrdiff_t bgr_fstride, int n_frames, uint8_t* d_out,
+                      ptrdiff_t out_stride, ptrdiff_t out_fstride, hipStream_t s, bool check_only) {
+    if (fmt != LVM_PIX_NV12 && fmt != LVM_PIX_NV21 && fmt != LVM_PIX_I420 && fmt != LVM_PIX_YV12) {
+        c->err = "lvm_canvas_convert_device: the format must be LVM_PIX_NV12 (4), _NV21 (5), _I420 (6) or _YV12 (7)"; return LVM_ERR_INVALID;
+    }
+    if (!d_bgr || !d_out || n_frames < 1 || n_frames > 65535) { c->err = "lvm_canvas_convert_device: null canvas pointer, or not 1..65535 frames"; return LVM_ERR_INVALID; }
+    CanvasLayout L;
+    if (const char* why = canvas_layout(fmt, w, h, out_stride, &L)) { c->err = why; return LVM_ERR_INVALID; }
+    if (bgr_stride < (ptrdiff_t)w * 3) { c->err = "lvm_canvas_convert_device: bgr_stride must be >= 3 * w"; return LVM_ERR_INVALID; }
+    if (n_frames > 1 && (out_fstride < 0 || (size_t)out_fstride < L.bytes)) { c->err = "lvm_canvas_convert_device: out_frame_stride must be >= the bytes of one canvas (the frames would overlap)"; return LVM_ERR_INVALID; }
+    if (check_only) return LVM_OK;
+    CanvasYuvArgs a{};
+    a.src[0] = a.src[1] = d_bgr; a.stride[0] = a.stride[1] = (long)bgr_stride; a.cn[0] = a.cn[1] = 3;
+    a.src_fstride = n_frames > 1 ? (long)bgr_fstride : 0;
+    a.pane_w = w; a.pane_h = h; a.npanes = 1; a.dx1 = 0; a.dy1 = 0;
+    bool vec = canvas_yuv_dst(a, fmt, w, h, d_out, out_stride, out_fstride, n_frames, L);
+    vec = vec && (uintptr_t)d_bgr % 4 == 0 && bgr_stride % 4 == 0 && a.src_fstride % 4 == 0;
+    return canvas_yuv_launch(c, a, vec, false, n_frames, s);
+}
+
+// compose_device's panes (same geometry, same fall-back for a missing original) straight into the surface: the BGR canvas is never written
+int canvas_yuv_fused(Ctx* c, int fmt, int split, const uint8_t* d_orig, int ow, int oh, int och, ptrdiff_t ostride, const uint8_t* d_proc, int pw, int ph,
+                     int pch, ptrdiff_t pstride, uint8_t* d_out, ptrdiff_t out_stride, hipStream_t s) {
+    if (split < LVM_SPLIT_NONE || split > LVM_SPLIT_TOP_BOTTOM) { c->err = "invalid split mode"; return LVM_ERR_INVALID; }
+    if (!d_proc || !d_out || (pch != 1 && pch != 3)) { c->err = "bad processed frame"; return LVM_ERR_INVALID; }
+    if (split != LVM_SPLIT_NONE && !d_orig) { d_orig = d_proc; ow = pw; oh = ph; och = pch; ostride = pstride; }
+    if (split != LVM_SPLIT_NONE && och != 1 && och != 3) { c->err = "bad original frame"; return LVM_ERR_INVALID; }
+    int w, h, cw, chh;
+    if (!compose_geometry(split, ow, oh, pw, ph, &w, &h, &cw, &chh)) return LVM_OK;
+    CanvasLayout L;
+    if (const char* why = canvas_layout(fmt, cw, chh, out_stride, &L)) { c->err = why; return LVM_ERR_INVALID; }
+    if (fmt == LVM_PIX_BGR) { c->err = "canvas format: a YUV format is needed here"; return LVM_ERR_INVALID; }
+    if (pstride < (ptrdiff_t)pw * pch || (split != LVM_SPLIT_NONE && ostride < (ptrdiff_t)ow * och)) { c->err = "frame stride too small"; return LVM_ERR_INVALID; }
+    CanvasYuvArgs a{};
+    const bool two = split != LVM_SPLIT_NONE;
+    a.src[0] = two ? d_orig : d_proc; a.stride[0] = (long)(two ? ostride : pstride); a.cn[0] = two ? och : pch;
+    a.src[1] = d_proc; a.stride[1] = (long)pstride; a.cn[1] = pch;
+    a.src_fstride = 0;
+    a.pane_w = w; a.pane_h = h; a.npanes = two ? 2 : 1;
+    a.dx1 = split == LVM_SPLIT_LEFT_RIGHT ? w : 0;
+    a.dy1 = split == LVM_SPLIT_TOP_BOTTOM ? h : 0;
+    bool vec = canvas_yuv_dst(a, fmt, cw, chh, d_out, out_stride, 0, 1, L);
+    // dword loads need every pane row segment dword-aligned and every 8-pixel block inside one pane: the pane-1 column (dx1 = pane_w, even
+    // but no multiple of 8 in general) decides, as 3 * dx1 does for compose_device's stores
+    vec = vec && a.dx1 % 8 == 0 && (uintptr_t)a.src[1] % 4 == 0 && a.stride[1] % 4 == 0 && (!two || ((uintptr_t)a.src[0] % 4 == 0 && a.stride[0] % 4 == 0));
+    return canvas_yuv_launch(c, a, vec, true, 1, s);
+}
+
 }  // namespace lvm

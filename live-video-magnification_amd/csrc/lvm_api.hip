@@ -718,8 +718,18 @@ static int export_frames_impl(lvm_ctx* c, const lvm_preprocess_params* pp, const
     if (!lvm::compose_geometry(split, g.ow, g.oh, g.ow, g.oh, &pw, &ph, &cw, &chh) || cw <= 0 || chh <= 0) {
         c->err = "lvm_export_frames: empty canvas (Exporter::compose returns an empty Mat for this geometry)"; return LVM_ERR_INVALID;
     }
-    if (!mj && canvas_stride < (ptrdiff_t)cw * 3) { c->err = "canvas stride too small"; return LVM_ERR_INVALID; }
+    // canvases as 4:2:0 surfaces (lvm_set_canvas_format; the JPEG sinks encode BGR canvases and do not take part): the caller's layout, and the
+    // device's -- rows packed, the same plane order
+    const int cfmt = mj ? LVM_PIX_BGR : c->canvas_format;
+    lvm::CanvasLayout host_l{}, dev_l{};
+    if (cfmt != LVM_PIX_BGR) {
+        if (const char* why = lvm::canvas_layout(cfmt, cw, chh, canvas_stride, &host_l)) { c->err = why; return LVM_ERR_INVALID; }
+        (void)lvm::canvas_layout(cfmt, cw, chh, (ptrdiff_t)cw, &dev_l);
+    } else if (!mj && canvas_stride < (ptrdiff_t)cw * 3) { c->err = "canvas stride too small"; return LVM_ERR_INVALID; }
     const size_t can_row = (size_t)cw * 3, can_bytes = can_row * chh;
+    // without labels the conversion reads the panes and the BGR canvas is never written; with labels: compose, overlay, convert (the definition's order)
+    bool fused = cfmt != LVM_PIX_BGR && c->overlay_n == 0;
+    if (fused) lvm::env_switch("LVM_CANVAS_FUSED", fused);
     hipStream_t s = c->own_stream;
     { const int orc = lvm::order_after_previous(c, s); if (orc != LVM_OK) return orc; }
     LVM_HIP_TRY(c, hipStreamSynchronize(s));      // staging buffers may be replaced below
@@ -732,7 +742,8 @@ static int export_frames_impl(lvm_ctx* c, const lvm_preprocess_params* pp, const
     const uint8_t* src_base = js ? c->d_pre_in + (size_t)g.ry * full_row + (size_t)g.rx * channels : c->d_pre_in;
     rc = c->d_pre_out.reserve(c, g.out_bytes * n_frames); if (rc != LVM_OK) return rc;
     rc = c->d_chain_out.reserve(c, g.out_bytes * n_frames); if (rc != LVM_OK) return rc;
-    rc = c->d_canvas.reserve(c, can_bytes * n_frames); if (rc != LVM_OK) return rc;
+    if (!fused) { rc = c->d_canvas.reserve(c, can_bytes * n_frames); if (rc != LVM_OK) return rc; }
+    if (cfmt != LVM_PIX_BGR) { rc = c->d_canvas_yuv.reserve(c, dev_l.bytes * n_frames); if (rc != LVM_OK) return rc; }
     if (gray_tap) { rc = c->d_pre_tap.reserve(c, g.tap_bytes * n_frames); if (rc != LVM_OK) return rc; }
     int chunk = mj ? 4 : 2;      // (JPEG frames: nothing large to download, the encoder's launches want more frames each)
     lvm::env_switch(mj ? "LVM_EXPORT_MJPEG_CHUNK" : "LVM_EXPORT_CHUNK", chunk, [](int v) { return v >= 1; });
@@ -782,14 +793,23 @@ static int export_frames_impl(lvm_ctx* c, const lvm_preprocess_params* pp, const
             const bool pr = produced[k] != 0;
             const uint8_t* proc = pr ? c->d_chain_out + (size_t)k * g.out_bytes : seen;               // MagnificationProcessor.cpp:61
             const uint8_t* orig = gray_tap ? c->d_pre_tap + (size_t)k * g.tap_bytes : seen;           // ChainBuilder.cpp:25
-            rc = lvm::compose_device(c, split, orig, g.ow, g.oh, gray_tap ? 3 : g.och, (ptrdiff_t)(gray_tap ? g.tap_row : mag_row), (ptrdiff_t)(gray_tap ? g.tap_bytes : mag_fbytes),
-                                     proc, g.ow, g.oh, g.och, (ptrdiff_t)(pr ? g.out_row : mag_row), (ptrdiff_t)(pr ? g.out_bytes : mag_fbytes), c->d_canvas + (size_t)k * can_bytes,
-                                     (ptrdiff_t)can_row, (ptrdiff_t)can_bytes, s);
+            if (fused)
+                rc = lvm::canvas_yuv_fused(c, cfmt, split, orig, g.ow, g.oh, gray_tap ? 3 : g.och, (ptrdiff_t)(gray_tap ? g.tap_row : mag_row), proc, g.ow, g.oh, g.och,
+                                           (ptrdiff_t)(pr ? g.out_row : mag_row), c->d_canvas_yuv + (size_t)k * dev_l.bytes, (ptrdiff_t)cw, s);
+            else
+                rc = lvm::compose_device(c, split, orig, g.ow, g.oh, gray_tap ? 3 : g.och, (ptrdiff_t)(gray_tap ? g.tap_row : mag_row), (ptrdiff_t)(gray_tap ? g.tap_bytes : mag_fbytes),
+                                         proc, g.ow, g.oh, g.och, (ptrdiff_t)(pr ? g.out_row : mag_row), (ptrdiff_t)(pr ? g.out_bytes : mag_fbytes), c->d_canvas + (size_t)k * can_bytes,
+                                         (ptrdiff_t)can_row, (ptrdiff_t)can_bytes, s);
             if (rc != LVM_OK) { drain(); return rc; }
         }
-        // drawLabel on every canvas of the sub-batch (Exporter.cpp:74-77, :82-85), from the tables of lvm_export_set_overlay
-        rc = lvm::overlay_device(c, c->d_canvas + (size_t)f0 * can_bytes, cw, chh, (ptrdiff_t)can_row, (ptrdiff_t)can_bytes, nf, s);
-        if (rc != LVM_OK) { drain(); return rc; }
+        if (!fused) {
+            // drawLabel on every canvas of the sub-batch (Exporter.cpp:74-77, :82-85), from the tables of lvm_export_set_overlay
+            rc = lvm::overlay_device(c, c->d_canvas + (size_t)f0 * can_bytes, cw, chh, (ptrdiff_t)can_row, (ptrdiff_t)can_bytes, nf, s);
+            if (rc == LVM_OK && cfmt != LVM_PIX_BGR)        // ... and the sub-batch's canvases become surfaces in one launch
+                rc = lvm::canvas_yuv_device(c, cfmt, c->d_canvas + (size_t)f0 * can_bytes, cw, chh, (ptrdiff_t)can_row, (ptrdiff_t)can_bytes, nf,
+                                            c->d_canvas_yuv + (size_t)f0 * dev_l.bytes, (ptrdiff_t)cw, (ptrdiff_t)dev_l.bytes, s);
+            if (rc != LVM_OK) { drain(); return rc; }
+        }
         LVM_EXPORT_TRY(hipEventRecord(c->ev_done[q], s));
         LVM_EXPORT_TRY(hipStreamWaitEvent(c->down_stream, c->ev_done[q], 0));
         if (mj) {       // stage 3 stays on the device (down_stream, next to the magnifier of the following sub-batch): the canvases become JPEG
@@ -800,7 +820,17 @@ static int export_frames_impl(lvm_ctx* c, const lvm_preprocess_params* pp, const
             continue;
         }
         // stage 3 (down_stream): the canvases of this sub-batch
-        for (int k = f0; k < f0 + nf; ++k)
+        for (int k = f0; k < f0 + nf && cfmt != LVM_PIX_BGR; ++k) {
+            // 1.5 B / pixel.  3h/2 rows of cw bytes in one copy where the chroma rows follow the Y rows at the Y stride (NV12 / NV21; the planar
+            // formats with packed rows: two chroma rows are one row of cw bytes); otherwise Y, then the two chroma planes
+            const uint8_t* d = c->d_canvas_yuv + (size_t)k * dev_l.bytes;
+            const bool one = dev_l.plane2 == 0 || canvas_stride == (ptrdiff_t)cw;
+            LVM_EXPORT_TRY(hipMemcpy2DAsync(canvases[k], (size_t)canvas_stride, d, (size_t)cw, (size_t)cw, (size_t)(one ? chh + chh / 2 : chh), hipMemcpyDeviceToHost, c->down_stream));
+            if (one) continue;
+            LVM_EXPORT_TRY(hipMemcpy2DAsync(canvases[k] + host_l.plane1, (size_t)host_l.cstride, d + dev_l.plane1, (size_t)cw / 2, (size_t)cw / 2, (size_t)chh / 2, hipMemcpyDeviceToHost, c->down_stream));
+            LVM_EXPORT_TRY(hipMemcpy2DAsync(canvases[k] + host_l.plane2, (size_t)host_l.cstride, d + dev_l.plane2, (size_t)cw / 2, (size_t)cw / 2, (size_t)chh / 2, hipMemcpyDeviceToHost, c->down_stream));
+        }
+        for (int k = f0; k < f0 + nf && cfmt == LVM_PIX_BGR; ++k)
             LVM_EXPORT_TRY(hipMemcpy2DAsync(canvases[k], (size_t)canvas_stride, c->d_canvas + (size_t)k * can_bytes, can_row, can_row, (size_t)chh,
                                             hipMemcpyDeviceToHost, c->down_stream));
     }
@@ -933,6 +963,49 @@ int lvm_get_source_format(lvm_ctx* c, int* fmt) {
     if (!c || !fmt) return LVM_ERR_INVALID;
     *fmt = c->source_format;
     return LVM_OK;
+}
+
+// Canvases as 4:2:0 surfaces, an extension beyond the reference (include/lvm_hip.h).  Only stored: lvm_export_frames reads it when it is called;
+// the magnifier, the tracked key and the overlay tables never see it.  Kept by lvm_reset.
+int lvm_set_canvas_format(lvm_ctx* c, int fmt) {
+    if (!c) return LVM_ERR_INVALID;
+    if (fmt != LVM_PIX_BGR && fmt != LVM_PIX_NV12 && fmt != LVM_PIX_NV21 && fmt != LVM_PIX_I420 && fmt != LVM_PIX_YV12) {
+        c->err = "lvm_set_canvas_format: the format must be LVM_PIX_BGR (0), _NV12 (4), _NV21 (5), _I420 (6) or _YV12 (7)";
+        return LVM_ERR_INVALID;
+    }
+    c->canvas_format = fmt;
+    return LVM_OK;
+}
+int lvm_get_canvas_format(lvm_ctx* c, int* fmt) {
+    if (!c || !fmt) return LVM_ERR_INVALID;
+    *fmt = c->canvas_format;
+    return LVM_OK;
+}
+
+int lvm_canvas_layout(int fmt, int canvas_w, int canvas_h, ptrdiff_t canvas_stride, size_t* bytes, size_t* plane1_offset, size_t* plane2_offset,
+                      ptrdiff_t* chroma_stride) {
+    lvm::CanvasLayout L;
+    if (lvm::canvas_layout(fmt, canvas_w, canvas_h, canvas_stride, &L)) return LVM_ERR_INVALID;
+    if (bytes) *bytes = L.bytes;
+    if (plane1_offset) *plane1_offset = L.plane1;
+    if (plane2_offset) *plane2_offset = L.plane2;
+    if (chroma_stride) *chroma_stride = L.cstride;
+    return LVM_OK;
+}
+
+int lvm_canvas_convert_device(lvm_ctx* c, int fmt, const uint8_t* d_bgr, int w, int h, ptrdiff_t bgr_stride, ptrdiff_t bgr_frame_stride, int n_frames,
+                              uint8_t* d_out, ptrdiff_t out_stride, ptrdiff_t out_frame_stride, void* hip_stream) {
+    if (!c) return LVM_ERR_INVALID;
+    LVM_HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
+    // (refused before anything runs: not even the wait that orders this call behind the previous one is enqueued)
+    int rc = lvm::canvas_yuv_device(c, fmt, d_bgr, w, h, bgr_stride, bgr_frame_stride, n_frames, d_out, out_stride, out_frame_stride, s, true);
+    if (rc != LVM_OK) return rc;
+    rc = lvm::order_after_previous(c, s);
+    if (rc != LVM_OK) return rc;
+    rc = lvm::canvas_yuv_device(c, fmt, d_bgr, w, h, bgr_stride, bgr_frame_stride, n_frames, d_out, out_stride, out_frame_stride, s);
+    lvm::mark_enqueued(c, s);
+    return rc;
 }
 
 size_t lvm_mjpeg_bound(int w, int h) { return (w < 1 || h < 1) ? 0 : lvm::mjpeg_bound(w, h); }

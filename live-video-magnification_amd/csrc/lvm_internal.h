@@ -547,6 +547,8 @@ struct Ctx {
     unsigned opencv_build = 0;        // lvm_set_opencv_build: which OpenCV build the Riesz arithmetic reproduces (a mask of LVM_CV_*; riesz.hip)
     bool phase_on_gray = false;       // lvm_set_phase_on_gray: LVM_MODE_PHASE magnifies 1-channel frames (an extension; off = MagnifyCore.hpp:212)
     int source_format = LVM_PIX_BGR;  // lvm_set_source_format: what the frames given to the chain / export / preprocess surfaces hold (preprocess.hip converts)
+    int canvas_format = LVM_PIX_BGR;  // lvm_set_canvas_format: what lvm_export_frames hands out (compose.hip converts: BT.601 4:2:0 of the BGR canvas)
+    DevBuf d_canvas_yuv;  // lvm_export_frames under a YUV canvas format: the converted canvases of a batch (rows packed)
     unsigned lab_lut_gen = 0;        // counts lvm_set_lab_lut calls: the per-value Lab table of a gray Riesz state (riesz.hip) follows the forward table
 };
 
@@ -704,6 +706,14 @@ int mjpeg_finish(Ctx* c, size_t total_frames, uint8_t* out_host, size_t* offsets
 int overlay_set(Ctx* c, int n, const lvm_overlay_label* labels);
 int overlay_device(Ctx* c, uint8_t* d_canvas, int cw, int chh, ptrdiff_t stride, ptrdiff_t fstride, int n_frames, hipStream_t s);
 void overlay_release(Ctx* c);
+// canvases as 4:2:0 surfaces (lvm_set_canvas_format): the layout rules of include/lvm_hip.h (null: fine, else the rule that was broken), the
+// conversion of BGR canvases in memory, and the same from the panes compose_device would write (one frame of a 1-stream context; no BGR canvas)
+struct CanvasLayout { size_t bytes, plane1, plane2; ptrdiff_t cstride; };
+const char* canvas_layout(int fmt, int w, int h, ptrdiff_t stride, CanvasLayout* out);
+int canvas_yuv_device(Ctx* c, int fmt, const uint8_t* d_bgr, int w, int h, ptrdiff_t bgr_stride, ptrdiff_t bgr_fstride, int n_frames, uint8_t* d_out,
+                      ptrdiff_t out_stride, ptrdiff_t out_fstride, hipStream_t s, bool check_only = false);
+int canvas_yuv_fused(Ctx* c, int fmt, int split, const uint8_t* d_orig, int ow, int oh, int och, ptrdiff_t ostride, const uint8_t* d_proc, int pw, int ph,
+                     int pch, ptrdiff_t pstride, uint8_t* d_out, ptrdiff_t out_stride, hipStream_t s);
 int compose_device(Ctx* c, int split, const uint8_t* d_orig, int ow, int oh, int och, ptrdiff_t ostride, ptrdiff_t osstride,
                    const uint8_t* d_proc, int pw, int ph, int pch, ptrdiff_t pstride, ptrdiff_t psstride, uint8_t* d_canvas,
                    ptrdiff_t cstride, ptrdiff_t csstride, hipStream_t s);

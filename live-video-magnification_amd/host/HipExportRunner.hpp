@@ -45,7 +45,8 @@ namespace lvm {
 //   struct View { const uint8_t* data; int w, h, channels; std::ptrdiff_t stride; bool empty; };
 //   using Source = ...;  bool next(Source&, View& raw);       raw stays valid until the next call (decoded in place)
 //   using Sink = ...;    bool write(Sink&, std::uint64_t seq, std::int64_t pts_us, std::uint8_t* canvas, int cw, int ch, std::ptrdiff_t stride);
-//                        draws the overlay if any, opens the writer on the first canvas, writes; false = cannot write (stop)
+//                        draws the overlay if any, opens the writer on the first canvas, writes; false = cannot write (stop).  Under
+//                        set_canvas_format(NV12 / NV21 / I420 / YV12) `canvas` is the 4:2:0 surface: 3 ch / 2 rows of cw bytes, stride = cw
 //   static bool aborted(const Sink&);
 //   (run_mjpeg only)     bool write_jpeg(Sink&, std::uint64_t seq, std::int64_t pts_us, const std::uint8_t* jpeg, std::size_t bytes, int cw, int ch);
 //                        the canvas as ONE complete JPEG frame, encoded on the device: what lvm::MjpegAviWriter::write takes
@@ -86,6 +87,18 @@ public:
     // Exporter.cpp:74-77 / :82-85).  It is run on constant canvases whenever the canvas geometry is (re)established and never on a frame:
     // the device applies the resulting tables (lvm_export_set_overlay).  An empty function switches the overlay off.
     void set_canvas_drawer(CanvasDrawer draw) { drawer_ = std::move(draw); overlay_dirty_ = true; }
+    // What run() hands to T::write (lvm_set_canvas_format): LVM_PIX_BGR -- the default, nothing changes without this call -- or a 4:2:0 surface,
+    // LVM_PIX_NV12 / _NV21 / _I420 / _YV12: cvtColor(canvas, COLOR_BGR2YUV_I420) of the BGR canvas, converted on the device, 1.5 bytes per pixel
+    // down instead of 3.  T::write then receives the planar canvas with stride = cw: (3 ch / 2) rows of cw bytes, what the reference-side binding
+    // wraps as a (3 ch / 2) x cw CV_8UC1 Mat for an encoder that takes 4:2:0 frames.  The text overlay under such a format is the device's alone:
+    // hand the label code to set_canvas_drawer() (its tables are applied to the BGR pixels before the conversion); a sink that draws on the host
+    // canvas it receives -- the fallback without a drawer -- would draw into Y samples.  run_mjpeg does not take part.  Throws lvm::Error on any
+    // other format; takes effect with the next batch.
+    void set_canvas_format(int fmt) {
+        if (lvm_set_canvas_format(mag_.handle(), fmt) != LVM_OK) throw Error(LVM_ERR_INVALID, std::string("lvm: ") + lvm_last_error(mag_.handle()));
+        overlay_dirty_ = overlay_dirty_ || fmt != fmt_;          // (the canvas slots are sized for the format: prepare() runs again)
+        fmt_ = fmt;
+    }
 
 private:
     template <bool MJPEG>
@@ -94,12 +107,13 @@ private:
         const lvm_params c = to_c(mag, 0);
         const double interval_us = 1'000'000.0 / (capture_fps > 0.0 ? capture_fps : 30.0);     // Exporter.cpp:196-199, :214
         std::uint64_t seq = 0, written = 0;
+        if (in_ && slots_mjpeg_ != MJPEG && fmt_ != LVM_PIX_BGR) overlay_dirty_ = true;          // (4:2:0 canvas slots are smaller than the JPEG sink's)
         bool more = true;
         while (more && !T::aborted(sink)) {
             int n = 0;
             if (has_carry_) {                                                                   // the frame that changed the geometry starts this batch
                 const typename T::View v{carry_.data(), cw0_, ch0_, cc0_, (std::ptrdiff_t)cw0_ * cc0_, false};
-                prepare(v, pre, split);
+                prepare(v, pre, split, MJPEG);
                 store(n, v); seqs_[(std::size_t)n++] = seq++;
                 has_carry_ = false;
             }
@@ -111,7 +125,7 @@ private:
                                                                                                 //  but it HAS taken its sequence number, :224 precedes :243: the pts of later frames count it;
                                                                                                 //  such a frame cannot pass the magnifier either: both of its sizes are < 2)
                 if (!slots_ready(raw)) {
-                    if (n == 0) prepare(raw, pre, split);
+                    if (n == 0) prepare(raw, pre, split, MJPEG);
                     else { keep(raw); break; }                                                  // flush what we have with the old geometry first
                 }
                 store(n, raw); seqs_[(std::size_t)n++] = seq++;
@@ -137,12 +151,18 @@ private:
         in_ = out_ = nullptr;
     }
     // pinned slots for `batch` input frames and canvases of this geometry (what core/FramePool.cpp:29-36 would hand out)
-    void prepare(const typename T::View& v, const lvm_preprocess_params& pre, int split) {
+    void prepare(const typename T::View& v, const lvm_preprocess_params& pre, int split, bool mjpeg) {
         release();
         w_ = v.w; h_ = v.h; ch_ = v.channels;
         if (lvm_export_geometry(&pre, split, w_, h_, ch_, &cw_, &chh_) != LVM_OK || cw_ <= 0 || chh_ <= 0)
             throw Error(LVM_ERR_INVALID, "export: empty canvas for this geometry");
-        frame_bytes_ = (std::size_t)w_ * h_ * ch_; canvas_bytes_ = (std::size_t)cw_ * chh_ * 3;
+        frame_bytes_ = (std::size_t)w_ * h_ * ch_;
+        // the canvas slots by the format's layout, rows packed (the JPEG sink's: sized for BGR canvases whatever the format, it does not take part)
+        const int slot_fmt = mjpeg ? LVM_PIX_BGR : fmt_;
+        slots_mjpeg_ = mjpeg;
+        canvas_stride_ = (std::ptrdiff_t)cw_ * (slot_fmt == LVM_PIX_BGR ? 3 : 1);
+        if (lvm_canvas_layout(slot_fmt, cw_, chh_, canvas_stride_, &canvas_bytes_, nullptr, nullptr, nullptr) != LVM_OK)
+            throw Error(LVM_ERR_INVALID, "export: no canvas layout for this format and geometry");
         if (drawer_) set_overlay(mag_.handle(), overlay_tables(cw_, chh_, drawer_));        // the labels of THIS canvas size
         else if (overlay_dirty_) set_overlay(mag_.handle(), {});
         overlay_dirty_ = false;
@@ -172,7 +192,7 @@ private:
                                          canvas_bytes_ * (std::size_t)batch_, offs.data(), produced.data());
         else
             rc = lvm_export_frames(mag_.handle(), &pre, &c, split, n, fin.data(), w_, h_, ch_, (std::ptrdiff_t)w_ * ch_, can.data(),
-                                   (std::ptrdiff_t)cw_ * 3, produced.data());
+                                   canvas_stride_, produced.data());
         if (rc != LVM_OK) throw Error(rc, std::string("lvm: ") + lvm_last_error(mag_.handle()));
         std::uint64_t written = 0;
         for (int k = 0; k < n; ++k) {
@@ -181,7 +201,7 @@ private:
             if constexpr (MJPEG) {
                 if (!T::write_jpeg(sink, seqs_[(std::size_t)k], pts, out_ + offs[(std::size_t)k], offs[(std::size_t)k + 1] - offs[(std::size_t)k], cw_, chh_)) return written;
             } else {
-                if (!T::write(sink, seqs_[(std::size_t)k], pts, can[(std::size_t)k], cw_, chh_, (std::ptrdiff_t)cw_ * 3)) return written;
+                if (!T::write(sink, seqs_[(std::size_t)k], pts, can[(std::size_t)k], cw_, chh_, canvas_stride_)) return written;
             }
             ++written;                                                                           // framesDone_ (:260)
         }
@@ -192,6 +212,7 @@ private:
     int batch_;
     int w_ = 0, h_ = 0, ch_ = 0, cw_ = 0, chh_ = 0;
     std::size_t frame_bytes_ = 0, canvas_bytes_ = 0;
+    std::ptrdiff_t canvas_stride_ = 0; int fmt_ = LVM_PIX_BGR; bool slots_mjpeg_ = false;
     std::uint8_t *in_ = nullptr, *out_ = nullptr;
     std::vector<std::uint64_t> seqs_;
     std::vector<std::uint8_t> carry_; bool has_carry_ = false; int cw0_ = 0, ch0_ = 0, cc0_ = 0;
@@ -232,7 +253,9 @@ struct LivimExportTraits {
     }
     using Sink = LivimExportSink;
     static bool write(Sink& k, std::uint64_t, std::int64_t, std::uint8_t* canvas, int cw, int ch, std::ptrdiff_t stride) {
-        cv::Mat m(ch, cw, CV_8UC3, canvas, static_cast<size_t>(stride));      // a view of the pinned canvas slot
+        // a view of the pinned canvas slot: BGR (stride 3 cw), or under set_canvas_format the 4:2:0 surface (stride cw) as OpenCV's (3 ch / 2) x cw Mat
+        cv::Mat m = stride < static_cast<std::ptrdiff_t>(cw) * 3 ? cv::Mat(ch * 3 / 2, cw, CV_8UC1, canvas, static_cast<size_t>(stride))
+                                                                 : cv::Mat(ch, cw, CV_8UC3, canvas, static_cast<size_t>(stride));
         if (!k.write_canvas(m)) return false;
         if (k.frames_done) k.frames_done->fetch_add(1, std::memory_order_relaxed);
         return true;

@@ -130,6 +130,12 @@ public:
     void set_source_format(int fmt) { check(lvm_set_source_format(ctx_, fmt)); }
     int source_format() { int v = 0; check(lvm_get_source_format(ctx_, &v)); return v; }
 
+    // Canvases of lvm_export_frames as 4:2:0 surfaces (LVM_PIX_NV12, _NV21, _I420, _YV12; LVM_PIX_BGR = the default) -- an extension beyond the
+    // reference: cvtColor(canvas, COLOR_BGR2YUV_I420) of the BGR canvas, converted on the device, 1.5 bytes per pixel down instead of 3
+    // (include/lvm_hip.h lvm_set_canvas_format; ExportRunner::set_canvas_format is the loop's switch).  Keeps the temporal state; kept across reset().
+    void set_canvas_format(int fmt) { check(lvm_set_canvas_format(ctx_, fmt)); }
+    int canvas_format() { int v = 0; check(lvm_get_canvas_format(ctx_, &v)); return v; }
+
     void synchronize() { check(lvm_synchronize(ctx_)); }
     lvm_ctx* handle() const { return ctx_; }
 

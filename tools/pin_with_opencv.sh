@@ -8,6 +8,8 @@
 #      -> tests/golden/frames_cfg{0,1,2,3}.npz (a few MB: commit them);
 #   2b. where the box has the cv2 module: cv2.cvtColor(COLOR_YUV2BGR_*) of one fixed raw frame per format -> tests/golden/yuv_cvtcolor.npz
 #      (the raw source formats of lvm_set_source_format, tests/test_yuv_source.py);
+#   2c. likewise cv2.cvtColor(COLOR_BGR2YUV_I420 / _YV12) of one fixed BGR frame -> tests/golden/bgr2yuv_420.npz (the canvas formats of
+#      lvm_set_canvas_format, tests/test_yuv_canvas.py);
 #   3. runs the pin tests: oracle AND library (emulation build; the gfx950 library where a GPU exists) against those files.
 # From then on `pytest -m refpin` is a parity gate that needs no OpenCV.
 set -e
@@ -31,4 +33,14 @@ for fmt in FORMATS:
     out["raw_" + NAMES[fmt]], out["bgr_" + NAMES[fmt]] = raw, cv2.cvtColor(src, CODES[NAMES[fmt]])
 np.savez("tests/golden/yuv_cvtcolor.npz", **out)
 PY
-python3 -m pytest tests/test_refpin.py tests/test_yuv_source.py -m refpin -q -s
+# 2c. cv2.cvtColor(COLOR_BGR2YUV_I420 / _YV12) of one fixed BGR frame (tests/test_yuv_canvas.py: golden_bgr) -> tests/golden/bgr2yuv_420.npz
+python3 - <<'PY' || echo "no cv2 module: the canvas formats stay unpinned"
+import sys
+import cv2
+import numpy as np
+sys.path.insert(0, "tests")
+from test_yuv_canvas import golden_bgr
+f = golden_bgr()
+np.savez("tests/golden/bgr2yuv_420.npz", bgr=f, i420=cv2.cvtColor(f, cv2.COLOR_BGR2YUV_I420), yv12=cv2.cvtColor(f, cv2.COLOR_BGR2YUV_YV12))
+PY
+python3 -m pytest tests/test_refpin.py tests/test_yuv_source.py tests/test_yuv_canvas.py -m refpin -q -s
