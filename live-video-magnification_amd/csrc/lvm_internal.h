@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -556,6 +557,23 @@ inline int lab_flavour(const Ctx* c) { return c->lab_analytic ? FL_ANALYTIC : (c
 // kernel instantiation of the context's flavour: LVM_FL_PICK(fl, k_name, other template arguments...)
 #define LVM_FL_PICK(fl, K, ...) ((fl) == FL_ANALYTIC ? K<__VA_ARGS__, FL_ANALYTIC> : ((fl) == FL_LUT_EXACT ? K<__VA_ARGS__, FL_LUT_EXACT> : K<__VA_ARGS__, FL_LUT_FAST>))
 #define LVM_FL_PICK0(fl, K) ((fl) == FL_ANALYTIC ? K<FL_ANALYTIC> : ((fl) == FL_LUT_EXACT ? K<FL_LUT_EXACT> : K<FL_LUT_FAST>))
+// Run-time values -> template arguments: lvm_pick(f, v...) calls the generic lambda f with one std::integral_constant per value -- a bool
+// as std::true_type / std::false_type, an int that is one of Vs... (the last of them when it is none) as PickInt<Vs...>{v} -- and returns
+// what f returns, a kernel instantiation.  Every call of f must return the same type; f instantiates only the combinations it names, so a
+// combination that does not exist is folded into one that does inside f (constexpr bool PT = E && pt).
+template <int... Vs> struct PickInt { int v; };
+inline PickInt<FL_ANALYTIC, FL_LUT_EXACT, FL_LUT_FAST> pick_flavour(int fl) { return {fl}; }
+template <class F> auto lvm_pick(F&& f) { return f(); }
+template <class F, int V, int... Vs, class... R> auto lvm_pick(F&& f, PickInt<V, Vs...> p, R... rest);
+template <class F, class... R> auto lvm_pick(F&& f, bool v, R... rest) {
+    auto with = [&](auto c) { return lvm_pick([&](auto... cs) { return f(c, cs...); }, rest...); };
+    return v ? with(std::true_type{}) : with(std::false_type{});
+}
+template <class F, int V, int... Vs, class... R> auto lvm_pick(F&& f, PickInt<V, Vs...> p, R... rest) {
+    auto with = [&](auto c) { return lvm_pick([&](auto... cs) { return f(c, cs...); }, rest...); };
+    if constexpr (sizeof...(Vs) == 0) return with(std::integral_constant<int, V>{});
+    else return p.v == V ? with(std::integral_constant<int, V>{}) : lvm_pick(f, PickInt<Vs...>{p.v}, rest...);
+}
 
 void sync_streams(Ctx* c);
 void mark_enqueued(Ctx* c, hipStream_t s);

@@ -352,6 +352,42 @@ __global__ __launch_bounds__(256) void k_rz_split2(const float* __restrict__ oct
 // REFLECT_101: rows by reflecting the row index of the load; columns at the image edge from the lane's own and its
 // inner neighbour's values (columns -4..-1 are columns 4, 3, 2, 1; columns w..w+3 are w-2, w-3, w-4, w-5).
 constexpr int SR_THREADS = 256, SR_OWN = 62;
+// The strip of one wave (k_rz_split_rows and the collapse strips): task -> plane z, strip (tx, ty) -> the lane's column group gl (clamped
+// into the plane), whether the lane owns it (lanes 0 and 63 only feed) and whether it is the image's first / last group; rows y0 .. y0 + rows
+// (rows is even: the strip starts on an even row), cut at h, are walked as the nq input rows y0 - 4 .. yend + 3.  false: the wave has no task.
+struct StripTask { int z, gl, y0, nq; bool owner, first, last; };
+template <int THREADS>
+__device__ __forceinline__ bool strip_task(int ntasks, int strips_x, int strips_y, int w, int h, int rows, StripTask& t) {
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const int task = blockIdx.x * (THREADS / 64) + wave;
+    if (task >= ntasks) return false;
+    t.z = task / (strips_x * strips_y);
+    const int r = task - t.z * (strips_x * strips_y);
+    const int ty = r / strips_x, tx = r - ty * strips_x;
+    const int G = w >> 2;                                           // w % 4 == 0, G >= 2
+    const int g = tx * SR_OWN - 1 + lane;
+    t.gl = g < 0 ? 0 : (g > G - 1 ? G - 1 : g);
+    t.owner = lane >= 1 && lane <= SR_OWN && g >= 0 && g < G;
+    t.first = g == 0; t.last = g == G - 1;
+    t.y0 = ty * rows;
+    const int yend = t.y0 + rows < h ? t.y0 + rows : h;
+    t.nq = yend - t.y0 + 8;
+    return true;
+}
+// REFLECT_101 row index of the NEXT load, advanced by selects: no control flow between the steps (a branch there -- reflect101's
+// loop -- splits the steps into basic blocks, and the compiler then sinks every fma chain down to the block of its store, keeping
+// the operand rows of nine steps alive: 1 KB of scratch per lane in the ISA)
+struct ReflectCursor {
+    int ry, rdir;                                                   // rdir = +1 / -1 (0: a one-row plane)
+    __device__ __forceinline__ ReflectCursor(int y, int h) : ry(reflect101(y, h)), rdir(reflect101(y + 1, h) - reflect101(y, h)) {}
+    __device__ __forceinline__ void advance(int h) {                // ry <- the reflected index of the row after it
+        const int t = ry + rdir;
+        const bool lo = t < 0, hi = t > h - 1;
+        ry = lo ? (h > 1 ? 1 : 0) : (hi ? (h > 1 ? h - 2 : 0) : t);
+        rdir = lo ? 1 : (hi ? -1 : rdir);
+    }
+};
+constexpr uint32_t kDrop = 0x80000000u;        // a lane offset that, + any row offset (< 2^31), stays outside every plane (< 2^31 bytes): the store is dropped
 // The high-pass accumulators of a slot are two register pairs -- outputs (0, 1) and (2, 3) -- and a tap is ONE v_pk_fma_f32 per
 // pair: tap j of outputs (m, m + 1) multiplies (v[j + m], v[j + m + 1]), which is the pair V[(j + m) / 2] of the row for an even
 // j + m and W[(j + m - 1) / 2] -- the same row shifted by one column -- for an odd one (VGPR pairs are even-aligned on gfx950, so
@@ -415,17 +451,10 @@ __device__ __forceinline__ void row12(const float4 v, bool first, bool last, lvm
 __global__ __launch_bounds__(SR_THREADS, 4) void k_rz_split_rows(const float* __restrict__ oct, int w, int h, float* __restrict__ band,
                                                                   float* __restrict__ next, int nw, int nh, int strips_x, int strips_y,
                                                                   int ntasks, int rows) {
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    const int task = blockIdx.x * (SR_THREADS / 64) + wave;
-    if (task >= ntasks) return;
-    const int z = task / (strips_x * strips_y);
-    const int r = task - z * (strips_x * strips_y);
-    const int ty = r / strips_x, tx = r - ty * strips_x;
-    const int G = w >> 2;                                           // w % 4 == 0, G >= 2
-    const int g = tx * SR_OWN - 1 + lane;
-    const int gl = g < 0 ? 0 : (g > G - 1 ? G - 1 : g);
-    const bool owner = lane >= 1 && lane <= SR_OWN && g >= 0 && g < G;
-    const bool first = g == 0, last = g == G - 1;
+    StripTask t;
+    if (!strip_task<SR_THREADS>(ntasks, strips_x, strips_y, w, h, rows, t)) return;
+    const int z = t.z, gl = t.gl, y0 = t.y0, nq = t.nq;
+    const bool owner = t.owner, first = t.first, last = t.last;
     // raw buffer addressing: one resource per plane (wave-uniform base), the lane's column group as a 32-bit byte offset, the row as
     // a scalar byte offset.  Stores are UNCONDITIONAL instructions: a lane that owns nothing (and every lane while the rows above
     // the strip complete) stores at an offset outside the resource, which the hardware drops.  (With the stores inside a branch the
@@ -434,26 +463,13 @@ __global__ __launch_bounds__(SR_THREADS, 4) void k_rz_split_rows(const float* __
     const BufRsrc rs = buf_rsrc(oct + (size_t)z * w * h, pbytes);
     const BufRsrc rb = buf_rsrc(band + (size_t)z * w * h, pbytes);
     const BufRsrc rn = buf_rsrc(next + (size_t)z * nw * nh, nbytes);
-    constexpr uint32_t kDrop = 0x80000000u;                         // + any row offset (< 2^31) stays outside every plane (< 2^31 bytes)
     const uint32_t lsrc = 16u * (uint32_t)gl, lband = owner ? 16u * (uint32_t)gl : kDrop, lnext = owner ? 8u * (uint32_t)gl : kDrop;
-    const int y0 = ty * rows;                                       // rows is even: the strip starts on an even row
-    const int yend = y0 + rows < h ? y0 + rows : h;
-    const int nq = yend - y0 + 8;                                   // input rows y0 - 4 .. yend + 3
     lvm_f2 hp[9][2];
     float lp[9][2];
 #pragma unroll
     for (int k = 0; k < 9; ++k) { hp[k][0] = hp[k][1] = f2_all(0.f); lp[k][0] = lp[k][1] = 0.f; }
-    // REFLECT_101 row index of the NEXT load, advanced by selects: no control flow between the steps (a branch there -- reflect101's
-    // loop -- splits the steps into basic blocks, and the compiler then sinks every fma chain down to the block of its store, keeping
-    // the operand rows of nine steps alive: 1 KB of scratch per lane in the ISA)
-    int ry = reflect101(y0 - 4, h), rdir = reflect101(y0 - 3, h) - ry;    // rdir = +1 / -1 (0: a one-row plane)
-    auto advance_row = [&]() __attribute__((always_inline)) {       // ry <- the reflected index of the row after it
-        const int t = ry + rdir;
-        const bool lo = t < 0, hi = t > h - 1;
-        ry = lo ? (h > 1 ? 1 : 0) : (hi ? (h > 1 ? h - 2 : 0) : t);
-        rdir = lo ? 1 : (hi ? -1 : rdir);
-    };
-    float4 nxt = buf_ld_f32x4(rs, lsrc, (uint32_t)ry * (uint32_t)w * 4u);
+    ReflectCursor row(y0 - 4, h);
+    float4 nxt = buf_ld_f32x4(rs, lsrc, (uint32_t)row.ry * (uint32_t)w * 4u);
     int q = 0;
 #define LVM_SPLIT_STEP(P18)                                                                                        \
     {                                                                                                               \
@@ -461,8 +477,8 @@ __global__ __launch_bounds__(SR_THREADS, 4) void k_rz_split_rows(const float* __
         constexpr int P = (P18) % 9;                                /* q = P18 (mod 18): slot phase and row parity are compile-time */ \
         constexpr bool EVEN = ((P18) & 1) == 0;                     /* input row y0 - 4 + q and output row y0 - 8 + q, y0 even */ \
         const float4 cur = nxt;                                                                                     \
-        advance_row();                                              /* row y0 - 3 + q, reflected */                 \
-        nxt = buf_ld_f32x4(rs, lsrc, (uint32_t)ry * (uint32_t)w * 4u);                                              \
+        row.advance(h);                                             /* row y0 - 3 + q, reflected */                 \
+        nxt = buf_ld_f32x4(rs, lsrc, (uint32_t)row.ry * (uint32_t)w * 4u);                                          \
         lvm_issue_fence();                                          /* the load is ISSUED here, a whole step ahead of its use */ \
         lvm_f2 V[6], W[5];                                                                                          \
         row12(cur, first, last, V, W);                                                                              \
@@ -532,24 +548,99 @@ __device__ __forceinline__ float mul_sd(float x, SdF s) { return __builtin_fmaf(
 // LVM_CV_MUL_F32: the scalar narrowed to float before the product (s.hi = (float)s), in every flavour
 __device__ __forceinline__ float mul_sf(float x, SdF s) { return x * s.hi; }
 
+// Which level and which tile of it a workgroup of a launch over all band levels works on (PhaseArgs / BlurArgs: the levels' workgroups follow
+// one another, level l from block0 on, stream by stream, tiles row-major).  Workgroups are taken in launch order: the XCD-aware order of
+// lvm_internal.h was measured here (blur 730 -> 875 us per 32 frames, phase unchanged).
+template <class Lv> struct LevelTile { const Lv& a; int x0, y0; size_t pl; };      // the level, the tile's origin, the stream's plane offset
+template <int TW, int TH, class Args>
+__device__ __forceinline__ auto level_tile(const Args& aa) {
+    int lvl = 0;
+    const int bid = (int)blockIdx.x;
+    while (lvl + 1 < aa.nlv && bid >= aa.lv[lvl + 1].block0) ++lvl;
+    const auto& a = aa.lv[lvl];
+    const int t = bid - a.block0;
+    const int bs = t / (a.tx * a.ty), tr = t - bs * (a.tx * a.ty);
+    return LevelTile<std::remove_const_t<std::remove_reference_t<decltype(a)>>>{a, (tr % a.tx) * TW, (tr / a.tx) * TH, (size_t)bs * a.w * a.h};
+}
+
+// The Riesz pair of one pixel: filter2D with [-0.2 -0.48 0 0.48 0.2] (1x5, and its transpose) given the two values before and the two after
+// the pixel -- non-zero taps, fma chain (RieszPyramid.cpp:71)
+template <bool UNF>
+__device__ __forceinline__ float riesz5(float m2, float m1, float p1, float p2) {
+    float r = tapf<UNF>(-0.2f, m2, 0.f);
+    r = tapf<UNF>(-0.48f, m1, r);
+    r = tapf<UNF>(0.48f, p1, r);
+    return tapf<UNF>(0.2f, p2, r);
+}
+// The phase step of ONE pixel and frame, the one text of it: quaternion product with the prior (P, R1, R2), phase difference and amplitude
+// (computePhaseDifferenceAndAmplitude, RieszPyramid.cpp:81-111), phase accumulation and both IIR sections (TemporalFilter.cpp:343-350),
+// prior <- current (MagnifyCore.hpp:267).  p, r1, r2: the band and its Riesz pair; the 13 state values are updated in place.
+// MF32: `Mat * double` of the IIR step with the scalar narrowed to float first (LVM_CV_MUL_F32) -- x * (float)s, in place of the exact
+// flavour's float64 product and of the default flavour's hi / lo pair.
+template <bool EXACT, bool MF32, bool PT>
+__device__ __forceinline__ void phase_px(const PhaseArgs& aa, float p, float r1, float r2, float& Pp, float& R1, float& R2, float& phc, float& phs,
+                                         float& lo0c, float& lo0s, float& lo1c, float& lo1s, float& hi0c, float& hi0s, float& hi1c, float& hi1s,
+                                         float& amp, float& tc, float& ts) {
+    const float q0 = (p * Pp + r1 * R1) + r2 * R2;                     // :82-84
+    const float np = p * (-1.f);
+    const float q1 = R1 * np + r1 * Pp;                                // :86
+    const float q2 = R2 * np + r2 * Pp;
+    const float xy = q1 * q1 + q2 * q2;                                // :89
+    const float ampq = sqrtf(q0 * q0 + xy);                            // :91
+    const float phi = arc_cos<PT>(q0 / ampq);                          // :93-97
+    // The acos argument above keeps IEEE sqrt and division in every flavour (it is the ill-conditioned step);
+    // the direction q/|q| and the amplitude are well-conditioned: the default flavour uses v_rsq / v_sqrt there.
+    float dc, ds;
+    if (EXACT) {
+        const float sxy = sqrtf(xy);                                   // :99-100
+        dc = (q1 / sxy) * phi; ds = (q2 / sxy) * phi;                  // :102-104
+    } else {
+        // v_rsq_f32 flushes a denormal argument to 0 (-> +inf) where sqrt + divide stay finite: rescale by 2^64
+        // below 2^-100 (xy == 0 still gives inf -> 0 * inf = NaN -> patched to 0 below, like the reference's 0 / 0)
+        const bool tiny = xy < 0x1p-100f;
+        float rs = __builtin_amdgcn_rsqf(tiny ? xy * 0x1p64f : xy);
+        rs = tiny ? rs * 0x1p32f : rs;
+        dc = (q1 * rs) * phi; ds = (q2 * rs) * phi;
+    }
+    if (dc != dc) dc = 0.f;                                            // :105-106
+    if (ds != ds) ds = 0.f;
+    const float am = EXACT ? sqrtf(ampq) : __builtin_amdgcn_sqrtf(ampq);   // :108
+    // IIRTemporalFilter for the low and the high cutoff (TemporalFilter.cpp:343-350); both keep
+    // their own copy of the accumulated phase in the reference, the copies are always equal.
+    phc = phc + dc; phs = phs + ds;
+#define MSD(x, c) (MF32 ? mul_sf((x), aa.f##c) : (EXACT ? mul_sd((x), aa.c) : mul_sd((x), aa.f##c)))
+    const float ylc = MSD(phc, lb0) + lo0c;
+    const float yls = MSD(phs, lb0) + lo0s;
+    lo0c = (MSD(phc, lb1) + lo1c) - MSD(ylc, la1);
+    lo0s = (MSD(phs, lb1) + lo1s) - MSD(yls, la1);
+    lo1c = MSD(phc, lb2) - MSD(ylc, la2);
+    lo1s = MSD(phs, lb2) - MSD(yls, la2);
+    const float yhc = MSD(phc, hb0) + hi0c;
+    const float yhs = MSD(phs, hb0) + hi0s;
+    hi0c = (MSD(phc, hb1) + hi1c) - MSD(yhc, ha1);
+    hi0s = (MSD(phs, hb1) + hi1s) - MSD(yhs, ha1);
+    hi1c = MSD(phc, hb2) - MSD(yhc, ha2);
+    hi1s = MSD(phs, hb2) - MSD(yhs, ha2);
+#undef MSD
+    amp = am;
+    tc = (yhc - ylc) * am;                                             // RieszPyramid.cpp:118-120
+    ts = (yhs - yls) * am;
+    Pp = p; R1 = r1; R2 = r2;                                          // MagnifyCore.hpp:267
+}
+
 // With nt > 1 the workgroup walks over nt consecutive frames: the 13 state values of a pixel (prior
 // band + Riesz pair, accumulated phase, 8 filter registers) stay in registers and move through HBM
 // once per launch instead of once per frame; the band tile of frame t+1 is prefetched while frame t
 // is processed.
-// UNF: the 5-tap Riesz pair with unfused taps (LVM_CV_FILTER_UNFUSED); MF32: `Mat * double` of the IIR step with the scalar narrowed to
-// float first (LVM_CV_MUL_F32) -- x * (float)s, in place of the exact flavour's float64 product and of the default flavour's hi / lo pair.
+// UNF: the 5-tap Riesz pair with unfused taps (LVM_CV_FILTER_UNFUSED); MF32, PT: phase_px.
 template <bool EXACT, bool UNF, bool MF32, bool PT = false>
 __global__ __launch_bounds__(256) void k_rz_phase(PhaseArgs aa) {
     static_assert(EXACT || !PT, "the portable functions belong to the exact flavour");
     __shared__ float s[PT_H + 4][PT_W + 4 + 1];
-    int lvl = 0;
-    const int bid = (int)blockIdx.x;       // (the XCD-aware order of lvm_internal.h was measured here: blur 730 -> 875 us per 32 frames, phase unchanged)
-    while (lvl + 1 < aa.nlv && bid >= aa.lv[lvl + 1].block0) ++lvl;
-    const PhaseLv& a = aa.lv[lvl];
-    const int tq = bid - a.block0;
-    const int bs = tq / (a.tx * a.ty), tr = tq - bs * (a.tx * a.ty);
-    const int x0 = (tr % a.tx) * PT_W, y0 = (tr / a.tx) * PT_H;
-    const size_t pl = (size_t)bs * a.w * a.h;
+    const auto lt = level_tile<PT_W, PT_H>(aa);
+    const PhaseLv& a = lt.a;
+    const int x0 = lt.x0, y0 = lt.y0;
+    const size_t pl = lt.pl;
     constexpr int NSE = ((PT_H + 4) * (PT_W + 4) + 255) / 256;
     size_t soff[NSE]; int sdst[NSE]; float pre[NSE];
 #pragma unroll
@@ -586,65 +677,18 @@ __global__ __launch_bounds__(256) void k_rz_phase(PhaseArgs aa) {
         if (!ok) continue;
         const size_t fidx = (size_t)t * a.fs + idx;
         const float p = s[y + 2][x + 2];
-        // filter2D with [-0.2 -0.48 0 0.48 0.2] (1x5) and its transpose: non-zero taps, fma chain
-        float r1 = tapf<UNF>(-0.2f, s[y + 2][x], 0.f);
-        r1 = tapf<UNF>(-0.48f, s[y + 2][x + 1], r1);
-        r1 = tapf<UNF>(0.48f, s[y + 2][x + 3], r1);
-        r1 = tapf<UNF>(0.2f, s[y + 2][x + 4], r1);
-        float r2 = tapf<UNF>(-0.2f, s[y][x + 2], 0.f);
-        r2 = tapf<UNF>(-0.48f, s[y + 1][x + 2], r2);
-        r2 = tapf<UNF>(0.48f, s[y + 3][x + 2], r2);
-        r2 = tapf<UNF>(0.2f, s[y + 4][x + 2], r2);
+        const float r1 = riesz5<UNF>(s[y + 2][x], s[y + 2][x + 1], s[y + 2][x + 3], s[y + 2][x + 4]);
+        const float r2 = riesz5<UNF>(s[y][x + 2], s[y + 1][x + 2], s[y + 3][x + 2], s[y + 4][x + 2]);
         if (aa.mode != 0) {   // seed: prior <- current (Riesz pair zeroed by RieszPyramid::init), filters cleared
             Pp = p; R1 = aa.mode == 1 ? 0.f : r1; R2 = aa.mode == 1 ? 0.f : r2;
             continue;
         }
-        const float q0 = (p * Pp + r1 * R1) + r2 * R2;                     // :82-84
-        const float np = p * (-1.f);
-        const float q1 = R1 * np + r1 * Pp;                                // :86
-        const float q2 = R2 * np + r2 * Pp;
-        const float xy = q1 * q1 + q2 * q2;                                // :89
-        const float ampq = sqrtf(q0 * q0 + xy);                            // :91
-        const float phi = arc_cos<PT>(q0 / ampq);                          // :93-97
-        // The acos argument above keeps IEEE sqrt and division in every flavour (it is the ill-conditioned step);
-        // the direction q/|q| and the amplitude are well-conditioned: the default flavour uses v_rsq / v_sqrt there.
-        float dc, ds;
-        if (EXACT) {
-            const float sxy = sqrtf(xy);                                   // :99-100
-            dc = (q1 / sxy) * phi; ds = (q2 / sxy) * phi;                  // :102-104
-        } else {
-            // v_rsq_f32 flushes a denormal argument to 0 (-> +inf) where sqrt + divide stay finite: rescale by 2^64
-            // below 2^-100 (xy == 0 still gives inf -> 0 * inf = NaN -> patched to 0 below, like the reference's 0 / 0)
-            const bool tiny = xy < 0x1p-100f;
-            float rs = __builtin_amdgcn_rsqf(tiny ? xy * 0x1p64f : xy);
-            rs = tiny ? rs * 0x1p32f : rs;
-            dc = (q1 * rs) * phi; ds = (q2 * rs) * phi;
-        }
-        if (dc != dc) dc = 0.f;                                            // :105-106
-        if (ds != ds) ds = 0.f;
-        const float am = EXACT ? sqrtf(ampq) : __builtin_amdgcn_sqrtf(ampq);   // :108
-        // IIRTemporalFilter for the low and the high cutoff (TemporalFilter.cpp:343-350); both keep
-        // their own copy of the accumulated phase in the reference, the copies are always equal.
-        phc = phc + dc; phs = phs + ds;
-#define MSD(x, c) (MF32 ? mul_sf((x), aa.f##c) : (EXACT ? mul_sd((x), aa.c) : mul_sd((x), aa.f##c)))
-        const float ylc = MSD(phc, lb0) + lo0c;
-        const float yls = MSD(phs, lb0) + lo0s;
-        lo0c = (MSD(phc, lb1) + lo1c) - MSD(ylc, la1);
-        lo0s = (MSD(phs, lb1) + lo1s) - MSD(yls, la1);
-        lo1c = MSD(phc, lb2) - MSD(ylc, la2);
-        lo1s = MSD(phs, lb2) - MSD(yls, la2);
-        const float yhc = MSD(phc, hb0) + hi0c;
-        const float yhs = MSD(phs, hb0) + hi0s;
-        hi0c = (MSD(phc, hb1) + hi1c) - MSD(yhc, ha1);
-        hi0s = (MSD(phs, hb1) + hi1s) - MSD(yhs, ha1);
-        hi1c = MSD(phc, hb2) - MSD(yhc, ha2);
-        hi1s = MSD(phs, hb2) - MSD(yhs, ha2);
-#undef MSD
+        float am, tc, ts;
+        phase_px<EXACT, MF32, PT>(aa, p, r1, r2, Pp, R1, R2, phc, phs, lo0c, lo0s, lo1c, lo1s, hi0c, hi0s, hi1c, hi1s, am, tc, ts);
         a.amp[fidx] = am;
-        a.tc[fidx] = (yhc - ylc) * am;                                     // RieszPyramid.cpp:118-120
-        a.ts[fidx] = (yhs - yls) * am;
+        a.tc[fidx] = tc;
+        a.ts[fidx] = ts;
         if (a.R1c != a.R1p) { a.R1c[fidx] = r1; a.R2c[fidx] = r2; }        // batched frames keep their own pair
-        Pp = p; R1 = r1; R2 = r2;                                          // MagnifyCore.hpp:267
     }
     if (!ok) return;
     a.P[idx] = Pp; a.R1p[idx] = R1; a.R2p[idx] = R2;
@@ -663,14 +707,10 @@ template <bool EXACT, bool UNF, bool MF32, bool PT = false>
 __global__ __launch_bounds__(256) void k_rz_phase4(PhaseArgs aa) {
     static_assert(EXACT || !PT, "the portable functions belong to the exact flavour");
     __shared__ __attribute__((aligned(16))) float s[P4_SH][P4_SW];
-    int lvl = 0;
-    const int bid = (int)blockIdx.x;       // (the XCD-aware order of lvm_internal.h was measured here: blur 730 -> 875 us per 32 frames, phase unchanged)
-    while (lvl + 1 < aa.nlv && bid >= aa.lv[lvl + 1].block0) ++lvl;
-    const PhaseLv& a = aa.lv[lvl];
-    const int tq = bid - a.block0;
-    const int bs = tq / (a.tx * a.ty), tr = tq - bs * (a.tx * a.ty);
-    const int x0 = (tr % a.tx) * P4_W, y0 = (tr / a.tx) * P4_H;
-    const size_t pl = (size_t)bs * a.w * a.h;
+    const auto lt = level_tile<P4_W, P4_H>(aa);
+    const PhaseLv& a = lt.a;
+    const int x0 = lt.x0, y0 = lt.y0;
+    const size_t pl = lt.pl;
     // staging: P4_SH rows x 18 column groups of 4; group g covers image columns x0 - 4 + 4 g .. + 3.  Groups inside the image
     // are one aligned 16-byte load (row reflected); the groups hanging over the left / right edge are gathered per element.
     constexpr int NG = P4_SH * (P4_SW / 4), NSE = (NG + 255) / 256;
@@ -741,56 +781,15 @@ __global__ __launch_bounds__(256) void k_rz_phase4(PhaseArgs aa) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const float p = hrow[4 + k];
-            float r1 = tapf<UNF>(-0.2f, hrow[2 + k], 0.f);
-            r1 = tapf<UNF>(-0.48f, hrow[3 + k], r1);
-            r1 = tapf<UNF>(0.48f, hrow[5 + k], r1);
-            r1 = tapf<UNF>(0.2f, hrow[6 + k], r1);
-            float r2 = tapf<UNF>(-0.2f, vcol[0][k], 0.f);
-            r2 = tapf<UNF>(-0.48f, vcol[1][k], r2);
-            r2 = tapf<UNF>(0.48f, vcol[3][k], r2);
-            r2 = tapf<UNF>(0.2f, vcol[4][k], r2);
+            const float r1 = riesz5<UNF>(hrow[2 + k], hrow[3 + k], hrow[5 + k], hrow[6 + k]);
+            const float r2 = riesz5<UNF>(vcol[0][k], vcol[1][k], vcol[3][k], vcol[4][k]);
             r1v[k] = r1; r2v[k] = r2;
             if (aa.mode != 0) {
                 Pp[k] = p; R1[k] = aa.mode == 1 ? 0.f : r1; R2[k] = aa.mode == 1 ? 0.f : r2;
                 continue;
             }
-            const float q0 = (p * Pp[k] + r1 * R1[k]) + r2 * R2[k];
-            const float np = p * (-1.f);
-            const float q1 = R1[k] * np + r1 * Pp[k];
-            const float q2 = R2[k] * np + r2 * Pp[k];
-            const float xy = q1 * q1 + q2 * q2;
-            const float ampq = sqrtf(q0 * q0 + xy);
-            const float phi = arc_cos<PT>(q0 / ampq);
-            float dc, ds;
-            if (EXACT) {
-                const float sxy = sqrtf(xy);
-                dc = (q1 / sxy) * phi; ds = (q2 / sxy) * phi;
-            } else {
-                const bool tiny = xy < 0x1p-100f;
-                float rs = __builtin_amdgcn_rsqf(tiny ? xy * 0x1p64f : xy);
-                rs = tiny ? rs * 0x1p32f : rs;
-                dc = (q1 * rs) * phi; ds = (q2 * rs) * phi;
-            }
-            if (dc != dc) dc = 0.f;
-            if (ds != ds) ds = 0.f;
-            const float am = EXACT ? sqrtf(ampq) : __builtin_amdgcn_sqrtf(ampq);
-            phc[k] = phc[k] + dc; phs[k] = phs[k] + ds;
-#define MSD(x, c) (MF32 ? mul_sf((x), aa.f##c) : (EXACT ? mul_sd((x), aa.c) : mul_sd((x), aa.f##c)))
-            const float ylc = MSD(phc[k], lb0) + lo0c[k];
-            const float yls = MSD(phs[k], lb0) + lo0s[k];
-            lo0c[k] = (MSD(phc[k], lb1) + lo1c[k]) - MSD(ylc, la1);
-            lo0s[k] = (MSD(phs[k], lb1) + lo1s[k]) - MSD(yls, la1);
-            lo1c[k] = MSD(phc[k], lb2) - MSD(ylc, la2);
-            lo1s[k] = MSD(phs[k], lb2) - MSD(yls, la2);
-            const float yhc = MSD(phc[k], hb0) + hi0c[k];
-            const float yhs = MSD(phs[k], hb0) + hi0s[k];
-            hi0c[k] = (MSD(phc[k], hb1) + hi1c[k]) - MSD(yhc, ha1);
-            hi0s[k] = (MSD(phs[k], hb1) + hi1s[k]) - MSD(yhs, ha1);
-            hi1c[k] = MSD(phc[k], hb2) - MSD(yhc, ha2);
-            hi1s[k] = MSD(phs[k], hb2) - MSD(yhs, ha2);
-#undef MSD
-            amv[k] = am; tcv[k] = (yhc - ylc) * am; tsv[k] = (yhs - yls) * am;
-            Pp[k] = p; R1[k] = r1; R2[k] = r2;
+            phase_px<EXACT, MF32, PT>(aa, p, r1, r2, Pp[k], R1[k], R2[k], phc[k], phs[k], lo0c[k], lo0s[k], lo1c[k], lo1s[k],
+                                      hi0c[k], hi0s[k], hi1c[k], hi1s[k], amv[k], tcv[k], tsv[k]);
         }
         if (aa.mode != 0) continue;
         st4(a.amp, fidx, amv); st4(a.tc, fidx, tcv); st4(a.ts, fidx, tsv);
@@ -853,14 +852,10 @@ template <bool EXACT, bool UNF, bool PT = false>
 __global__ __launch_bounds__(256) void k_rz_blur_amp(BlurArgs aa) {
     __shared__ float s[3][BSH][BS + 1];
     __shared__ float hr[3][BSH][BT + 1];
-    int lvl = 0;
-    const int bid = (int)blockIdx.x;       // (the XCD-aware order of lvm_internal.h was measured here: blur 730 -> 875 us per 32 frames, phase unchanged)
-    while (lvl + 1 < aa.nlv && bid >= aa.lv[lvl + 1].block0) ++lvl;
-    const BlurLv& a = aa.lv[lvl];
-    const int t = bid - a.block0;
-    const int bs = t / (a.tx * a.ty), tr = t - bs * (a.tx * a.ty);
-    const int x0 = (tr % a.tx) * BT, y0 = (tr / a.tx) * BTH;
-    const size_t pl = (size_t)bs * a.w * a.h;
+    const auto lt = level_tile<BT, BTH>(aa);
+    const BlurLv& a = lt.a;
+    const int x0 = lt.x0, y0 = lt.y0;
+    const size_t pl = lt.pl;
     for (int i = threadIdx.x; i < BSH * BS; i += 256) {
         const int ly = i / BS, lx = i - ly * BS;
         const size_t si = pl + (size_t)reflect101(y0 - BH + ly, a.h) * a.w + reflect101(x0 - BH + lx, a.w);
@@ -918,14 +913,10 @@ template <bool EXACT, bool UNF, bool PT = false>
 __global__ LVM_BLUR_BOUNDS void k_rz_blur_amp4(BlurArgs aa) {
     __shared__ __attribute__((aligned(16))) float s[B2SH][B2SW];
     __shared__ __attribute__((aligned(16))) float hr[B2SH][B2W];
-    int lvl = 0;
-    const int bid = (int)blockIdx.x;       // (the XCD-aware order of lvm_internal.h was measured here: blur 730 -> 875 us per 32 frames, phase unchanged)
-    while (lvl + 1 < aa.nlv && bid >= aa.lv[lvl + 1].block0) ++lvl;
-    const BlurLv& a = aa.lv[lvl];
-    const int t = bid - a.block0;
-    const int bs = t / (a.tx * a.ty), tr = t - bs * (a.tx * a.ty);
-    const int x0 = (tr % a.tx) * B2W, y0 = (tr / a.tx) * B2H;
-    const size_t pl = (size_t)bs * a.w * a.h;
+    const auto lt = level_tile<B2W, B2H>(aa);
+    const BlurLv& a = lt.a;
+    const int x0 = lt.x0, y0 = lt.y0;
+    const size_t pl = lt.pl;
     const bool interior = x0 - B2HX >= 0 && x0 + B2W + B2HX <= a.w && y0 - B2HY >= 0 && y0 + B2H + B2HY <= a.h;
     const int gq = threadIdx.x & 15, yq = threadIdx.x >> 4;           // column pass: 16 column groups x 16 row pairs
     const int x = 4 * gq, y = 2 * yq;
@@ -1288,26 +1279,55 @@ __global__ __launch_bounds__(BS_THREADS) void k_rz_blur_strips(BlurStripArgs aa)
     }
 }
 
-// level-0 collapse (or plain L plane when there are no bands) + Lab2BGR + u8 (MagnifyCore.hpp:272-277).
-// 4 pixels per thread; VEC = the frame's 4-pixel groups are dword aligned (12-byte loads/stores).
+// level-0 collapse (or plain L plane when there are no bands) + Lab2BGR + u8 (MagnifyCore.hpp:272-277), tiled: ONE body for BGR frames
+// (k_rz_final) and gray frames (k_rz_final_gray).  4 pixels per thread; VEC = the frames' 4-pixel groups are dword aligned (BGR: 12-byte
+// loads / stores; gray: rows, streams and base pointers of both frames dword aligned and w % 4 == 0, one dword each way).
 struct __attribute__((packed, aligned(4))) RzPx4 { uint32_t a, b, c; };
-// LPLANE (without BANDS, analytic flavour): L' is the float plane `Lplane` -- level 0 collapsed by k_rz_collapse under a build kind of
-// lvm_set_opencv_build -- where the flavour would otherwise take L from the frame (the table flavours read Lplane anyway).
-template <bool BANDS, int FL, bool VEC, bool COMPACT, bool DBG, bool LPLANE = false>   // DBG: also store the float frame (compile time: no per-pixel branch otherwise)
-__global__ __launch_bounds__(256) void k_rz_final(const uint8_t* __restrict__ in, long in_stride, long in_sstride,
-                                                  uint8_t* __restrict__ out, long out_stride, long out_sstride, int w, int h,
-                                                  const float* __restrict__ bandA, const float* __restrict__ resn, int nw,
-                                                  int nh, LabCoef lab, int tiles_x, int tiles_y, int nstreams,
-                                                  float* __restrict__ dbg, const float* __restrict__ Lplane, const uint32_t* __restrict__ iab) {
+struct FinalArgs {
+    const uint8_t* in; long in_stride, in_sstride;               // the input frames (BGR: read by the analytic flavour; gray: read for (a, b))
+    uint8_t* out; long out_stride, out_sstride;
+    int w, h;
+    const float* bandA; const float* resn; int nw, nh;           // BANDS: level 0 of the amplified pyramid and the collapsed level 1
+    LabCoef lab;
+    int tiles_x, tiles_y, nstreams;
+    float* dbg;                                                  // DBG: the kept float frame of stream 0 (null: not kept)
+    const float* Lplane;                                         // L' where it is a plane (no BANDS; see LPLANE)
+    const uint32_t* iab;                                         // BGR frames, table flavours: the (ia, ib) plane
+    const float* gtab;                                           // gray frames: the per-value table of the state
+};
+// four L', four (a, b) -- ab(m, a, b) hands out those of pixel m -- -> Lab2BGR -> the kept float frame (DBG and keep: columns gx .. gx + 3
+// of the row that starts at pixel `row`, as far as they are inside the width w) -> the three bytes of each pixel, handed to put(m, b, g, r)
+template <bool EXACT, bool DBG, class AB, class Put>
+__device__ __forceinline__ void final_px4(const float (&L)[4], AB&& ab, const LabCoef& lab, const float* s_igt,
+                                          bool keep, float* dbg, size_t row, int gx, int w, Put&& put) {
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        float av, bv, o0, o1, o2;
+        ab(m, av, bv);
+        lab_to_bgr<EXACT>(L[m], av, bv, EXACT ? lab.inv : lab.inv1024, s_igt, o0, o1, o2);
+        if (DBG && keep && gx + m < w) { float* d = dbg + (row + gx + m) * 3; d[0] = o0; d[1] = o1; d[2] = o2; }
+        put(m, sat_u8(o0 * 255.0f + lab.a255), sat_u8(o1 * 255.0f + lab.a255), sat_u8(o2 * 255.0f + lab.a255));
+    }
+}
+// The variants differ in where (a, b) come from -- the (ia, ib) plane (table flavours), the analytic conversion of the frame, or (GRAY) the
+// per-value table a(v), b(v) of the state in LDS at the pixel's input byte (labconv.hip k_lab_gray_table: what the BGR kernels get for the
+// colour (v, v, v)) -- and in how the bytes leave: three per pixel, or (GRAY) one, GrayscaleProcessor's weighting of the three (gray15).
+// L' without BANDS is the float plane `Lplane` (oct_0, or res_0 under a build kind), except that the analytic flavour of BGR frames takes
+// L from the frame unless LPLANE.  DBG: also store the float frame (compile time: no per-pixel branch otherwise).
+template <bool GRAY, bool BANDS, int FL, bool VEC, bool COMPACT, bool DBG, bool LPLANE>
+__device__ __forceinline__ void rz_final_tiles(const FinalArgs& a) {
     constexpr bool EXACT = fl_exact(FL);
+    constexpr bool GAMMA = !GRAY && !fl_lut(FL);                   // the analytic forward conversion needs the u8 gamma table
     __shared__ __attribute__((aligned(16))) float s_igt[4096];
-    __shared__ float s_gam[fl_lut(FL) ? 1 : 256];
+    __shared__ float s_tab[GRAY ? 512 : (GAMMA ? 256 : 1)];      // GRAY: a(v), then b(v); else the gamma table
     __shared__ __attribute__((aligned(16))) float sb[CSH][CSP];
     __shared__ __attribute__((aligned(16))) CollapseTile<COMPACT> su;
-    load_invgamma(s_igt, lab.invgamma);
-    if (!fl_lut(FL)) load_gamma_u8(s_gam, lab.gamma_u8);
+    load_invgamma(s_igt, a.lab.invgamma);
+    if (GRAY) { s_tab[threadIdx.x] = a.gtab[256 + threadIdx.x]; s_tab[256 + threadIdx.x] = a.gtab[512 + threadIdx.x]; }
+    else if (GAMMA) load_gamma_u8(s_tab, a.lab.gamma_u8);
     __syncthreads();
-    const int ntiles = tiles_x * tiles_y * nstreams;
+    const int w = a.w, h = a.h, tiles_x = a.tiles_x, tiles_y = a.tiles_y;
+    const int ntiles = tiles_x * tiles_y * a.nstreams;
     const int y = collapse_row(), x = (threadIdx.x & 15) * 4;
     // every workgroup takes a contiguous run of tiles, every XCD a contiguous run of workgroups (xcd_swizzle)
     const int tper = (ntiles + (int)gridDim.x - 1) / (int)gridDim.x;
@@ -1322,7 +1342,7 @@ __global__ __launch_bounds__(256) void k_rz_final(const uint8_t* __restrict__ in
         // phase A: collapse (register-heavy 9x9 taps); its 4 results go through LDS so that the register
         // allocation of phase B (colour math) does not add to it
         if (BANDS) {
-            collapse_stage(sb, su, bandA + (size_t)b * w * h, resn + (size_t)b * nw * nh, w, h, nw, nh, x0, y0);
+            collapse_stage(sb, su, a.bandA + (size_t)b * w * h, a.resn + (size_t)b * a.nw * a.nh, w, h, a.nw, a.nh, x0, y0);
             __syncthreads();
             float Lc[4] = {0.f, 0.f, 0.f, 0.f};
             if (ok) collapse_px4(sb, su, x, y, gy, Lc);
@@ -1331,23 +1351,24 @@ __global__ __launch_bounds__(256) void k_rz_final(const uint8_t* __restrict__ in
             __builtin_amdgcn_sched_barrier(0);
         }
         if (ok) {
-            // Lab(in): analytic flavour from the u8 frame; LUT flavours from the planes the conversion kernel wrote
-            float Lin[4] = {0.f, 0.f, 0.f, 0.f}, ain[4], bin[4];
-            if (fl_lut(FL)) {
-                const size_t i = ((size_t)b * h + gy) * w + gx;
-                uint32_t q[4];
-                if (VEC) { const uint4 v = *reinterpret_cast<const uint4*>(iab + i); q[0] = v.x; q[1] = v.y; q[2] = v.z; q[3] = v.w; }
+            const size_t i = ((size_t)b * h + gy) * w + gx;        // the thread's first pixel in a plane
+            float L[4] = {0.f, 0.f, 0.f, 0.f}, av[4], bv[4];   // (av, bv: the analytic flavour's)
+            uint32_t q[4];                                         // the pixels' input bytes (GRAY) or (ia, ib) dwords (table flavours)
+            if constexpr (GRAY) {
+                const uint8_t* p = a.in + (size_t)b * a.in_sstride + (size_t)gy * a.in_stride + (size_t)gx;
+                if (VEC) { const uint32_t v = *reinterpret_cast<const uint32_t*>(p); q[0] = v & 255u; q[1] = (v >> 8) & 255u; q[2] = (v >> 16) & 255u; q[3] = v >> 24; }
                 else {
 #pragma unroll
-                    for (int m = 0; m < 4; ++m) q[m] = (gx + m < w) ? iab[i + m] : 0u;
+                    for (int m = 0; m < 4; ++m) q[m] = (gx + m < w) ? p[m] : 0;
                 }
+            } else if constexpr (fl_lut(FL)) {                     // the planes the conversion kernel wrote
+                if (VEC) { const uint4 v = *reinterpret_cast<const uint4*>(a.iab + i); q[0] = v.x; q[1] = v.y; q[2] = v.z; q[3] = v.w; }
+                else {
 #pragma unroll
-                for (int m = 0; m < 4; ++m) {
-                    ain[m] = lut_ab((int)(q[m] & 0xffffu)); bin[m] = lut_ab((int)(q[m] >> 16));
-                    if (!BANDS) Lin[m] = (gx + m < w) ? Lplane[i + m] : 0.f;
+                    for (int m = 0; m < 4; ++m) q[m] = (gx + m < w) ? a.iab[i + m] : 0u;
                 }
-            } else {
-                const uint8_t* p = in + (size_t)b * in_sstride + (size_t)gy * in_stride + (size_t)gx * 3;
+            } else {                                               // Lab(in) from the u8 frame
+                const uint8_t* p = a.in + (size_t)b * a.in_sstride + (size_t)gy * a.in_stride + (size_t)gx * 3;
                 uint32_t pb[12];
                 if (VEC) {
                     const RzPx4 v = *reinterpret_cast<const RzPx4*>(p);
@@ -1359,116 +1380,56 @@ __global__ __launch_bounds__(256) void k_rz_final(const uint8_t* __restrict__ in
                     for (int m = 0; m < 12; ++m) pb[m] = (gx + m / 3 < w) ? p[m] : 0;
                 }
 #pragma unroll
-                for (int m = 0; m < 4; ++m) lin_bgr_to_lab<true>(s_gam[pb[3 * m]], s_gam[pb[3 * m + 1]], s_gam[pb[3 * m + 2]], lab.fwd, Lin[m], ain[m], bin[m]);
-                if (LPLANE) {
-                    const size_t i = ((size_t)b * h + gy) * w + gx;
+                for (int m = 0; m < 4; ++m) lin_bgr_to_lab<true>(s_tab[pb[3 * m]], s_tab[pb[3 * m + 1]], s_tab[pb[3 * m + 2]], a.lab.fwd, L[m], av[m], bv[m]);
+            }
+            if (BANDS) { const float4 Lq = *reinterpret_cast<const float4*>(&sb[y][x]); L[0] = Lq.x; L[1] = Lq.y; L[2] = Lq.z; L[3] = Lq.w; }   // written by this very thread
+            else if (GRAY || fl_lut(FL) || LPLANE) {
 #pragma unroll
-                    for (int m = 0; m < 4; ++m) Lin[m] = (gx + m < w) ? Lplane[i + m] : 0.f;
+                for (int m = 0; m < 4; ++m) L[m] = (gx + m < w) ? a.Lplane[i + m] : 0.f;
+            }
+            uint32_t ob[GRAY ? 4 : 12];                            // the bytes that leave
+            auto ab = [&](int m, float& am, float& bm) __attribute__((always_inline)) {
+                if constexpr (GRAY) { am = s_tab[q[m]]; bm = s_tab[256 + q[m]]; }
+                else if constexpr (fl_lut(FL)) { am = lut_ab((int)(q[m] & 0xffffu)); bm = lut_ab((int)(q[m] >> 16)); }
+                else { am = av[m]; bm = bv[m]; }
+            };
+            auto put = [&](int m, uint8_t o0, uint8_t o1, uint8_t o2) __attribute__((always_inline)) {
+                if constexpr (GRAY) ob[m] = gray15(o0, o1, o2);
+                else { ob[3 * m] = o0; ob[3 * m + 1] = o1; ob[3 * m + 2] = o2; }
+            };
+            final_px4<EXACT, DBG>(L, ab, a.lab, s_igt, DBG && a.dbg && b == 0, a.dbg, (size_t)gy * w, gx, w, put);
+            if constexpr (GRAY) {
+                uint8_t* q = a.out + (size_t)b * a.out_sstride + (size_t)gy * a.out_stride + (size_t)gx;
+                if (VEC) *reinterpret_cast<uint32_t*>(q) = ob[0] | (ob[1] << 8) | (ob[2] << 16) | (ob[3] << 24);
+                else {
+#pragma unroll
+                    for (int m = 0; m < 4; ++m) if (gx + m < w) q[m] = (uint8_t)ob[m];
+                }
+            } else {
+                uint8_t* q = a.out + (size_t)b * a.out_sstride + (size_t)gy * a.out_stride + (size_t)gx * 3;
+                if (VEC) {
+                    RzPx4 qo;
+                    qo.a = ob[0] | (ob[1] << 8) | (ob[2] << 16) | (ob[3] << 24);
+                    qo.b = ob[4] | (ob[5] << 8) | (ob[6] << 16) | (ob[7] << 24);
+                    qo.c = ob[8] | (ob[9] << 8) | (ob[10] << 16) | (ob[11] << 24);
+                    *reinterpret_cast<RzPx4*>(q) = qo;
+                } else {
+#pragma unroll
+                    for (int m = 0; m < 12; ++m) if (gx + m / 3 < w) q[m] = (uint8_t)ob[m];
                 }
             }
-            float4 Lq = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (BANDS) Lq = *reinterpret_cast<const float4*>(&sb[y][x]);   // written by this very thread
-            const float Lc[4] = {Lq.x, Lq.y, Lq.z, Lq.w};
-            uint32_t ob[12];
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                const float L = BANDS ? Lc[m] : Lin[m], a = ain[m], bb = bin[m];
-                float o0, o1, o2;
-                lab_to_bgr<EXACT>(L, a, bb, EXACT ? lab.inv : lab.inv1024, s_igt, o0, o1, o2);
-                if (DBG && dbg && b == 0 && gx + m < w) { float* d = dbg + ((size_t)gy * w + gx + m) * 3; d[0] = o0; d[1] = o1; d[2] = o2; }
-                ob[3 * m] = sat_u8(o0 * 255.0f + lab.a255);
-                ob[3 * m + 1] = sat_u8(o1 * 255.0f + lab.a255);
-                ob[3 * m + 2] = sat_u8(o2 * 255.0f + lab.a255);
-            }
-            uint8_t* q = out + (size_t)b * out_sstride + (size_t)gy * out_stride + (size_t)gx * 3;
-            if (VEC) {
-                RzPx4 qo;
-                qo.a = ob[0] | (ob[1] << 8) | (ob[2] << 16) | (ob[3] << 24);
-                qo.b = ob[4] | (ob[5] << 8) | (ob[6] << 16) | (ob[7] << 24);
-                qo.c = ob[8] | (ob[9] << 8) | (ob[10] << 16) | (ob[11] << 24);
-                *reinterpret_cast<RzPx4*>(q) = qo;
-            } else {
-#pragma unroll
-                for (int m = 0; m < 12; ++m) if (gx + m / 3 < w) q[m] = (uint8_t)ob[m];
-            }
         }
         if (BANDS) __syncthreads();
     }
 }
-
-// The same for GRAY frames (lvm_set_phase_on_gray): out = BGR2GRAY(Lab2BGR(L', a(v), b(v)) -> u8) with v the input byte of the pixel and
-// a(), b() the per-value table of the state (labconv.hip k_lab_gray_table: what the BGR kernels get for the colour (v, v, v)) in LDS.  The
-// inverse conversion, the quantiser and -- DBG -- the kept float frame (three channels) are k_rz_final's; the three bytes of a pixel meet in
-// GrayscaleProcessor's weighting (gray15) and one byte leaves.  1 byte of frame read and 1 written per pixel against 3 + 3 (+ 4 of the
-// (ia, ib) plane).  Without BANDS L' is the plane `Lplane` in every flavour (oct_0, or res_0 under a build kind).
-// VEC = rows, streams and base pointers of both frames are dword aligned and w % 4 == 0: one dword load and one dword store per thread.
+// LPLANE (without BANDS, analytic flavour): L' is the float plane `Lplane` -- level 0 collapsed by k_rz_collapse under a build kind of
+// lvm_set_opencv_build -- where the flavour would otherwise take L from the frame (the table flavours read Lplane anyway).
+template <bool BANDS, int FL, bool VEC, bool COMPACT, bool DBG, bool LPLANE = false>
+__global__ __launch_bounds__(256) void k_rz_final(FinalArgs a) { rz_final_tiles<false, BANDS, FL, VEC, COMPACT, DBG, LPLANE>(a); }
+// GRAY frames (lvm_set_phase_on_gray): out = BGR2GRAY(Lab2BGR(L', a(v), b(v)) -> u8).  1 byte of frame read and 1 written per pixel against
+// 3 + 3 (+ 4 of the (ia, ib) plane).
 template <bool BANDS, int FL, bool VEC, bool COMPACT, bool DBG>
-__global__ __launch_bounds__(256) void k_rz_final_gray(const uint8_t* __restrict__ in, long in_stride, long in_sstride,
-                                                       uint8_t* __restrict__ out, long out_stride, long out_sstride, int w, int h,
-                                                       const float* __restrict__ bandA, const float* __restrict__ resn, int nw,
-                                                       int nh, LabCoef lab, int tiles_x, int tiles_y, int nstreams,
-                                                       float* __restrict__ dbg, const float* __restrict__ Lplane, const float* __restrict__ gtab) {
-    constexpr bool EXACT = fl_exact(FL);
-    __shared__ __attribute__((aligned(16))) float s_igt[4096];
-    __shared__ float s_a[256], s_b[256];
-    __shared__ __attribute__((aligned(16))) float sb[CSH][CSP];
-    __shared__ __attribute__((aligned(16))) CollapseTile<COMPACT> su;
-    load_invgamma(s_igt, lab.invgamma);
-    s_a[threadIdx.x] = gtab[256 + threadIdx.x]; s_b[threadIdx.x] = gtab[512 + threadIdx.x];
-    __syncthreads();
-    const int ntiles = tiles_x * tiles_y * nstreams;
-    const int y = collapse_row(), x = (threadIdx.x & 15) * 4;
-    const int tper = (ntiles + (int)gridDim.x - 1) / (int)gridDim.x;
-    const int t0 = (int)xcd_swizzle(blockIdx.x, gridDim.x) * tper, t1 = t0 + tper < ntiles ? t0 + tper : ntiles;
-    for (int t = t0; t < t1; ++t) {
-        const int b = t / (tiles_x * tiles_y);
-        const int r = t - b * (tiles_x * tiles_y);
-        const int ty = r / tiles_x, tx = r - ty * tiles_x;
-        const int x0 = tx * CW, y0 = ty * CH;
-        const int gx = x0 + x, gy = y0 + y;
-        const bool ok = gx < w && gy < h;
-        if (BANDS) {                                               // phase A of k_rz_final
-            collapse_stage(sb, su, bandA + (size_t)b * w * h, resn + (size_t)b * nw * nh, w, h, nw, nh, x0, y0);
-            __syncthreads();
-            float Lc[4] = {0.f, 0.f, 0.f, 0.f};
-            if (ok) collapse_px4(sb, su, x, y, gy, Lc);
-            __syncthreads();
-            *reinterpret_cast<float4*>(&sb[y][x]) = make_float4(Lc[0], Lc[1], Lc[2], Lc[3]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if (ok) {
-            const uint8_t* p = in + (size_t)b * in_sstride + (size_t)gy * in_stride + (size_t)gx;
-            uint32_t pv[4];
-            if (VEC) { const uint32_t v = *reinterpret_cast<const uint32_t*>(p); pv[0] = v & 255u; pv[1] = (v >> 8) & 255u; pv[2] = (v >> 16) & 255u; pv[3] = v >> 24; }
-            else {
-#pragma unroll
-                for (int m = 0; m < 4; ++m) pv[m] = (gx + m < w) ? p[m] : 0;
-            }
-            float Lc[4] = {0.f, 0.f, 0.f, 0.f};
-            if (BANDS) { const float4 Lq = *reinterpret_cast<const float4*>(&sb[y][x]); Lc[0] = Lq.x; Lc[1] = Lq.y; Lc[2] = Lq.z; Lc[3] = Lq.w; }   // written by this very thread
-            else {
-                const size_t i = ((size_t)b * h + gy) * w + gx;
-#pragma unroll
-                for (int m = 0; m < 4; ++m) Lc[m] = (gx + m < w) ? Lplane[i + m] : 0.f;
-            }
-            uint32_t og[4];
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                float o0, o1, o2;
-                lab_to_bgr<EXACT>(Lc[m], s_a[pv[m]], s_b[pv[m]], EXACT ? lab.inv : lab.inv1024, s_igt, o0, o1, o2);
-                if (DBG && dbg && b == 0 && gx + m < w) { float* d = dbg + ((size_t)gy * w + gx + m) * 3; d[0] = o0; d[1] = o1; d[2] = o2; }
-                og[m] = gray15(sat_u8(o0 * 255.0f + lab.a255), sat_u8(o1 * 255.0f + lab.a255), sat_u8(o2 * 255.0f + lab.a255));
-            }
-            uint8_t* q = out + (size_t)b * out_sstride + (size_t)gy * out_stride + (size_t)gx;
-            if (VEC) *reinterpret_cast<uint32_t*>(q) = og[0] | (og[1] << 8) | (og[2] << 16) | (og[3] << 24);
-            else {
-#pragma unroll
-                for (int m = 0; m < 4; ++m) if (gx + m < w) q[m] = (uint8_t)og[m];
-            }
-        }
-        if (BANDS) __syncthreads();
-    }
-}
+__global__ __launch_bounds__(256) void k_rz_final_gray(FinalArgs a) { rz_final_tiles<true, BANDS, FL, VEC, COMPACT, DBG, false>(a); }
 
 // ---- collapse and output as WAVE STRIPS (planes with even width and height, width a multiple of 4) ---------------------------
 // The tiled kernels above read every fma operand from LDS (k_rz_final: 2.1 TB/s, neither pipe saturated).  Here a wave walks down
@@ -1482,6 +1443,10 @@ __global__ __launch_bounds__(256) void k_rz_final_gray(const uint8_t* __restrict
 // REFLECT_101 of the zero-injected image: rows through the reflected row index (even planes: parity is kept); columns -4, -2 are
 // the coarse columns 2, 1 and columns w, w + 2 the coarse columns nw - 1, nw - 2.
 // FINAL: the completed row of L' goes through Lab2BGR with (a, b) of the frame's integer plane and leaves as u8 (MagnifyCore.hpp:272-277).
+// One text (LVM_COLLAPSE_STRIPS_WALK) serves the three forms -- res_l of a level, the BGR output, the gray output (StripToPlane / StripToBgr /
+// StripToGray) -- and the strip prologue is k_rz_split_rows' (strip_task, ReflectCursor).  What holds the kernels to what they were is NOT their instruction
+// streams: a change here is checked by the bits (the parity tests of every form), by registers / scratch / occupancy / LDS of every
+// instantiation (tools/kru.sh) and by the time on the GPU; tools/riesz_isa_vs_rev.py reports which streams moved.
 constexpr int CS_THREADS = 256;
 struct CollapseStripArgs {
     const float* bandA; const float* resn; float* res;          // [z][h][w], [z][nh][nw], [z][h][w] (res: !FINAL)
@@ -1510,9 +1475,6 @@ __device__ __forceinline__ void collapse_lp_taps(const lvm_f2 (&A)[3], const lvm
         }
     }
 }
-// The conversions of collapse_emit (below) with (a, b) given as floats, for the gray emit: the same calls in the same order.  (collapse_emit keeps
-// its own text: routed through these, the compiler schedules k_rz_collapse_strips<true, ...> differently, and the BGR kernels are to stay the
-// instruction streams they were.)
 // four pixels of a lane, Lab -> the three bytes each through the u8 step table (fin_steps flavours; steps = the table in LDS)
 __device__ __forceinline__ void strip_lab_to_u8(const float (&Lc)[4], const float (&av)[4], const float (&bv)[4], const LabCoef& lab, const uint2* steps, uint32_t (&u)[4][3]) {
 #pragma unroll
@@ -1547,55 +1509,31 @@ __device__ __forceinline__ void strip_keep_float(const float (&o)[4][3], const B
 template <int FL, bool DBG>
 __device__ __forceinline__ void collapse_emit(float L0, float L1, float L2, float L3, const float4 iabq, const LabCoef& lab, const float* s_igt,
                                               const BufRsrc& ro, uint32_t voff, uint32_t soff, const BufRsrc& rd, uint32_t dvoff, uint32_t dsoff) {
-    constexpr bool EXACT = fl_exact(FL);
     const float Lc[4] = {L0, L1, L2, L3};
     const uint32_t q[4] = {__float_as_uint(iabq.x), __float_as_uint(iabq.y), __float_as_uint(iabq.z), __float_as_uint(iabq.w)};
+    float av[4], bv[4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) { av[m] = lut_ab((int)(q[m] & 0xffffu)); bv[m] = lut_ab((int)(q[m] >> 16)); }
+    B96 v;
     if (fin_steps(FL, DBG)) {        // s_igt = the u8 step table: linear BGR -> byte by a table hit and a compare (lvm_internal.h u8_step)
-        const uint2* steps = reinterpret_cast<const uint2*>(s_igt);
         uint32_t u[4][3];
-#pragma unroll
-        for (int m = 0; m < 4; m += 2) {
-            lvm_f2 c0, c1, c2;
-            lab_to_linear_pair(f2_set(Lc[m], Lc[m + 1]), f2_set(lut_ab((int)(q[m] & 0xffffu)), lut_ab((int)(q[m + 1] & 0xffffu))),
-                               f2_set(lut_ab((int)(q[m] >> 16)), lut_ab((int)(q[m + 1] >> 16))), lab.inv4096, c0, c1, c2);
-#pragma unroll
-            for (int k = 0; k < 2; ++k) { u[m + k][0] = u8_step(c0[k], steps); u[m + k][1] = u8_step(c1[k], steps); u[m + k][2] = u8_step(c2[k], steps); }
-        }
-        B96 v;
+        strip_lab_to_u8(Lc, av, bv, lab, reinterpret_cast<const uint2*>(s_igt), u);
         v.a = lvm_pack_b4(u[0][0], u[0][1], u[0][2], u[1][0]);
         v.b = lvm_pack_b4(u[1][1], u[1][2], u[2][0], u[2][1]);
         v.c = lvm_pack_b4(u[2][2], u[3][0], u[3][1], u[3][2]);
-        buf_sts_b96(v, ro, voff, soff);
-        return;
-    }
-    float o[4][3];
-    if (EXACT) {
+    } else {
+        float o[4][3];
+        strip_lab_to_bgr<fl_exact(FL)>(Lc, av, bv, lab, s_igt, o);
+        if (DBG) strip_keep_float(o, rd, dvoff, dsoff);
+        float t[4][3];
 #pragma unroll
         for (int m = 0; m < 4; ++m)
-            lab_to_bgr<true>(Lc[m], lut_ab((int)(q[m] & 0xffffu)), lut_ab((int)(q[m] >> 16)), lab.inv, s_igt, o[m][0], o[m][1], o[m][2]);
-    } else {
 #pragma unroll
-        for (int m = 0; m < 4; m += 2) {
-            lvm_f2 o0, o1, o2;
-            lab_to_bgr_pair(f2_set(Lc[m], Lc[m + 1]), f2_set(lut_ab((int)(q[m] & 0xffffu)), lut_ab((int)(q[m + 1] & 0xffffu))),
-                            f2_set(lut_ab((int)(q[m] >> 16)), lut_ab((int)(q[m + 1] >> 16))), lab.inv1024, s_igt, o0, o1, o2);
-            o[m][0] = o0[0]; o[m][1] = o1[0]; o[m][2] = o2[0]; o[m + 1][0] = o0[1]; o[m + 1][1] = o1[1]; o[m + 1][2] = o2[1];
-        }
+            for (int k = 0; k < 3; ++k) t[m][k] = o[m][k] * 255.0f + lab.a255;
+        v.a = pack_u8x4(t[0][0], t[0][1], t[0][2], t[1][0]);
+        v.b = pack_u8x4(t[1][1], t[1][2], t[2][0], t[2][1]);
+        v.c = pack_u8x4(t[2][2], t[3][0], t[3][1], t[3][2]);
     }
-    if (DBG) {
-        buf_st_f32x4(o[0][0], o[0][1], o[0][2], o[1][0], rd, dvoff, dsoff);
-        buf_st_f32x4(o[1][1], o[1][2], o[2][0], o[2][1], rd, dvoff, dsoff + 16u);
-        buf_st_f32x4(o[2][2], o[3][0], o[3][1], o[3][2], rd, dvoff, dsoff + 32u);
-    }
-    float t[4][3];
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) t[m][k] = o[m][k] * 255.0f + lab.a255;
-    B96 v;
-    v.a = pack_u8x4(t[0][0], t[0][1], t[0][2], t[1][0]);
-    v.b = pack_u8x4(t[1][1], t[1][2], t[2][0], t[2][1]);
-    v.c = pack_u8x4(t[2][2], t[3][0], t[3][1], t[3][2]);
     buf_sts_b96(v, ro, voff, soff);                 // (the output frame is not read again on the device: streaming store)
 }
 // The same row of a GRAY frame (lvm_set_phase_on_gray): (a, b) from the per-value table in LDS (s_ab[v] = a, s_ab[256 + v] = b) at the four input
@@ -1627,70 +1565,80 @@ __device__ __forceinline__ void collapse_emit_gray(float L0, float L1, float L2,
 }
 // the frames of a gray launch: the input bytes are read again for (a, b), the output has one byte per pixel (both dword aligned, w % 4 == 0)
 struct GrayStripIO { const uint8_t* in; long in_stride, in_sstride; const float* gtab; };
-// The strip walk of k_rz_collapse_strips<true, ...> for gray frames: the same steps, taps and order; what differs is the row of input bytes where the
-// BGR kernel fetches the (ia, ib) row, and the emit.  (It is a copy, not a function both kernels call: with the walk in a shared function the
-// compiler schedules k_rz_collapse_strips differently -- 4926 -> 4919 instructions without FINAL, 9260 -> 9258 with -- and the BGR kernels are
-// to stay the instruction streams they were, tools/riesz_isa_vs_rev.py.)  s_igt: the spline or the u8 step table in LDS.
+
+// The per-form parts of the strip walk.  A form says what a wave sets up once it knows its strip (begin), which auxiliary row it prefetches for
+// the output row that completes one step later (prefetch: `row` is clamped into the plane; Aux = what a lane holds of it), and what leaves
+// for a completed row of a lane's four L' (emit: output row o; !inside = rows above and below the strip, nothing may be stored).
+struct StripToPlane {                       // res_l = the collapsed level: no auxiliary row, the four floats leave as they are
+    typedef int Aux;
+    BufRsrc ro; uint32_t lout;
+    __device__ __forceinline__ void begin(const CollapseStripArgs& a, const StripTask& t) {
+        ro = buf_rsrc(a.res + (size_t)t.z * a.w * a.h, (uint32_t)a.w * (uint32_t)a.h * 4u);
+        lout = t.owner ? 16u * (uint32_t)t.gl : kDrop;
+    }
+    __device__ __forceinline__ Aux prefetch(const CollapseStripArgs&, int) const { return 0; }
+    __device__ __forceinline__ void emit(const CollapseStripArgs& a, float L0, float L1, float L2, float L3, Aux, bool inside, uint32_t o) const {
+        buf_st_f32x4(L0, L1, L2, L3, ro, inside ? lout : kDrop, o * ((uint32_t)a.w * 4u));
+    }
+};
 template <int FL, bool DBG>
-__device__ __forceinline__ void collapse_strips_walk_gray(const CollapseStripArgs& a, const GrayStripIO& gio, const float* s_igt, const float* s_ab) {
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    const int task = blockIdx.x * (CS_THREADS / 64) + wave;
-    if (task >= a.ntasks) return;
-    const int w = a.w, h = a.h, nw = a.nw, nh = a.nh;
-    const int z = task / (a.strips_x * a.strips_y);
-    const int r = task - z * (a.strips_x * a.strips_y);
-    const int ty = r / a.strips_x, tx = r - ty * a.strips_x;
-    const int G = w >> 2;                                           // w % 4 == 0, G >= 2
-    const int g = tx * SR_OWN - 1 + lane;
-    const int gl = g < 0 ? 0 : (g > G - 1 ? G - 1 : g);
-    const bool owner = lane >= 1 && lane <= SR_OWN && g >= 0 && g < G;
-    const bool first = g == 0, last = g == G - 1;
-    constexpr uint32_t kDrop = 0x80000000u;
-    const uint32_t pbytes = (uint32_t)w * (uint32_t)h * 4u;
-    const BufRsrc rb = buf_rsrc(a.bandA + (size_t)z * w * h, pbytes);
-    const BufRsrc rc = buf_rsrc(a.resn + (size_t)z * nw * nh, (uint32_t)nw * (uint32_t)nh * 4u);
+struct StripToBgr {                         // BGR frames: the (ia, ib) row of the frame's integer plane, collapse_emit
+    typedef float4 Aux;
+    const float* s_igt;                     // the spline or the u8 step table in LDS
+    BufRsrc ro, ri, rd; uint32_t lab_off, lout, ldbg;
+    __device__ __forceinline__ void begin(const CollapseStripArgs& a, const StripTask& t) {
+        const uint32_t pbytes = (uint32_t)a.w * (uint32_t)a.h * 4u;
+        ro = buf_rsrc(a.out + (size_t)t.z * a.out_sstride, (uint32_t)a.h * (uint32_t)a.out_stride);
+        ri = buf_rsrc(a.iab + (size_t)t.z * a.w * a.h, pbytes);
+        rd = buf_rsrc(a.dbg, (DBG && a.dbg && t.z == 0) ? pbytes * 3u : 0u);   // float frame of stream 0
+        lab_off = 16u * (uint32_t)t.gl;
+        lout = t.owner ? 12u * (uint32_t)t.gl : kDrop; ldbg = t.owner ? 48u * (uint32_t)t.gl : kDrop;
+    }
+    __device__ __forceinline__ Aux prefetch(const CollapseStripArgs& a, int row) const { return buf_lds_f32x4(ri, lab_off, (uint32_t)row * (uint32_t)a.w * 4u); }
+    __device__ __forceinline__ void emit(const CollapseStripArgs& a, float L0, float L1, float L2, float L3, Aux iabq, bool inside, uint32_t o) const {
+        collapse_emit<FL, DBG>(L0, L1, L2, L3, iabq, a.lab, s_igt, ro, inside ? lout : kDrop, o * (uint32_t)a.out_stride, rd, inside ? ldbg : kDrop, o * (uint32_t)a.w * 12u);
+    }
+};
+template <int FL, bool DBG>
+struct StripToGray {                        // gray frames: the row of input bytes, collapse_emit_gray
+    typedef uint32_t Aux;
+    const float* s_igt; const float* s_ab;  // the spline or the u8 step table, and the per-value (a, b) table, in LDS
+    const GrayStripIO& gio;
     // the lane's four bytes of a row of the input / output frame (gl is clamped and an output row is only written by its owner inside the strip:
     // every address lies inside the w x h rectangle of the frame)
-    const uint8_t* gin = gio.in + (size_t)z * gio.in_sstride + 4u * (uint32_t)gl;
-    uint8_t* gout = owner ? a.out + (size_t)z * a.out_sstride + 4u * (uint32_t)gl : nullptr;
-    const BufRsrc rd = buf_rsrc(a.dbg, (DBG && a.dbg && z == 0) ? pbytes * 3u : 0u);   // float frame of stream 0 (three channels)
-    const uint32_t lband = 16u * (uint32_t)gl, lcoarse = 8u * (uint32_t)gl;
-    const uint32_t ldbg = owner ? 48u * (uint32_t)gl : kDrop;
-    const int y0 = ty * a.rows;                                     // rows is even
-    const int yend = y0 + a.rows < h ? y0 + a.rows : h;
-    const int nq = yend - y0 + 8;                                   // input rows y0 - 4 .. yend + 3
-    lvm_f2 hp[9][2], lp[9][2];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) { hp[k][0] = hp[k][1] = f2_all(0.f); lp[k][0] = lp[k][1] = f2_all(0.f); }
-    int ry = reflect101(y0 - 4, h), rdir = reflect101(y0 - 3, h) - ry;
-    auto advance_row = [&]() __attribute__((always_inline)) {
-        const int t = ry + rdir;
-        const bool lo = t < 0, hi = t > h - 1;
-        ry = lo ? (h > 1 ? 1 : 0) : (hi ? (h > 1 ? h - 2 : 0) : t);
-        rdir = lo ? 1 : (hi ? -1 : rdir);
-    };
-    // in flight per wave: the band row of the next step, the coarse row of the next even step, the (a, b) row of the next output row
-    float4 nxt = buf_ld_f32x4(rb, lband, (uint32_t)ry * (uint32_t)w * 4u);
-    float2 nxtc;
-    { const lvm_f2 c = buf_ld_f32x2(rc, lcoarse, (uint32_t)(ry >> 1) * (uint32_t)nw * 4u); nxtc = make_float2(c[0], c[1]); }
-    uint32_t nxti = 0u;
-    int q = 0;
+    const uint8_t* gin; uint8_t* gout; BufRsrc rd; uint32_t ldbg;
+    __device__ __forceinline__ void begin(const CollapseStripArgs& a, const StripTask& t) {
+        gin = gio.in + (size_t)t.z * gio.in_sstride + 4u * (uint32_t)t.gl;
+        gout = t.owner ? a.out + (size_t)t.z * a.out_sstride + 4u * (uint32_t)t.gl : nullptr;
+        rd = buf_rsrc(a.dbg, (DBG && a.dbg && t.z == 0) ? (uint32_t)a.w * (uint32_t)a.h * 12u : 0u);   // float frame of stream 0 (three channels)
+        ldbg = t.owner ? 48u * (uint32_t)t.gl : kDrop;
+    }
+    __device__ __forceinline__ Aux prefetch(const CollapseStripArgs&, int row) const { return *reinterpret_cast<const uint32_t*>(gin + (size_t)row * gio.in_stride); }
+    __device__ __forceinline__ void emit(const CollapseStripArgs& a, float L0, float L1, float L2, float L3, Aux px, bool inside, uint32_t o) const {
+        collapse_emit_gray<FL, DBG>(L0, L1, L2, L3, px, s_ab, a.lab, s_igt, (inside && gout) ? gout + (size_t)o * a.out_stride : nullptr, rd, inside ? ldbg : kDrop, o * (uint32_t)a.w * 12u);
+    }
+};
+// The strip walk, the one text of it for the three forms: the same steps, taps and order.  LVM_COLLAPSE_STRIPS_WALK(a, f) is expanded in the
+// kernels, with the form `f` as its hooks.  (A macro and not a function template that the kernels call: inlined from a function, the walk of
+// the shipped output kernel k_rz_collapse_strips<true, FL_LUT_FAST, false> keeps fewer values in scalar registers -- 442 v_readlane
+// reloads in its loop against 138 -- and is 9649 instructions long instead of 9260; expanded in place it has 162 and 9290.  tools/kru.sh does not
+// tell the forms apart: 141 VGPRs, 106 SGPRs, no scratch, 3 waves either way; profiles/r16_riesz_shared_text.txt has both.)
 #define LVM_COLLAPSE_STEP(P18)                                                                                     \
     {                                                                                                               \
-        if ((P18) % 9 == 0 && q >= nq) break;                                                                       \
-        constexpr int P = (P18) % 9;                                                                                \
+        if ((P18) % 9 == 0 && q >= nq) break;                       /* two exits per 18 steps: up to 8 extra rows (loads reflected, stores dropped) */ \
+        constexpr int P = (P18) % 9;                                /* q = P18 (mod 18): slot phase and row parity are compile-time */ \
         constexpr bool EVEN = ((P18) & 1) == 0;                     /* input row y0 - 4 + q and output row y0 - 8 + q, y0 even */ \
         const float4 cur = nxt;                                                                                     \
         const float2 curc = nxtc;                                                                                   \
-        const uint32_t curi = nxti;                                                                                 \
-        advance_row();                                              /* row y0 - 3 + q, reflected */                 \
-        nxt = buf_ld_f32x4(rb, lband, (uint32_t)ry * (uint32_t)w * 4u);                                             \
-        if (!EVEN) { const lvm_f2 c = buf_ld_f32x2(rc, lcoarse, (uint32_t)(ry >> 1) * (uint32_t)nw * 4u); nxtc = make_float2(c[0], c[1]); }   /* that row is even */ \
-        {                                                           /* input bytes of output row y0 - 7 + q: complete one step from now */ \
+        const auto curi = nxti;                                                                                     \
+        row.advance(h);                                             /* row y0 - 3 + q, reflected */                 \
+        nxt = buf_ld_f32x4(rb, lband, (uint32_t)row.ry * (uint32_t)w * 4u);                                         \
+        if (!EVEN) { const lvm_f2 c = buf_ld_f32x2(rc, lcoarse, (uint32_t)(row.ry >> 1) * (uint32_t)nw * 4u); nxtc = make_float2(c[0], c[1]); }   /* that row is even */ \
+        {                                                           /* auxiliary row of output row y0 - 7 + q: complete one step from now */ \
             const int orow = y0 - 7 + q;                                                                            \
-            nxti = *reinterpret_cast<const uint32_t*>(gin + (size_t)(orow < 0 ? 0 : (orow > h - 1 ? h - 1 : orow)) * gio.in_stride);   \
+            nxti = f.prefetch(a, orow < 0 ? 0 : (orow > h - 1 ? h - 1 : orow));                                     \
         }                                                                                                           \
-        lvm_issue_fence();                                                                                        \
+        lvm_issue_fence();                                          /* the loads are ISSUED here, a whole step ahead of their use */ \
         lvm_f2 V[6], W[5];                                                                                          \
         row12(cur, first, last, V, W);                                                                              \
         hp_row_taps<P>(V, W, hp);                                                                                   \
@@ -1700,119 +1648,56 @@ __device__ __forceinline__ void collapse_strips_walk_gray(const CollapseStripArg
             collapse_lp_taps<P>(A, B, lp);                                                                          \
         }                                                                                                           \
         constexpr int E = (P + 1) % 9;                              /* output row o = y0 - 8 + q is complete */     \
-        const bool inside = q >= 8 && q < nq;                                                                       \
+        const bool inside = q >= 8 && q < nq;                       /* (rows above and below the strip: dropped) */ \
         const uint32_t o = inside ? (uint32_t)(y0 - 8 + q) : 0u;                                                    \
         const float L0 = lp[E][0][0] + hp[E][0][0], L1 = lp[E][1][0] + hp[E][0][1];   /* RieszPyramid.cpp:322 */    \
         const float L2 = lp[E][0][1] + hp[E][1][0], L3 = lp[E][1][1] + hp[E][1][1];                                 \
-        collapse_emit_gray<FL, DBG>(L0, L1, L2, L3, curi, s_ab, a.lab, s_igt, (inside && gout) ? gout + (size_t)o * a.out_stride : nullptr, rd, inside ? ldbg : kDrop, o * (uint32_t)w * 12u); \
+        f.emit(a, L0, L1, L2, L3, curi, inside, o);                                                                 \
         hp[E][0] = hp[E][1] = f2_all(0.f); lp[E][0] = lp[E][1] = f2_all(0.f);                                      \
         ++q;                                                                                                        \
-        _Pragma("unroll") for (int d = 1; d < 9; ++d) {                                                             \
+        _Pragma("unroll") for (int d = 1; d < 9; ++d) {             /* one row at a time: every partial sum exists HERE (lvm_pin) */ \
             lvm_pin(hp[(E + d) % 9][0], hp[(E + d) % 9][1]);                                                        \
             lvm_pin(lp[(E + d) % 9][0], lp[(E + d) % 9][1]);                                                        \
         }                                                                                                           \
     }
-    for (;;) {
-        LVM_COLLAPSE_STEP(0) LVM_COLLAPSE_STEP(1) LVM_COLLAPSE_STEP(2) LVM_COLLAPSE_STEP(3) LVM_COLLAPSE_STEP(4) LVM_COLLAPSE_STEP(5)
-        LVM_COLLAPSE_STEP(6) LVM_COLLAPSE_STEP(7) LVM_COLLAPSE_STEP(8) LVM_COLLAPSE_STEP(9) LVM_COLLAPSE_STEP(10) LVM_COLLAPSE_STEP(11)
-        LVM_COLLAPSE_STEP(12) LVM_COLLAPSE_STEP(13) LVM_COLLAPSE_STEP(14) LVM_COLLAPSE_STEP(15) LVM_COLLAPSE_STEP(16) LVM_COLLAPSE_STEP(17)
+#define LVM_COLLAPSE_STRIPS_WALK(a, f) \
+    StripTask t; \
+    if (!strip_task<CS_THREADS>(a.ntasks, a.strips_x, a.strips_y, a.w, a.h, a.rows, t)) return; \
+    const int w = a.w, h = a.h, nw = a.nw, nh = a.nh, y0 = t.y0, nq = t.nq; \
+    const bool first = t.first, last = t.last; \
+    const BufRsrc rb = buf_rsrc(a.bandA + (size_t)t.z * w * h, (uint32_t)w * (uint32_t)h * 4u); \
+    const BufRsrc rc = buf_rsrc(a.resn + (size_t)t.z * nw * nh, (uint32_t)nw * (uint32_t)nh * 4u); \
+    const uint32_t lband = 16u * (uint32_t)t.gl, lcoarse = 8u * (uint32_t)t.gl; \
+    f.begin(a, t); \
+    lvm_f2 hp[9][2], lp[9][2]; \
+    _Pragma("unroll") \
+    for (int k = 0; k < 9; ++k) { hp[k][0] = hp[k][1] = f2_all(0.f); lp[k][0] = lp[k][1] = f2_all(0.f); } \
+    ReflectCursor row(y0 - 4, h); \
+    /* in flight per wave: the band row of the next step, the coarse row of the next even step, the auxiliary row of the next output row */ \
+    float4 nxt = buf_ld_f32x4(rb, lband, (uint32_t)row.ry * (uint32_t)w * 4u); \
+    float2 nxtc; \
+    { const lvm_f2 c = buf_ld_f32x2(rc, lcoarse, (uint32_t)(row.ry >> 1) * (uint32_t)nw * 4u); nxtc = make_float2(c[0], c[1]); } \
+    typename decltype(f)::Aux nxti{}; \
+    int q = 0; \
+    for (;;) { \
+        LVM_COLLAPSE_STEP(0) LVM_COLLAPSE_STEP(1) LVM_COLLAPSE_STEP(2) LVM_COLLAPSE_STEP(3) LVM_COLLAPSE_STEP(4) LVM_COLLAPSE_STEP(5) \
+        LVM_COLLAPSE_STEP(6) LVM_COLLAPSE_STEP(7) LVM_COLLAPSE_STEP(8) LVM_COLLAPSE_STEP(9) LVM_COLLAPSE_STEP(10) LVM_COLLAPSE_STEP(11) \
+        LVM_COLLAPSE_STEP(12) LVM_COLLAPSE_STEP(13) LVM_COLLAPSE_STEP(14) LVM_COLLAPSE_STEP(15) LVM_COLLAPSE_STEP(16) LVM_COLLAPSE_STEP(17) \
     }
-#undef LVM_COLLAPSE_STEP
-}
+
+// FINAL: level 0 + output of BGR frames (a.res is not used); else res_l of a level (FL, DBG and the frame fields of `a` are not used)
 template <bool FINAL, int FL, bool DBG>
 __global__ __launch_bounds__(CS_THREADS, 3) void k_rz_collapse_strips(CollapseStripArgs a) {
-    constexpr bool EXACT = fl_exact(FL);
     __shared__ __attribute__((aligned(16))) float s_igt[FINAL ? (fin_steps(FL, DBG) ? 2 * kU8StepSlices : 4096) : 4];      // spline | u8 step table
-    if (FINAL) {
+    if constexpr (FINAL) {
         if (fin_steps(FL, DBG)) load_u8steps(reinterpret_cast<uint2*>(s_igt), a.lab.u8steps); else load_invgamma(s_igt, a.lab.invgamma);
         __syncthreads();
+        StripToBgr<FL, DBG> f{s_igt};
+        LVM_COLLAPSE_STRIPS_WALK(a, f)
+    } else {
+        StripToPlane f;
+        LVM_COLLAPSE_STRIPS_WALK(a, f)
     }
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    const int task = blockIdx.x * (CS_THREADS / 64) + wave;
-    if (task >= a.ntasks) return;
-    const int w = a.w, h = a.h, nw = a.nw, nh = a.nh;
-    const int z = task / (a.strips_x * a.strips_y);
-    const int r = task - z * (a.strips_x * a.strips_y);
-    const int ty = r / a.strips_x, tx = r - ty * a.strips_x;
-    const int G = w >> 2;                                           // w % 4 == 0, G >= 2
-    const int g = tx * SR_OWN - 1 + lane;
-    const int gl = g < 0 ? 0 : (g > G - 1 ? G - 1 : g);
-    const bool owner = lane >= 1 && lane <= SR_OWN && g >= 0 && g < G;
-    const bool first = g == 0, last = g == G - 1;
-    constexpr uint32_t kDrop = 0x80000000u;
-    const uint32_t pbytes = (uint32_t)w * (uint32_t)h * 4u;
-    const BufRsrc rb = buf_rsrc(a.bandA + (size_t)z * w * h, pbytes);
-    const BufRsrc rc = buf_rsrc(a.resn + (size_t)z * nw * nh, (uint32_t)nw * (uint32_t)nh * 4u);
-    const BufRsrc ro = FINAL ? buf_rsrc(a.out + (size_t)z * a.out_sstride, (uint32_t)h * (uint32_t)a.out_stride)
-                             : buf_rsrc(a.res + (size_t)z * w * h, pbytes);
-    const BufRsrc ri = buf_rsrc(FINAL ? (const void*)(a.iab + (size_t)z * w * h) : (const void*)a.bandA, FINAL ? pbytes : 0u);
-    const BufRsrc rd = buf_rsrc(a.dbg, (DBG && FINAL && a.dbg && z == 0) ? pbytes * 3u : 0u);   // float frame of stream 0
-    const uint32_t lband = 16u * (uint32_t)gl, lcoarse = 8u * (uint32_t)gl;
-    const uint32_t lout = owner ? (FINAL ? 12u : 16u) * (uint32_t)gl : kDrop, ldbg = owner ? 48u * (uint32_t)gl : kDrop;
-    const uint32_t ostride = FINAL ? (uint32_t)a.out_stride : (uint32_t)w * 4u;
-    const int y0 = ty * a.rows;                                     // rows is even
-    const int yend = y0 + a.rows < h ? y0 + a.rows : h;
-    const int nq = yend - y0 + 8;                                   // input rows y0 - 4 .. yend + 3
-    lvm_f2 hp[9][2], lp[9][2];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) { hp[k][0] = hp[k][1] = f2_all(0.f); lp[k][0] = lp[k][1] = f2_all(0.f); }
-    int ry = reflect101(y0 - 4, h), rdir = reflect101(y0 - 3, h) - ry;
-    auto advance_row = [&]() __attribute__((always_inline)) {
-        const int t = ry + rdir;
-        const bool lo = t < 0, hi = t > h - 1;
-        ry = lo ? (h > 1 ? 1 : 0) : (hi ? (h > 1 ? h - 2 : 0) : t);
-        rdir = lo ? 1 : (hi ? -1 : rdir);
-    };
-    // in flight per wave: the band row of the next step, the coarse row of the next even step, the (a, b) row of the next output row
-    float4 nxt = buf_ld_f32x4(rb, lband, (uint32_t)ry * (uint32_t)w * 4u);
-    float2 nxtc;
-    { const lvm_f2 c = buf_ld_f32x2(rc, lcoarse, (uint32_t)(ry >> 1) * (uint32_t)nw * 4u); nxtc = make_float2(c[0], c[1]); }
-    float4 nxti = make_float4(0.f, 0.f, 0.f, 0.f);
-    int q = 0;
-#define LVM_COLLAPSE_STEP(P18)                                                                                     \
-    {                                                                                                               \
-        if ((P18) % 9 == 0 && q >= nq) break;                                                                       \
-        constexpr int P = (P18) % 9;                                                                                \
-        constexpr bool EVEN = ((P18) & 1) == 0;                     /* input row y0 - 4 + q and output row y0 - 8 + q, y0 even */ \
-        const float4 cur = nxt;                                                                                     \
-        const float2 curc = nxtc;                                                                                   \
-        const float4 curi = nxti;                                                                                   \
-        advance_row();                                              /* row y0 - 3 + q, reflected */                 \
-        nxt = buf_ld_f32x4(rb, lband, (uint32_t)ry * (uint32_t)w * 4u);                                             \
-        if (!EVEN) { const lvm_f2 c = buf_ld_f32x2(rc, lcoarse, (uint32_t)(ry >> 1) * (uint32_t)nw * 4u); nxtc = make_float2(c[0], c[1]); }   /* that row is even */ \
-        if (FINAL) {                                                /* (a, b) of output row y0 - 7 + q: complete one step from now */ \
-            const int orow = y0 - 7 + q;                                                                            \
-            nxti = buf_lds_f32x4(ri, lband, (uint32_t)(orow < 0 ? 0 : (orow > h - 1 ? h - 1 : orow)) * (uint32_t)w * 4u);   \
-        }                                                                                                           \
-        lvm_issue_fence();                                                                                          \
-        lvm_f2 V[6], W[5];                                                                                          \
-        row12(cur, first, last, V, W);                                                                              \
-        hp_row_taps<P>(V, W, hp);                                                                                   \
-        if (EVEN) {                                                                                                 \
-            lvm_f2 A[3], B[2];                                                                                      \
-            coarse6(curc, first, last, A, B);                                                                       \
-            collapse_lp_taps<P>(A, B, lp);                                                                          \
-        }                                                                                                           \
-        constexpr int E = (P + 1) % 9;                              /* output row o = y0 - 8 + q is complete */     \
-        const bool inside = q >= 8 && q < nq;                                                                       \
-        const uint32_t o = inside ? (uint32_t)(y0 - 8 + q) : 0u;                                                    \
-        const float L0 = lp[E][0][0] + hp[E][0][0], L1 = lp[E][1][0] + hp[E][0][1];   /* RieszPyramid.cpp:322 */    \
-        const float L2 = lp[E][0][1] + hp[E][1][0], L3 = lp[E][1][1] + hp[E][1][1];                                 \
-        if (!FINAL) buf_st_f32x4(L0, L1, L2, L3, ro, inside ? lout : kDrop, o * ostride);                           \
-        else collapse_emit<FL, DBG>(L0, L1, L2, L3, curi, a.lab, s_igt, ro, inside ? lout : kDrop, o * ostride, rd, inside ? ldbg : kDrop, o * (uint32_t)w * 12u); \
-        hp[E][0] = hp[E][1] = f2_all(0.f); lp[E][0] = lp[E][1] = f2_all(0.f);                                      \
-        ++q;                                                                                                        \
-        _Pragma("unroll") for (int d = 1; d < 9; ++d) {                                                             \
-            lvm_pin(hp[(E + d) % 9][0], hp[(E + d) % 9][1]);                                                        \
-            lvm_pin(lp[(E + d) % 9][0], lp[(E + d) % 9][1]);                                                        \
-        }                                                                                                           \
-    }
-    for (;;) {
-        LVM_COLLAPSE_STEP(0) LVM_COLLAPSE_STEP(1) LVM_COLLAPSE_STEP(2) LVM_COLLAPSE_STEP(3) LVM_COLLAPSE_STEP(4) LVM_COLLAPSE_STEP(5)
-        LVM_COLLAPSE_STEP(6) LVM_COLLAPSE_STEP(7) LVM_COLLAPSE_STEP(8) LVM_COLLAPSE_STEP(9) LVM_COLLAPSE_STEP(10) LVM_COLLAPSE_STEP(11)
-        LVM_COLLAPSE_STEP(12) LVM_COLLAPSE_STEP(13) LVM_COLLAPSE_STEP(14) LVM_COLLAPSE_STEP(15) LVM_COLLAPSE_STEP(16) LVM_COLLAPSE_STEP(17)
-    }
-#undef LVM_COLLAPSE_STEP
 }
 // level-0 collapse + output of GRAY frames (lvm_set_phase_on_gray): a.out is the 1-channel output frame, a.iab is not used.
 // (The float-keeping builds hold the twelve floats of a lane's four pixels across the stores on top of the two frame pointers: at three
@@ -1824,8 +1709,11 @@ __global__ __launch_bounds__(CS_THREADS, DBG ? 2 : 3) void k_rz_collapse_strips_
     if (fin_steps(FL, DBG)) load_u8steps(reinterpret_cast<uint2*>(s_igt), a.lab.u8steps); else load_invgamma(s_igt, a.lab.invgamma);
     for (int i = threadIdx.x; i < 512; i += CS_THREADS) s_ab[i] = gio.gtab[256 + i];
     __syncthreads();
-    collapse_strips_walk_gray<FL, DBG>(a, gio, s_igt, s_ab);
+    StripToGray<FL, DBG> f{s_igt, s_ab, gio};
+    LVM_COLLAPSE_STRIPS_WALK(a, f)
 }
+#undef LVM_COLLAPSE_STRIPS_WALK
+#undef LVM_COLLAPSE_STEP
 
 // ------------------------------------------------------------------------------------------
 // host side
@@ -1940,6 +1828,9 @@ static bool rz_mul_f32(const Ctx* c) { return (c->opencv_build & LVM_CV_MUL_F32)
         else LVM_LAUNCH(c, nm, kern, grid, block, stream, __VA_ARGS__);                   \
     } while (0)
 
+// Launch geometry of a wave-strip kernel: one wave per task, workgroups of `threads`
+static dim3 strip_grid(long ntasks, int threads) { return dim3((unsigned)((ntasks + threads / 64 - 1) / (threads / 64))); }
+
 // pyramid of the nt frames: L plane + 9x9 split chain
 static void rz_build(Ctx* c, RieszState* st, const FrameIO& io, const RzBufs& B, hipStream_t s) {
     const int NZ = c->nstreams * B.nt, w = io.w, h = io.h, nb = st->levels - 1;
@@ -1982,7 +1873,7 @@ static void rz_build(Ctx* c, RieszState* st, const FrameIO& io, const RzBufs& B,
             if (rows <= 0) rows = strip_rows_by_work(sx, a.h, NZ);
             const int sy = (a.h + rows - 1) / rows;
             const long ntasks = (long)sx * sy * NZ;
-            LVM_LAUNCH_V(c, LName("rz_split", l), "strips", k_rz_split_rows, dim3((unsigned)((ntasks + SR_THREADS / 64 - 1) / (SR_THREADS / 64))), dim3(SR_THREADS), s,
+            LVM_LAUNCH_V(c, LName("rz_split", l), "strips", k_rz_split_rows, strip_grid(ntasks, SR_THREADS), dim3(SR_THREADS), s,
                        (const float*)B.oct[l], a.w, a.h, B.pf[l][F_BAND], B.oct[l + 1], b.w, b.h, sx, sy, (int)ntasks, rows);
             continue;
         }
@@ -2028,22 +1919,18 @@ static void rz_phase(Ctx* c, RieszState* st, const RzBufs& B, int mode, hipStrea
         (vec ? blocks4 : blocks) += v.tx * v.ty * NS;
     }
     a.nlv = n1; a4.nlv = n4;
-    // (EXACT, UNF, MF32) -> instantiation
     const bool exact = lab_flavour(c) != FL_LUT_FAST, unf = rz_unfused(c), mf32 = rz_mul_f32(c), ptrig = exact && st->portable_trig;
-    auto pick = [&](auto vec4) {
-        constexpr bool V4 = decltype(vec4)::value;
-        auto p2 = [&](auto e, auto u, auto pt) {
-            constexpr bool E = decltype(e)::value, U = decltype(u)::value, PT = decltype(pt)::value;
-            if constexpr (V4) return mf32 ? k_rz_phase4<E, U, true, PT> : k_rz_phase4<E, U, false, PT>;
-            else return mf32 ? k_rz_phase<E, U, true, PT> : k_rz_phase<E, U, false, PT>;
-        };
-        auto p1 = [&](auto e, auto pt) { return unf ? p2(e, std::true_type{}, pt) : p2(e, std::false_type{}, pt); };
-        return exact ? (ptrig ? p1(std::true_type{}, std::true_type{}) : p1(std::true_type{}, std::false_type{})) : p1(std::false_type{}, std::false_type{});
+    auto pick = [&](bool vec4) {                // (V4; EXACT, UNF, MF32, PT) -> instantiation
+        return lvm_pick([](auto v4, auto e, auto u, auto m, auto pt) {
+            constexpr bool E = decltype(e)::value, U = decltype(u)::value, M = decltype(m)::value, PT = E && decltype(pt)::value;
+            if constexpr (decltype(v4)::value) return k_rz_phase4<E, U, M, PT>;
+            else return k_rz_phase<E, U, M, PT>;
+        }, vec4, exact, unf, mf32, ptrig);
     };
     const char* var = ptrig ? (unf ? (mf32 ? "unfused+mulf32+ptrig" : "unfused+ptrig") : (mf32 ? "mulf32+ptrig" : "ptrig"))
                             : (unf ? (mf32 ? "unfused+mulf32" : "unfused") : (mf32 ? "mulf32" : nullptr));
-    if (n4) LVM_LAUNCH_KIND(c, mode ? "rz_seed" : "rz_phase", var, pick(std::true_type{}), dim3(blocks4), dim3(256), s, a4);
-    if (n1) LVM_LAUNCH_KIND(c, mode ? "rz_seed_small" : "rz_phase_small", var, pick(std::false_type{}), dim3(blocks), dim3(256), s, a);
+    if (n4) LVM_LAUNCH_KIND(c, mode ? "rz_seed" : "rz_phase", var, pick(true), dim3(blocks4), dim3(256), s, a4);
+    if (n1) LVM_LAUNCH_KIND(c, mode ? "rz_seed_small" : "rz_phase_small", var, pick(false), dim3(blocks), dim3(256), s, a);
 }
 
 static bool rz_level_uses_strips(const RieszState* st, int l, int NZ) {
@@ -2105,13 +1992,13 @@ static void rz_amplify(Ctx* c, RieszState* st, const lvm_params& p, const FrameI
         a.nlv = n1; a4.nlv = n4;
         const bool exact = lab_flavour(c) != FL_LUT_FAST, unf = rz_unfused(c), ptrig = exact && st->portable_trig;
         const char* var = ptrig ? (unf ? "unfused+ptrig" : "ptrig") : (unf ? "unfused" : nullptr);
-#define LVM_RZ_BLUR_PICK(K) (exact ? (ptrig ? (unf ? K<true, true, true> : K<true, false, true>) : (unf ? K<true, true> : K<true, false>)) \
-                                   : (unf ? K<false, true> : K<false, false>))
-        if (as.nlv) LVM_LAUNCH_KIND(c, "rz_blur_amp", var, LVM_RZ_BLUR_PICK(k_rz_blur_strips),
-                                    dim3((unsigned)((as.ntasks + BS_THREADS / 64 - 1) / (BS_THREADS / 64))), dim3(BS_THREADS), s, as);
-        if (n4) LVM_LAUNCH_KIND(c, as.nlv ? "rz_blur_amp_tiles" : "rz_blur_amp", var, LVM_RZ_BLUR_PICK(k_rz_blur_amp4), dim3(blocks4), dim3(B2T), s, a4);
-        if (n1) LVM_LAUNCH_KIND(c, "rz_blur_amp_small", var, LVM_RZ_BLUR_PICK(k_rz_blur_amp), dim3(blocks), blk, s, a);
-#undef LVM_RZ_BLUR_PICK
+        // (EXACT, UNF, PT) -> instantiation, per kernel
+        auto kstrips = lvm_pick([](auto e, auto u, auto pt) { return k_rz_blur_strips<decltype(e)::value, decltype(u)::value, decltype(e)::value && decltype(pt)::value>; }, exact, unf, ptrig);
+        auto ktiles4 = lvm_pick([](auto e, auto u, auto pt) { return k_rz_blur_amp4<decltype(e)::value, decltype(u)::value, decltype(e)::value && decltype(pt)::value>; }, exact, unf, ptrig);
+        auto ktiles = lvm_pick([](auto e, auto u, auto pt) { return k_rz_blur_amp<decltype(e)::value, decltype(u)::value, decltype(e)::value && decltype(pt)::value>; }, exact, unf, ptrig);
+        if (as.nlv) LVM_LAUNCH_KIND(c, "rz_blur_amp", var, kstrips, strip_grid(as.ntasks, BS_THREADS), dim3(BS_THREADS), s, as);
+        if (n4) LVM_LAUNCH_KIND(c, as.nlv ? "rz_blur_amp_tiles" : "rz_blur_amp", var, ktiles4, dim3(blocks4), dim3(B2T), s, a4);
+        if (n1) LVM_LAUNCH_KIND(c, "rz_blur_amp_small", var, ktiles, dim3(blocks), blk, s, a);
     }
 }
 // residual = res_{L-1} (the context's own residual octave, or -- tiling -- the collapsed coarse levels of another context);
@@ -2143,16 +2030,13 @@ static void rz_collapse_out(Ctx* c, RieszState* st, const lvm_params& p, const F
             CollapseStripArgs ca{};
             ca.bandA = B.pf[l][F_BANDA]; ca.resn = resn; ca.res = res_l;
             strips_geom(ca, a, b);
-            LVM_LAUNCH(c, LName("rz_collapse", l), (k_rz_collapse_strips<false, FL_LUT_FAST, false>),
-                       dim3((unsigned)((ca.ntasks + CS_THREADS / 64 - 1) / (CS_THREADS / 64))), dim3(CS_THREADS), s, ca);
+            LVM_LAUNCH(c, LName("rz_collapse", l), (k_rz_collapse_strips<false, FL_LUT_FAST, false>), strip_grid(ca.ntasks, CS_THREADS), dim3(CS_THREADS), s, ca);
             resn = res_l;
             continue;
         }
         const dim3 grid((a.w + CW - 1) / CW, (a.h + CH - 1) / CH, NZ);
         const bool compact = st->compact && a.w % 2 == 0 && a.h % 2 == 0;
-        auto kc = tk == TK_F64 ? (compact ? k_rz_collapse<true, TK_F64> : k_rz_collapse<false, TK_F64>)
-                               : (tk == TK_UNFUSED ? (compact ? k_rz_collapse<true, TK_UNFUSED> : k_rz_collapse<false, TK_UNFUSED>)
-                                                   : (compact ? k_rz_collapse<true, TK_FMA> : k_rz_collapse<false, TK_FMA>));
+        auto kc = lvm_pick([](auto cp, auto k) { return k_rz_collapse<decltype(cp)::value, decltype(k)::value>; }, compact, PickInt<TK_F64, TK_UNFUSED, TK_FMA>{tk});
         LVM_LAUNCH_KIND(c, LName("rz_collapse", l), tk != TK_FMA ? rz_tap_name(tk) : nullptr, kc, grid, blk, s, (const float*)B.pf[l][F_BANDA], resn,
                         res_l, a.w, a.h, b.w, b.h);
         resn = res_l;
@@ -2170,78 +2054,48 @@ static void rz_collapse_out(Ctx* c, RieszState* st, const lvm_params& p, const F
                      io.out_sstride % 4 == 0 && ((uintptr_t)io.d_in % 4) == 0 && ((uintptr_t)io.d_out % 4) == 0;
     const int fl = lab_flavour(c);
     const bool compact = st->compact && w % 2 == 0 && h % 2 == 0;
-    // (BANDS, FL, VEC, COMPACT, DBG) -> instantiation
-    auto pick = [&](auto bands) {
-        constexpr bool BN = decltype(bands)::value;
-        auto p3 = [&](auto e, auto v, auto cp) {
-            constexpr int E = decltype(e)::value; constexpr bool V = decltype(v)::value, CP = decltype(cp)::value;
-            return dbg ? k_rz_final<BN, E, V, CP, true> : k_rz_final<BN, E, V, CP, false>;
-        };
-        auto p2 = [&](auto e, auto v) { return (compact && BN) ? p3(e, v, std::true_type{}) : p3(e, v, std::false_type{}); };
-        auto p1 = [&](auto e) { return vec ? p2(e, std::true_type{}) : p2(e, std::false_type{}); };
-        return fl == FL_ANALYTIC ? p1(std::integral_constant<int, FL_ANALYTIC>{})
-                                 : (fl == FL_LUT_EXACT ? p1(std::integral_constant<int, FL_LUT_EXACT>{}) : p1(std::integral_constant<int, FL_LUT_FAST>{}));
-    };
-    auto kfb = pick(std::true_type{});
-    auto kfn = pick(std::false_type{});
     const bool out_ok = io.out_stride % 4 == 0 && io.out_sstride % 4 == 0 && ((uintptr_t)io.d_out % 4) == 0 && (long)io.out_stride * h < (1L << 31);
-    if (st->gray) {
-        // gray frames (lvm_set_phase_on_gray): the same choice among the same three routes, the gray forms of their kernels
-        auto pickg = [&](auto bands) {
-            constexpr bool BN = decltype(bands)::value;
-            auto p3 = [&](auto e, auto v, auto cp) {
-                constexpr int E = decltype(e)::value; constexpr bool V = decltype(v)::value, CP = decltype(cp)::value;
-                return dbg ? k_rz_final_gray<BN, E, V, CP, true> : k_rz_final_gray<BN, E, V, CP, false>;
-            };
-            auto p2 = [&](auto e, auto v) { return (compact && BN) ? p3(e, v, std::true_type{}) : p3(e, v, std::false_type{}); };
-            auto p1 = [&](auto e) { return vec ? p2(e, std::true_type{}) : p2(e, std::false_type{}); };
-            return fl == FL_ANALYTIC ? p1(std::integral_constant<int, FL_ANALYTIC>{})
-                                     : (fl == FL_LUT_EXACT ? p1(std::integral_constant<int, FL_LUT_EXACT>{}) : p1(std::integral_constant<int, FL_LUT_FAST>{}));
-        };
-        const bool bands = nb >= 1 && !kind_l0;
-        if (bands && fl != FL_ANALYTIC && out_ok && vec && strips_ok(st->g[0], st->g[1])) {       // (vec: the strip kernel reads the input frame dword-wide as well)
-            CollapseStripArgs ca{};
-            ca.bandA = B.pf[0][F_BANDA]; ca.resn = resn; ca.res = nullptr;
-            ca.iab = nullptr; ca.out = (uint8_t*)io.d_out; ca.out_stride = (long)io.out_stride; ca.out_sstride = (long)io.out_sstride; ca.dbg = dbg; ca.lab = c->lab;
-            strips_geom(ca, st->g[0], st->g[1]);
-            const GrayStripIO gio{io.d_in, (long)io.in_stride, (long)io.in_sstride, st->gray_tab};
-            auto kf = fl == FL_LUT_EXACT ? (dbg ? k_rz_collapse_strips_gray<FL_LUT_EXACT, true> : k_rz_collapse_strips_gray<FL_LUT_EXACT, false>)
-                                         : (dbg ? k_rz_collapse_strips_gray<FL_LUT_FAST, true> : k_rz_collapse_strips_gray<FL_LUT_FAST, false>);
-            LVM_LAUNCH_V(c, "rz_final", "gray-strips", kf, dim3((unsigned)((ca.ntasks + CS_THREADS / 64 - 1) / (CS_THREADS / 64))), dim3(CS_THREADS), s, ca, gio);
-        } else if (bands)
-            LVM_LAUNCH_V(c, "rz_final", vec ? "gray4" : "gray", pickg(std::true_type{}), grid, blk, s, io.d_in, (long)io.in_stride, (long)io.in_sstride, io.d_out,
-                       (long)io.out_stride, (long)io.out_sstride, w, h, (const float*)B.pf[0][F_BANDA], resn, st->g[1].w, st->g[1].h,
-                       c->lab, tx, ty, NZ, dbg, (const float*)B.oct[0], (const float*)st->gray_tab);
-        else       // no bands, or level 0 collapsed into res_0 by a build kind: L' is that plane
-            LVM_LAUNCH_V(c, "rz_final", vec ? "gray4" : "gray", pickg(std::false_type{}), grid, blk, s, io.d_in, (long)io.in_stride, (long)io.in_sstride, io.d_out,
-                       (long)io.out_stride, (long)io.out_sstride, w, h, (const float*)nullptr, (const float*)nullptr, 0, 0,
-                       c->lab, tx, ty, NZ, dbg, kind_l0 ? resn : (const float*)B.oct[0], (const float*)st->gray_tab);
-    } else if (kind_l0) {
-        // L' = res_0 (collapsed above): the band-less last kernel, which reads the plane (analytic flavour: LPLANE)
-        auto p2 = [&](auto v) {
-            constexpr bool V = decltype(v)::value;
-            return dbg ? k_rz_final<false, FL_ANALYTIC, V, false, true, true> : k_rz_final<false, FL_ANALYTIC, V, false, false, true>;
-        };
-        auto kfp = fl == FL_ANALYTIC ? (vec ? p2(std::true_type{}) : p2(std::false_type{})) : kfn;
-        LVM_LAUNCH_V(c, "rz_final", vec ? "vec4" : "bytes", kfp, grid, blk, s, io.d_in, (long)io.in_stride, (long)io.in_sstride, io.d_out,
-                   (long)io.out_stride, (long)io.out_sstride, w, h, (const float*)nullptr, (const float*)nullptr, 0, 0,
-                   c->lab, tx, ty, NZ, dbg, resn, (const uint32_t*)B.iab);
-    } else if (nb >= 1 && fl != FL_ANALYTIC && out_ok && strips_ok(st->g[0], st->g[1])) {
+    const bool bands = nb >= 1 && !kind_l0, keep = dbg != nullptr;
+    // Three routes, the same for BGR and gray frames (lvm_set_phase_on_gray: the gray forms of the kernels): wave strips, the tiled kernel
+    // with BANDS, and the band-less tiled kernel -- no bands, or level 0 collapsed into res_0 by a build kind: L' is that plane.
+    // (gray strips need vec: the strip kernel reads the input frame dword-wide as well)
+    if (bands && fl != FL_ANALYTIC && out_ok && (vec || !st->gray) && strips_ok(st->g[0], st->g[1])) {
         CollapseStripArgs ca{};
         ca.bandA = B.pf[0][F_BANDA]; ca.resn = resn; ca.res = nullptr;
         ca.iab = B.iab; ca.out = (uint8_t*)io.d_out; ca.out_stride = (long)io.out_stride; ca.out_sstride = (long)io.out_sstride; ca.dbg = dbg; ca.lab = c->lab;
         strips_geom(ca, st->g[0], st->g[1]);
-        auto kf = fl == FL_LUT_EXACT ? (dbg ? k_rz_collapse_strips<true, FL_LUT_EXACT, true> : k_rz_collapse_strips<true, FL_LUT_EXACT, false>)
-                                     : (dbg ? k_rz_collapse_strips<true, FL_LUT_FAST, true> : k_rz_collapse_strips<true, FL_LUT_FAST, false>);
-        LVM_LAUNCH_V(c, "rz_final", "strips", kf, dim3((unsigned)((ca.ntasks + CS_THREADS / 64 - 1) / (CS_THREADS / 64))), dim3(CS_THREADS), s, ca);
-    } else if (nb >= 1)
-        LVM_LAUNCH_V(c, "rz_final", vec ? "vec4" : "bytes", kfb, grid, blk, s, io.d_in, (long)io.in_stride, (long)io.in_sstride, io.d_out,
-                   (long)io.out_stride, (long)io.out_sstride, w, h, (const float*)B.pf[0][F_BANDA], resn, st->g[1].w, st->g[1].h,
-                   c->lab, tx, ty, NZ, dbg, (const float*)B.oct[0], (const uint32_t*)B.iab);
-    else
-        LVM_LAUNCH_V(c, "rz_final", vec ? "vec4" : "bytes", kfn, grid, blk, s, io.d_in, (long)io.in_stride, (long)io.in_sstride, io.d_out,
-                   (long)io.out_stride, (long)io.out_sstride, w, h, (const float*)nullptr, (const float*)nullptr, 0, 0,
-                   c->lab, tx, ty, NZ, dbg, (const float*)B.oct[0], (const uint32_t*)B.iab);
+        const PickInt<FL_LUT_EXACT, FL_LUT_FAST> sfl{fl};
+        if (st->gray) {
+            const GrayStripIO gio{io.d_in, (long)io.in_stride, (long)io.in_sstride, st->gray_tab};
+            auto kf = lvm_pick([](auto e, auto d) { return k_rz_collapse_strips_gray<decltype(e)::value, decltype(d)::value>; }, sfl, keep);
+            LVM_LAUNCH_V(c, "rz_final", "gray-strips", kf, strip_grid(ca.ntasks, CS_THREADS), dim3(CS_THREADS), s, ca, gio);
+        } else {
+            auto kf = lvm_pick([](auto e, auto d) { return k_rz_collapse_strips<true, decltype(e)::value, decltype(d)::value>; }, sfl, keep);
+            LVM_LAUNCH_V(c, "rz_final", "strips", kf, strip_grid(ca.ntasks, CS_THREADS), dim3(CS_THREADS), s, ca);
+        }
+        return;
+    }
+    FinalArgs fa{};
+    fa.in = io.d_in; fa.in_stride = (long)io.in_stride; fa.in_sstride = (long)io.in_sstride;
+    fa.out = (uint8_t*)io.d_out; fa.out_stride = (long)io.out_stride; fa.out_sstride = (long)io.out_sstride;
+    fa.w = w; fa.h = h; fa.lab = c->lab; fa.tiles_x = tx; fa.tiles_y = ty; fa.nstreams = NZ; fa.dbg = dbg;
+    fa.iab = B.iab; fa.gtab = st->gray_tab;
+    if (bands) { fa.bandA = B.pf[0][F_BANDA]; fa.resn = resn; fa.nw = st->g[1].w; fa.nh = st->g[1].h; }
+    fa.Lplane = kind_l0 ? resn : B.oct[0];
+    // (BANDS, FL, VEC, COMPACT, DBG, LPLANE) -> instantiation; LPLANE: the analytic flavour reads L' = res_0 under a build kind
+    if (st->gray) {
+        auto kf = lvm_pick([](auto bn, auto e, auto v, auto cp, auto d) {
+            constexpr bool BN = decltype(bn)::value;
+            return k_rz_final_gray<BN, decltype(e)::value, decltype(v)::value, BN && decltype(cp)::value, decltype(d)::value>;
+        }, bands, pick_flavour(fl), vec, compact, keep);
+        LVM_LAUNCH_V(c, "rz_final", vec ? "gray4" : "gray", kf, grid, blk, s, fa);
+    } else {
+        auto kf = lvm_pick([](auto bn, auto e, auto v, auto cp, auto d, auto lp) {
+            constexpr bool BN = decltype(bn)::value; constexpr int E = decltype(e)::value;
+            return k_rz_final<BN, E, decltype(v)::value, BN && decltype(cp)::value, decltype(d)::value, !BN && E == FL_ANALYTIC && decltype(lp)::value>;
+        }, bands, pick_flavour(fl), vec, compact, keep, kind_l0);
+        LVM_LAUNCH_V(c, "rz_final", vec ? "vec4" : "bytes", kf, grid, blk, s, fa);
+    }
 }
 
 // ---- lvm_debug_trig_eval: rz_trig.h on the device, value by value (tests hold it against the oracle's lvmo_trig_eval bit for bit) ----

@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""Are the default-kind Riesz kernels the code they were?  Compiles csrc/riesz.hip of a git revision (default: HEAD~1) and of the working tree to
+"""Which Riesz kernels moved, and by how much?  A REPORT, not a gate: what holds a change of csrc/riesz.hip to the parent is the bits (parity tests),
+the resources (tools/kru.sh) and the time on the GPU ("One text per step"); a kernel listed here with a count that moved by much more than
+half a percent is more than scheduling, and the two listings are to be read.  Compiles csrc/riesz.hip of a git revision (default: HEAD~1) and of the working tree to
 gfx950 assembly with the Makefile's flags and compares, kernel by kernel, the instruction streams of the kernels the revision has with their
 mask-0 instantiations here (k_rz_split -> k_rz_split<TK_FMA>, k_rz_phase<E> -> k_rz_phase<E, false, false>, ...; the instantiations without the
 portable functions of LVM_RZ_PORTABLE_TRIG -- last template argument false -- stand for the kernels of a revision from before that argument), labels
