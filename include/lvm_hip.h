@@ -96,9 +96,12 @@ int  lvm_process(lvm_ctx* ctx, const lvm_params* p, const uint8_t* in, int w, in
  * rectangles of the streams must not overlap.  Bytes outside the w*channels x h rectangles are never
  * written.  Dword-aligned pointers and strides with w % 4 == 0 select the vector kernels, everything
  * else the byte kernels; in the bit-exact flavour the bytes do not depend on that choice.
- * A row stride that cannot hold its pixels (negative ones included) or a non-positive output
- * stream stride is refused with LVM_ERR_INVALID before any state changes or any kernel runs:
- * the next valid frame continues the clip.                                                  */
+ * One frame spans at most 2 GiB: (h - 1) * stride + w*channels <= INT32_MAX for in_stride and for
+ * out_stride (the kernels address inside a frame with 32 bits); streams and frames may lie any
+ * distance apart.
+ * A row stride that cannot hold its pixels (negative ones included), a frame whose rows span more
+ * than that, or a non-positive output stream stride is refused with LVM_ERR_INVALID before any state
+ * changes or any kernel runs: the next valid frame continues the clip.                      */
 int  lvm_process_device(lvm_ctx* ctx, const lvm_params* p, const uint8_t* d_in, int w, int h,
                         int channels, ptrdiff_t in_stride, ptrdiff_t in_stream_stride,
                         uint8_t* d_out, ptrdiff_t out_stride, ptrdiff_t out_stream_stride,

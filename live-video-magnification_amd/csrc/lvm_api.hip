@@ -168,11 +168,16 @@ int ensure_float(Ctx* c, size_t count) {
 
 // The layouts the device surfaces take (include/lvm_hip.h): rows that hold their pixels (compose_device's rule); stream strides are
 // free -- two streams side by side in one mosaic frame have a stream stride of one row -- except that the outputs of several
-// streams must not land on each other.  Null: fine.
+// streams must not land on each other.  Inside one frame the kernels address with 32 bits -- unsigned row offsets, buffer resources of
+// stride * (h - 1) + w * channels bytes, the signed offsets of the buffer intrinsics -- so the rows of a frame, first byte to last, span
+// at most INT32_MAX bytes; streams and frames of a call may lie any distance apart (64-bit bases).  Null: fine.
 static const char* layout_error(const FrameIO& io, int nstreams) {
-    const ptrdiff_t row = (ptrdiff_t)io.w * io.channels;
+    const ptrdiff_t row = (ptrdiff_t)io.w * io.channels, span_max = INT32_MAX;
     if (io.in_stride < row || io.out_stride < row) return "frame stride too small";
     if (nstreams > 1 && io.out_sstride <= 0) return "stream stride too small";
+    // (h - 1) * stride + row > span_max, without the product
+    auto too_far = [&](ptrdiff_t stride) { return row > span_max || (io.h > 1 && stride > (span_max - row) / (io.h - 1)); };
+    if (too_far(io.in_stride) || too_far(io.out_stride)) return "frame rows span more than 2 GiB";
     return nullptr;
 }
 
@@ -206,7 +211,7 @@ static int process_device(Ctx* c, const lvm_params* p, const FrameIO& io, hipStr
     if (io.d_out == nullptr) { c->err = "null output"; return LVM_ERR_INVALID; }
     const StructKey key = struct_key(*p, io.w, io.h, io.channels);                      // :32-34
     if (key.levels < 1) return LVM_OK;
-    // the kernels address rows and streams with unsigned offsets: refuse what they cannot walk before any state is touched
+    // the kernels address the rows of a frame with 32-bit offsets: refuse what they cannot walk (layout_error) before any state is touched
     if (const char* why = layout_error(io, c->nstreams)) { c->err = why; return LVM_ERR_INVALID; }
     if (key != c->tracked) {                                                            // MagnifyCore.hpp:53-65
         // buffers of the old geometry may still be in use by queued kernels

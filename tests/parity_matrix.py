@@ -10,7 +10,7 @@ import re
 import numpy as np
 
 import content
-from helpers import frames_clip, layout_clip, run_pair
+from helpers import far_clip, far_units, frames_clip, layout_clip, run_pair
 
 
 def _color_fps(ck, pk, fps=15.0):
@@ -461,11 +461,19 @@ def layout_case(lvm, po, lib, mem, idx, w, h, levels, n_streams, name, env=None,
                        exact=exact, profile=profile, clip_fn=clip_fn)
 
 
-def layout_forced_case(lvm, po, lib, mem, force, name, exact=True, clip_fn=None, ptrig=False):
+def layout_forced_case(lvm, po, lib, mem, force, name, exact=True, clip_fn=None, ptrig=False, n_streams=1, calls=None, env_extra=None, size=None):
     """one forced case: the bytes, and the kernels LAYOUT_LAUNCHES names for this layout -- a silent fall-back to another kernel family fails.
-    ptrig (under portable_trig()): the phase and blur / amplify launches LAYOUT_LAUNCHES expects run as their `ptrig` variant"""
+    ptrig (under portable_trig()): the phase and blur / amplify launches LAYOUT_LAUNCHES expects run as their `ptrig` variant.
+    calls: call lengths in place of the mode's of LAYOUT_MODES; env_extra: switches besides the entry's; size: (w, h, levels) in place of its"""
     idx, w, h, levels, env = LAYOUT_FORCED[force]
-    worst, names = layout_case(lvm, po, lib, mem, idx, w, h, levels, 1, name, env=env, exact=exact, profile=True, clip_fn=clip_fn)
+    w, h, levels = size or (w, h, levels)
+    env = dict(env, **(env_extra or {}))
+    if calls is None:
+        worst, names = layout_case(lvm, po, lib, mem, idx, w, h, levels, n_streams, name, env=env, exact=exact, profile=True, clip_fn=clip_fn)
+    else:
+        _, over, clip_over = LAYOUT_MODES[idx]
+        worst, names = layout_clip(lvm, po, lib, mem, idx, w, h, levels, n_streams, calls, LAYOUTS[name], env=env, over=over, clip_over=clip_over,
+                                   exact=exact, profile=True, clip_fn=clip_fn)
     want = dict(LAYOUT_LAUNCHES[force]["*"], **LAYOUT_LAUNCHES[force][name])
     if ptrig:
         want = {n: ({"ptrig"} if n in PTRIG_NAMES and v == set() else v) for n, v in want.items()}
@@ -475,6 +483,155 @@ def layout_forced_case(lvm, po, lib, mem, force, name, exact=True, clip_fn=None,
         else:
             assert n in names and names[n] == variants, (force, name, n, variants, names)
     return worst, {n: sorted(names[n]) for n, v in want.items() if v is not None}
+
+
+# ---- many streams, full-length batches (tests/test_emu_many_streams.py, tests/test_gpu_exact.py, tests/test_gpu_riesz_exact.py) ---------
+# In a batch the kernels see b = frame * n_streams + stream and take from it a stream's temporal state, a frame's planes and a wave's
+# task.  bench.py runs 4 streams x 32 frames and 16 x 16 per call; the cases above stop at 3 streams and b of about 40.  Here: the
+# benchmark's stream counts, 5 (odd: b / n and b % n are no shift and no mask) and 17 (one past 16), in calls of 16 and 32 frames (32 is
+# Color's batch cap) and a short one behind them -- b reaches 32 * n_streams - 1: 511 at 16 streams, 543 at 17.  Every stream has a
+# clip of its own (seed 1234 + stream), so output that lands in another stream's place, or state taken from it, changes bytes.
+MANY_STREAMS = (4, 5, 16, 17)
+MANY_TAIL = (16, 32, 3)
+# per mode: the seeding calls (Laplace: the first frame; Riesz: the passthrough frame and the first filtered one; Color: 18 frames fill
+# the window of COLOR_BATCH_PARAMS), parameter and clip overrides
+MANY_MODES = {0: ((1,), None, None), 2: ((1, 1), None, None), 3: ((18,),) + COLOR_BATCH_PARAMS}
+# (mode, w, h, levels): Laplace 64 x 48 takes the vector kernels and 67 x 45 the byte kernels
+MANY_SHAPES = [(0, 64, 48, 3), (0, 67, 45, 2), (2, 64, 48, 2), (2, 67, 45, 2), (3, 40, 30, 1), (3, 64, 48, 2)]
+MANY_CASES = [shape + (ns,) for shape in MANY_SHAPES for ns in MANY_STREAMS]
+MANY_PER_FRAME = [(idx, ns) for idx in (0, 2, 3) for ns in (4, 16)]           # bench.py's per_frame_streams: lvm_process_device in a loop
+MANY_PIPELINE = [(4, 4), (9, 4)]                                            # (frames, ring) of the 4-stream depth-1 pipeline
+MANY_FORCED_STREAMS = 5
+# With several streams the task count of "lap_rows" passes the threshold (it counts the CUs) from which lap_down0_lut replaces the pair
+# lab_lut + lap_down0 that the entry is there for ("lap_fused" forces that kernel): the fused first kernel is switched off beside it.
+MANY_FORCED_EXTRA = {"lap_rows": {"LVM_D0_FUSED": "0"}}
+MANY_DEFAULT = (16, 16)                                                     # (streams, frames) of the default-flavour cases
+
+
+def many_calls(idx, tail=MANY_TAIL):
+    return MANY_MODES[idx][0] + tuple(tail)
+
+
+def many_streams_case(lvm, po, lib, mem, idx, w, h, levels, ns, refs="libm", tail=MANY_TAIL, device=False, exact=True, profile_call=None):
+    """One case of MANY_CASES through helpers.frames_clip, the oracle's frames from the shared cache (`refs`: "libm", or "ptrig" under
+    portable_trig())."""
+    seed, over, clip_over = MANY_MODES[idx]
+    return frames_clip(lvm, po, lib, mem, idx, w, h, levels, ns, seed + tuple(tail), over, clip_over, refs=refs, device=device, exact=exact,
+                       profile_call=profile_call)
+
+
+def many_per_frame(lvm, po, lib, mem, idx, ns, refs="libm"):
+    """six frames of every stream, one lvm_process_device call per frame (Color: behind the 18 frames that fill its window, per frame too)"""
+    w, h, levels = [s[1:] for s in MANY_SHAPES if s[0] == idx][-1]
+    return many_streams_case(lvm, po, lib, mem, idx, w, h, levels, ns, refs=refs, tail=(6,), device=True)
+
+
+def many_forced(lvm, po, lib, mem, force, exact=True, ptrig=False, size=None):
+    """an entry of LAYOUT_FORCED at MANY_FORCED_STREAMS streams on the view that keeps every strip kernel (B), the mode's seeding calls and a
+    call of 9 frames: the bytes, and the kernels LAYOUT_LAUNCHES names.  size: a smaller (w, h, levels) for the emulation build"""
+    idx = LAYOUT_FORCED[force][0]
+    return layout_forced_case(lvm, po, lib, mem, force, "B", exact=exact, ptrig=ptrig, n_streams=MANY_FORCED_STREAMS, calls=many_calls(idx, (9,)),
+                              env_extra=MANY_FORCED_EXTRA.get(force), size=size)
+
+
+# ---- surfaces that lie far apart (helpers.far_clip): stream and frame strides of 2^31 + 64 and 2^32 + 128 bytes ------------------------------
+# key -> (mode, w, h, levels, forced entry of LAYOUT_FORCED or None, odd base).  The default switches on the smallest shapes with w % 4 == 0
+# (the far view is dword-aligned: vector kernels), Laplace once more from an odd base (byte kernels), and each mode's strip set of
+# LAYOUT_FORCED at its own size, whose kernels build buffer resources on the far base: LAYOUT_LAUNCHES[...]["B"] must have run.
+FAR_CASES = {
+    "laplace": (0, 64, 48, 3, None, False), "laplace-odd-base": (0, 64, 48, 3, None, True), "laplace-rows": (0,) + LAYOUT_FORCED["lap_rows"][1:4] + ("lap_rows", False),
+    "laplace-fused": (0,) + LAYOUT_FORCED["lap_fused"][1:4] + ("lap_fused", False),
+    "riesz": (2, 64, 48, 2, None, False), "riesz-strips": (2,) + LAYOUT_FORCED["rz_strips"][1:4] + ("rz_strips", False),
+    "color": (3, 64, 48, 2, None, False), "color-down01": (3,) + LAYOUT_FORCED["col_down01"][1:4] + ("col_down01", False),
+    "color-out-rows": (3,) + LAYOUT_FORCED["col_out_rows"][1:4] + ("col_out_rows", False),
+}
+
+
+def far_case(lvm, po, lib, mem, key, refs="libm", ptrig=False):
+    idx, w, h, levels, force, odd = FAR_CASES[key]
+    seed, over, clip_over = MANY_MODES[idx]
+    env = dict(LAYOUT_FORCED[force][4], **MANY_FORCED_EXTRA.get(force, {})) if force else None
+    names = far_clip(lvm, po, lib, mem, idx, w, h, levels, sum(seed), over=over, clip_over=clip_over, env=env, odd=odd, refs=refs)
+    if not force:
+        return {n: sorted(v) for n, v in names.items()}
+    want = dict(LAYOUT_LAUNCHES[force]["*"], **LAYOUT_LAUNCHES[force]["B"])
+    if ptrig:
+        want = {n: ({"ptrig"} if n in PTRIG_NAMES and v == set() else v) for n, v in want.items()}
+    for n, variants in want.items():
+        if variants is None:
+            assert n not in names, (key, n, names)
+        else:
+            assert n in names and names[n] == variants, (key, n, variants, names)
+    return {n: sorted(names[n]) for n, v in want.items() if v is not None}
+
+
+# The other device surfaces that take a stream or frame stride (helpers.far_units): two units 2^32 + 128 bytes apart against the bytes the
+# surface gives on packed buffers, and where the oracle restates the surface, against the oracle.
+def _far_noise(shape, seed):
+    return np.random.default_rng(seed).integers(0, 256, size=(2,) + shape, dtype=np.uint8)
+
+
+def far_preprocess(lvm, po, lib, mem):
+    """lvm_preprocess_device, two streams: ROI + fractional INTER_AREA cells + the gray stage (67 x 45, divisor 4: tests/test_preprocess.py)"""
+    w, h, ds, roi = 67, 45, 4, (0.1, 0.2, 0.7, 0.55)
+    kw = dict(downscale=ds, roiEnabled=True, roiX=roi[0], roiY=roi[1], roiW=roi[2], roiH=roi[3])
+    cpre, opre = lvm.to_c_preprocess(lvm.PreprocessParams(**kw), True), po.make_pre_params(grayscale=True, **kw)
+    frames = _far_noise((h, w, 3), 41)
+    ow, oh, och = po.preprocess_geometry(opre, w, h, 3)[4:]
+    assert och == 1
+    _, want = far_units(lvm, lib, mem, 2, [frames], ow * oh, lambda ctx, ins, out: ctx.preprocess_device(
+        cpre, ins[0][0], w, h, 3, w * 3, ins[0][1], out[0], ow, out[1], mem.stream()))
+    for s in range(2):
+        assert np.array_equal(want[s].reshape(oh, ow), po.preprocess(frames[s], opre)), s
+
+
+def far_compose(lvm, po, lib, mem):
+    """lvm_compose_device, two streams, LeftRight"""
+    w, h, LR = 64, 48, 1
+    orig, proc = _far_noise((h, w, 3), 42), _far_noise((h, w, 3), 43)
+    ref = [po.compose(LR, orig[s], proc[s]) for s in range(2)]
+    chh, cw = ref[0].shape[:2]
+    _, want = far_units(lvm, lib, mem, 2, [orig, proc], cw * chh * 3, lambda ctx, ins, out: ctx.compose_device(
+        LR, ins[0][0], w, h, 3, w * 3, ins[0][1], ins[1][0], w, h, 3, w * 3, ins[1][1], out[0], cw * 3, out[1], mem.stream()))
+    for s in range(2):
+        assert np.array_equal(want[s].reshape(ref[s].shape), ref[s]), s
+
+
+def far_overlay(lvm, po, lib, mem):
+    """lvm_overlay_device, two frames, in place (the tables of tests/test_export.py)"""
+    cw, chh = 200, 40
+    canvases = _far_noise((chh, cw, 3), 44)
+    labels = [po.standin_label_tables(70, 14, 3, 6, 6, cw, chh, seed=4), po.standin_label_tables(80, 14, 3, 106, 6, cw, chh, seed=5)]
+    _, want = far_units(lvm, lib, mem, 1, [], cw * chh * 3, lambda ctx, ins, out: ctx.overlay_device(out[0], cw, chh, 2, cw * 3, out[1], mem.stream()),
+                        out_init=canvases, setup=lambda ctx: ctx.export_set_overlay(labels))
+    for k in range(2):
+        assert np.array_equal(want[k].reshape(chh, cw, 3), po.apply_overlay(canvases[k].copy(), labels)), k
+
+
+def far_canvas_convert(lvm, po, lib, mem):
+    """lvm_canvas_convert_device, two frames, NV12"""
+    w, h = 64, 48
+    frames = _far_noise((h, w, 3), 45)
+    nbytes = w * h * 3 // 2
+
+    def layout(ctx):
+        assert ctx.canvas_layout(lvm.PIX_NV12, w, h, w)[0] == nbytes
+    far_units(lvm, lib, mem, 1, [frames], nbytes, lambda ctx, ins, out: ctx.canvas_convert_device(
+        lvm.PIX_NV12, ins[0][0], w, h, w * 3, ins[0][1], 2, out[0], w, out[1], mem.stream()), setup=layout)
+
+
+def far_mjpeg_encode(lvm, po, lib, mem):
+    """lvm_mjpeg_encode_device, two frames with a far frame_stride: the same JPEG bytes as from packed frames"""
+    w, h = 64, 48
+    ck, _ = lvm.synth.config(0, (w, h, 3))
+    clip = lvm.synth.Clip(**ck)
+    frames = np.stack([clip.frame(t) for t in range(2)])
+    jpegs, _ = far_units(lvm, lib, mem, 1, [frames], 0, lambda ctx, ins, out: ctx.mjpeg_encode_device(ins[0][0], w, h, 2, stride=w * 3, frame_stride=ins[0][1]))
+    assert len(jpegs) == 2 and jpegs[0] != jpegs[1] and all(j[:2] == b"\xff\xd8" and j[-2:] == b"\xff\xd9" for j in jpegs)
+
+
+FAR_SURFACES = {"preprocess": far_preprocess, "compose": far_compose, "overlay": far_overlay, "canvas_convert": far_canvas_convert,
+                "mjpeg_encode": far_mjpeg_encode}
 
 
 class PatchedClip:

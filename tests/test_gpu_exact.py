@@ -256,6 +256,66 @@ def test_chroma_far_out_of_gamut_exact(lvm, po, hip):
     M.chroma_out_of_gamut(lvm, po, hip)
 
 
+# many streams, full-length batches, surfaces that lie far apart (parity_matrix.MANY_*, FAR_*): the schedules bench.py runs -- 4 and 16 streams,
+# calls of 16 and 32 frames, the per-frame loop, the 4-stream depth-1 pipeline -- and 5 and 17 streams, on grids, LDS and 64-bit address
+# arithmetic of the gfx950 build.  Laplace and Color here, Riesz in tests/test_gpu_riesz_exact.py.
+def _ids(cases):
+    return ["-".join(str(x) for x in c) for c in cases]
+
+
+_MANY_LC = M.no_riesz(M.MANY_CASES)
+
+
+@pytest.mark.parametrize("idx,w,h,levels,ns", _MANY_LC, ids=_ids(_MANY_LC))
+def test_many_streams_full_batches_exact(lvm, po, hip, dev, idx, w, h, levels, ns):
+    M.many_streams_case(lvm, po, hip, dev, idx, w, h, levels, ns)
+
+
+@pytest.mark.parametrize("idx", [0, 3])
+def test_many_streams_kernels_chosen_without_forcing(lvm, po, hip, dev, idx):
+    """16 streams x 32 frames once more with the call of 32 frames profiled: the printed record says which kernels these small frames
+    reached unforced (the choice counts the CUs: no assertion on it)"""
+    _, w, h, levels = [s for s in M.MANY_SHAPES if s[0] == idx and s[1] % 4 == 0][-1]
+    calls = M.many_calls(idx)
+    names = M.many_streams_case(lvm, po, hip, dev, idx, w, h, levels, 16, profile_call=calls.index(32))
+    print("unforced at 16 streams x 32 frames, mode", idx, (w, h, levels), {n: sorted(v) for n, v in sorted(names.items())})
+
+
+@pytest.mark.parametrize("idx,ns", M.no_riesz(M.MANY_PER_FRAME), ids=_ids(M.no_riesz(M.MANY_PER_FRAME)))
+def test_many_streams_per_frame_schedule_exact(lvm, po, hip, dev, idx, ns):
+    M.many_per_frame(lvm, po, hip, dev, idx, ns)
+
+
+@pytest.mark.parametrize("nframes,ring", M.MANY_PIPELINE, ids=_ids(M.MANY_PIPELINE))
+def test_four_streams_pipelined_exact(lvm, po, hip, dev, nframes, ring):
+    pipelined_clip(lvm, po, hip, dev, 64, 48, 3, nframes, ring=ring, n_streams=4)
+
+
+@pytest.mark.parametrize("force", [f for f, c in M.LAYOUT_FORCED.items() if c[0] != 2])
+def test_five_streams_forced_strip_kernels_exact(lvm, po, hip, dev, force):
+    _, launched = M.many_forced(lvm, po, hip, dev, force)
+    print("five streams, forced", force, "launched as asserted:", launched)
+
+
+@pytest.mark.parametrize("idx", [0, 3])
+def test_many_streams_default_flavour_within_the_bars(lvm, po, hip, dev, idx):
+    """what bench.py runs is the default flavour: 16 streams x 16 frames at the bars of helpers.layout_clip (1 LSB, >= 0.999 identical)"""
+    _, w, h, levels = [s for s in M.MANY_SHAPES if s[0] == idx][-1]
+    ns, nf = M.MANY_DEFAULT
+    worst = M.many_streams_case(lvm, po, hip, dev, idx, w, h, levels, ns, tail=(nf,), exact=False)
+    print("default flavour, mode", idx, "%d streams x %d frames vs oracle: worst u8 diff %d, worst identical fraction %.6f" % ((ns, nf) + tuple(worst)))
+
+
+@pytest.mark.parametrize("key", [k for k, c in M.FAR_CASES.items() if c[0] != 2])
+def test_far_surfaces_exact(lvm, po, hip, dev, key):
+    print("far surfaces", key, "launched:", M.far_case(lvm, po, hip, dev, key))
+
+
+@pytest.mark.parametrize("surface", list(M.FAR_SURFACES))
+def test_far_units_of_the_other_device_surfaces(lvm, po, hip, dev, surface):
+    M.FAR_SURFACES[surface](lvm, po, hip, dev)
+
+
 LC_SEEDS = [s for s in range(24) if draw(s)[1] != 2]
 
 

@@ -197,6 +197,48 @@ def test_riesz_layout_forced_strip_kernels_exact(lvm, po, hip, dev, ptrig, name)
     M.layout_forced_case(lvm, po, hip, dev, "rz_strips", name, ptrig=True)
 
 
+# ---- many streams, full-length batches, surfaces that lie far apart (parity_matrix.MANY_*, FAR_*) -------------------------------------------
+_MANY_RZ = _riesz(M.MANY_CASES)
+
+
+@pytest.mark.parametrize("idx,w,h,levels,ns", _MANY_RZ, ids=_ids(_MANY_RZ))
+def test_riesz_many_streams_full_batches_exact(lvm, po, hip, dev, ptrig, idx, w, h, levels, ns):
+    M.many_streams_case(lvm, po, hip, dev, idx, w, h, levels, ns, refs="ptrig")
+
+
+def test_riesz_many_streams_kernels_chosen_without_forcing(lvm, po, hip, dev, ptrig):
+    """16 streams x 32 frames once more with the call of 32 frames profiled: the printed record says which kernels these small frames
+    reached unforced (the choice counts the CUs: no assertion on it)"""
+    _, w, h, levels = _MANY_RZ[0][:4]
+    calls = M.many_calls(2)
+    names = M.many_streams_case(lvm, po, hip, dev, 2, w, h, levels, 16, refs="ptrig", profile_call=calls.index(32))
+    print("unforced at 16 streams x 32 frames, mode 2", (w, h, levels), {n: sorted(v) for n, v in sorted(names.items())})
+
+
+@pytest.mark.parametrize("idx,ns", _riesz(M.MANY_PER_FRAME), ids=_ids(_riesz(M.MANY_PER_FRAME)))
+def test_riesz_many_streams_per_frame_schedule_exact(lvm, po, hip, dev, ptrig, idx, ns):
+    M.many_per_frame(lvm, po, hip, dev, idx, ns, refs="ptrig")
+
+
+def test_riesz_five_streams_forced_strip_kernels_exact(lvm, po, hip, dev, ptrig):
+    _, launched = M.many_forced(lvm, po, hip, dev, "rz_strips", ptrig=True)
+    print("five streams, forced rz_strips launched as asserted:", launched)
+
+
+def test_riesz_many_streams_default_flavour_within_the_bars(lvm, po, hip, dev):
+    """what bench.py runs is the default flavour (device sine / cosine, the oracle on libm): 16 streams x 16 frames at the bars of
+    helpers.layout_clip (1 LSB, >= 0.999 identical)"""
+    _, w, h, levels = _MANY_RZ[0][:4]
+    ns, nf = M.MANY_DEFAULT
+    worst = M.many_streams_case(lvm, po, hip, dev, 2, w, h, levels, ns, tail=(nf,), exact=False)
+    print("default flavour, mode 2 %d streams x %d frames vs oracle: worst u8 diff %d, worst identical fraction %.6f" % ((ns, nf) + tuple(worst)))
+
+
+@pytest.mark.parametrize("key", [k for k, c in M.FAR_CASES.items() if c[0] == 2])
+def test_riesz_far_surfaces_exact(lvm, po, hip, dev, ptrig, key):
+    print("far surfaces", key, "launched:", M.far_case(lvm, po, hip, dev, key, refs="ptrig", ptrig=M.FAR_CASES[key][4] is not None))
+
+
 # ---- switches -----------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("key", [k for k, c in M.SWITCH_CASES.items() if c["idx"] == 2])
 def test_riesz_switch_case_against_the_oracle(lvm, po, hip, dev, ptrig, key):

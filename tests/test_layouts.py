@@ -50,6 +50,21 @@ REFUSED = [
     (2, ROW, FB, ROW, 0, "stream stride too small"),
     (2, ROW, FB, ROW, -FB, "stream stride too small"),
 ]
+# One frame spans at most INT32_MAX bytes, (h - 1) * stride + w * channels (include/lvm_hip.h): the kernels address inside a frame with
+# 32 bits.  SPAN_STRIDE is the largest row stride inside the bound for these frames; a refused call takes its arguments and touches no
+# memory, so the rows just over it need no large buffer.  (Just inside: test_layout_emu_frame_span_just_inside_the_bound_is_accepted.)
+SPAN_MSG = "frame rows span more than 2 GiB"
+SPAN_STRIDE = (2**31 - 1 - ROW) // (H - 1)
+assert (H - 1) * SPAN_STRIDE + ROW <= 2**31 - 1 < (H - 1) * (SPAN_STRIDE + 1) + ROW
+REFUSED += [
+    (1, SPAN_STRIDE + 1, FB, ROW, FB, SPAN_MSG),
+    (1, ROW, FB, SPAN_STRIDE + 1, FB, SPAN_MSG),
+    (2, SPAN_STRIDE + 1, FB, ROW, FB, SPAN_MSG),
+    (2, ROW, FB, SPAN_STRIDE + 1, FB, SPAN_MSG),
+    (1, 2**32 + ROW, FB, ROW, FB, SPAN_MSG),          # a stride whose low 32 bits are a legal one
+    (1, ROW, FB, 2**32 + ROW, FB, SPAN_MSG),
+    (1, 2**62, FB, ROW, FB, SPAN_MSG),                # (h - 1) * stride itself overflows 64 bits
+]
 
 
 def _launches(ctx):
@@ -103,6 +118,47 @@ def test_layout_emu_bad_strides_are_refused_and_the_clip_continues(lvm, po, emu,
         ctx.close()
         for o in orcs:
             o.close()
+
+
+@pytest.mark.parametrize("side", ["in", "out"])
+def test_layout_emu_frame_span_just_inside_the_bound_is_accepted(lvm, po, emu, side):
+    """The largest row stride of the bound, SPAN_STRIDE, on real memory: one allocation of 2 GiB whose pages are committed only where a
+    row lies (np.empty), the other side packed.  Three Laplace frames equal the oracle's bit for bit; on the output side the 64 bytes
+    behind every row stay 0xCD."""
+    from numpy.lib.stride_tricks import as_strided
+    ck, pk = lvm.synth.config(0, (W, H, LEVELS))
+    clip = lvm.synth.Clip(**ck)
+    P, cp = po.make_params(**pk), c_params(lvm, pk)
+    guard = 64
+    far = np.empty((H - 1) * SPAN_STRIDE + ROW + guard, np.uint8)
+    rows = as_strided(far, shape=(H, ROW + guard), strides=(SPAN_STRIDE, 1))
+    packed = np.zeros((H, ROW), np.uint8)
+    ctx = lvm.Context(0, 1, emu)
+    ctx.exact_lab(True)
+    orc = po.Oracle()
+    try:
+        for t in range(3):
+            f = clip.frame(t)
+            ref, pr = orc.process(f, P)
+            if side == "in":
+                rows[:, :ROW] = f.reshape(H, ROW)
+                rows[:, ROW:] = 0xAB
+                packed[...] = 0xCD
+                pg = ctx.process_device(cp, far.ctypes.data, W, H, 3, SPAN_STRIDE, far.size, packed.ctypes.data, ROW, FB)
+            else:
+                packed[...] = f.reshape(H, ROW)
+                rows[...] = 0xCD
+                pg = ctx.process_device(cp, packed.ctypes.data, W, H, 3, ROW, FB, far.ctypes.data, SPAN_STRIDE, far.size)
+            ctx.synchronize()
+            assert pg == pr and pr
+            got = packed if side == "in" else rows[:, :ROW]
+            assert np.array_equal(got.reshape(H, W, 3), ref), "frame %d: %d bytes differ" % (t, int((got.reshape(H, W, 3) != ref).sum()))
+            if side == "out":
+                assert (rows[:, ROW:] == 0xCD).all(), "frame %d: bytes behind the rows were written" % t
+    finally:
+        ctx.close()
+        orc.close()
+        del rows, far
 
 
 def test_layout_emu_refused_batch_call_reserves_no_float_frame(lvm, emu):
