@@ -12,17 +12,25 @@
 // (w_L 2^k) x (h_L 2^k), two min/max pairs per stream and the bilinear resize tables.
 //
 // Launch sequence (one frame, or a batch of <= 32 frames of every stream):
-//   k_down0_rows | k_down0_v4, k_pyr_down_rows | _multi   u8 -> float -> Gaussian pyramid (pyramid.h)
+//   k_down01_rows | k_down0_rows | k_down0_v4 | k_down0, k_pyr_down_rows | _multi | k_pyr_down
+//                                  u8 -> float -> Gaussian pyramid (pyramid.h; k_down01_rows: the first two levels in one pass)
 //   k_col_append                   smallest level -> window slots; resets the min/max cells
-//   k_col_dft | k_col_dft_thin     per row: packed real DFT of the needed elements (float64 sums), 0/1 mask applied
+//   k_col_dft_thin8 | _thin | k_col_dft
+//                                  per row: packed real DFT of the needed elements (float64 sums), 0/1 mask applied
 //                                  as a packed complex spectrum (mulSpectrums), inverse transform of all T samples
-//                                  -> global min/max, keep column 1   (wave per row | thread per row, narrow bands;
+//                                  -> global min/max, keep column 1   (narrow bands: eight lanes per row, <= 4 entries and
+//                                  <= 256 frames | thread per row, <= 8 entries; else wave per row.
 //                                  k_col_dft_long: windows of 1025..4096 frames, thread per entry and per sample over
 //                                  the 4 | 2 rows of a workgroup; k_col_dft_serial, frame by frame, beyond)
-//   k_col_norm                     min-max normalise column 1, x alpha -> up_0
-//   k_pyr_up x (L-1)               up_k -> up_{k+1}
-//   k_col_out_rows<false>          last pyrUp + bilinear resize + input add -> global min/max   (wave strips;
-//   k_col_out_rows<true>           same values again -> u8 with the min/max rescale             k_col_out* = tiles)
+//   k_pyr_up_rows_norm             min-max normalise column 1, x alpha, inside the first pyrUp: col1 -> up_1
+//                                  (k_col_norm -> up_0 as a launch of its own where the first pyrUp is not a rows launch)
+//   k_pyr_up_rows | k_pyr_up       up_k -> up_{k+1}, up to up_{L-2}
+//   k_col_out_strips<false>        last TWO pyrUps + vertical bilinear resize + input add -> global min/max   (wave strips)
+//   k_col_out_strips<true>         same values again -> u8 with the min/max rescale
+//                                  (k_col_out_rows: wave strips with the last pyrUp only, after L-1 generic pyrUps;
+//                                  k_col_out_v4, k_col_out: tiles, dword | byte frame I/O, any resize)
+// The kernels of a step share its arithmetic as device functions ("One text per step"): the filter pieces below,
+// pyrup_h4 / pyrup_v_even / pyrup_v_odd / pyr_up_rows_block (pyramid.h), norm_scale, out_scale, emit_px4.
 #include <cmath>
 #include <cstdlib>
 
@@ -61,24 +69,9 @@ __device__ __forceinline__ void block_minmax(float mn, float mx, int* gmn, int* 
         atomicMin(gmn + cell, fkey(s_mn[0])); atomicMax(gmx + cell, fkey(s_mx[0]));
     }
 }
-// Per-wave variant for kernels whose waves may belong to different frames: every wave folds its 64 values
-// through LDS (one barrier for the workgroup) and its first lane issues the two atomics into the output
-// range cells of frame `z`.
-__device__ __forceinline__ void block_minmax_waves(float mn, float mx, MinMax* mm, int z, bool active) {
-    __shared__ float s_mn[256], s_mx[256];
-    const int t = threadIdx.x;
-    s_mn[t] = mn; s_mx[t] = mx;
-    __syncthreads();
-    if ((t & 63) == 0 && active) {
-        float a = s_mn[t], b = s_mx[t];
-        for (int i = 1; i < 64; ++i) { a = s_mn[t + i] < a ? s_mn[t + i] : a; b = s_mx[t + i] > b ? s_mx[t + i] : b; }
-        const int cell = (int)((blockIdx.x * 4u + (unsigned)(t >> 6)) % kMMCells);
-        atomicMin(mm[z].mn2 + cell, fkey(a)); atomicMax(mm[z].mx2 + cell, fkey(b));
-    }
-}
-
-// Barrier-free variant: six ds_bpermute butterfly steps per extreme fold the wave (no LDS memory, no workgroup barrier at the
-// tail of every workgroup: the LDS scan above cost the min/max pass 10 of its 140 us per 32 frames), lane 0 issues the atomics.
+// Per-wave variant for kernels whose waves may belong to different frames: six ds_bpermute butterfly steps per extreme fold the wave
+// (no LDS memory, no workgroup barrier at the tail of every workgroup: an LDS scan cost the min/max pass 10 of its 140 us per 32
+// frames), lane 0 issues the two atomics into the output range cells of frame `z`.
 __device__ __forceinline__ void wave_minmax(float mn, float mx, MinMax* mm, int z, bool active) {
     const int lane = (int)(threadIdx.x & 63u);
 #pragma unroll
@@ -97,10 +90,11 @@ __device__ __forceinline__ void wave_minmax(float mn, float mx, MinMax* mm, int 
 // (time-contiguous per row, ring of `cap` slots) so that a wave reads one row's history as one
 // contiguous run.
 // grid (row blocks, streams, frames): frame f of the batch goes to ring slot (slot + f) mod cap
+__device__ __forceinline__ int ring_slot(int slot0, int t, int cap) { int s = slot0 + t; if (s >= cap) s -= cap; return s; }   // t <= cap
 __global__ __launch_bounds__(256) void k_col_append(const float* __restrict__ GL, float* __restrict__ win, int rows,
                                                     int rows_per_stream, int cap, int slot, MinMax* mm, int nstreams) {
     const int r = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y, f = blockIdx.z;
-    int sl = slot + f; if (sl >= cap) sl -= cap;
+    const int sl = ring_slot(slot, f, cap);
     if (r < rows) win[((size_t)b * rows_per_stream + r) * cap + sl] = GL[((size_t)f * nstreams + b) * rows + r];
     if (blockIdx.x == 0 && threadIdx.x < kMMCells) {
         MinMax& m = mm[f * nstreams + b];
@@ -126,6 +120,70 @@ constexpr int kDftMaxN = 1024;             // window lengths above this use k_co
 constexpr int kTwAllMax = 512;             // window lengths up to this get their twiddle tables built once for every warm-up length
 constexpr int kDftRows = 4;                // rows (waves) per workgroup
 struct DftEntry { short bin; short kind; };   // kind 0 = complex bin, 1 = DC, 2 = Nyquist
+
+// ---- the pieces of the filter, written once: the five kernels below differ in who owns which sum, not in the arithmetic ----
+// 0/1 mask of createIdealBandpassFilter at packed element x (TemporalFilter.cpp:70-77)
+__host__ __device__ __forceinline__ float dft_mask(int x, double fl, double fh) { return (x >= fl && x <= fh) ? 1.0f : 0.0f; }
+// mask pair of an entry: (ma, mb) of a complex bin's (Re, Im) elements, (ma, 0) of the DC / Nyquist element
+__host__ __device__ __forceinline__ void entry_mask(int bin, int kind, int n, double fl, double fh, float& ma, float& mb) {
+    ma = dft_mask(kind == 0 ? 2 * bin - 1 : (kind == 1 ? 0 : n - 1), fl, fh);
+    mb = kind == 0 ? dft_mask(2 * bin, fl, fh) : 0.f;
+}
+// the entry walk, in ascending bin order: emit(bin, kind, ma, mb) for the DC element, every complex bin whose mask pair is not all-zero, the
+// Nyquist element
+template <class Emit>
+__host__ __device__ __forceinline__ void for_each_entry(int n, double fl, double fh, Emit&& emit) {
+    float ma, mb;
+    entry_mask(0, 1, n, fl, fh, ma, mb);
+    if (ma != 0.f) emit(0, 1, ma, mb);
+    for (int k = 1; k <= (n - 1) / 2; ++k) {
+        entry_mask(k, 0, n, fl, fh, ma, mb);
+        if (ma != 0.f || mb != 0.f) emit(k, 0, ma, mb);
+    }
+    if (n % 2 == 0) {
+        entry_mask(n / 2, 2, n, fl, fh, ma, mb);
+        if (ma != 0.f) emit(n / 2, 2, ma, mb);
+    }
+}
+// thread 0 of a workgroup: the entry list into LDS (the wide-band kernels; the narrow-band ones get theirs, at most kThinBins, as an argument)
+__device__ __forceinline__ void build_entries(int n, double fl, double fh, DftEntry* s_ent, int* s_ne) {
+    int ne = 0;
+    for_each_entry(n, fl, fh, [&](int bin, int kind, float, float) { s_ent[ne].bin = (short)bin; s_ent[ne].kind = (short)kind; ++ne; });
+    *s_ne = ne;
+}
+// frame fr of a batch sees the window shifted by fr columns and has its own column 1 and min/max cells (grid: x, streams, frames)
+__device__ __forceinline__ void frame_view(int fr, int cap, int rows_per_stream, int& slot0, float* __restrict__& col1, MinMax*& mm) {
+    slot0 = ring_slot(slot0, fr, cap);
+    col1 += (size_t)fr * gridDim.y * rows_per_stream;
+    mm += fr * gridDim.y;
+}
+// twiddles into LDS (cos at [0, n), sin at [n, 2n)); the caller's barrier follows
+__device__ __forceinline__ void stage_twiddles(double* s_tw, const double* __restrict__ tw, int n) {
+    for (int i = threadIdx.x; i < 2 * n; i += 256) s_tw[i] = tw[i];
+}
+// the 1 / n of DFT_SCALE: x / 2^k == x * 2^-k exactly, so a power-of-two window skips the float64 division
+struct DftScale {
+    int n; bool pow2; double inv_n;
+    __device__ explicit DftScale(int n_) : n(n_), pow2((n_ & (n_ - 1)) == 0), inv_n(1.0 / (double)n_) {}
+    __device__ __forceinline__ double mul(double x) const { return x * inv_n; }
+    __device__ __forceinline__ double div(double x) const { return x / n; }
+    __device__ __forceinline__ double operator()(double x) const { return pow2 ? mul(x) : div(x); }
+};
+// mulSpectrums of the packed element pair (a, bq) with the packed mask
+__device__ __forceinline__ void mul_mask(float a, float bq, int kind, float ma, float mb, float& yre, float& yim) {
+    if (kind == 0) { yre = a * ma - bq * mb; yim = bq * ma + a * mb; }
+    else { yre = a * ma; yim = 0.f; }
+}
+// one complex bin's term of an inverse sum; c, s = cos, sin(2 pi bin t / n)
+__device__ __forceinline__ double inv_term(float yre, float yim, double c, double s) { return 2.0 * ((double)yre * c - (double)yim * s); }
+// what follows the inverse sum of sample t: the Nyquist term, the scale, the running min/max, column 1 (MagnifyCore.hpp:190-192)
+template <class Scale>
+__device__ __forceinline__ void inv_tail(double acc, int t, int n, float yny, const Scale& scale, float& vmin, float& vmax, float* col1_row) {
+    if (n % 2 == 0) acc += (t % 2 ? -1.0 : 1.0) * (double)yny;
+    const float v = (float)scale(acc);
+    vmin = v < vmin ? v : vmin; vmax = v > vmax ? v : vmax;
+    if (t == 1) *col1_row = v;
+}
 __global__ __launch_bounds__(256) void k_col_dft(const float* __restrict__ win, int slot0, int n, int cap,
                                                  int rows_per_stream, int live_per_stream, double fl, double fh,
                                                  const double* __restrict__ tw, float* __restrict__ col1, MinMax* mm) {
@@ -135,25 +193,15 @@ __global__ __launch_bounds__(256) void k_col_dft(const float* __restrict__ win, 
     __shared__ DftEntry s_ent[kDftMaxN / 2 + 2];
     __shared__ int s_ne;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int b = blockIdx.y, fr = blockIdx.z;              // stream, frame of the batch
-    slot0 += fr; if (slot0 >= cap) slot0 -= cap;            // frame fr sees the window shifted by fr columns
-    col1 += (size_t)fr * gridDim.y * rows_per_stream;
-    mm += fr * gridDim.y;
-    auto m = [&](int x) { return (x >= fl && x <= fh) ? 1.0f : 0.0f; };              // :70-77
-    for (int i = threadIdx.x; i < 2 * n; i += 256) s_tw[i] = tw[i];
-    if (threadIdx.x == 0) {
-        int ne = 0;
-        const int half = (n - 1) / 2;
-        if (m(0) != 0.f) { s_ent[ne].bin = 0; s_ent[ne].kind = 1; ++ne; }
-        for (int k = 1; k <= half; ++k)
-            if (m(2 * k - 1) != 0.f || m(2 * k) != 0.f) { s_ent[ne].bin = (short)k; s_ent[ne].kind = 0; ++ne; }
-        if (n % 2 == 0 && m(n - 1) != 0.f) { s_ent[ne].bin = (short)(n / 2); s_ent[ne].kind = 2; ++ne; }
-        s_ne = ne;
-    }
+    const int b = blockIdx.y;                               // stream; blockIdx.z = frame of the batch
+    frame_view(blockIdx.z, cap, rows_per_stream, slot0, col1, mm);
+    stage_twiddles(s_tw, tw, n);
+    if (threadIdx.x == 0) build_entries(n, fl, fh, s_ent, &s_ne);
     __syncthreads();
     const int ne = s_ne;
     const double* cs = s_tw;
     const double* sn = s_tw + n;
+    const DftScale scale(n);
     float vmin = INFINITY, vmax = -INFINITY;
     const int iters = (live_per_stream + gridDim.x * kDftRows - 1) / (gridDim.x * kDftRows);
     for (int it = 0; it < iters; ++it) {
@@ -162,7 +210,7 @@ __global__ __launch_bounds__(256) void k_col_dft(const float* __restrict__ win, 
         const size_t grow = (size_t)b * rows_per_stream + (live ? r : 0);
         if (live) {
             const float* wr = win + grow * cap;
-            for (int t = lane; t < n; t += 64) { int slot = slot0 + t; if (slot >= cap) slot -= cap; s_row[wv][t] = wr[slot]; }
+            for (int t = lane; t < n; t += 64) s_row[wv][t] = wr[ring_slot(slot0, t, cap)];
         }
         __syncthreads();
         if (live) {
@@ -176,15 +224,9 @@ __global__ __launch_bounds__(256) void k_col_dft(const float* __restrict__ win, 
                     ai += -v * sn[idx];
                     idx += k; if (idx >= n) idx -= n;
                 }
-                const float a = (float)(ar / n), bq = (float)(ai / n);
-                if (kind == 0) {
-                    const float ma = m(2 * k - 1), mb = m(2 * k);
-                    s_y[wv][2 * j] = a * ma - bq * mb;
-                    s_y[wv][2 * j + 1] = bq * ma + a * mb;
-                } else {
-                    s_y[wv][2 * j] = a * (kind == 1 ? m(0) : m(n - 1));
-                    s_y[wv][2 * j + 1] = 0.f;
-                }
+                float ma, mb;
+                entry_mask(k, kind, n, fl, fh, ma, mb);
+                mul_mask((float)scale(ar), (float)scale(ai), kind, ma, mb, s_y[wv][2 * j], s_y[wv][2 * j + 1]);
             }
         }
         __syncthreads();
@@ -192,17 +234,15 @@ __global__ __launch_bounds__(256) void k_col_dft(const float* __restrict__ win, 
             const bool has_dc = ne > 0 && s_ent[0].kind == 1;
             const bool has_ny = ne > 0 && s_ent[ne - 1].kind == 2;
             const int j0 = has_dc ? 1 : 0, j1 = has_ny ? ne - 1 : ne;
+            const float yny = has_ny ? s_y[wv][2 * (ne - 1)] : 0.f;
             for (int t = lane; t < n; t += 64) {                                      // idft, every sample
                 double acc = has_dc ? s_y[wv][0] : 0.f;
                 for (int j = j0; j < j1; ++j) {
                     const int k = s_ent[j].bin;
                     const int idx = (int)(((unsigned)k * (unsigned)t) % (unsigned)n);
-                    acc += 2.0 * ((double)s_y[wv][2 * j] * cs[idx] - (double)s_y[wv][2 * j + 1] * sn[idx]);
+                    acc += inv_term(s_y[wv][2 * j], s_y[wv][2 * j + 1], cs[idx], sn[idx]);
                 }
-                if (n % 2 == 0) acc += (t % 2 ? -1.0 : 1.0) * (double)(has_ny ? s_y[wv][2 * (ne - 1)] : 0.f);
-                const float v = (float)(acc / n);
-                vmin = v < vmin ? v : vmin; vmax = v > vmax ? v : vmax;
-                if (t == 1) col1[grow] = v;                                           // MagnifyCore.hpp:190-192
+                inv_tail(acc, t, n, yny, scale, vmin, vmax, col1 + grow);
             }
         }
         __syncthreads();
@@ -220,21 +260,18 @@ __global__ __launch_bounds__(256) void k_col_dft_thin(const float* __restrict__ 
                                                       int rows_per_stream, int live_per_stream,
                                                       const double* __restrict__ tw, float* __restrict__ col1, MinMax* mm,
                                                       ThinBins eb) {
-    const int r = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y, fr = blockIdx.z;
-    slot0 += fr; if (slot0 >= cap) slot0 -= cap;
-    col1 += (size_t)fr * gridDim.y * rows_per_stream;
-    mm += fr * gridDim.y;
+    const int r = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+    frame_view(blockIdx.z, cap, rows_per_stream, slot0, col1, mm);
     const bool live = r < live_per_stream;
     const size_t grow = (size_t)b * rows_per_stream + (live ? r : 0);
     // twiddles in LDS: the table index depends on the running bin phase, so a global (scalar) load per
     // sample would put its latency on every step of the serial sums
     __shared__ double s_tw[2 * kDftMaxN];
-    for (int i = threadIdx.x; i < 2 * n; i += 256) s_tw[i] = tw[i];
+    stage_twiddles(s_tw, tw, n);
     __syncthreads();
     const double* cs = s_tw;
     const double* sn = s_tw + n;
-    const bool pow2 = (n & (n - 1)) == 0;            // x / 2^k == x * 2^-k exactly: skip the float64 division
-    const double inv_n = 1.0 / (double)n;
+    const DftScale scale(n);
     float vmin = INFINITY, vmax = -INFINITY;
     if (live) {
         const float* wr = win + grow * cap;
@@ -245,11 +282,7 @@ __global__ __launch_bounds__(256) void k_col_dft_thin(const float* __restrict__ 
         constexpr int U = 8;                         // samples per batch; the next batch is in flight while this one is summed
         auto fetch = [&](int t0, float (&v)[U]) __attribute__((always_inline)) {
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                int slot = slot0 + (t0 + u < n ? t0 + u : n - 1);
-                if (slot >= cap) slot -= cap;
-                v[u] = wr[slot];
-            }
+            for (int u = 0; u < U; ++u) v[u] = wr[ring_slot(slot0, t0 + u < n ? t0 + u : n - 1, cap)];
         };
         float cur8[U], nxt8[U];
         fetch(0, cur8);
@@ -275,9 +308,7 @@ __global__ __launch_bounds__(256) void k_col_dft_thin(const float* __restrict__ 
         for (int j = 0; j < kThinBins; ++j) {                                         // mulSpectrums with the packed mask
             yre[j] = yim[j] = 0.f;
             if (j >= eb.ne) continue;
-            const float a = (float)(pow2 ? ar[j] * inv_n : ar[j] / n), bq = (float)(pow2 ? ai[j] * inv_n : ai[j] / n);
-            if (eb.kind[j] == 0) { yre[j] = a * eb.ma[j] - bq * eb.mb[j]; yim[j] = bq * eb.ma[j] + a * eb.mb[j]; }
-            else yre[j] = a * eb.ma[j];
+            mul_mask((float)scale(ar[j]), (float)scale(ai[j]), eb.kind[j], eb.ma[j], eb.mb[j], yre[j], yim[j]);
             idx[j] = 0;
         }
         const bool has_dc = eb.ne > 0 && eb.kind[0] == 1;
@@ -285,24 +316,21 @@ __global__ __launch_bounds__(256) void k_col_dft_thin(const float* __restrict__ 
         float yny = 0.f;
 #pragma unroll
         for (int j = 0; j < kThinBins; ++j) if (has_ny && j == eb.ne - 1) yny = yre[j];
-        auto idft = [&](auto scale) __attribute__((always_inline)) {                  // idft of every sample
+        auto idft = [&](auto sc) __attribute__((always_inline)) {                     // idft of every sample
             for (int t = 0; t < n; ++t) {
                 double acc = has_dc ? yre[0] : 0.f;
 #pragma unroll
                 for (int j = 0; j < kThinBins; ++j) {
                     if (j >= eb.ne) break;
                     if (eb.kind[j] != 0) continue;
-                    acc += 2.0 * ((double)yre[j] * cs[idx[j]] - (double)yim[j] * sn[idx[j]]);
+                    acc += inv_term(yre[j], yim[j], cs[idx[j]], sn[idx[j]]);
                     idx[j] += eb.bin[j]; if (idx[j] >= n) idx[j] -= n;
                 }
-                if (n % 2 == 0) acc += (t % 2 ? -1.0 : 1.0) * (double)yny;
-                const float v = (float)scale(acc);
-                vmin = v < vmin ? v : vmin; vmax = v > vmax ? v : vmax;
-                if (t == 1) col1[grow] = v;                                           // MagnifyCore.hpp:190-192
+                inv_tail(acc, t, n, yny, sc, vmin, vmax, col1 + grow);
             }
         };
-        if (pow2) idft([&](double x) { return x * inv_n; });                          // (uniform branch: no division in the loop)
-        else idft([&](double x) { return x / n; });
+        if (scale.pow2) idft([&](double x) { return scale.mul(x); });                 // (uniform branch: no division in the loop)
+        else idft([&](double x) { return scale.div(x); });
     }
     block_minmax(vmin, vmax, mm[b].mn1, mm[b].mx1);
 }
@@ -321,16 +349,14 @@ __global__ __launch_bounds__(256) void k_col_dft_thin8(const float* __restrict__
                                                        const double* __restrict__ tw, float* __restrict__ col1, MinMax* mm,
                                                        ThinBins eb) {
     const int sub = threadIdx.x & 7, lr = threadIdx.x >> 3;
-    const int r = blockIdx.x * kThin8Rows + lr, b = blockIdx.y, fr = blockIdx.z;
-    slot0 += fr; if (slot0 >= cap) slot0 -= cap;
-    col1 += (size_t)fr * gridDim.y * rows_per_stream;
-    mm += fr * gridDim.y;
+    const int r = blockIdx.x * kThin8Rows + lr, b = blockIdx.y;
+    frame_view(blockIdx.z, cap, rows_per_stream, slot0, col1, mm);
     const bool live = r < live_per_stream;
     const size_t grow = (size_t)b * rows_per_stream + (live ? r : 0);
     __shared__ double s_tw[2 * NMAX];
     __shared__ float s_row[kThin8Rows][NMAX + 1];
     __shared__ float s_sum[kThin8Rows][8];
-    for (int i = threadIdx.x; i < 2 * n; i += 256) s_tw[i] = tw[i];
+    stage_twiddles(s_tw, tw, n);
     {
         const float* wr = win + grow * cap;
         for (int t0 = 0; t0 < n; t0 += 64) {                       // eight loads in flight per lane (a rolled loop serialises the round trips)
@@ -338,8 +364,7 @@ __global__ __launch_bounds__(256) void k_col_dft_thin8(const float* __restrict__
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const int t = t0 + 8 * u + sub;
-                int slot = slot0 + (t < n ? t : n - 1); if (slot >= cap) slot -= cap;
-                v[u] = wr[slot];
+                v[u] = wr[ring_slot(slot0, t < n ? t : n - 1, cap)];
             }
 #pragma unroll
             for (int u = 0; u < 8; ++u) { const int t = t0 + 8 * u + sub; if (t < n) s_row[lr][t] = v[u]; }
@@ -348,8 +373,7 @@ __global__ __launch_bounds__(256) void k_col_dft_thin8(const float* __restrict__
     __syncthreads();
     const double* cs = s_tw;
     const double* sn = s_tw + n;
-    const bool pow2 = (n & (n - 1)) == 0;
-    const double inv_n = 1.0 / (double)n;
+    const DftScale scale(n);
     {   // forward: the 2 ne sums of the 32 rows on the first 64 ne threads -- ne whole waves run the n-step chains, the others wait at
         // the barrier without issuing (dft + the 1 / n of DFT_SCALE)
         const int nch = 2 * eb.ne;
@@ -372,7 +396,7 @@ __global__ __launch_bounds__(256) void k_col_dft_thin8(const float* __restrict__
 #pragma unroll
                 for (int u = 0; u < 8; ++u) if (t0 + u < n) acc += pr[u];
             }
-            s_sum[frow][ch] = (float)(pow2 ? acc * inv_n : acc / n);
+            s_sum[frow][ch] = (float)scale(acc);
         }
     }
     __syncthreads();
@@ -381,9 +405,7 @@ __global__ __launch_bounds__(256) void k_col_dft_thin8(const float* __restrict__
     for (int j = 0; j < kThin8Bins; ++j) {                                            // mulSpectrums with the packed mask
         yre[j] = yim[j] = 0.f;
         if (j >= eb.ne) continue;
-        const float a = s_sum[lr][2 * j], bq = s_sum[lr][2 * j + 1];
-        if (eb.kind[j] == 0) { yre[j] = a * eb.ma[j] - bq * eb.mb[j]; yim[j] = bq * eb.ma[j] + a * eb.mb[j]; }
-        else yre[j] = a * eb.ma[j];
+        mul_mask(s_sum[lr][2 * j], s_sum[lr][2 * j + 1], eb.kind[j], eb.ma[j], eb.mb[j], yre[j], yim[j]);
     }
     const bool has_dc = eb.ne > 0 && eb.kind[0] == 1;
     const bool has_ny = eb.ne > 0 && eb.kind[eb.ne - 1] == 2;
@@ -406,13 +428,10 @@ __global__ __launch_bounds__(256) void k_col_dft_thin8(const float* __restrict__
             for (int j = 0; j < kThin8Bins; ++j) {
                 if (j >= eb.ne) break;
                 if (eb.kind[j] != 0) continue;
-                acc += 2.0 * ((double)yre[j] * cs[idx[j]] - (double)yim[j] * sn[idx[j]]);
+                acc += inv_term(yre[j], yim[j], cs[idx[j]], sn[idx[j]]);
                 idx[j] += step[j]; if (idx[j] >= n) idx[j] -= n;
             }
-            if (n % 2 == 0) acc += (t % 2 ? -1.0 : 1.0) * (double)yny;
-            const float v = (float)(pow2 ? acc * inv_n : acc / n);
-            vmin = v < vmin ? v : vmin; vmax = v > vmax ? v : vmax;
-            if (t == 1) col1[grow] = v;                                               // MagnifyCore.hpp:190-192
+            inv_tail(acc, t, n, yny, scale, vmin, vmax, col1 + grow);
         }
     }
     block_minmax(vmin, vmax, mm[b].mn1, mm[b].mx1);
@@ -436,27 +455,15 @@ __global__ __launch_bounds__(256) void k_col_dft_long(const float* __restrict__ 
     __shared__ __attribute__((aligned(16))) float s_y[NMAX / 2 + 1][ROWS][2];
     __shared__ DftEntry s_ent[NMAX / 2 + 2];
     __shared__ int s_ne;
-    const int b = blockIdx.y, fr = blockIdx.z;              // stream, frame of the batch
-    slot0 += fr; if (slot0 >= cap) slot0 -= cap;            // frame fr sees the window shifted by fr columns
-    col1 += (size_t)fr * gridDim.y * rows_per_stream;
-    mm += fr * gridDim.y;
-    auto m = [&](int x) { return (x >= fl && x <= fh) ? 1.0f : 0.0f; };              // :70-77
-    for (int i = threadIdx.x; i < 2 * n; i += 256) s_tw[i] = tw[i];
-    if (threadIdx.x == 0) {
-        int ne = 0;
-        const int half = (n - 1) / 2;
-        if (m(0) != 0.f) { s_ent[ne].bin = 0; s_ent[ne].kind = 1; ++ne; }
-        for (int k = 1; k <= half; ++k)
-            if (m(2 * k - 1) != 0.f || m(2 * k) != 0.f) { s_ent[ne].bin = (short)k; s_ent[ne].kind = 0; ++ne; }
-        if (n % 2 == 0 && m(n - 1) != 0.f) { s_ent[ne].bin = (short)(n / 2); s_ent[ne].kind = 2; ++ne; }
-        s_ne = ne;
-    }
+    const int b = blockIdx.y;                               // stream; blockIdx.z = frame of the batch
+    frame_view(blockIdx.z, cap, rows_per_stream, slot0, col1, mm);
+    stage_twiddles(s_tw, tw, n);
+    if (threadIdx.x == 0) build_entries(n, fl, fh, s_ent, &s_ne);
     __syncthreads();
     const int ne = s_ne;
     const double* cs = s_tw;
     const double* sn = s_tw + n;
-    const bool pow2 = (n & (n - 1)) == 0;            // x / 2^k == x * 2^-k exactly: skip the float64 division
-    const double inv_n = 1.0 / (double)n;
+    const DftScale scale(n);
     const bool has_dc = ne > 0 && s_ent[0].kind == 1;
     const bool has_ny = ne > 0 && s_ent[ne - 1].kind == 2;
     const int j0 = has_dc ? 1 : 0, j1 = has_ny ? ne - 1 : ne;
@@ -468,7 +475,7 @@ __global__ __launch_bounds__(256) void k_col_dft_long(const float* __restrict__ 
         for (int rr = 0; rr < ROWS; ++rr) {                                           // rows past the last live one: zeros, results unused
             const bool live = r0 + rr < live_per_stream;
             const float* wr = win + ((size_t)b * rows_per_stream + (live ? r0 + rr : 0)) * cap;
-            for (int t = threadIdx.x; t < n; t += 256) { int slot = slot0 + t; if (slot >= cap) slot -= cap; s_row[t][rr] = live ? wr[slot] : 0.f; }
+            for (int t = threadIdx.x; t < n; t += 256) s_row[t][rr] = live ? wr[ring_slot(slot0, t, cap)] : 0.f;
         }
         __syncthreads();
         for (int j = threadIdx.x; j < ne; j += 256) {                                 // dft + mulSpectrums
@@ -487,18 +494,10 @@ __global__ __launch_bounds__(256) void k_col_dft_long(const float* __restrict__ 
                 }
                 idx += k; if (idx >= n) idx -= n;
             }
-            const float ma = kind == 0 ? m(2 * k - 1) : (kind == 1 ? m(0) : m(n - 1)), mb = kind == 0 ? m(2 * k) : 0.f;
+            float ma, mb;
+            entry_mask(k, kind, n, fl, fh, ma, mb);
 #pragma unroll
-            for (int rr = 0; rr < ROWS; ++rr) {
-                const float a = (float)(pow2 ? ar[rr] * inv_n : ar[rr] / n), bq = (float)(pow2 ? ai[rr] * inv_n : ai[rr] / n);
-                if (kind == 0) {
-                    s_y[j][rr][0] = a * ma - bq * mb;
-                    s_y[j][rr][1] = bq * ma + a * mb;
-                } else {
-                    s_y[j][rr][0] = a * ma;
-                    s_y[j][rr][1] = 0.f;
-                }
-            }
+            for (int rr = 0; rr < ROWS; ++rr) mul_mask((float)scale(ar[rr]), (float)scale(ai[rr]), kind, ma, mb, s_y[j][rr][0], s_y[j][rr][1]);
         }
         __syncthreads();
         for (int t = threadIdx.x; t < n; t += 256) {                                  // idft, every sample
@@ -513,17 +512,12 @@ __global__ __launch_bounds__(256) void k_col_dft_long(const float* __restrict__ 
                 prev = k;
                 const double c = cs[idx], s = sn[idx];
 #pragma unroll
-                for (int rr = 0; rr < ROWS; ++rr) acc[rr] += 2.0 * ((double)s_y[j][rr][0] * c - (double)s_y[j][rr][1] * s);
+                for (int rr = 0; rr < ROWS; ++rr) acc[rr] += inv_term(s_y[j][rr][0], s_y[j][rr][1], c, s);
             }
 #pragma unroll
-            for (int rr = 0; rr < ROWS; ++rr) {
-                if (n % 2 == 0) acc[rr] += (t % 2 ? -1.0 : 1.0) * (double)(has_ny ? s_y[ne - 1][rr][0] : 0.f);
-                if (r0 + rr < live_per_stream) {
-                    const float v = (float)(pow2 ? acc[rr] * inv_n : acc[rr] / n);
-                    vmin = v < vmin ? v : vmin; vmax = v > vmax ? v : vmax;
-                    if (t == 1) col1[(size_t)b * rows_per_stream + r0 + rr] = v;     // MagnifyCore.hpp:190-192
-                }
-            }
+            for (int rr = 0; rr < ROWS; ++rr)
+                if (r0 + rr < live_per_stream)
+                    inv_tail(acc[rr], t, n, has_ny ? s_y[ne - 1][rr][0] : 0.f, scale, vmin, vmax, col1 + (size_t)b * rows_per_stream + r0 + rr);
         }
         __syncthreads();
     }
@@ -540,8 +534,7 @@ __global__ __launch_bounds__(256) void k_col_dft_serial(const float* __restrict_
     const size_t grow = (size_t)b * rows_per_stream + (live ? r : 0);
     const double* cs = tw;
     const double* sn = tw + n;
-    const int half = (n - 1) / 2;
-    auto m = [&](int x) { return (x >= fl && x <= fh) ? 1.0f : 0.0f; };
+    const DftScale scale(n);
     float vmin = INFINITY, vmax = -INFINITY;
     if (live) {
         const float* wr = win + grow * cap;
@@ -553,96 +546,68 @@ __global__ __launch_bounds__(256) void k_col_dft_serial(const float* __restrict_
                 const double v = (double)wr[slot];
                 acc += im ? -v * sn[idx] : v * cs[idx];
                 idx += bin; if (idx >= n) idx -= n;
-                if (++slot >= cap) slot -= cap;
+                slot = ring_slot(slot, 1, cap);
             }
-            return (float)(acc / n);
+            return (float)scale(acc);
         };
-        const float m0 = m(0);
-        const float y0 = m0 != 0.f ? dot(0, false) * m0 : 0.f;
-        for (int k = 1; k <= half; ++k) {
-            const float ma = m(2 * k - 1), mb = m(2 * k);
-            if (ma == 0.f && mb == 0.f) continue;
-            const float a = dot(k, false), bq = dot(k, true);
-            Yr[2 * k - 1] = a * ma - bq * mb;
-            Yr[2 * k] = bq * ma + a * mb;
-        }
-        float yl = 0.f;
-        const float ml = (n % 2 == 0) ? m(n - 1) : 0.f;
-        if (ml != 0.f) yl = dot(n / 2, false) * ml;
+        float y0 = 0.f, yl = 0.f, unused;                                            // DC and Nyquist elements; the complex bins go to Y
+        for_each_entry(n, fl, fh, [&](int k, int kind, float ma, float mb) {
+            if (kind == 0) mul_mask(dot(k, false), dot(k, true), kind, ma, mb, Yr[2 * k - 1], Yr[2 * k]);
+            else mul_mask(dot(k, false), 0.f, kind, ma, mb, kind == 1 ? y0 : yl, unused);
+        });
         for (int t = 0; t < n; ++t) {
             double acc = y0;
-            for (int k = 1; k <= half; ++k) {
-                if (m(2 * k - 1) == 0.f && m(2 * k) == 0.f) continue;
+            for_each_entry(n, fl, fh, [&](int k, int kind, float, float) {
+                if (kind != 0) return;
                 const int idx = (int)(((unsigned long long)k * (unsigned long long)t) % (unsigned long long)n);
-                acc += 2.0 * ((double)Yr[2 * k - 1] * cs[idx] - (double)Yr[2 * k] * sn[idx]);
-            }
-            if (n % 2 == 0) acc += (t % 2 ? -1.0 : 1.0) * (double)yl;
-            const float v = (float)(acc / n);
-            vmin = v < vmin ? v : vmin; vmax = v > vmax ? v : vmax;
-            if (t == 1) col1[grow] = v;
+                acc += inv_term(Yr[2 * k - 1], Yr[2 * k], cs[idx], sn[idx]);
+            });
+            inv_tail(acc, t, n, yl, scale, vmin, vmax, col1 + grow);
         }
     }
     block_minmax(vmin, vmax, mm[b].mn1, mm[b].mx1);
 }
 
-// normalize(0, 1, NORM_MINMAX) (TemporalFilter.cpp:55) of column 1, x amplification (MagnifyCore.hpp:185)
+// x -> x * sc + sh of the two min-max rescalings, from the folded cells of a frame:
+// normalize(0, 1, NORM_MINMAX) of the filtered window (TemporalFilter.cpp:55) ...
+struct ScaleShift { float sc, sh; };
+__device__ __forceinline__ ScaleShift norm_scale(const MinMax& m) {
+    const double mn = (double)mm_min(m.mn1), mx = (double)mm_max(m.mx1);
+    const double scale = (mx - mn > 2.220446049250313e-16) ? 1. / (mx - mn) : 0.;
+    const double shift = 0. - mn * scale;
+    return {(float)scale, (float)shift};
+}
+// ... and convertTo(CV_8U, 255/(max-min), -min*255/(max-min)) of the output (MagnifyCore.hpp:202)
+__device__ __forceinline__ ScaleShift out_scale(const MinMax& m) {
+    const double mn = (double)mm_min(m.mn2), mx = (double)mm_max(m.mx2);
+    return {(float)(255.0 / (mx - mn)), (float)(-mn * 255.0 / (mx - mn))};
+}
+
+// normalize(0, 1, NORM_MINMAX) of column 1, x amplification (MagnifyCore.hpp:185)
 // grid (row blocks, streams * frames)
 __global__ __launch_bounds__(256) void k_col_norm(const float* __restrict__ col1, float* __restrict__ up0, int rows,
                                                   int rows_per_stream, const MinMax* mm, float amp) {
     const int r = blockIdx.x * 256 + threadIdx.x, z = blockIdx.y;
     if (r >= rows) return;
     col1 += (size_t)z * rows_per_stream; up0 += (size_t)z * rows;
-    const double mn = (double)mm_min(mm[z].mn1), mx = (double)mm_max(mm[z].mx1);
-    const double scale = (mx - mn > 2.220446049250313e-16) ? 1. / (mx - mn) : 0.;
-    const double shift = 0. - mn * scale;
-    const float fs = (float)scale, fsh = (float)shift;
-    up0[r] = (col1[r] * fs + fsh) * amp;
+    const ScaleShift ns = norm_scale(mm[z]);
+    up0[r] = (col1[r] * ns.sc + ns.sh) * amp;
 }
 
-// k_col_norm and the FIRST pyrUp of the up chain in one launch: k_pyr_up_rows' blocks of 4 x 2 outputs (pyramid.h) whose source values
-// are normalised on the fly -- (col1 * fs + fsh) * amp, the same three operations per value -- instead of read from a normalised copy.
-// One dependent launch less per batch (6 us of launch + latency for 49 k values); plane = (frame * streams + stream) * C + channel.
+// k_col_norm and the FIRST pyrUp of the up chain in one launch: k_pyr_up_rows' blocks of 4 x 2 outputs (pyr_up_rows_block, pyramid.h) whose
+// source values are normalised on the fly -- (col1 * fs + fsh) * amp, the same three operations per value -- instead of read from a normalised
+// copy.  One dependent launch less per batch (6 us of launch + latency for 49 k values); plane = (frame * streams + stream) * C + channel.
 __global__ __launch_bounds__(256) void k_pyr_up_rows_norm(const float* __restrict__ col1, int rows_per_stream, int C, int sw, int sh,
                                                           float* __restrict__ dst, int ngroups, const MinMax* mm, float amp) {
     __shared__ float s_sc[2];
     const int plane = blockIdx.y, z = plane / C, ch = plane - z * C;
-    if (threadIdx.x == 0) {
-        const double mn = (double)mm_min(mm[z].mn1), mx = (double)mm_max(mm[z].mx1);
-        const double scale = (mx - mn > 2.220446049250313e-16) ? 1. / (mx - mn) : 0.;
-        const double shift = 0. - mn * scale;
-        s_sc[0] = (float)scale; s_sc[1] = (float)shift;
-    }
+    if (threadIdx.x == 0) { const ScaleShift ns = norm_scale(mm[z]); s_sc[0] = ns.sc; s_sc[1] = ns.sh; }
     __syncthreads();
     const int gi = blockIdx.x * 256 + threadIdx.x;
     if (gi >= ngroups) return;
     const float fs = s_sc[0], fsh = s_sc[1];
-    const int dw = 2 * sw, gw = dw >> 2;
-    const int j = gi / gw, gx = (gi - j * gw) * 4;
-    const float* sp = col1 + (size_t)z * rows_per_stream + (size_t)ch * sw * sh;
-    float* dp = dst + (size_t)plane * (size_t)dw * (2 * sh);
-    const int i0 = gx >> 1;
-    const int cm1 = i0 > 0 ? i0 - 1 : 0, cp1 = i0 + 1 < sw ? i0 + 1 : sw - 1, cp2 = i0 + 2 < sw ? i0 + 2 : sw - 1;
-    const bool f0 = i0 == 0, l0 = i0 == sw - 1, l1 = i0 + 1 == sw - 1;
-    float h[3][4];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        int sy = j - 1 + q; sy = sy < 0 ? 1 : (sy >= sh ? sh - 1 : sy);
-        const float* r = sp + (size_t)sy * sw;
-        const float sm1 = (r[cm1] * fs + fsh) * amp, s0 = (r[i0] * fs + fsh) * amp, s1 = (r[cp1] * fs + fsh) * amp, s2 = (r[cp2] * fs + fsh) * amp;
-        h[q][0] = sel(f0, s0 * 6.f + s1 * 2.f, sel(l0, sm1 + s0 * 7.f, sm1 + s0 * 6.f + s1));
-        h[q][1] = sel(l0, s0 * 8.f, (s0 + s1) * 4.f);
-        h[q][2] = sel(l1, s0 + s1 * 7.f, s0 + s1 * 6.f + s2);
-        h[q][3] = sel(l1, s1 * 8.f, (s1 + s2) * 4.f);
-    }
-    float e[4], o[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        e[k] = (h[0][k] + h[1][k] * 6.f + h[2][k]) * (1.f / 64.f);
-        o[k] = ((h[1][k] + h[2][k]) * 4.f) * (1.f / 64.f);
-    }
-    float* d0 = dp + (size_t)(2 * j) * dw + gx;
-    *reinterpret_cast<float4*>(d0) = make_float4(e[0], e[1], e[2], e[3]);
-    *reinterpret_cast<float4*>(d0 + dw) = make_float4(o[0], o[1], o[2], o[3]);
+    pyr_up_rows_block(gi, col1 + (size_t)z * rows_per_stream + (size_t)ch * sw * sh, sw, sh, dst + (size_t)plane * (size_t)(2 * sw) * (2 * sh),
+                      [&](const float* p) { return (*p * fs + fsh) * amp; });
 }
 
 // ---- last pyrUp + resize(INTER_LINEAR) + input add (SpatialFilter.cpp:45-48, MagnifyCore.hpp:197-203)
@@ -704,8 +669,7 @@ __global__ __launch_bounds__(256) void k_col_out(OutArgs a) {
         for (int i = threadIdx.x; i < nuy * nux; i += 256) {
             const int y = i / nux, x = i - y * nux;
             const int gy = uy0 + y, lj = (gy >> 1) - vy0;
-            su[y][x] = ((gy & 1) == 0) ? (hv[lj - 1][x] + hv[lj][x] * 6.f + hv[lj + 1][x]) * (1.f / 64.f)
-                                       : ((hv[lj][x] + hv[lj + 1][x]) * 4.f) * (1.f / 64.f);
+            su[y][x] = ((gy & 1) == 0) ? pyrup_v_even(hv[lj - 1][x], hv[lj][x], hv[lj + 1][x]) : pyrup_v_odd(hv[lj][x], hv[lj + 1][x]);
         }
         __syncthreads();
 #pragma unroll
@@ -727,12 +691,7 @@ __global__ __launch_bounds__(256) void k_col_out(OutArgs a) {
         }
     }
     float vmin = INFINITY, vmax = -INFINITY;
-    double mn = 0, mx = 0;
-    float osc = 0.f, osh = 0.f;
-    if (WRITE) {   // convertTo(CV_8U, 255/(max-min), -min*255/(max-min)) (MagnifyCore.hpp:202)
-        mn = (double)mm_min(a.mm[b].mn2); mx = (double)mm_max(a.mm[b].mx2);
-        osc = (float)(255.0 / (mx - mn)); osh = (float)(-mn * 255.0 / (mx - mn));
-    }
+    const ScaleShift os = WRITE ? out_scale(a.mm[b]) : ScaleShift{0.f, 0.f};
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int i = threadIdx.x + k * 256;
@@ -744,7 +703,7 @@ __global__ __launch_bounds__(256) void k_col_out(OutArgs a) {
         for (int c = 0; c < C; ++c) {
             const float o = (float)p[c] * 1.0f + val[k][c];                 // :169 (unscaled input), :197
             if (WRITE) {
-                a.out[(size_t)b * a.out_sstride + (size_t)gy * a.out_stride + (size_t)gx * C + c] = sat_u8(o * osc + osh);
+                a.out[(size_t)b * a.out_sstride + (size_t)gy * a.out_stride + (size_t)gx * C + c] = sat_u8(o * os.sc + os.sh);
                 if (a.dbg && b == 0) a.dbg[((size_t)gy * a.w + gx) * C + c] = o;
             } else {
                 vmin = o < vmin ? o : vmin; vmax = o > vmax ? o : vmax;
@@ -752,6 +711,28 @@ __global__ __launch_bounds__(256) void k_col_out(OutArgs a) {
         }
     }
     if (!WRITE) block_minmax(vmin, vmax, a.mm[b].mn2, a.mm[b].mx2);
+}
+
+// Tail of the two vectorised kernels below: a lane's 4 pixels of output row gy from column gx on -- the unscaled input (:169) + the up chain's
+// values (:197), then the output range (WRITE = false) or the rescaled bytes, quantised by the caller's quant(12 floats) -> Px4, and with DBG
+// the float frame of stream 0.
+template <bool WRITE, bool DBG, class Quant>
+__device__ __forceinline__ void emit_px4(const OutArgs& a, int b, int gx, int gy, const Px4 pin, const float (&val)[3][4], const ScaleShift os,
+                                         uint8_t* out_px, float& vmin, float& vmax, Quant&& quant) {
+    int Bv[4], Gv[4], Rv[4];
+    unpack_px4(pin, Bv, Gv, Rv);
+    float ov[12];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float o0 = (float)Bv[k] * 1.0f + val[0][k], o1 = (float)Gv[k] * 1.0f + val[1][k], o2 = (float)Rv[k] * 1.0f + val[2][k];
+        if (WRITE) {
+            ov[3 * k] = o0 * os.sc + os.sh; ov[3 * k + 1] = o1 * os.sc + os.sh; ov[3 * k + 2] = o2 * os.sc + os.sh;
+            if (DBG && a.dbg && b == 0) { float* d = a.dbg + ((size_t)gy * a.w + gx + k) * 3; d[0] = o0; d[1] = o1; d[2] = o2; }
+        } else {
+            vmin = fminf(vmin, fminf(o0, fminf(o1, o2))); vmax = fmaxf(vmax, fmaxf(o0, fmaxf(o1, o2)));
+        }
+    }
+    if (WRITE) *reinterpret_cast<Px4*>(out_px) = quant(ov);
 }
 
 // Vectorised variant for the common geometry: 3 channels, dword-aligned 4-pixel groups and a width
@@ -779,12 +760,7 @@ __global__ __launch_bounds__(256) void k_col_out_v4(OutArgs a) {
             int gy = vy0 + ly; gy = gy < 0 ? 1 : (gy >= a.vh ? a.vh - 1 : gy);
             const float* row = a.V + ((size_t)b * 3 + c) * ((size_t)a.vw * a.vh) + (size_t)gy * a.vw;
             const int i0 = gx0 >> 1;
-            const float sm1 = row[i0 > 0 ? i0 - 1 : 0], s0 = row[i0], s1 = row[i0 + 1 < a.vw ? i0 + 1 : a.vw - 1],
-                        s2 = row[i0 + 2 < a.vw ? i0 + 2 : a.vw - 1];
-            o.x = (i0 == 0) ? s0 * 6.f + s1 * 2.f : ((i0 == a.vw - 1) ? sm1 + s0 * 7.f : sm1 + s0 * 6.f + s1);
-            o.y = (i0 == a.vw - 1) ? s0 * 8.f : (s0 + s1) * 4.f;
-            o.z = (i0 + 1 == a.vw - 1) ? s0 + s1 * 7.f : s0 + s1 * 6.f + s2;
-            o.w = (i0 + 1 == a.vw - 1) ? s1 * 8.f : (s1 + s2) * 4.f;
+            o = pyrup_h4(row[i0 > 0 ? i0 - 1 : 0], row[i0], row[i0 + 1 < a.vw ? i0 + 1 : a.vw - 1], row[i0 + 2 < a.vw ? i0 + 2 : a.vw - 1], i0, a.vw);
         }
         *reinterpret_cast<float4*>(&hv[c][ly][4 * g]) = o;
     }
@@ -800,15 +776,7 @@ __global__ __launch_bounds__(256) void k_col_out_v4(OutArgs a) {
             const float4 r0 = *reinterpret_cast<const float4*>(&hv[c][lj - 1][4 * xg]);
             const float4 r1 = *reinterpret_cast<const float4*>(&hv[c][lj][4 * xg]);
             const float4 r2 = *reinterpret_cast<const float4*>(&hv[c][lj + 1][4 * xg]);
-            float4 u;
-            if ((uy & 1) == 0) {
-                u.x = (r0.x + r1.x * 6.f + r2.x) * (1.f / 64.f); u.y = (r0.y + r1.y * 6.f + r2.y) * (1.f / 64.f);
-                u.z = (r0.z + r1.z * 6.f + r2.z) * (1.f / 64.f); u.w = (r0.w + r1.w * 6.f + r2.w) * (1.f / 64.f);
-            } else {
-                u.x = ((r1.x + r2.x) * 4.f) * (1.f / 64.f); u.y = ((r1.y + r2.y) * 4.f) * (1.f / 64.f);
-                u.z = ((r1.z + r2.z) * 4.f) * (1.f / 64.f); u.w = ((r1.w + r2.w) * 4.f) * (1.f / 64.f);
-            }
-            return u;
+            return (uy & 1) == 0 ? pyrup_v_even(r0, r1, r2) : pyrup_v_odd(r1, r2);
         };
         float val[3][4];
 #pragma unroll
@@ -819,31 +787,17 @@ __global__ __launch_bounds__(256) void k_col_out_v4(OutArgs a) {
             val[c][2] = u0.z * b0 + u1.z * b1; val[c][3] = u0.w * b0 + u1.w * b1;
         }
         const Px4 pin = *reinterpret_cast<const Px4*>(a.in + (size_t)b * a.in_sstride + (size_t)gy * a.in_stride + (size_t)gx * 3);
-        int Bv[4], Gv[4], Rv[4];
-        unpack_px4(pin, Bv, Gv, Rv);
-        float osc = 0.f, osh = 0.f;
-        if (WRITE) {   // convertTo(CV_8U, 255/(max-min), -min*255/(max-min)) (MagnifyCore.hpp:202)
-            const double mn = (double)mm_min(a.mm[b].mn2), mx = (double)mm_max(a.mm[b].mx2);
-            osc = (float)(255.0 / (mx - mn)); osh = (float)(-mn * 255.0 / (mx - mn));
-        }
-        uint32_t ob[12];
+        emit_px4<WRITE, true>(a, b, gx, gy, pin, val, WRITE ? out_scale(a.mm[b]) : ScaleShift{0.f, 0.f},
+                              a.out + (size_t)b * a.out_sstride + (size_t)gy * a.out_stride + (size_t)gx * 3, vmin, vmax, [](const float (&ov)[12]) {
+            uint32_t ob[12];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float o0 = (float)Bv[k] * 1.0f + val[0][k], o1 = (float)Gv[k] * 1.0f + val[1][k], o2 = (float)Rv[k] * 1.0f + val[2][k];
-            if (WRITE) {
-                ob[3 * k] = sat_u8(o0 * osc + osh); ob[3 * k + 1] = sat_u8(o1 * osc + osh); ob[3 * k + 2] = sat_u8(o2 * osc + osh);
-                if (a.dbg && b == 0) { float* d = a.dbg + ((size_t)gy * a.w + gx + k) * 3; d[0] = o0; d[1] = o1; d[2] = o2; }
-            } else {
-                vmin = fminf(vmin, fminf(o0, fminf(o1, o2))); vmax = fmaxf(vmax, fmaxf(o0, fmaxf(o1, o2)));
-            }
-        }
-        if (WRITE) {
+            for (int k = 0; k < 12; ++k) ob[k] = sat_u8(ov[k]);
             Px4 q;
             q.a = ob[0] | (ob[1] << 8) | (ob[2] << 16) | (ob[3] << 24);
             q.b = ob[4] | (ob[5] << 8) | (ob[6] << 16) | (ob[7] << 24);
             q.c = ob[8] | (ob[9] << 8) | (ob[10] << 16) | (ob[11] << 24);
-            *reinterpret_cast<Px4*>(a.out + (size_t)b * a.out_sstride + (size_t)gy * a.out_stride + (size_t)gx * 3) = q;
-        }
+            return q;
+        });
     }
     if (!WRITE) block_minmax(vmin, vmax, a.mm[b].mn2, a.mm[b].mx2);
 }
@@ -853,8 +807,7 @@ __global__ __launch_bounds__(256) void k_col_out_v4(OutArgs a) {
 // pyrUp rows sy0 = yofs[gy] and sy0 + 1, and those two rows need exactly three consecutive rows of the
 // horizontal pass of V starting at js = (sy0 - 1) >> 1: the lane computes that horizontal pass straight
 // from global memory and keeps the three rows in registers, advancing the window as js grows (js and
-// the row parity are uniform across the wave: no divergence, no LDS, no barrier until the final
-// min/max reduction of the workgroup).
+// the row parity are uniform across the wave: no divergence, no LDS, no barrier).
 struct HRow3 { float4 c[3]; };
 template <bool WRITE, bool DBG>     // DBG: also store the float frame (compile time: no per-pixel branch in the production kernel)
 __global__ __launch_bounds__(256) void k_col_out_rows(OutArgs a, int strips_x, int strips_y, int ntasks, int rows) {
@@ -884,21 +837,12 @@ __global__ __launch_bounds__(256) void k_col_out_rows(OutArgs a, int strips_x, i
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
                     const char* rc = row + c * pstride * sizeof(float);
-                    const float sm1 = *reinterpret_cast<const float*>(rc + cm1), s0 = *reinterpret_cast<const float*>(rc + c00),
-                                s1 = *reinterpret_cast<const float*>(rc + cp1), s2 = *reinterpret_cast<const float*>(rc + cp2);
-                    const bool f0 = i0 == 0, l0 = i0 == a.vw - 1, l1 = i0 + 1 == a.vw - 1;
-                    o.c[c].x = sel(f0, s0 * 6.f + s1 * 2.f, sel(l0, sm1 + s0 * 7.f, sm1 + s0 * 6.f + s1));
-                    o.c[c].y = sel(l0, s0 * 8.f, (s0 + s1) * 4.f);
-                    o.c[c].z = sel(l1, s0 + s1 * 7.f, s0 + s1 * 6.f + s2);
-                    o.c[c].w = sel(l1, s1 * 8.f, (s1 + s2) * 4.f);
+                    o.c[c] = pyrup_h4(*reinterpret_cast<const float*>(rc + cm1), *reinterpret_cast<const float*>(rc + c00),
+                                      *reinterpret_cast<const float*>(rc + cp1), *reinterpret_cast<const float*>(rc + cp2), i0, a.vw);
                 }
                 return o;
             };
-            float osc = 0.f, osh = 0.f;
-            if (WRITE) {   // convertTo(CV_8U, 255/(max-min), -min*255/(max-min)) (MagnifyCore.hpp:202)
-                const double mn = (double)mm_min(a.mm[b].mn2), mx = (double)mm_max(a.mm[b].mx2);
-                osc = (float)(255.0 / (mx - mn)); osh = (float)(-mn * 255.0 / (mx - mn));
-            }
+            const ScaleShift os = WRITE ? out_scale(a.mm[b]) : ScaleShift{0.f, 0.f};
             const int yend = y0 + rows < a.h ? y0 + rows : a.h;
             int js = (a.yofs[y0] - 1) >> 1;
             HRow3 A = hrow(js), B = hrow(js + 1), C = hrow(js + 2);
@@ -921,43 +865,27 @@ __global__ __launch_bounds__(256) void k_col_out_rows(OutArgs a, int strips_x, i
                     for (int k = 0; k < 4; ++k) {
                         float u0, u1;
                         if ((sy0 & 1) == 0) {             // rows 2j (window j-1, j, j+1) and 2j+1 (j, j+1)
-                            u0 = (pa[k] + pb[k] * 6.f + pc[k]) * (1.f / 64.f);
-                            u1 = ((pb[k] + pc[k]) * 4.f) * (1.f / 64.f);
+                            u0 = pyrup_v_even(pa[k], pb[k], pc[k]);
+                            u1 = pyrup_v_odd(pb[k], pc[k]);
                         } else {                          // rows 2j+1 (window j, j+1) and 2j+2 (j, j+1, j+2)
-                            u0 = ((pa[k] + pb[k]) * 4.f) * (1.f / 64.f);
-                            u1 = (pa[k] + pb[k] * 6.f + pc[k]) * (1.f / 64.f);
+                            u0 = pyrup_v_odd(pa[k], pb[k]);
+                            u1 = pyrup_v_even(pa[k], pb[k], pc[k]);
                         }
                         if (clamp1) u1 = u0;
                         // resize INTER_LINEAR: horizontal taps are (1, 0) here; vertical D = S0*b0 + S1*b1
                         val[c][k] = u0 * b0 + u1 * b1;
                     }
                 }
-                int Bv[4], Gv[4], Rv[4];
-                unpack_px4(pin, Bv, Gv, Rv);
-                float ov[12];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float o0 = (float)Bv[k] * 1.0f + val[0][k], o1 = (float)Gv[k] * 1.0f + val[1][k], o2 = (float)Rv[k] * 1.0f + val[2][k];
-                    if (WRITE) {
-                        ov[3 * k] = o0 * osc + osh; ov[3 * k + 1] = o1 * osc + osh; ov[3 * k + 2] = o2 * osc + osh;
-                        if (DBG && a.dbg && b == 0) { float* d = a.dbg + ((size_t)gy * a.w + gx + k) * 3; d[0] = o0; d[1] = o1; d[2] = o2; }
-                    } else {
-                        vmin = fminf(vmin, fminf(o0, fminf(o1, o2))); vmax = fmaxf(vmax, fmaxf(o0, fmaxf(o1, o2)));
-                    }
-                }
-                if (WRITE) {
+                emit_px4<WRITE, DBG>(a, b, gx, gy, pin, val, os, dst + (size_t)gy * a.out_stride + xoff, vmin, vmax, [](const float (&ov)[12]) {
                     Px4 q;
                     q.a = pack_u8x4(ov[0], ov[1], ov[2], ov[3]); q.b = pack_u8x4(ov[4], ov[5], ov[6], ov[7]); q.c = pack_u8x4(ov[8], ov[9], ov[10], ov[11]);
-                    *reinterpret_cast<Px4*>(dst + (size_t)gy * a.out_stride + xoff) = q;
-                }
+                    return q;
+                });
             }
         }
     }
-    if (!WRITE) {
-        // all four waves of a workgroup belong to the same frame when strips_x * strips_y is a multiple of 4 or
-        // the workgroup does not straddle a frame boundary; otherwise reduce per wave into that wave's frame
-        block_minmax_waves(vmin, vmax, a.mm, b, task < ntasks);
-    }
+    // the waves of a workgroup may belong to different frames: every wave reduces into its own frame's cells
+    if (!WRITE) wave_minmax(vmin, vmax, a.mm, b, task < ntasks);
 }
 
 // ---- strip output kernels, second form (round 3): both pyrUps inside, packed FP32, loads a whole iteration ahead -------------
@@ -1100,11 +1028,8 @@ __device__ __forceinline__ void col_out_strip(const OutArgs& a, int b, int tx, i
         jcur = jj;
         return hrow(vy);
     };
-    float osc = 0.f, osh = 0.f;
-    if (WRITE) {   // convertTo(CV_8U, 255/(max-min), -min*255/(max-min)) (MagnifyCore.hpp:202)
-        const double mn = (double)mm_min(a.mm[b].mn2), mx = (double)mm_max(a.mm[b].mx2);
-        osc = (float)(255.0 / (mx - mn)); osh = (float)(-mn * 255.0 / (mx - mn));
-    }
+    const ScaleShift os = WRITE ? out_scale(a.mm[b]) : ScaleShift{0.f, 0.f};
+    const float osc = os.sc, osh = os.sh;
     const int yend = y0 + rows < a.h ? y0 + rows : a.h;
     int js = (yofs[y0] - 1) >> 1;
     const int jlast = (yofs[yend - 1] - 1) >> 1;
@@ -1408,10 +1333,10 @@ static void col_down(Ctx* c, ColorState* st, const FrameIO& io, const ColBufs& B
         q.G2 = B.G[2]; q.w2 = st->g[2].w; q.h2 = st->g[2].h; q.h1 = st->g[1].h;
         q.strips_x = (st->g[2].w + D01_OUT - 1) / D01_OUT; q.rows = d01_rows; q.strips_y = (st->g[2].h + d01_rows - 1) / d01_rows;
         q.ntasks = (int)d01_tasks;
-        LVM_LAUNCH(c, "col_down01", k_down01_rows<1>, dim3((unsigned)((d01_tasks + D01_THREADS / 64 - 1) / (D01_THREADS / 64))), dim3(D01_THREADS), s, q);
+        LVM_LAUNCH(c, "col_down01", k_down01_rows<1>, strip_grid(d01_tasks, D01_THREADS), dim3(D01_THREADS), s, q);
         l = 2;
     } else if (vec4 && st->d0_rows_on && d0_tasks > 0) {   // wave strips with DPP halo exchange (pyramid.h)
-        const dim3 gridr((unsigned)((d0_tasks + D0R_THREADS / 64 - 1) / (D0R_THREADS / 64)));
+        const dim3 gridr = strip_grid(d0_tasks, D0R_THREADS);
         LVM_LAUNCH_V(c, "col_down0", "strips", (k_down0_rows<false, FL_LUT_EXACT>), gridr, dim3(D0R_THREADS), s, io.d_in, (long)io.in_stride, (long)io.in_sstride,
                    w, h, B.G[1], g1.w, g1.h, c->lab, d0_sx, (g1.h + d0_rows - 1) / d0_rows, (int)d0_tasks, d0_rows, LabPlanes{nullptr, nullptr});
     } else if (vec4) {
@@ -1430,7 +1355,7 @@ static void col_down(Ctx* c, ColorState* st, const FrameIO& io, const ColBufs& B
             while (rows > 4 && (long)sx * ((b.h + rows - 1) / rows) * planes < 8192) rows >>= 1;
             const int sy = (b.h + rows - 1) / rows;
             const long ntasks = (long)sx * sy * planes;
-            const dim3 grid((unsigned)((ntasks + PD_THREADS / 64 - 1) / (PD_THREADS / 64)));
+            const dim3 grid = strip_grid(ntasks, PD_THREADS);
             LVM_LAUNCH(c, LName("pyr_down_rows", l), k_pyr_down_rows<1>, grid, dim3(PD_THREADS), s, (const float*)B.G[l], a.w, a.h, B.G[l + 1], b.w, b.h,
                        sx, sy, (int)ntasks, rows);
             l += 1;
@@ -1472,27 +1397,19 @@ static int col_filter(Ctx* c, ColorState* st, const lvm_params& p, const ColBufs
     // entries of the packed spectrum the 0/1 mask lets through (TemporalFilter.cpp:65-77)
     ThinBins eb{};
     int ne = 0;
-    {
-        auto m = [&](int x) { return (x >= fl && x <= fh) ? 1.0f : 0.0f; };
-        const int half = (n - 1) / 2;
-        auto push = [&](int bin, int kind, float ma, float mb) { if (ne < kThinBins) { eb.bin[ne] = bin; eb.kind[ne] = kind; eb.ma[ne] = ma; eb.mb[ne] = mb; } ++ne; };
-        if (m(0) != 0.f) push(0, 1, m(0), 0.f);
-        for (int k = 1; k <= half; ++k) if (m(2 * k - 1) != 0.f || m(2 * k) != 0.f) push(k, 0, m(2 * k - 1), m(2 * k));
-        if (n % 2 == 0 && m(n - 1) != 0.f) push(n / 2, 2, m(n - 1), 0.f);
-        eb.ne = ne;
-    }
+    for_each_entry(n, fl, fh, [&](int bin, int kind, float ma, float mb) {
+        if (ne < kThinBins) { eb.bin[ne] = bin; eb.kind[ne] = kind; eb.ma[ne] = ma; eb.mb[ne] = mb; }
+        ++ne;
+    });
+    eb.ne = ne;
     const int kind = col_dft_kind(st, n);
     if (kind == 1) {
         const int rows_wg = n <= 2048 ? 4 : 2;
         int gx = (live + rows_wg - 1) / rows_wg;
         gx = gx < 1024 ? gx : 1024;
-        if (n <= 2048) {
-            LVM_LAUNCH_V(c, "col_dft", "long", (k_col_dft_long<2048, 4>), dim3(gx, NS, B.nt), blk, s, (const float*)st->win, slot0, n, st->cap, st->rows_ps, live,
-                         fl, fh, (const double*)st->tw, B.col1, B.mm);
-        } else {
-            LVM_LAUNCH_V(c, "col_dft", "long", (k_col_dft_long<kLongMaxN, 2>), dim3(gx, NS, B.nt), blk, s, (const float*)st->win, slot0, n, st->cap, st->rows_ps, live,
-                         fl, fh, (const double*)st->tw, B.col1, B.mm);
-        }
+        auto kl = lvm_pick([](auto big) { if constexpr (decltype(big)::value) return k_col_dft_long<kLongMaxN, 2>; else return k_col_dft_long<2048, 4>; }, n > 2048);
+        LVM_LAUNCH_V(c, "col_dft", "long", kl, dim3(gx, NS, B.nt), blk, s, (const float*)st->win, slot0, n, st->cap, st->rows_ps, live, fl, fh,
+                     (const double*)st->tw, B.col1, B.mm);
     } else if (kind == 2) {   // very long windows: serial kernel, one frame per launch (batch_frames refuses them)
         LVM_LAUNCH_V(c, "col_dft", "serial", k_col_dft_serial, dim3((live + 255) / 256, NS), blk, s, (const float*)st->win, slot0, n, st->cap,
                      st->rows_ps, live, fl, fh, (const double*)st->tw, st->Y, B.col1, B.mm);
@@ -1519,12 +1436,13 @@ static void col_up_out(Ctx* c, ColorState* st, const FrameIO& io, const ColBufs&
     int uw = st->g[levels].w, uh = st->g[levels].h;
     // (a fused LDS-resident launch for the first three pyrUps measured 23.5 us against 3 x 7 us: not kept)
     // vectorised strip output kernels: decided up front, because with them the LAST generic pyrUp is not launched either
-    // (the up chain doubles the TOP level's size every step: its images are not the pyramid's sizes when a level was odd)
+    // (the up chain doubles the TOP level's size every step: its images are not the pyramid's sizes when a level was odd; vw_f is the width
+    // of the last pyrUp's source, a.vw below)
     const int vw_f = levels >= 1 ? st->g[levels].w << (levels - 1) : 0;
-    const bool vec4_f = C == 3 && io.w == 2 * vw_f && io.w % 4 == 0 && io.in_stride % 4 == 0 && io.in_sstride % 4 == 0 && io.out_stride % 4 == 0 &&
+    const bool vec4 = C == 3 && io.w == 2 * vw_f && io.w % 4 == 0 && io.in_stride % 4 == 0 && io.in_sstride % 4 == 0 && io.out_stride % 4 == 0 &&
                         io.out_sstride % 4 == 0 && ((uintptr_t)io.d_in % 4) == 0 && ((uintptr_t)io.d_out % 4) == 0 && st->co_rows_ok;
     // k_col_out_strips: both pyrUps inside (strictly increasing row map; a level-2 image of at least 2 x 2 for the border maps)
-    const bool lean = st->out_lean && st->yofs_strict && vec4_f && st->out_rows > 0 && levels >= 2 &&
+    const bool lean = st->out_lean && st->yofs_strict && vec4 && st->out_rows > 0 && levels >= 2 &&
                       (st->g[levels].w << (levels - 2)) >= 2 && (st->g[levels].h << (levels - 2)) >= 2 &&
                       io.in_stride > 0 && io.out_stride > 0 && (long)io.in_stride * io.h < (1L << 31) && (long)io.out_stride * io.h < (1L << 31);
     const bool fuse2 = lean;                      // k_col_out_strips makes the last TWO pyrUps itself
@@ -1561,9 +1479,6 @@ static void col_up_out(Ctx* c, ColorState* st, const FrameIO& io, const ColBufs&
     a.tiles_x = (io.w + CT_W - 1) / CT_W; a.tiles_y = (io.h + CT_H - 1) / CT_H;
     a.dbg = c->keep_float ? c->d_float.as<float>() : nullptr;
     const dim3 grid(a.tiles_x, a.tiles_y, NZ);
-    const bool vec4 = C == 3 && io.w == 2 * uw && io.w % 4 == 0 && io.in_stride % 4 == 0 && io.in_sstride % 4 == 0 &&
-                      io.out_stride % 4 == 0 && io.out_sstride % 4 == 0 && ((uintptr_t)io.d_in % 4) == 0 && ((uintptr_t)io.d_out % 4) == 0 &&
-                      st->co_rows_ok;
     if (vec4 && st->out_rows > 0) {
         const int sx = (io.w + 255) / 256;
         int rows = lean ? st->out_rows_lean : st->out_rows;
@@ -1571,15 +1486,15 @@ static void col_up_out(Ctx* c, ColorState* st, const FrameIO& io, const ColBufs&
         while (rows > 2 && (long)sx * ((io.h + rows - 1) / rows) * NZ < min_tasks) rows >>= 1;
         const int sy = (io.h + rows - 1) / rows;
         const long ntasks = (long)sx * sy * NZ;
-        const dim3 g2((unsigned)((ntasks + 3) / 4));
+        const dim3 g2 = strip_grid(ntasks, 256);
         if (lean) {
+            auto kout = lvm_pick([](auto d) { return k_col_out_strips<true, decltype(d)::value>; }, a.dbg != nullptr);
             LVM_LAUNCH(c, "col_minmax_u2", (k_col_out_strips<false, false>), g2, blk, s, a, sx, sy, (int)ntasks, rows);
-            if (a.dbg) LVM_LAUNCH(c, "col_out_u2", (k_col_out_strips<true, true>), g2, blk, s, a, sx, sy, (int)ntasks, rows);
-            else LVM_LAUNCH(c, "col_out_u2", (k_col_out_strips<true, false>), g2, blk, s, a, sx, sy, (int)ntasks, rows);
+            LVM_LAUNCH(c, "col_out_u2", kout, g2, blk, s, a, sx, sy, (int)ntasks, rows);
         } else {
+            auto kout = lvm_pick([](auto d) { return k_col_out_rows<true, decltype(d)::value>; }, a.dbg != nullptr);
             LVM_LAUNCH_V(c, "col_minmax", "strips", (k_col_out_rows<false, false>), g2, blk, s, a, sx, sy, (int)ntasks, rows);
-            if (a.dbg) LVM_LAUNCH_V(c, "col_out", "strips", (k_col_out_rows<true, true>), g2, blk, s, a, sx, sy, (int)ntasks, rows);
-            else LVM_LAUNCH_V(c, "col_out", "strips", (k_col_out_rows<true, false>), g2, blk, s, a, sx, sy, (int)ntasks, rows);
+            LVM_LAUNCH_V(c, "col_out", "strips", kout, g2, blk, s, a, sx, sy, (int)ntasks, rows);
         }
     } else if (vec4) {
         LVM_LAUNCH_V(c, "col_minmax", "vec4", k_col_out_v4<false>, grid, blk, s, a);
@@ -1619,6 +1534,64 @@ int color_create(Ctx* c, int levels, const FrameIO& io, hipStream_t s) {
     return rc;
 }
 
+// Twiddles cos/sin(2 pi k / n) of a window of n >= 2 frames, float64, computed on the host like the oracle's: st->tw points at the device table.
+static int color_twiddles(Ctx* c, ColorState* st, int n, int maxImages, hipStream_t s) {
+    if (st->tw_n == n) return LVM_OK;
+    // The window length grows by one per frame during warm-up (2, 3, .. maxImages): the tables of every length up
+    // to maxImages are built and uploaded ONCE (sum 2n doubles: 132 KB for T = 128), so a warm-up frame costs no
+    // host synchronisation, allocation or copy.  Lengths beyond kTwAllMax (fps > 256) keep the per-length upload.
+    const double two_pi = 2.0 * 3.1415926535897932384626433832795;
+    if (maxImages <= kTwAllMax && n <= maxImages) {
+        if (st->tw_all_max < maxImages) {
+            std::vector<double> t; std::vector<size_t> off((size_t)maxImages + 1, 0);
+            for (int m = 2; m <= maxImages; ++m) {
+                off[(size_t)m] = t.size();
+                for (int k = 0; k < m; ++k) t.push_back(std::cos(two_pi * k / m));
+                for (int k = 0; k < m; ++k) t.push_back(std::sin(two_pi * k / m));
+            }
+            LVM_HIP_TRY(c, hipStreamSynchronize(s));
+            sync_streams(c);
+            if (st->tw_all) (void)hipFree(st->tw_all);
+            st->tw_all = nullptr; st->tw_all_max = 0;
+            LVM_HIP_TRY(c, hipMalloc((void**)&st->tw_all, t.size() * sizeof(double)));
+            LVM_HIP_TRY(c, hipMemcpy(st->tw_all, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice));
+            st->tw_off = off; st->tw_all_max = maxImages;
+        }
+        st->tw = st->tw_all + st->tw_off[(size_t)n];
+    } else {
+        // One device table, refilled per length.  It is sized once for the longest window of this capture rate (up to kLongMaxN
+        // frames: 2 maxImages doubles), so a warm-up frame allocates nothing; longer windows grow it length by length.  The refill
+        // is a copy enqueued on `s`, behind the previous frame's kernels (every call's stream is ordered behind the previous
+        // call's: order_after_previous), from pinned staging memory used in turns: a staging buffer is rewritten only after the
+        // event behind its last copy has completed.
+        const size_t need = 2 * (size_t)n, want = maxImages <= kLongMaxN && maxImages > n ? 2 * (size_t)maxImages : need;
+        if (st->tw_own_cap < need) {
+            LVM_HIP_TRY(c, hipStreamSynchronize(s));
+            sync_streams(c);
+            if (st->tw_own) (void)hipFree(st->tw_own);
+            st->tw_own = nullptr; st->tw_own_cap = 0;
+            for (int k = 0; k < 2; ++k) {
+                if (st->tw_stage[k]) (void)hipHostFree(st->tw_stage[k]);
+                st->tw_stage[k] = nullptr;
+                if (!st->tw_ev[k]) LVM_HIP_TRY(c, hipEventCreateWithFlags(&st->tw_ev[k], hipEventDisableTiming));
+            }
+            LVM_HIP_TRY(c, hipMalloc((void**)&st->tw_own, want * sizeof(double)));
+            for (int k = 0; k < 2; ++k) LVM_HIP_TRY(c, hipHostMalloc((void**)&st->tw_stage[k], want * sizeof(double)));
+            st->tw_own_cap = want;
+        } else {
+            LVM_HIP_TRY(c, hipEventSynchronize(st->tw_ev[st->tw_turn]));
+        }
+        double* t = st->tw_stage[st->tw_turn];
+        for (int k = 0; k < n; ++k) { t[k] = std::cos(two_pi * k / n); t[n + k] = std::sin(two_pi * k / n); }
+        LVM_HIP_TRY(c, hipMemcpyAsync(st->tw_own, t, need * sizeof(double), hipMemcpyHostToDevice, s));
+        LVM_HIP_TRY(c, hipEventRecord(st->tw_ev[st->tw_turn], s));
+        st->tw_turn ^= 1;
+        st->tw = st->tw_own;
+    }
+    st->tw_n = n;
+    return LVM_OK;
+}
+
 int ColorState::process(Ctx* c, const lvm_params& p, const FrameIO& io, hipStream_t s, int* produced) {
     ColorState* st = this;
     *produced = 0;
@@ -1635,60 +1608,7 @@ int ColorState::process(Ctx* c, const lvm_params& p, const FrameIO& io, hipStrea
     const int slot = (st->slot0 + st->n) % st->cap;
     int n = st->n + 1, slot0 = st->slot0;
     if (n > maxImages && maxImages > 0) { slot0 = (slot0 + 1) % st->cap; n -= 1; }
-    if (n >= 2 && st->tw_n != n) {   // twiddles cos/sin(2 pi k / n), float64, computed on the host like the oracle's
-        // The window length grows by one per frame during warm-up (2, 3, .. maxImages): the tables of every length up
-        // to maxImages are built and uploaded ONCE (sum 2n doubles: 132 KB for T = 128), so a warm-up frame costs no
-        // host synchronisation, allocation or copy.  Lengths beyond kTwAllMax (fps > 256) keep the per-length upload.
-        const double two_pi = 2.0 * 3.1415926535897932384626433832795;
-        if (maxImages <= kTwAllMax && n <= maxImages) {
-            if (st->tw_all_max < maxImages) {
-                std::vector<double> t; std::vector<size_t> off((size_t)maxImages + 1, 0);
-                for (int m = 2; m <= maxImages; ++m) {
-                    off[(size_t)m] = t.size();
-                    for (int k = 0; k < m; ++k) t.push_back(std::cos(two_pi * k / m));
-                    for (int k = 0; k < m; ++k) t.push_back(std::sin(two_pi * k / m));
-                }
-                LVM_HIP_TRY(c, hipStreamSynchronize(s));
-                sync_streams(c);
-                if (st->tw_all) (void)hipFree(st->tw_all);
-                st->tw_all = nullptr; st->tw_all_max = 0;
-                LVM_HIP_TRY(c, hipMalloc((void**)&st->tw_all, t.size() * sizeof(double)));
-                LVM_HIP_TRY(c, hipMemcpy(st->tw_all, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice));
-                st->tw_off = off; st->tw_all_max = maxImages;
-            }
-            st->tw = st->tw_all + st->tw_off[(size_t)n];
-        } else {
-            // One device table, refilled per length.  It is sized once for the longest window of this capture rate (up to kLongMaxN
-            // frames: 2 maxImages doubles), so a warm-up frame allocates nothing; longer windows grow it length by length.  The refill
-            // is a copy enqueued on `s`, behind the previous frame's kernels (every call's stream is ordered behind the previous
-            // call's: order_after_previous), from pinned staging memory used in turns: a staging buffer is rewritten only after the
-            // event behind its last copy has completed.
-            const size_t need = 2 * (size_t)n, want = maxImages <= kLongMaxN && maxImages > n ? 2 * (size_t)maxImages : need;
-            if (st->tw_own_cap < need) {
-                LVM_HIP_TRY(c, hipStreamSynchronize(s));
-                sync_streams(c);
-                if (st->tw_own) (void)hipFree(st->tw_own);
-                st->tw_own = nullptr; st->tw_own_cap = 0;
-                for (int k = 0; k < 2; ++k) {
-                    if (st->tw_stage[k]) (void)hipHostFree(st->tw_stage[k]);
-                    st->tw_stage[k] = nullptr;
-                    if (!st->tw_ev[k]) LVM_HIP_TRY(c, hipEventCreateWithFlags(&st->tw_ev[k], hipEventDisableTiming));
-                }
-                LVM_HIP_TRY(c, hipMalloc((void**)&st->tw_own, want * sizeof(double)));
-                for (int k = 0; k < 2; ++k) LVM_HIP_TRY(c, hipHostMalloc((void**)&st->tw_stage[k], want * sizeof(double)));
-                st->tw_own_cap = want;
-            } else {
-                LVM_HIP_TRY(c, hipEventSynchronize(st->tw_ev[st->tw_turn]));
-            }
-            double* t = st->tw_stage[st->tw_turn];
-            for (int k = 0; k < n; ++k) { t[k] = std::cos(two_pi * k / n); t[n + k] = std::sin(two_pi * k / n); }
-            LVM_HIP_TRY(c, hipMemcpyAsync(st->tw_own, t, need * sizeof(double), hipMemcpyHostToDevice, s));
-            LVM_HIP_TRY(c, hipEventRecord(st->tw_ev[st->tw_turn], s));
-            st->tw_turn ^= 1;
-            st->tw = st->tw_own;
-        }
-        st->tw_n = n;
-    }
+    if (n >= 2) { const int rc = color_twiddles(c, st, n, maxImages, s); if (rc != LVM_OK) return rc; }
     const int rc = col_filter(c, st, p, B, slot, slot0, n, s);
     if (rc != LVM_OK) return rc;
     st->n = n; st->slot0 = slot0;

@@ -155,25 +155,6 @@ __global__ __launch_bounds__(256) void k_lap_up(UpArgs a) {
         if (ok[k]) { (a.hi + pl)[idx_r[k]] = hi_r[k]; (a.lo + pl)[idx_r[k]] = lo_r[k]; }
 }
 
-// pyrUp horizontal pass for 4 consecutive destination columns gx0..gx0+3 (gx0 even) from the source
-// values s[i0-1..i0+2], i0 = gx0/2 (indices outside the plane are never used by the border rules)
-__device__ __forceinline__ float4 pyrup_h4(float sm1, float s0, float s1, float s2, int i0, int sw) {
-    // every border variant is evaluated and the result selected (v_cndmask): divergent branches around
-    // two or three float operations cost far more than the operations
-    const bool f0 = i0 == 0, l0 = i0 == sw - 1, l1 = i0 + 1 == sw - 1;
-    const float p6 = s0 * 6.f, q6 = s1 * 6.f;
-    const float e_gen = sm1 + p6 + s1, e_first = p6 + s1 * 2.f, e_last = sm1 + s0 * 7.f;
-    const float o_gen = (s0 + s1) * 4.f, o_last = s0 * 8.f;
-    const float z_gen = s0 + q6 + s2, z_last = s0 + s1 * 7.f;      // i0 + 1 >= 1 always
-    const float w_gen = (s1 + s2) * 4.f, w_last = s1 * 8.f;
-    float4 o;
-    o.x = sel(f0, e_first, sel(l0, e_last, e_gen));
-    o.y = sel(l0, o_last, o_gen);
-    o.z = sel(l1, z_last, z_gen);
-    o.w = sel(l1, w_last, w_gen);
-    return o;
-}
-
 // The same fused step without LDS and without barriers (levels whose width is a multiple of W, steady
 // state).  A lane owns a block of W x 2 pixels of one plane for all nt frames: it keeps their two
 // low-pass states in registers, computes the horizontal pyrUp pass of the three rows of G_{l+1} and

@@ -575,6 +575,9 @@ template <class F, int V, int... Vs, class... R> auto lvm_pick(F&& f, PickInt<V,
     else return p.v == V ? with(std::integral_constant<int, V>{}) : lvm_pick(f, PickInt<Vs...>{p.v}, rest...);
 }
 
+// Launch geometry of a wave-strip kernel: one wave per task, workgroups of `threads`
+inline dim3 strip_grid(long ntasks, int threads) { return dim3((unsigned)((ntasks + threads / 64 - 1) / (threads / 64))); }
+
 void sync_streams(Ctx* c);
 void mark_enqueued(Ctx* c, hipStream_t s);
 int order_after_previous(Ctx* c, hipStream_t s);

@@ -127,11 +127,38 @@ __device__ __forceinline__ void pyrup_hpass(float (&hrow)[US_H][UT_W + 1], const
         hrow[ly][x] = (gx < dw) ? pyrup_h(&s[ly][0], gx, sx0, sw) : 0.f;
     }
 }
+// pyrUp horizontal pass for 4 consecutive destination columns gx0..gx0+3 (gx0 even) from the source
+// values s[i0-1..i0+2], i0 = gx0/2 (indices outside the plane are never used by the border rules)
+__device__ __forceinline__ float4 pyrup_h4(float sm1, float s0, float s1, float s2, int i0, int sw) {
+    // every border variant is evaluated and the result selected (v_cndmask): divergent branches around
+    // two or three float operations cost far more than the operations
+    const bool f0 = i0 == 0, l0 = i0 == sw - 1, l1 = i0 + 1 == sw - 1;
+    const float p6 = s0 * 6.f, q6 = s1 * 6.f;
+    const float e_gen = sm1 + p6 + s1, e_first = p6 + s1 * 2.f, e_last = sm1 + s0 * 7.f;
+    const float o_gen = (s0 + s1) * 4.f, o_last = s0 * 8.f;
+    const float z_gen = s0 + q6 + s2, z_last = s0 + s1 * 7.f;      // i0 + 1 >= 1 always
+    const float w_gen = (s1 + s2) * 4.f, w_last = s1 * 8.f;
+    float4 o;
+    o.x = sel(f0, e_first, sel(l0, e_last, e_gen));
+    o.y = sel(l0, o_last, o_gen);
+    o.z = sel(l1, z_last, z_gen);
+    o.w = sel(l1, w_last, w_gen);
+    return o;
+}
+// pyrUp vertical pass, the pair: destination row 2j from the horizontal passes of the source rows j-1, j, j+1, row 2j+1 from those of j, j+1
+__device__ __forceinline__ float pyrup_v_even(float h0, float h1, float h2) { return (h0 + h1 * 6.f + h2) * (1.f / 64.f); }
+__device__ __forceinline__ float pyrup_v_odd(float h1, float h2) { return ((h1 + h2) * 4.f) * (1.f / 64.f); }
+__device__ __forceinline__ float4 pyrup_v_even(const float4 h0, const float4 h1, const float4 h2) {
+    return make_float4(pyrup_v_even(h0.x, h1.x, h2.x), pyrup_v_even(h0.y, h1.y, h2.y), pyrup_v_even(h0.z, h1.z, h2.z), pyrup_v_even(h0.w, h1.w, h2.w));
+}
+__device__ __forceinline__ float4 pyrup_v_odd(const float4 h1, const float4 h2) {
+    return make_float4(pyrup_v_odd(h1.x, h2.x), pyrup_v_odd(h1.y, h2.y), pyrup_v_odd(h1.z, h2.z), pyrup_v_odd(h1.w, h2.w));
+}
 // vertical pass for destination row gy; lj = local row of source row gy>>1
 __device__ __forceinline__ float pyrup_v(const float (&hrow)[US_H][UT_W + 1], int x, int gy, int sy0) {
     const int lj = (gy >> 1) - sy0;
     const float r0 = hrow[lj - 1][x], r1 = hrow[lj][x], r2 = hrow[lj + 1][x];
-    return sel((gy & 1) == 0, (r0 + r1 * 6.f + r2) * (1.f / 64.f), ((r1 + r2) * 4.f) * (1.f / 64.f));
+    return sel((gy & 1) == 0, pyrup_v_even(r0, r1, r2), pyrup_v_odd(r1, r2));
 }
 
 // ---- vectorised u8 -> planes -> pyrDown (frames whose pixel groups of 4 are dword aligned) ----
@@ -245,38 +272,31 @@ __global__ __launch_bounds__(256) void k_down0_v4(const uint8_t* __restrict__ in
 // The tiled k_pyr_up spends ~48 instructions per output pixel (92 % VALU-busy in the colour up chain).  Here a
 // lane owns a block of 4 columns x 2 rows (output rows 2j, 2j+1): three source rows x four dword loads, the
 // horizontal pass with the border variants selected per lane, both vertical formulas, two 16-byte stores.
+// Block `gi` of the plane sp (sw x sh) -> dp; ld(pointer into sp) is the source value there (the colour up chain normalises on the fly).
+template <class Load>
+__device__ __forceinline__ void pyr_up_rows_block(int gi, const float* __restrict__ sp, int sw, int sh, float* __restrict__ dp, Load&& ld) {
+    const int dw = 2 * sw, gw = dw >> 2;                 // groups of 4 output columns per row
+    const int j = gi / gw, gx = (gi - j * gw) * 4;
+    const int i0 = gx >> 1;
+    const int cm1 = i0 > 0 ? i0 - 1 : 0, cp1 = i0 + 1 < sw ? i0 + 1 : sw - 1, cp2 = i0 + 2 < sw ? i0 + 2 : sw - 1;
+    float4 h[3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        int sy = j - 1 + q; sy = sy < 0 ? 1 : (sy >= sh ? sh - 1 : sy);       // vertical border map: row -1 -> 1, row sh -> sh - 1
+        const float* r = sp + (size_t)sy * sw;
+        h[q] = pyrup_h4(ld(r + cm1), ld(r + i0), ld(r + cp1), ld(r + cp2), i0, sw);
+    }
+    float* d0 = dp + (size_t)(2 * j) * dw + gx;
+    *reinterpret_cast<float4*>(d0) = pyrup_v_even(h[0], h[1], h[2]);
+    *reinterpret_cast<float4*>(d0 + dw) = pyrup_v_odd(h[1], h[2]);
+}
 template <int TU>
 __global__ __launch_bounds__(256) void k_pyr_up_rows(const float* __restrict__ src, int sw, int sh,
                                                      float* __restrict__ dst, int ngroups) {
     const int gi = blockIdx.x * 256 + threadIdx.x;
     if (gi >= ngroups) return;
-    const int dw = 2 * sw, gw = dw >> 2;                 // groups of 4 output columns per row
-    const int j = gi / gw, gx = (gi - j * gw) * 4;
-    const float* sp = src + (size_t)blockIdx.y * sw * sh;
-    float* dp = dst + (size_t)blockIdx.y * (size_t)dw * (2 * sh);
-    const int i0 = gx >> 1;
-    const int cm1 = i0 > 0 ? i0 - 1 : 0, cp1 = i0 + 1 < sw ? i0 + 1 : sw - 1, cp2 = i0 + 2 < sw ? i0 + 2 : sw - 1;
-    const bool f0 = i0 == 0, l0 = i0 == sw - 1, l1 = i0 + 1 == sw - 1;
-    float h[3][4];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        int sy = j - 1 + q; sy = sy < 0 ? 1 : (sy >= sh ? sh - 1 : sy);       // vertical border map: row -1 -> 1, row sh -> sh - 1
-        const float* r = sp + (size_t)sy * sw;
-        const float sm1 = r[cm1], s0 = r[i0], s1 = r[cp1], s2 = r[cp2];
-        h[q][0] = sel(f0, s0 * 6.f + s1 * 2.f, sel(l0, sm1 + s0 * 7.f, sm1 + s0 * 6.f + s1));
-        h[q][1] = sel(l0, s0 * 8.f, (s0 + s1) * 4.f);
-        h[q][2] = sel(l1, s0 + s1 * 7.f, s0 + s1 * 6.f + s2);
-        h[q][3] = sel(l1, s1 * 8.f, (s1 + s2) * 4.f);
-    }
-    float e[4], o[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        e[k] = (h[0][k] + h[1][k] * 6.f + h[2][k]) * (1.f / 64.f);
-        o[k] = ((h[1][k] + h[2][k]) * 4.f) * (1.f / 64.f);
-    }
-    float* d0 = dp + (size_t)(2 * j) * dw + gx;
-    *reinterpret_cast<float4*>(d0) = make_float4(e[0], e[1], e[2], e[3]);
-    *reinterpret_cast<float4*>(d0 + dw) = make_float4(o[0], o[1], o[2], o[3]);
+    pyr_up_rows_block(gi, src + (size_t)blockIdx.y * sw * sh, sw, sh, dst + (size_t)blockIdx.y * (size_t)(2 * sw) * (2 * sh),
+                      [](const float* p) { return *p; });
 }
 
 // ---- u8 BGR -> (Lab) -> pyrDown -> G_1 as wave strips ----------------------------------------------

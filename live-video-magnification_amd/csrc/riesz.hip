@@ -1446,7 +1446,7 @@ __global__ __launch_bounds__(256) void k_rz_final_gray(FinalArgs a) { rz_final_t
 // One text (LVM_COLLAPSE_STRIPS_WALK) serves the three forms -- res_l of a level, the BGR output, the gray output (StripToPlane / StripToBgr /
 // StripToGray) -- and the strip prologue is k_rz_split_rows' (strip_task, ReflectCursor).  What holds the kernels to what they were is NOT their instruction
 // streams: a change here is checked by the bits (the parity tests of every form), by registers / scratch / occupancy / LDS of every
-// instantiation (tools/kru.sh) and by the time on the GPU; tools/riesz_isa_vs_rev.py reports which streams moved.
+// instantiation (tools/kru.sh) and by the time on the GPU; tools/isa_vs_rev.py reports which streams moved.
 constexpr int CS_THREADS = 256;
 struct CollapseStripArgs {
     const float* bandA; const float* resn; float* res;          // [z][h][w], [z][nh][nw], [z][h][w] (res: !FINAL)
@@ -1827,9 +1827,6 @@ static bool rz_mul_f32(const Ctx* c) { return (c->opencv_build & LVM_CV_MUL_F32)
         if ((var) != nullptr) LVM_LAUNCH_V(c, nm, var, kern, grid, block, stream, __VA_ARGS__); \
         else LVM_LAUNCH(c, nm, kern, grid, block, stream, __VA_ARGS__);                   \
     } while (0)
-
-// Launch geometry of a wave-strip kernel: one wave per task, workgroups of `threads`
-static dim3 strip_grid(long ntasks, int threads) { return dim3((unsigned)((ntasks + threads / 64 - 1) / (threads / 64))); }
 
 // pyramid of the nt frames: L plane + 9x9 split chain
 static void rz_build(Ctx* c, RieszState* st, const FrameIO& io, const RzBufs& B, hipStream_t s) {

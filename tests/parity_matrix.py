@@ -960,6 +960,11 @@ _case("up_tiled-2levels", 0, (320, 180, 2), UP_CALLS, {"LVM_UP_ROWS": "0"}, _by_
 _NARROW = dict(_FPS7[0], coLow=0.8, coHigh=1.6)
 _case("col_dft_thin8", 3, (64, 48, 2), (18, 5, 1), {}, _present("col_dft", {"thin8-128"}, calls=(0, 1)), over=_NARROW, clip_over=_FPS7[1])
 _case("col_dft_thin", 3, (64, 48, 2), (18, 5, 1), {"LVM_COL_THIN8_DFT": "0"}, _present("col_dft", {"thin"}, calls=(0, 1)), over=_NARROW, clip_over=_FPS7[1])
+# 0.8-3.3 Hz at 7 fps: the full 16-frame window passes the bins 2 .. 7 and the Nyquist element, seven entries -- more than k_col_dft_thin8's
+# four, so the thread-per-row kernel with no switch set, and its loops over five to eight entries (the shorter windows of the first call have
+# fewer entries and take other kernels: the check is on the calls with the full window)
+_case("col_dft_thin_7entries", 3, (64, 48, 2), (18, 5, 1), {}, _present("col_dft", {"thin"}, calls=(1, 2)), over=dict(_FPS7[0], coLow=0.8, coHigh=3.3),
+      clip_over=_FPS7[1])
 _case("col_dft_long", 3, (64, 48, 2), (18, 5, 1), {"LVM_COL_LONG_FROM": "2"}, _present("col_dft", {"long"}, calls=(0, 1)), over=_NARROW, clip_over=_FPS7[1])
 _case("col_dft_serial", 3, (64, 48, 2), (18, 5, 1), {"LVM_COL_LONG_FROM": "2", "LVM_COL_LONG_DFT": "0"}, _present("col_dft", {"serial"}, calls=(0, 1)),
       over=_NARROW, clip_over=_FPS7[1])
