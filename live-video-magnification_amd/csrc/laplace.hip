@@ -12,16 +12,30 @@
 // Band 0 and the residual are multiplied by 0 in the reference (MagnifyCore.hpp:129-131), so
 // their bands and IIR states are never computed (dead state).
 //
-// Launch sequence (L levels; a launch covers one frame or, in temporal batches, T frames of every stream):
-//   k_down0_rows | k_down0_v4        u8 BGR -> Lab -> pyrDown -> G_1   (wave strips + DPP halo | LDS tile)
-//   k_pyr_down_rows | _multi | plain G_l -> G_{l+1}                      (wave strips for large planes)
-//   k_lap_up | k_lap_up_rows         l = L-1..1, fused: band_l = G_l - pyrUp(G_{l+1}); IIR x2; x gain_l;
-//                                    cur_l = pyrUp(cur_{l+1}) + motion_l; in a batch the frame loop runs inside
-//                                    the kernel with the IIR states in registers (LDS tiles | 2x2 blocks per lane)
-//   k_lap_tail                       per-frame calls: all levels with <= 8192 pixels in one LDS-resident launch
-//   k_lap_final_v4 | k_lap_final     out = u8(Lab2BGR(Lab(u8 in) + [1,ca,ca] * pyrUp(cur_1)))   (wave strips | tile)
-// pyrDown/pyrUp follow OpenCV's border rules and operation order exactly (see the per-kernel comments) so
-// every variant is order-faithful to the oracle; which variant runs is decided per launch from its size.
+// Launch sequence (L levels; a launch covers one frame or, in temporal batches, T frames of every stream; which
+// kernel of a line runs is decided per launch from its size and the frame's alignment, lap_stage_b / lap_stage_a):
+//   k_down0_lut_rows                 u8 BGR -> forward Lab table -> integer Lab planes AND pyrDown -> G_1 in one pass
+//                                    (large launches; persistent wave strips, table in LDS)
+//   lab_lut_planes, then k_down0_rows | k_down0_v4 | k_down0
+//                                    the same as separate launches (wave strips + DPP halo | LDS tile | byte-wise tile)
+//   k_pyr_down_rows | k_pyr_down_multi<3|2> | k_pyr_down
+//                                    G_l -> G_{l+1} (wave strips for large planes | three or two levels per launch | one)
+//   k_lap_iir_levels + k_lap_collapse  levels F..L-1 (F = 2 or 3): every band / IIR / gain step side by side in one launch
+//                                    (2 x 2 blocks per lane, states in registers over the frames), one stateless launch
+//                                    collapses m_F..m_{L-1} to cur_F
+//   k_lap_tail                       instead, in per-frame calls that do not split (the first frame, which seeds the states;
+//                                    odd level widths; LVM_LAP_SPLIT=0, LVM_LAP_SPLIT_MIN_NT > 1): all levels with <= 8192
+//                                    pixels, down and up sweep, in one LDS-resident launch
+//   k_lap_up_rows | k_lap_up         the levels below, l = ..1, fused: band_l = G_l - pyrUp(G_{l+1}); IIR x2; x gain_l;
+//                                    cur_l = pyrUp(cur_{l+1}) + m_l; in a batch the frame loop runs inside the kernel
+//                                    with the IIR states in registers (2 x 2 blocks per lane | LDS tiles; the first
+//                                    frame seeds the states with k_lap_up<true, 1>)
+//   k_lap_final_v4 | k_lap_final     out = u8(Lab2BGR(Lab(u8 in) + [1,ca,ca] * pyrUp(cur_1)))   (persistent wave strips | tile)
+// pyrDown/pyrUp follow OpenCV's border rules and operation order exactly, and every kernel takes its arithmetic from one
+// text per step: pyrdown_taps, pyrup_h_pair, pyrup_v_even / _odd, pyrup_src_row / _col (pyramid.h) and lap_level_step
+// (below), so every variant is order-faithful to the oracle.  Four kernels keep text of their own: k_lap_final_v4 and
+// k_down0_lut_rows where calling the shared one would move their instruction streams, k_pyr_down_multi and k_lap_collapse
+// because the calls measured slower ("One text per step").
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -30,27 +44,45 @@
 
 namespace lvm {
 
-struct UpArgs {
+struct IirCoef { float aHi, bHi, aLo, bLo; };   // the two first-order low-passes of iirFilter: state * a + band * b
+// One level l of the up sweep, as its kernels see it
+struct LapLevel {
     const float* Gl;    // G_l            [frame][planes][h][w]
     const float* Gn;    // G_{l+1}        [frame][planes][hn][wn]
     const float* curn;  // cur_{l+1} or nullptr (top live level: pyrUp of the zeroed residual)
     float* hi; float* lo;  // IIR states  [planes][h*w]
-    float* cur;         // cur_l          [frame][planes][h*w]
+    float* cur;         // cur_l          [frame][planes][h*w]  (k_lap_iir_levels: m_l, which k_lap_collapse turns into cur_l)
     int w, h, wn, hn;
-    float aHi, bHi, aLo, bLo, gain;
-    int nt;             // frames handled by this launch, in temporal order (1 = per-frame mode)
+    float gain;
     long fsl, fsn;      // frame strides (floats) of the level-l and level-(l+1) arrays
+    int gw, ngroups;    // the block walk: 2 x 2 blocks per row and per plane
+    int block0, top;    // k_lap_iir_levels: the level's first workgroup; is it the top live level
 };
+struct UpArgs { LapLevel lv; IirCoef k; int nt; };   // nt: frames handled by this launch, in temporal order (1 = per-frame mode)
 
-// Fused band + temporal IIR + gain + collapse step of one level.  SEED = first frame: both
-// low-pass states are seeded with the band (MagnifyCore.hpp:100-103) and nothing else happens.
+// The step of one pixel of level l from band_l = G_l - pyrUp(G_{l+1}) (SpatialFilter.cpp:33): both low-pass states, the gain and
+// cur_l = pyrUp(cur_{l+1}) + m_l.  SEED = first frame: both states are seeded with the band and nothing else happens.  add_up false:
+// m_l alone (k_lap_iir_levels below the top live level, where k_lap_collapse adds later).  The top live level adds up = 0.f -- pyrUp of
+// the zeroed residual -- which turns a -0 into +0 as the reference's addition does.
+template <bool SEED>
+__device__ __forceinline__ float lap_level_step(const float band, float& hi, float& lo, const IirCoef& k, const float gain, const bool add_up, const float up) {
+    if (SEED) { hi = band; lo = band; return 0.f; }                  // MagnifyCore.hpp:100-103
+    const float t1 = hi * k.aHi + band * k.bHi;                      // TemporalFilter.cpp:16
+    const float t2 = lo * k.aLo + band * k.bLo;                      // :17
+    hi = t1; lo = t2;
+    const float m = (t1 - t2) * gain;                                // :21, MagnifyCore.hpp:129-132
+    return add_up ? up + m : m;                                      // SpatialFilter.cpp:58
+}
+
+// Fused band + temporal IIR + gain + collapse step of one level on LDS tiles.
 // With nt > 1 the workgroup walks over nt consecutive frames of the stream: every thread owns the
 // same 4 pixels for all frames and keeps their two low-pass states in registers, so the state is
 // read and written once per launch instead of once per frame.
 template <bool SEED, int D>
-__global__ __launch_bounds__(256) void k_lap_up(UpArgs a) {
+__global__ __launch_bounds__(256) void k_lap_up(UpArgs ua) {
     __shared__ float s_g[US_H][US_W + 1], s_c[US_H][US_W + 1];
     __shared__ float h_g[US_H][UT_W + 1], h_c[US_H][UT_W + 1];
+    const LapLevel& a = ua.lv;
     const Bid3 bq = xcd_swizzle3();
     const int x0 = bq.x * UT_W, y0 = bq.y * UT_H;
     const int sx0 = x0 / 2 - 1, sy0 = y0 / 2 - 1;
@@ -71,8 +103,7 @@ __global__ __launch_bounds__(256) void k_lap_up(UpArgs a) {
         hi_r[k] = lo_r[k] = 0.f;
         if (!SEED && ok[k]) { hi_r[k] = (a.hi + pl)[idx_r[k]]; lo_r[k] = (a.lo + pl)[idx_r[k]]; }
     }
-    // source-tile elements this thread stages (same for every frame): vertical border map row -1 -> 1,
-    // row >= hn -> hn-1; columns clamped (the border columns are handled by pyrup_h's formulas)
+    // source-tile elements this thread stages (same for every frame), through pyrUp's source border map
     unsigned soff[NS]; int sdst[NS];
 #pragma unroll
     for (int k = 0; k < NS; ++k) {
@@ -80,9 +111,7 @@ __global__ __launch_bounds__(256) void k_lap_up(UpArgs a) {
         sdst[k] = -1; soff[k] = 0;
         if (i < US_H * US_W) {
             const int ly = i / US_W, lx = i - ly * US_W;
-            int gy = sy0 + ly; gy = gy < 0 ? 1 : (gy >= a.hn ? a.hn - 1 : gy);
-            int gx = sx0 + lx; gx = gx < 0 ? 0 : (gx >= a.wn ? a.wn - 1 : gx);
-            soff[k] = (unsigned)(gy * a.wn + gx);
+            soff[k] = (unsigned)(pyrup_src_row(sy0 + ly, a.hn) * a.wn + pyrup_src_col(sx0 + lx, a.wn));
             sdst[k] = ly * (US_W + 1) + lx;
         }
     }
@@ -103,7 +132,7 @@ __global__ __launch_bounds__(256) void k_lap_up(UpArgs a) {
 #pragma unroll
         for (int k = 0; k < NP; ++k) gl[d][k] = ld_stream_f32(Gl + idx_r[k]);   // (last reader of G_l: streaming load)
     }
-    for (int t0 = 0; t0 < a.nt; t0 += D) {
+    for (int t0 = 0; t0 < ua.nt; t0 += D) {
 #pragma unroll
         for (int d = 0; d < D; ++d) {
             const int t = t0 + d;
@@ -117,7 +146,7 @@ __global__ __launch_bounds__(256) void k_lap_up(UpArgs a) {
             for (int k = 0; k < NP; ++k) glc[k] = gl[d][k];
             __syncthreads();
             {
-                const int tn = t + D < a.nt ? t + D : a.nt - 1;
+                const int tn = t + D < ua.nt ? t + D : ua.nt - 1;
                 const float* Gn = a.Gn + pn + (size_t)tn * a.fsn;
                 const float* Cn = has_cur ? a.curn + pn + (size_t)tn * a.fsn : nullptr;
                 const float* Gl = a.Gl + pl + (size_t)tn * a.fsl;
@@ -137,16 +166,9 @@ __global__ __launch_bounds__(256) void k_lap_up(UpArgs a) {
                 const int y = i / UT_W, x = i - y * UT_W;
                 const int gy = y0 + y;
                 const float band = glc[k] - pyrup_v(h_g, x, gy, sy0);           // SpatialFilter.cpp:33
-                if (SEED) {
-                    hi_r[k] = band; lo_r[k] = band;
-                } else {
-                    const float t1 = hi_r[k] * a.aHi + band * a.bHi;            // TemporalFilter.cpp:16
-                    const float t2 = lo_r[k] * a.aLo + band * a.bLo;            // :17
-                    hi_r[k] = t1; lo_r[k] = t2;
-                    const float m = (t1 - t2) * a.gain;                         // :21, MagnifyCore.hpp:129-132
-                    const float up = has_cur ? pyrup_v(h_c, x, gy, sy0) : 0.f;
-                    cur[idx_r[k]] = up + m;                                     // SpatialFilter.cpp:58
-                }
+                const float up = has_cur ? pyrup_v(h_c, x, gy, sy0) : 0.f;
+                const float v = lap_level_step<SEED>(band, hi_r[k], lo_r[k], ua.k, a.gain, true, up);
+                if (!SEED) cur[idx_r[k]] = v;
             }
         }
     }
@@ -155,178 +177,31 @@ __global__ __launch_bounds__(256) void k_lap_up(UpArgs a) {
         if (ok[k]) { (a.hi + pl)[idx_r[k]] = hi_r[k]; (a.lo + pl)[idx_r[k]] = lo_r[k]; }
 }
 
-// The same fused step without LDS and without barriers (levels whose width is a multiple of W, steady
-// state).  A lane owns a block of W x 2 pixels of one plane for all nt frames: it keeps their two
-// low-pass states in registers, computes the horizontal pyrUp pass of the three rows of G_{l+1} and
-// cur_{l+1} it needs straight from global memory and reads / writes level l as 4W-byte vectors.  The raw
-// loads of the next D frames are kept in flight in a register ring (D divides nt; refills past the
-// last frame re-read the last frame so that every slot is refilled unconditionally).
-// Used with W = 2 for the coarse levels, where a launch is only a few hundred waves and the length of
-// the dependent instruction stream per frame, not throughput, sets the time (W = 4 measured slower
-// everywhere: 167 registers at ring depth 2).
-template <int W> struct UpRaw { float g[3][W / 2 + 2]; float c[3][W / 2 + 2]; float gl[2][W]; };
-template <int W, int D, bool HC>                        // HC: cur_{l+1} exists (every level but the top live one)
-__global__ __launch_bounds__(256) void k_lap_up_rows(UpArgs a, int gw, int ngroups) {
-    constexpr int NT = W / 2 + 2;                        // source taps per row: columns i0-1 .. i0+W/2
-    const int gi = blockIdx.x * 256 + threadIdx.x;
-    if (gi >= ngroups) return;
-    const int plane = blockIdx.y;
-    const int gy = gi / gw, gxg = gi - gy * gw;
-    const int gx = gxg * W, y0 = gy * 2;
-    constexpr bool has_cur = HC;
-    const bool row1 = y0 + 1 < a.h;                      // the second row of the block exists
-    const size_t pn = (size_t)plane * a.wn * a.hn, pl = (size_t)plane * a.w * a.h;
-    const int i0 = gx >> 1, j0 = y0 >> 1;
-    unsigned soff[3][NT];                                // byte offsets of the taps inside the level-(l+1) plane
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        int sy = j0 - 1 + q; sy = sy < 0 ? 1 : (sy >= a.hn ? a.hn - 1 : sy);       // vertical border map
-#pragma unroll
-        for (int k = 0; k < NT; ++k) {
-            int sx = i0 - 1 + k; sx = sx < 0 ? 0 : (sx >= a.wn ? a.wn - 1 : sx);
-            soff[q][k] = 4u * (unsigned)(sy * a.wn + sx);
-        }
-    }
-    const unsigned loff0 = 4u * (unsigned)(y0 * a.w + gx), loff1 = row1 ? loff0 + 4u * (unsigned)a.w : loff0;
-    float hi_r[2][W], lo_r[2][W];
-    {
-        const char* H = reinterpret_cast<const char*>(a.hi + pl); const char* Lo = reinterpret_cast<const char*>(a.lo + pl);
-#pragma unroll
-        for (int k = 0; k < W; ++k) {
-            hi_r[0][k] = *reinterpret_cast<const float*>(H + loff0 + 4 * k); lo_r[0][k] = *reinterpret_cast<const float*>(Lo + loff0 + 4 * k);
-            hi_r[1][k] = *reinterpret_cast<const float*>(H + loff1 + 4 * k); lo_r[1][k] = *reinterpret_cast<const float*>(Lo + loff1 + 4 * k);
-        }
-    }
-    // frame cursors of the ring refills (uniform pointers, advanced by one frame per refill and parked on
-    // the last frame)
-    const char* Gn = reinterpret_cast<const char*>(a.Gn + pn);
-    const char* Cn = reinterpret_cast<const char*>((has_cur ? a.curn : a.Gn) + pn);
-    const char* Gl = reinterpret_cast<const char*>(a.Gl + pl);
-    int tl = 0;
-    auto load = [&](UpRaw<W>& r) __attribute__((always_inline)) {
-#pragma unroll
-        for (int q = 0; q < 3; ++q)
-#pragma unroll
-            for (int k = 0; k < NT; ++k) {
-                r.g[q][k] = *reinterpret_cast<const float*>(Gn + soff[q][k]);
-                r.c[q][k] = has_cur ? *reinterpret_cast<const float*>(Cn + soff[q][k]) : 0.f;
-            }
-#pragma unroll
-        for (int k = 0; k < W; ++k) {
-            r.gl[0][k] = *reinterpret_cast<const float*>(Gl + loff0 + 4 * k);
-            r.gl[1][k] = *reinterpret_cast<const float*>(Gl + loff1 + 4 * k);
-        }
-        if (tl + 1 < a.nt) { ++tl; Gn += a.fsn * sizeof(float); Cn += a.fsn * sizeof(float); Gl += a.fsl * sizeof(float); }
-    };
-    // horizontal pyrUp pass of one source row for the W destination columns gx .. gx+W-1 (all border
-    // variants evaluated, result selected: no divergent branches)
-    auto hpass = [&](const float (&sv)[NT], float (&o)[W]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int k = 0; k < W / 2; ++k) {
-            const int i = i0 + k;                        // source column of the destination pair (2i, 2i+1)
-            const bool fi = i == 0, la = i == a.wn - 1;
-            const float sm1 = sv[k], s0 = sv[k + 1], s1 = sv[k + 2];
-            const float p6 = s0 * 6.f;
-            const float e_gen = sm1 + p6 + s1, e_first = p6 + s1 * 2.f, e_last = sm1 + s0 * 7.f;
-            const float o_gen = (s0 + s1) * 4.f, o_last = s0 * 8.f;
-            o[2 * k] = sel(fi, e_first, sel(la, e_last, e_gen));
-            o[2 * k + 1] = sel(la, o_last, o_gen);
-        }
-    };
-    char* cur = reinterpret_cast<char*>(a.cur + pl);
-    auto filter = [&](const UpRaw<W>& r) __attribute__((always_inline)) {
-        float hg[3][W], hc[3][W];
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            hpass(r.g[q], hg[q]);
-            if (has_cur) hpass(r.c[q], hc[q]);
-        }
-        float o[2][W];
-#pragma unroll
-        for (int y = 0; y < 2; ++y)
-#pragma unroll
-            for (int k = 0; k < W; ++k) {
-                const float upg = y == 0 ? (hg[0][k] + hg[1][k] * 6.f + hg[2][k]) * (1.f / 64.f) : ((hg[1][k] + hg[2][k]) * 4.f) * (1.f / 64.f);
-                const float band = r.gl[y][k] - upg;                             // SpatialFilter.cpp:33
-                const float t1 = hi_r[y][k] * a.aHi + band * a.bHi;              // TemporalFilter.cpp:16
-                const float t2 = lo_r[y][k] * a.aLo + band * a.bLo;              // :17
-                hi_r[y][k] = t1; lo_r[y][k] = t2;
-                const float m = (t1 - t2) * a.gain;                              // :21, MagnifyCore.hpp:129-132
-                const float up = has_cur ? (y == 0 ? (hc[0][k] + hc[1][k] * 6.f + hc[2][k]) * (1.f / 64.f) : ((hc[1][k] + hc[2][k]) * 4.f) * (1.f / 64.f)) : 0.f;
-                o[y][k] = up + m;                                                // SpatialFilter.cpp:58
-            }
-#pragma unroll
-        for (int k = 0; k < W; ++k) *reinterpret_cast<float*>(cur + loff0 + 4 * k) = o[0][k];
-        if (row1) {
-#pragma unroll
-            for (int k = 0; k < W; ++k) *reinterpret_cast<float*>(cur + loff1 + 4 * k) = o[1][k];
-        }
-        cur += a.fsl * sizeof(float);
-    };
-    UpRaw<W> ring[D];
-#pragma unroll
-    for (int d = 0; d < D; ++d) load(ring[d]);
-    for (int t0 = 0; t0 < a.nt; t0 += D) {
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-            const UpRaw<W> now = ring[d];
-            load(ring[d]);
-            filter(now);
-        }
-    }
-    {
-        char* H = reinterpret_cast<char*>(a.hi + pl); char* Lo = reinterpret_cast<char*>(a.lo + pl);
-#pragma unroll
-        for (int k = 0; k < W; ++k) { *reinterpret_cast<float*>(H + loff0 + 4 * k) = hi_r[0][k]; *reinterpret_cast<float*>(Lo + loff0 + 4 * k) = lo_r[0][k]; }
-        if (row1) {
-#pragma unroll
-            for (int k = 0; k < W; ++k) { *reinterpret_cast<float*>(H + loff1 + 4 * k) = hi_r[1][k]; *reinterpret_cast<float*>(Lo + loff1 + 4 * k) = lo_r[1][k]; }
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// Temporal batches, levels 2 .. L-1: the level-by-level chain of fused launches (each a few hundred waves walking
-// over the frames of the batch, i.e. the length of the dependent instruction stream times the number of levels) is
-// cut in two:
-//   k_lap_iir_levels   ONE launch for all those levels.  m_l(t) = gain_l * (hi_l(t) - lo_l(t)) depends on G_l and
-//                      G_{l+1} only, not on the other levels' results, so every level runs side by side: a lane owns
-//                      a 2 x 2 block of one (level, plane) for all frames, states in registers, raw loads of the next
-//                      D frames in flight (as k_lap_up_rows).  m_l is stored where cur_l will be.
-//   k_lap_collapse     cur_l = pyrUp(cur_{l+1}) + m_l for l = L-2 .. 2 is stateless: ONE launch, a workgroup per
-//                      (frame, plane, 64 x 32 tile of level 2), the few coarse pixels a tile depends on recomputed in
-//                      LDS (34 x 18, 19 x 11, 12 x 8 .. per level).
-// Same arithmetic and operation order as k_lap_up / k_lap_tail, hence the same frames.
-// ------------------------------------------------------------------------------------------
-constexpr int kIirLevels = 10;
-struct IirLevel {
-    const float* Gl; const float* Gn; float* hi; float* lo; float* out;
-    int w, h, wn, hn; float gain; long fsl, fsn; int block0, gw, ngroups, top;
-};
-struct IirArgs { IirLevel lv[kIirLevels]; int nlv, nt; float aHi, bHi, aLo, bLo; };
-
-template <int D>
-__global__ __launch_bounds__(256) void k_lap_iir_levels(IirArgs aa) {
-    int k = 0;
-    while (k + 1 < aa.nlv && (int)blockIdx.x >= aa.lv[k + 1].block0) ++k;
-    const IirLevel& a = aa.lv[k];
-    const int gi = ((int)blockIdx.x - a.block0) * 256 + threadIdx.x;
+// The same fused step without LDS and without barriers (levels of even width, steady state): the block walk.  A lane owns a block
+// of 2 x 2 pixels of one plane for all nt frames: it keeps their two low-pass states in registers, computes the horizontal pyrUp pass
+// of the three rows of G_{l+1} (HC: and of cur_{l+1}) it needs straight from global memory and reads / writes level l as 8-byte
+// vectors (w is even and the arrays are 256-byte aligned).  The raw loads of the next D frames are kept in flight in a register ring
+// (D divides nt; refills past the last frame re-read the last frame so that every slot is refilled unconditionally).
+// Used for the coarse levels, where a launch is only a few hundred waves and the length of the dependent instruction stream per
+// frame, not throughput, sets the time (4 x 2 blocks measured slower everywhere: 167 registers at ring depth 2).
+// gi: the block inside the plane blockIdx.y.  HC: cur_{l+1} is upsampled and added; otherwise `top` says whether 0.f is (the top live
+// level) or m_l is stored as it is.
+struct BlockRaw { float g[3][3]; float c[3][3]; float2 gl[2]; };
+template <int D, bool HC>
+__device__ __forceinline__ void lap_block_walk(const LapLevel& a, const IirCoef& kf, const int nt, const int gi, const bool top) {
     if (gi >= a.ngroups) return;
     const int plane = blockIdx.y;
     const int gy = gi / a.gw, gxg = gi - gy * a.gw;
     const int gx = gxg * 2, y0 = gy * 2;
-    const bool row1 = y0 + 1 < a.h;
+    const bool row1 = y0 + 1 < a.h;                      // the second row of the block exists
     const size_t pn = (size_t)plane * a.wn * a.hn, pl = (size_t)plane * a.w * a.h;
     const int i0 = gx >> 1, j0 = y0 >> 1;
-    unsigned soff[3][3];
+    unsigned soff[3][3];                                 // byte offsets of the taps inside the level-(l+1) plane: rows j0-1 .. j0+1, columns i0-1 .. i0+1
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
-        int sy = j0 - 1 + q; sy = sy < 0 ? 1 : (sy >= a.hn ? a.hn - 1 : sy);       // vertical border map
+        const int sy = pyrup_src_row(j0 - 1 + q, a.hn);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            int sx = i0 - 1 + c; sx = sx < 0 ? 0 : (sx >= a.wn ? a.wn - 1 : sx);
-            soff[q][c] = 4u * (unsigned)(sy * a.wn + sx);
-        }
+        for (int c = 0; c < 3; ++c) soff[q][c] = 4u * (unsigned)(sy * a.wn + pyrup_src_col(i0 - 1 + c, a.wn));
     }
     const unsigned loff0 = 4u * (unsigned)(y0 * a.w + gx), loff1 = row1 ? loff0 + 4u * (unsigned)a.w : loff0;
     float hi_r[2][2], lo_r[2][2];
@@ -337,55 +212,54 @@ __global__ __launch_bounds__(256) void k_lap_iir_levels(IirArgs aa) {
         hi_r[0][0] = h0.x; hi_r[0][1] = h0.y; hi_r[1][0] = h1.x; hi_r[1][1] = h1.y;
         lo_r[0][0] = l0.x; lo_r[0][1] = l0.y; lo_r[1][0] = l1.x; lo_r[1][1] = l1.y;
     }
-    struct Raw { float g[3][3]; float2 gl[2]; };
+    // frame cursors of the ring refills (uniform pointers, advanced by one frame per refill and parked on the last frame)
     const char* Gn = reinterpret_cast<const char*>(a.Gn + pn);
+    const char* Cn = reinterpret_cast<const char*>((HC ? a.curn : a.Gn) + pn);
     const char* Gl = reinterpret_cast<const char*>(a.Gl + pl);
     int tl = 0;
-    auto load = [&](Raw& r) __attribute__((always_inline)) {
+    auto load = [&](BlockRaw& r) __attribute__((always_inline)) {
 #pragma unroll
         for (int q = 0; q < 3; ++q)
 #pragma unroll
-            for (int c = 0; c < 3; ++c) r.g[q][c] = *reinterpret_cast<const float*>(Gn + soff[q][c]);
+            for (int c = 0; c < 3; ++c) {
+                r.g[q][c] = *reinterpret_cast<const float*>(Gn + soff[q][c]);
+                r.c[q][c] = HC ? *reinterpret_cast<const float*>(Cn + soff[q][c]) : 0.f;
+            }
         r.gl[0] = *reinterpret_cast<const float2*>(Gl + loff0);
         r.gl[1] = *reinterpret_cast<const float2*>(Gl + loff1);
-        if (tl + 1 < aa.nt) { ++tl; Gn += a.fsn * sizeof(float); Gl += a.fsl * sizeof(float); }
+        if (tl + 1 < nt) { ++tl; Gn += a.fsn * sizeof(float); if (HC) Cn += a.fsn * sizeof(float); Gl += a.fsl * sizeof(float); }
     };
     const bool fi = i0 == 0, la = i0 == a.wn - 1;
-    char* out = reinterpret_cast<char*>(a.out + pl);
-    auto filter = [&](const Raw& r) __attribute__((always_inline)) {
-        float hg[3][2];
+    char* cur = reinterpret_cast<char*>(a.cur + pl);
+    auto filter = [&](const BlockRaw& r) __attribute__((always_inline)) {
+        float hg[3][2], hc[3][2];
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
-            const float sm1 = r.g[q][0], s0 = r.g[q][1], s1 = r.g[q][2];
-            const float p6 = s0 * 6.f;
-            hg[q][0] = sel(fi, p6 + s1 * 2.f, sel(la, sm1 + s0 * 7.f, sm1 + p6 + s1));
-            hg[q][1] = sel(la, s0 * 8.f, (s0 + s1) * 4.f);
+            const UpPair g = pyrup_h_pair(r.g[q][0], r.g[q][1], r.g[q][2], fi, la);
+            hg[q][0] = g.e; hg[q][1] = g.o;
+            if (HC) { const UpPair u = pyrup_h_pair(r.c[q][0], r.c[q][1], r.c[q][2], fi, la); hc[q][0] = u.e; hc[q][1] = u.o; }
         }
         float o[2][2];
 #pragma unroll
         for (int y = 0; y < 2; ++y)
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
-                const float upg = y == 0 ? (hg[0][c] + hg[1][c] * 6.f + hg[2][c]) * (1.f / 64.f) : ((hg[1][c] + hg[2][c]) * 4.f) * (1.f / 64.f);
-                const float glv = y == 0 ? (c == 0 ? r.gl[0].x : r.gl[0].y) : (c == 0 ? r.gl[1].x : r.gl[1].y);
-                const float band = glv - upg;                                    // SpatialFilter.cpp:33
-                const float t1 = hi_r[y][c] * aa.aHi + band * aa.bHi;            // TemporalFilter.cpp:16
-                const float t2 = lo_r[y][c] * aa.aLo + band * aa.bLo;            // :17
-                hi_r[y][c] = t1; lo_r[y][c] = t2;
-                const float m = (t1 - t2) * a.gain;                              // :21, MagnifyCore.hpp:129-132
-                o[y][c] = a.top ? 0.f + m : m;                                   // top live level: pyrUp of the zeroed residual + m
+                const float glv = c == 0 ? r.gl[y].x : r.gl[y].y;
+                const float band = glv - (y == 0 ? pyrup_v_even(hg[0][c], hg[1][c], hg[2][c]) : pyrup_v_odd(hg[1][c], hg[2][c]));   // SpatialFilter.cpp:33
+                const float up = !HC ? 0.f : (y == 0 ? pyrup_v_even(hc[0][c], hc[1][c], hc[2][c]) : pyrup_v_odd(hc[1][c], hc[2][c]));
+                o[y][c] = lap_level_step<false>(band, hi_r[y][c], lo_r[y][c], kf, a.gain, HC || top, up);
             }
-        *reinterpret_cast<float2*>(out + loff0) = make_float2(o[0][0], o[0][1]);
-        if (row1) *reinterpret_cast<float2*>(out + loff1) = make_float2(o[1][0], o[1][1]);
-        out += a.fsl * sizeof(float);
+        *reinterpret_cast<float2*>(cur + loff0) = make_float2(o[0][0], o[0][1]);
+        if (row1) *reinterpret_cast<float2*>(cur + loff1) = make_float2(o[1][0], o[1][1]);
+        cur += a.fsl * sizeof(float);
     };
-    Raw ring[D];
+    BlockRaw ring[D];
 #pragma unroll
     for (int d = 0; d < D; ++d) load(ring[d]);
-    for (int t0 = 0; t0 < aa.nt; t0 += D) {
+    for (int t0 = 0; t0 < nt; t0 += D) {
 #pragma unroll
         for (int d = 0; d < D; ++d) {
-            const Raw now = ring[d];
+            const BlockRaw now = ring[d];
             load(ring[d]);
             filter(now);
         }
@@ -400,6 +274,36 @@ __global__ __launch_bounds__(256) void k_lap_iir_levels(IirArgs aa) {
         }
     }
 }
+// one level per launch: cur_l = pyrUp(cur_{l+1}) + m_l (HC), or 0.f + m_l at the top live level.  (top = true always: the host launches
+// HC = false only where cur_{l+1} does not exist, which is the top live level; with HC the walk ignores the flag)
+template <int D, bool HC>
+__global__ __launch_bounds__(256) void k_lap_up_rows(UpArgs a) {
+    lap_block_walk<D, HC>(a.lv, a.k, a.nt, blockIdx.x * 256 + threadIdx.x, true);
+}
+
+// ------------------------------------------------------------------------------------------
+// Temporal batches, levels 2 .. L-1: the level-by-level chain of fused launches (each a few hundred waves walking
+// over the frames of the batch, i.e. the length of the dependent instruction stream times the number of levels) is
+// cut in two:
+//   k_lap_iir_levels   ONE launch for all those levels.  m_l(t) = gain_l * (hi_l(t) - lo_l(t)) depends on G_l and
+//                      G_{l+1} only, not on the other levels' results, so every level runs side by side: the block walk
+//                      of k_lap_up_rows on the level that blockIdx.x falls into, without cur_{l+1}.  m_l is stored
+//                      where cur_l will be.
+//   k_lap_collapse     cur_l = pyrUp(cur_{l+1}) + m_l for l = L-2 .. 2 is stateless: ONE launch, a workgroup per
+//                      (frame, plane, 64 x 32 tile of level 2), the few coarse pixels a tile depends on recomputed in
+//                      LDS (34 x 18, 19 x 11, 12 x 8 .. per level).
+// Same arithmetic and operation order as k_lap_up / k_lap_tail, hence the same frames.
+// ------------------------------------------------------------------------------------------
+constexpr int kIirLevels = 10;
+struct IirArgs { LapLevel lv[kIirLevels]; int nlv, nt; IirCoef k; };
+
+template <int D>
+__global__ __launch_bounds__(256) void k_lap_iir_levels(IirArgs aa) {
+    int k = 0;
+    while (k + 1 < aa.nlv && (int)blockIdx.x >= aa.lv[k + 1].block0) ++k;
+    const LapLevel a = aa.lv[k];         // (a copy: read through a reference into the argument array, D = 2 takes 86 VGPRs and loses a wave)
+    lap_block_walk<D, false>(a, aa.k, aa.nt, ((int)blockIdx.x - a.block0) * 256 + threadIdx.x, a.top != 0);
+}
 
 constexpr int CT_W = 64, CT_H = 32, CP_R = 36, kCollapsePool = 4096;      // CP_R: row pitch of the coarser levels' regions (<= 34 columns)
 struct CollapseArgs { float* cur[kIirLevels]; int w[kIirLevels], h[kIirLevels]; int nlv; };   // index 0 = level 2, nlv - 1 = top live level
@@ -413,6 +317,8 @@ constexpr int collapse_pool_floats(int nlv) {
 }
 static_assert(collapse_pool_floats(kIirLevels) <= kCollapsePool, "k_lap_collapse: LDS pool too small for CT_W / CT_H / CP_R / kIirLevels");
 static_assert(CT_W / 2 + 2 <= CP_R, "k_lap_collapse: a region row of the level above does not fit the row pitch");
+// Its pyrUp arithmetic is its own text of pyrup_h_pair, pyrup_v_even / _odd and pyrup_src_row (an exception by measurement: written as calls
+// the launch measured 0.4 us longer in the benchmark, profiles/r18_laplace_shared_text.txt).
 template <int NLV>                                      // number of levels (compile time: the per-level region scalars stay in SGPRs)
 __global__ __launch_bounds__(256) void k_lap_collapse(CollapseArgs a) {
     __shared__ float pool[kCollapsePool];
@@ -612,6 +518,16 @@ __global__ __launch_bounds__(256) void k_lap_final(const uint8_t* __restrict__ i
 #endif
 constexpr int FIN_THREADS = LVM_FIN_THREADS;
 struct Row3 { float4 c[3]; };            // horizontal-pass results of one source row, 3 channels x 4 columns
+// own text of pyrup_h4 (pyramid.h) for the exact flavours of k_lap_final_v4: the shared one, two pyrup_h_pair calls, reorders their instruction streams
+__device__ __forceinline__ float4 fin_pyrup_h4(float sm1, float s0, float s1, float s2, int i0, int sw) {
+    const bool f0 = i0 == 0, l0 = i0 == sw - 1, l1 = i0 + 1 == sw - 1;
+    const float p6 = s0 * 6.f, q6 = s1 * 6.f;
+    const float e_gen = sm1 + p6 + s1, e_first = p6 + s1 * 2.f, e_last = sm1 + s0 * 7.f;
+    const float o_gen = (s0 + s1) * 4.f, o_last = s0 * 8.f;
+    const float z_gen = s0 + q6 + s2, z_last = s0 + s1 * 7.f;      // i0 + 1 >= 1 always
+    const float w_gen = (s1 + s2) * 4.f, w_last = s1 * 8.f;
+    return make_float4(sel(f0, e_first, sel(l0, e_last, e_gen)), sel(l0, o_last, o_gen), sel(l1, z_last, z_gen), sel(l1, w_last, w_gen));
+}
 #ifndef LVM_FIN_WAVES
 #define LVM_FIN_WAVES 0          // minimum waves per SIMD asked of the register allocator for EVERY instance (measurements; 0: fin_waves' own choice)
 #endif
@@ -717,13 +633,13 @@ __device__ __forceinline__ void lap_final_strip(const FinArgs& q, int task, int 
     // base is uniform, the four column offsets are per-lane byte offsets
     auto hrow = [&](int sy) __attribute__((always_inline)) {
         Row3 o;
-        sy = sy < 0 ? 1 : (sy >= h1 ? h1 - 1 : sy);
+        sy = sy < 0 ? 1 : (sy >= h1 ? h1 - 1 : sy);     // own text of pyrup_src_row: the call moves this kernel's scalar register assignment
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const uint32_t rb = (uint32_t)(((size_t)sy * w1 + c * pstride) * sizeof(float));
             const uint32_t cr = c00 + rb;      // (formed per row, so that the + 4 of column i0 + 1 stays next to its load and becomes its immediate offset)
             const float sm1 = buf_ld_f32(rcur, cm1, rb), s0 = buf_ld_f32(rcur, cr, 0u), s1 = buf_ld_f32(rcur, cr + 4u, 0u), s2 = buf_ld_f32(rcur, cp2, rb);
-            if (EXACT) o.c[c] = pyrup_h4(sm1, s0, s1, s2, i0, w1);
+            if (EXACT) o.c[c] = fin_pyrup_h4(sm1, s0, s1, s2, i0, w1);
             else if (LVM_FAST_FMA) {   // one rounding less per even column (fma), a few 1e-8 of the motion image
                 o.c[c].x = __builtin_fmaf(s0, 6.f, sm1 + s1); o.c[c].y = (s0 + s1) * 4.f; o.c[c].z = __builtin_fmaf(s1, 6.f, s0 + s2); o.c[c].w = (s1 + s2) * 4.f;
             } else { o.c[c].x = sm1 + s0 * 6.f + s1; o.c[c].y = (s0 + s1) * 4.f; o.c[c].z = s0 + s1 * 6.f + s2; o.c[c].w = (s1 + s2) * 4.f; }
@@ -764,14 +680,16 @@ __device__ __forceinline__ void lap_final_strip(const FinArgs& q, int task, int 
         if (MOTION) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                const float sc = EXACT ? (1.f / 64.f) : 1.f;           // (x * 1.f folds away)
-                if (!EXACT && LVM_FAST_FMA) {
+                if (EXACT) {
+                    const float4 v = pyrup_v_even(A.c[c], B.c[c], C.c[c]);
+                    m[c][0] = v.x; m[c][1] = v.y; m[c][2] = v.z; m[c][3] = v.w;
+                } else if (LVM_FAST_FMA) {     // this kernel's own: the unscaled sum (emit folds the 1/64 into its fma), one rounding less
                     m[c][0] = __builtin_fmaf(B.c[c].x, 6.f, A.c[c].x + C.c[c].x); m[c][1] = __builtin_fmaf(B.c[c].y, 6.f, A.c[c].y + C.c[c].y);
                     m[c][2] = __builtin_fmaf(B.c[c].z, 6.f, A.c[c].z + C.c[c].z); m[c][3] = __builtin_fmaf(B.c[c].w, 6.f, A.c[c].w + C.c[c].w);
-                    continue;
+                } else {
+                    m[c][0] = A.c[c].x + B.c[c].x * 6.f + C.c[c].x; m[c][1] = A.c[c].y + B.c[c].y * 6.f + C.c[c].y;
+                    m[c][2] = A.c[c].z + B.c[c].z * 6.f + C.c[c].z; m[c][3] = A.c[c].w + B.c[c].w * 6.f + C.c[c].w;
                 }
-                m[c][0] = (A.c[c].x + B.c[c].x * 6.f + C.c[c].x) * sc; m[c][1] = (A.c[c].y + B.c[c].y * 6.f + C.c[c].y) * sc;
-                m[c][2] = (A.c[c].z + B.c[c].z * 6.f + C.c[c].z) * sc; m[c][3] = (A.c[c].w + B.c[c].w * 6.f + C.c[c].w) * sc;
             }
         }
         const bool more = gy + 2 < yend;
@@ -787,8 +705,8 @@ __device__ __forceinline__ void lap_final_strip(const FinArgs& q, int task, int 
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 if (EXACT) {
-                    m[c][0] = ((B.c[c].x + C.c[c].x) * 4.f) * (1.f / 64.f); m[c][1] = ((B.c[c].y + C.c[c].y) * 4.f) * (1.f / 64.f);
-                    m[c][2] = ((B.c[c].z + C.c[c].z) * 4.f) * (1.f / 64.f); m[c][3] = ((B.c[c].w + C.c[c].w) * 4.f) * (1.f / 64.f);
+                    const float4 v = pyrup_v_odd(B.c[c], C.c[c]);
+                    m[c][0] = v.x; m[c][1] = v.y; m[c][2] = v.z; m[c][3] = v.w;
                 } else {
                     m[c][0] = B.c[c].x + C.c[c].x; m[c][1] = B.c[c].y + C.c[c].y; m[c][2] = B.c[c].z + C.c[c].z; m[c][3] = B.c[c].w + C.c[c].w;
                 }
@@ -850,13 +768,9 @@ struct TailArgs {
     int offG[kTailLevels + 1], offC[kTailLevels + 1]; // LDS offsets of G_{T+k}, cur_{T+k} (k >= 1)
     int offA, offB;                     // two temporaries
     float gain[kTailLevels];
-    float aHi, bHi, aLo, bLo;
+    IirCoef k;
     int n;                              // number of down steps = L - T (>= 1)
-    int nt;                             // frames handled by this launch, in temporal order
-    long fsT;                           // frame stride (floats) of the level-T arrays (G_T, cur_T)
 };
-
-__device__ __forceinline__ float tail_src(const float* s, int w, int h, int y, int x) { return s[(size_t)y * w + x]; }
 
 // i = y * w + x for 0 <= i < 2^20, w < 2^12: (i + 0.5) / w is at least 0.5 / w away from an integer,
 // far more than the float error of the product, so the truncation is exact
@@ -868,14 +782,11 @@ __global__ __launch_bounds__(TAIL_THREADS) void k_lap_tail(TailArgs a) {
     __shared__ float pool[kTailPool];
     const int tid = threadIdx.x;
     const size_t plane = blockIdx.x;
-    for (int t = 0; t < a.nt; ++t) {     // frames in temporal order; the states of frame t-1 were written by this workgroup
-    const float* GTt = a.GT + (size_t)t * a.fsT;
-    float* curTt = a.curT + (size_t)t * a.fsT;
     // ---- down sweep ----
     for (int k = 0; k < a.n; ++k) {
         const int w = a.w[k], h = a.h[k], dw = a.w[k + 1], dh = a.h[k + 1];
         const float inv_dw = 1.0f / (float)dw;
-        const float* __restrict__ src = (k == 0) ? GTt + plane * ((size_t)w * h) : pool + a.offG[k];
+        const float* __restrict__ src = (k == 0) ? a.GT + plane * ((size_t)w * h) : pool + a.offG[k];
         float* __restrict__ tmp = pool + a.offA;                       // h x dw horizontal results
 #pragma unroll 4
         for (int i = tid; i < h * dw; i += TAIL_THREADS) {
@@ -883,7 +794,7 @@ __global__ __launch_bounds__(TAIL_THREADS) void k_lap_tail(TailArgs a) {
             const float* s = src + (size_t)y * w;
             const int x0 = reflect101(2 * x - 2, w), x1 = reflect101(2 * x - 1, w), x2 = 2 * x,
                       x3 = reflect101(2 * x + 1, w), x4 = reflect101(2 * x + 2, w);
-            tmp[i] = s[x2] * 6.f + (s[x1] + s[x3]) * 4.f + s[x0] + s[x4];
+            tmp[i] = pyrdown_taps<false>(s[x0], s[x1], s[x2], s[x3], s[x4]);
         }
         __syncthreads();
         float* __restrict__ dst = pool + a.offG[k + 1];
@@ -892,7 +803,7 @@ __global__ __launch_bounds__(TAIL_THREADS) void k_lap_tail(TailArgs a) {
             const float r0 = tmp[reflect101(2 * y - 2, h) * dw + x], r1 = tmp[reflect101(2 * y - 1, h) * dw + x],
                         r2 = tmp[(2 * y) * dw + x], r3 = tmp[reflect101(2 * y + 1, h) * dw + x],
                         r4 = tmp[reflect101(2 * y + 2, h) * dw + x];
-            dst[i] = (r2 * 6.f + (r1 + r3) * 4.f + r0 + r4) * (1.f / 256.f);
+            dst[i] = pyrdown_taps_v<false>(r0, r1, r2, r3, r4);
         }
         __syncthreads();
     }
@@ -911,35 +822,24 @@ __global__ __launch_bounds__(TAIL_THREADS) void k_lap_tail(TailArgs a) {
             if (has_cur) tB[i] = pyrup_h(Cn + (size_t)y * sw, x, 0, sw);
         }
         __syncthreads();
-        const float* __restrict__ Gl = (k == 0) ? GTt + plane * ((size_t)w * h) : pool + a.offG[k];
+        const float* __restrict__ Gl = (k == 0) ? a.GT + plane * ((size_t)w * h) : pool + a.offG[k];
         float* __restrict__ hi = a.hi[k] + plane * ((size_t)w * h);
         float* __restrict__ lo = a.lo[k] + plane * ((size_t)w * h);
-        float* __restrict__ cur = (k == 0) ? curTt + plane * ((size_t)w * h) : pool + a.offC[k];
+        float* __restrict__ cur = (k == 0) ? a.curT + plane * ((size_t)w * h) : pool + a.offC[k];
 #pragma unroll 4
         for (int i = tid; i < h * w; i += TAIL_THREADS) {
             const int y = row_of(i, inv_w), x = i - y * w;
             const int j = y >> 1;
-            const int jm = j == 0 ? 1 : j - 1, jp = j == sh - 1 ? sh - 1 : j + 1;
-            const float upG = ((y & 1) == 0) ? (tA[jm * w + x] + tA[j * w + x] * 6.f + tA[jp * w + x]) * (1.f / 64.f)
-                                             : ((tA[j * w + x] + tA[jp * w + x]) * 4.f) * (1.f / 64.f);
-            const float band = Gl[i] - upG;
-            if (SEED) {
-                hi[i] = band; lo[i] = band;
-            } else {
-                const float t1 = hi[i] * a.aHi + band * a.bHi;
-                const float t2 = lo[i] * a.aLo + band * a.bLo;
-                hi[i] = t1; lo[i] = t2;
-                const float m = (t1 - t2) * a.gain[k];
-                float up = 0.f;
-                if (has_cur)
-                    up = ((y & 1) == 0) ? (tB[jm * w + x] + tB[j * w + x] * 6.f + tB[jp * w + x]) * (1.f / 64.f)
-                                        : ((tB[j * w + x] + tB[jp * w + x]) * 4.f) * (1.f / 64.f);
-                cur[i] = up + m;
-            }
+            const int jm = pyrup_src_row(j - 1, sh), jp = pyrup_src_row(j + 1, sh);
+            const bool even = (y & 1) == 0;
+            const float band = Gl[i] - (even ? pyrup_v_even(tA[jm * w + x], tA[j * w + x], tA[jp * w + x]) : pyrup_v_odd(tA[j * w + x], tA[jp * w + x]));
+            float up = 0.f;
+            if (has_cur) up = even ? pyrup_v_even(tB[jm * w + x], tB[j * w + x], tB[jp * w + x]) : pyrup_v_odd(tB[j * w + x], tB[jp * w + x]);
+            const float v = lap_level_step<SEED>(band, hi[i], lo[i], a.k, a.gain[k], true, up);
+            if (!SEED) cur[i] = v;
         }
         __syncthreads();
     }
-    }   // frames
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1067,6 +967,13 @@ static void laplace_gains(int w, int h, int levels, double amplification, double
     }
 }
 
+// TemporalFilter.cpp:9-17: the two cut-offs as the coefficients of the low-pass pair
+static IirCoef iir_coef(const lvm_params& p) {
+    double cLo = p.coLow, cHi = p.coHigh;
+    if (cLo == 0) cLo = 0.01;                                            // TemporalFilter.cpp:11-12
+    return IirCoef{(float)(1 - cHi), (float)cHi, (float)(1 - cLo), (float)cLo};
+}
+
 static bool lap_vec4(const FrameIO& io) {   // 4-pixel (12-byte) vector I/O needs dword-aligned pixel groups
     return io.channels == 3 && io.w % 4 == 0 && io.in_stride % 4 == 0 && io.in_sstride % 4 == 0 &&
            io.out_stride % 4 == 0 && io.out_sstride % 4 == 0 && ((uintptr_t)io.d_in % 4) == 0 &&
@@ -1137,21 +1044,22 @@ static void lap_stage_b(Ctx* c, LaplaceState* st, const lvm_params& p, const Fra
     const int d0_sx = (g1.w + D0R_OUT - 1) / D0R_OUT;
     long d0_tasks = 0;
     const int d0_rows = down0_rows_choice(g1.w, g1.h, NS, st->d0_min_tasks, &d0_tasks);
-    const int fl = lab_flavour(c);
+    const auto fl = pick_flavour(lab_flavour(c));
     if (fused) {
-        auto kdl = fl == FL_LUT_EXACT ? k_down0_lut_rows<FL_LUT_EXACT> : k_down0_lut_rows<FL_LUT_FAST>;
+        auto kdl = lvm_pick([](auto f) { return k_down0_lut_rows<decltype(f)::value>; }, PickInt<FL_LUT_EXACT, FL_LUT_FAST>{fl.v});
         LVM_LAUNCH(c, "lap_down0_lut", kdl, dim3((unsigned)lap_d0l_groups(c, st)), dim3(D0L_THREADS), s, da);
     } else if (lap_vec4(io) && st->d0_rows_on && d0_tasks > 0) {
-        auto kd0 = LVM_FL_PICK(fl, k_down0_rows, true);
+        auto kd0 = lvm_pick([](auto f) { return k_down0_rows<true, decltype(f)::value>; }, fl);
         const dim3 gridr((unsigned)((d0_tasks + D0R_THREADS / 64 - 1) / (D0R_THREADS / 64)));
         LVM_LAUNCH_V(c, "lap_down0", "strips", kd0, gridr, dim3(D0R_THREADS), s, io.d_in, (long)io.in_stride, (long)io.in_sstride, io.w, io.h,
                    G[1], g1.w, g1.h, c->lab, d0_sx, (g1.h + d0_rows - 1) / d0_rows, (int)d0_tasks, d0_rows, lp);
     } else if (lap_vec4(io)) {
-        auto kd0 = LVM_FL_PICK(fl, k_down0_v4, true);
+        auto kd0 = lvm_pick([](auto f) { return k_down0_v4<true, decltype(f)::value>; }, fl);
         LVM_LAUNCH_V(c, "lap_down0", "vec4", kd0, grid0, blk, s, io.d_in, (long)io.in_stride, (long)io.in_sstride, io.w, io.h,
                    G[1], g1.w, g1.h, c->lab, lp);
     } else {
-        auto kd0 = (C == 3) ? LVM_FL_PICK(fl, k_down0, 3, true) : k_down0<1, false, FL_LUT_EXACT>;
+        // (gray frames have no Lab conversion: one instance, whatever the flavour)
+        auto kd0 = lvm_pick([](auto c3, auto f) { constexpr bool C3 = decltype(c3)::value; return k_down0<C3 ? 3 : 1, C3, C3 ? decltype(f)::value : FL_LUT_EXACT>; }, C == 3, fl);
         LVM_LAUNCH_V(c, "lap_down0", "bytes", kd0, grid0, blk, s, io.d_in, (long)io.in_stride, (long)io.in_sstride, io.w, io.h,
                    G[1], g1.w, g1.h, c->lab, c->lab.a255, lp);
     }
@@ -1195,16 +1103,13 @@ static void lap_stage_b(Ctx* c, LaplaceState* st, const lvm_params& p, const Fra
     if (use_tail) {
         float gains[kMaxLevels + 2];
         laplace_gains(io.w, io.h, levels, p.amplification, p.coWavelength, gains);
-        double cLo = p.coLow, cHi = p.coHigh;
-        if (cLo == 0) cLo = 0.01;                                        // TemporalFilter.cpp:11-12
         TailArgs& t = st->tail;
         const int T = st->tailT;
         t.GT = G[T]; t.curT = B.curT;
-        t.nt = B.nt; t.fsT = (long)st->planes * (long)st->g[T].n;
         for (int k = 0; k < t.n; ++k) { t.hi[k] = st->hi[T + k]; t.lo[k] = st->lo[T + k]; t.gain[k] = gains[T + k]; }
-        t.aHi = (float)(1 - cHi); t.bHi = (float)cHi; t.aLo = (float)(1 - cLo); t.bLo = (float)cLo;
-        if (first) LVM_LAUNCH(c, "lap_tail_seed", k_lap_tail<true>, dim3(st->planes), dim3(TAIL_THREADS), s, t);
-        else LVM_LAUNCH(c, "lap_tail", k_lap_tail<false>, dim3(st->planes), dim3(TAIL_THREADS), s, t);
+        t.k = iir_coef(p);
+        auto kt = lvm_pick([](auto seed) { return k_lap_tail<decltype(seed)::value>; }, first);
+        LVM_LAUNCH(c, first ? "lap_tail_seed" : "lap_tail", kt, dim3(st->planes), dim3(TAIL_THREADS), s, t);
     }
 }
 
@@ -1226,17 +1131,26 @@ static int lap_fin_resident(Ctx* c, K kern) {
     return c->fin_occ_groups;
 }
 
+// level l of the up sweep over the frames of B; curn: cur_{l+1} where the launch adds it (block0 is the IIR launch's to fill)
+static LapLevel lap_level(const LaplaceState* st, const LapBufs& B, int l, const float* gains, const float* curn) {
+    const LevelGeom &g = st->g[l], &gn = st->g[l + 1];
+    LapLevel v{};
+    v.Gl = B.G[l]; v.Gn = B.G[l + 1]; v.curn = curn; v.hi = st->hi[l]; v.lo = st->lo[l]; v.cur = B.cur[l];
+    v.w = g.w; v.h = g.h; v.wn = gn.w; v.hn = gn.h; v.gain = gains[l];
+    v.fsl = (long)st->planes * (long)g.n; v.fsn = (long)st->planes * (long)gn.n;
+    v.gw = g.w / 2; v.ngroups = v.gw * ((g.h + 1) / 2); v.top = l == st->levels - 1;
+    return v;
+}
+
 // Stage A of a frame: the fused band/IIR/collapse steps of the levels below T and the final kernel.
 static void lap_stage_a(Ctx* c, LaplaceState* st, const lvm_params& p, const FrameIO& io, const LapBufs& B, bool first, hipStream_t s) {
     const int C = io.channels, levels = st->levels;
     const int NS = c->nstreams * B.nt;
     const dim3 blk(256);
     const LabPlanes lp = lap_planes(c, io, B);
-    float** G = B.G;
     float gains[kMaxLevels + 2];
     laplace_gains(io.w, io.h, levels, p.amplification, p.coWavelength, gains);
-    double cLo = p.coLow, cHi = p.coHigh;
-    if (cLo == 0) cLo = 0.01;                                            // TemporalFilter.cpp:11-12
+    const IirCoef coef = iir_coef(p);
     const bool split = lap_split_now(st, B, first);
     const bool use_tail = st->tailT && B.nt == 1 && !B.no_tail && !split;
     int up_start = use_tail ? st->tailT - 1 : levels - 1;
@@ -1245,73 +1159,54 @@ static void lap_stage_a(Ctx* c, LaplaceState* st, const lvm_params& p, const Fra
     if (split) {
         const int F = (st->split_from == 3 && levels >= 5 && B.nt >= 4) ? 3 : 2;      // (per-frame calls: one launch more would cost more than m_2's round trip)
         IirArgs ia;
-        ia.nlv = levels - F; ia.nt = B.nt;
-        ia.aHi = (float)(1 - cHi); ia.bHi = (float)cHi; ia.aLo = (float)(1 - cLo); ia.bLo = (float)cLo;
+        ia.nlv = levels - F; ia.nt = B.nt; ia.k = coef;
         int blocks = 0;
         for (int l = F; l <= levels - 1; ++l) {          // finest level first: its blocks are the long ones
-            IirLevel& v = ia.lv[l - F];
-            v.Gl = G[l]; v.Gn = G[l + 1]; v.hi = st->hi[l]; v.lo = st->lo[l]; v.out = B.cur[l];
-            v.w = st->g[l].w; v.h = st->g[l].h; v.wn = st->g[l + 1].w; v.hn = st->g[l + 1].h;
-            v.gain = gains[l]; v.fsl = (long)st->planes * (long)st->g[l].n; v.fsn = (long)st->planes * (long)st->g[l + 1].n;
-            v.gw = v.w / 2; v.ngroups = v.gw * ((v.h + 1) / 2); v.block0 = blocks; v.top = l == levels - 1;
+            LapLevel& v = ia.lv[l - F];
+            v = lap_level(st, B, l, gains, nullptr);
+            v.block0 = blocks;
             blocks += (v.ngroups + 255) / 256;
         }
         int depth = 8;
         while (depth > 1 && B.nt % depth != 0) depth >>= 1;
-        auto ki = depth == 8 ? k_lap_iir_levels<8> : (depth == 4 ? k_lap_iir_levels<4> : (depth == 2 ? k_lap_iir_levels<2> : k_lap_iir_levels<1>));
+        auto ki = lvm_pick([](auto d) { return k_lap_iir_levels<decltype(d)::value>; }, PickInt<1, 2, 4, 8>{depth});
         LVM_LAUNCH_V(c, "lap_iir", LVar("d", depth), ki, dim3((unsigned)blocks, (unsigned)st->planes), blk, s, ia);
         if (levels >= F + 2) {
             CollapseArgs ca;
             ca.nlv = levels - F;
             for (int l = F; l <= levels - 1; ++l) { ca.cur[l - F] = B.cur[l]; ca.w[l - F] = st->g[l].w; ca.h[l - F] = st->g[l].h; }
             const dim3 gridc((st->g[F].w + CT_W - 1) / CT_W, (st->g[F].h + CT_H - 1) / CT_H, (unsigned)(st->planes * B.nt));
-            void (*kc)(CollapseArgs) = nullptr;
-            switch (ca.nlv) {
-            case 2: kc = k_lap_collapse<2>; break; case 3: kc = k_lap_collapse<3>; break; case 4: kc = k_lap_collapse<4>; break;
-            case 5: kc = k_lap_collapse<5>; break; case 6: kc = k_lap_collapse<6>; break; case 7: kc = k_lap_collapse<7>; break;
-            case 8: kc = k_lap_collapse<8>; break; case 9: kc = k_lap_collapse<9>; break; default: kc = k_lap_collapse<10>; break;
-            }
+            auto kc = lvm_pick([](auto n) { return k_lap_collapse<decltype(n)::value>; }, PickInt<2, 3, 4, 5, 6, 7, 8, 9, 10>{ca.nlv});
             LVM_LAUNCH_V(c, "lap_collapse", LVar("n", ca.nlv < 10 ? ca.nlv : 10), kc, gridc, blk, s, ca);
         }
         up_start = F - 1;
     }
     for (int l = up_start; l >= 1; --l) {
-        UpArgs a;
-        a.Gl = G[l]; a.Gn = G[l + 1];
-        a.curn = (l + 1 <= levels - 1) ? ((use_tail && l + 1 == st->tailT) ? B.curT : B.cur[l + 1]) : nullptr;
-        a.hi = st->hi[l]; a.lo = st->lo[l]; a.cur = B.cur[l];
-        a.nt = B.nt; a.fsl = (long)st->planes * (long)st->g[l].n; a.fsn = (long)st->planes * (long)st->g[l + 1].n;
-        a.w = st->g[l].w; a.h = st->g[l].h; a.wn = st->g[l + 1].w; a.hn = st->g[l + 1].h;
-        a.aHi = (float)(1 - cHi); a.bHi = (float)cHi; a.aLo = (float)(1 - cLo); a.bLo = (float)cLo;
-        a.gain = gains[l];
-        const dim3 grid((a.w + UT_W - 1) / UT_W, (a.h + UT_H - 1) / UT_H, st->planes);
+        const float* curn = (l + 1 <= levels - 1) ? ((use_tail && l + 1 == st->tailT) ? B.curT : B.cur[l + 1]) : nullptr;
+        const UpArgs a{lap_level(st, B, l, gains, curn), coef, B.nt};
+        const LapLevel& v = a.lv;
+        const dim3 grid((v.w + UT_W - 1) / UT_W, (v.h + UT_H - 1) / UT_H, st->planes);
         const long blocks = (long)grid.x * grid.y * grid.z;
-        if (!first && st->up_rows && a.w % 2 == 0 && blocks < st->up_rows_max_blocks) {
+        const char* hcv = curn ? " curn" : "";                        // (the variant: which ring depth, and whether cur_{l+1} is added)
+        if (!first && st->up_rows && v.w % 2 == 0 && blocks < st->up_rows_max_blocks) {
             // small launches (coarse levels of few streams): barrier-free 2 x 2 blocks per lane with a
             // 4-frame load ring; measured 14-25 us per 16 frames against 27-43 us for the tiled kernel.
             // Large launches keep the LDS-tiled kernel (bandwidth-bound there, and it needs fewer registers).
-            const int gw = a.w / 2;
-            const long ngroups = (long)gw * ((a.h + 1) / 2);
-            const dim3 g2((unsigned)((ngroups + 255) / 256), (unsigned)st->planes);
+            const dim3 g2((unsigned)((v.ngroups + 255) / 256), (unsigned)st->planes);
             int depth = 4;
             while (depth > 1 && a.nt % depth != 0) depth >>= 1;
-            const bool hc = a.curn != nullptr;
-            auto kr = depth == 4 ? (hc ? k_lap_up_rows<2, 4, true> : k_lap_up_rows<2, 4, false>)
-                                 : (depth == 2 ? (hc ? k_lap_up_rows<2, 2, true> : k_lap_up_rows<2, 2, false>)
-                                               : (hc ? k_lap_up_rows<2, 1, true> : k_lap_up_rows<2, 1, false>));
-            LVM_LAUNCH_V(c, LName("lap_up", l), LVar("rows d", depth, hc ? " curn" : ""), kr, g2, blk, s, a, gw, (int)ngroups);
+            auto kr = lvm_pick([](auto d, auto hc) { return k_lap_up_rows<decltype(d)::value, decltype(hc)::value>; }, PickInt<1, 2, 4>{depth}, curn != nullptr);
+            LVM_LAUNCH_V(c, LName("lap_up", l), LVar("rows d", depth, hcv), kr, g2, blk, s, a);
             continue;
         }
         int depth = (blocks >= 1024) ? st->up_depth_big : st->up_depth;   // frame ring of the tiled kernel: 1, 2, 4 or 8 (laplace_switches)
         while (depth > 1 && a.nt % depth != 0) depth >>= 1;           // the ring depth must divide the frame count (a power of two stays one)
-        const char* hcv = a.curn ? " curn" : "";                      // (the variant: which ring depth, and whether cur_{l+1} is added)
-        if (first) LVM_LAUNCH(c, LName("lap_seed", l), (k_lap_up<true, 1>), grid, blk, s, a);
-        else if (depth == 1) LVM_LAUNCH_V(c, LName("lap_up", l), LVar("tiled d", 1, hcv), (k_lap_up<false, 1>), grid, blk, s, a);
-        else if (depth == 2) LVM_LAUNCH_V(c, LName("lap_up", l), LVar("tiled d", 2, hcv), (k_lap_up<false, 2>), grid, blk, s, a);
-        else if (depth == 4) LVM_LAUNCH_V(c, LName("lap_up", l), LVar("tiled d", 4, hcv), (k_lap_up<false, 4>), grid, blk, s, a);
-        else LVM_LAUNCH_V(c, LName("lap_up", l), LVar("tiled d", 8, hcv), (k_lap_up<false, 8>), grid, blk, s, a);
+        // (the seed launch keeps nothing in flight: one instance, depth 1)
+        auto ku = lvm_pick([](auto seed, auto d) { constexpr bool S = decltype(seed)::value; return k_lap_up<S, S ? 1 : decltype(d)::value>; }, first, PickInt<1, 2, 4, 8>{depth});
+        if (first) LVM_LAUNCH(c, LName("lap_seed", l), ku, grid, blk, s, a);
+        else LVM_LAUNCH_V(c, LName("lap_up", l), LVar("tiled d", depth, hcv), ku, grid, blk, s, a);
     }
-    const int fl = lab_flavour(c);
+    const auto fl = pick_flavour(lab_flavour(c));
     float* dbg = (c->keep_float && B.dbg_frame) ? c->d_float.as<float>() : nullptr;   // (the float frame kept is the first one of the batch)
     const int tx = (io.w + UT_W - 1) / UT_W, ty = (io.h + UT_H - 1) / UT_H;
     const int ntiles = tx * ty * NS;
@@ -1320,10 +1215,9 @@ static void lap_stage_a(Ctx* c, LaplaceState* st, const lvm_params& p, const Fra
     const float ca = (float)p.chromAttenuation;
     const float* cur1 = motion ? ((use_tail && st->tailT == 1) ? B.curT : B.cur[1]) : nullptr;
     const int w1 = st->g[1].w, h1 = st->g[1].h;
-    auto kf4 = dbg ? (motion ? LVM_FL_PICK(fl, k_lap_final_v4, true, true) : LVM_FL_PICK(fl, k_lap_final_v4, false, true))
-                   : (motion ? LVM_FL_PICK(fl, k_lap_final_v4, true, false) : LVM_FL_PICK(fl, k_lap_final_v4, false, false));
-    auto kf = (C == 3) ? (motion ? LVM_FL_PICK(fl, k_lap_final, 3, true) : LVM_FL_PICK(fl, k_lap_final, 3, false))
-                       : (motion ? k_lap_final<1, true, FL_LUT_EXACT> : k_lap_final<1, false, FL_LUT_EXACT>);
+    auto kf4 = lvm_pick([](auto m, auto d, auto f) { return k_lap_final_v4<decltype(m)::value, decltype(d)::value, decltype(f)::value>; }, motion, dbg != nullptr, fl);
+    // (gray frames have no Lab conversion: one instance per MOTION, whatever the flavour)
+    auto kf = lvm_pick([](auto c3, auto m, auto f) { constexpr bool C3 = decltype(c3)::value; return k_lap_final<C3 ? 3 : 1, decltype(m)::value, C3 ? decltype(f)::value : FL_LUT_EXACT>; }, C == 3, motion, fl);
     if (lap_vec4(io)) {
         // wave strips of 256 x rows pixels; shorter strips when there are few of them (per-frame calls)
         const int sx = (io.w + 255) / 256;

@@ -416,19 +416,6 @@ __device__ __forceinline__ T wg_exclusive_scan(T* s, int n, T* part, int tid) {
     __syncthreads();
     return total;
 }
-// pyrUp horizontal pass for destination column gx from source row `s` whose element for
-// source column i sits at s[i - sx0] (OpenCV pyrUp_ border rules, see laplace.hip).
-__device__ __forceinline__ float pyrup_h(const float* s, int gx, int sx0, int sw) {
-    // all border variants are evaluated on clamped indices and the result selected: no divergent branches
-    const int i = gx >> 1, li = i - sx0;
-    const bool first = i == 0, last = i == sw - 1;
-    const float sm1 = s[first ? li : li - 1], s0 = s[li], s1 = s[last ? li : li + 1];
-    const float p6 = s0 * 6.f;
-    const float even = sel(first, p6 + s1 * 2.f, sel(last, sm1 + s0 * 7.f, sm1 + p6 + s1));
-    const float odd = sel(last, s0 * 8.f, (s0 + s1) * 4.f);
-    return sel((gx & 1) == 0, even, odd);
-}
-
 // ---------------------------------------------------------------------------------------
 // host-side context
 // ---------------------------------------------------------------------------------------
@@ -554,9 +541,6 @@ struct Ctx {
 };
 
 inline int lab_flavour(const Ctx* c) { return c->lab_analytic ? FL_ANALYTIC : (c->exact_lab ? FL_LUT_EXACT : FL_LUT_FAST); }
-// kernel instantiation of the context's flavour: LVM_FL_PICK(fl, k_name, other template arguments...)
-#define LVM_FL_PICK(fl, K, ...) ((fl) == FL_ANALYTIC ? K<__VA_ARGS__, FL_ANALYTIC> : ((fl) == FL_LUT_EXACT ? K<__VA_ARGS__, FL_LUT_EXACT> : K<__VA_ARGS__, FL_LUT_FAST>))
-#define LVM_FL_PICK0(fl, K) ((fl) == FL_ANALYTIC ? K<FL_ANALYTIC> : ((fl) == FL_LUT_EXACT ? K<FL_LUT_EXACT> : K<FL_LUT_FAST>))
 // Run-time values -> template arguments: lvm_pick(f, v...) calls the generic lambda f with one std::integral_constant per value -- a bool
 // as std::true_type / std::false_type, an int that is one of Vs... (the last of them when it is none) as PickInt<Vs...>{v} -- and returns
 // what f returns, a kernel instantiation.  Every call of f must return the same type; f instantiates only the combinations it names, so a

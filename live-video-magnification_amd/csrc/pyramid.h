@@ -14,6 +14,17 @@ namespace lvm {
 constexpr int DT_W = 32, DT_H = 16;
 constexpr int DS_W = 2 * DT_W + 3, DS_H = 2 * DT_H + 3;
 
+// The 5-tap sum of both passes, taps a .. e left to right (c the centre): c*6 + (b+d)*4 + a + e in exactly this order, which is OpenCV's;
+// FMA = the same sum as two fmas (two roundings less: the default flavour's first kernels, LVM_FAST_FMA, and exact sums).  The
+// vertical pass scales by 1/256.
+template <bool FMA>
+__device__ __forceinline__ float pyrdown_taps(float a, float b, float c, float d, float e) {
+    if (FMA) return __builtin_fmaf(c, 6.f, __builtin_fmaf(b + d, 4.f, a + e));
+    return c * 6.f + (b + d) * 4.f + a + e;
+}
+template <bool FMA>
+__device__ __forceinline__ float pyrdown_taps_v(float a, float b, float c, float d, float e) { return pyrdown_taps<FMA>(a, b, c, d, e) * (1.f / 256.f); }
+
 template <int C>
 __device__ __forceinline__ void pyrdown_tile(float (&s_src)[C][DS_H][DS_W], float (&s_row)[C][DS_H][DT_W],
                                              float* __restrict__ dst, int dw, int dh, size_t dplane,
@@ -24,7 +35,7 @@ __device__ __forceinline__ void pyrdown_tile(float (&s_src)[C][DS_H][DS_W], floa
         const int r = i - c * (DS_H * DT_W);
         const int ly = r / DT_W, x = r - ly * DT_W;
         const float* s = &s_src[c][ly][2 * x];
-        s_row[c][ly][x] = s[2] * 6.f + (s[1] + s[3]) * 4.f + s[0] + s[4];
+        s_row[c][ly][x] = pyrdown_taps<false>(s[0], s[1], s[2], s[3], s[4]);
     }
     __syncthreads();
     for (int i = tid; i < C * DT_H * DT_W; i += 256) {
@@ -35,7 +46,7 @@ __device__ __forceinline__ void pyrdown_tile(float (&s_src)[C][DS_H][DS_W], floa
         if (gx < dw && gy < dh) {
             const float r0 = s_row[c][2 * y][x], r1 = s_row[c][2 * y + 1][x], r2 = s_row[c][2 * y + 2][x],
                         r3 = s_row[c][2 * y + 3][x], r4 = s_row[c][2 * y + 4][x];
-            dst[c * dplane + (size_t)gy * dw + gx] = (r2 * 6.f + (r1 + r3) * 4.f + r0 + r4) * (1.f / 256.f);
+            dst[c * dplane + (size_t)gy * dw + gx] = pyrdown_taps_v<false>(r0, r1, r2, r3, r4);
         }
     }
 }
@@ -105,17 +116,34 @@ constexpr int UT_W = LVM_UT_W, UT_H = LVM_UT_H;     // (128 x 8 measured too: se
 static_assert(UT_W * UT_H == 1024 && UT_W % 2 == 0 && UT_H % 2 == 0, "four pixels per thread of a 256-thread workgroup");
 constexpr int US_W = UT_W / 2 + 2, US_H = UT_H / 2 + 2;
 
-// stage the source tile of one plane: rows sy0..sy0+US_H-1 (vertical border map), columns
-// sx0..sx0+US_W-1 clamped into the plane (border columns are handled by pyrup_h's formulas)
+// The source border map: row -1 -> 1, row sh -> sh - 1; columns are clamped into the plane (a clamped column is only ever loaded,
+// the border columns' formulas of pyrup_h_pair do not use it)
+__device__ __forceinline__ int pyrup_src_row(int sy, int sh) { return sy < 0 ? 1 : (sy >= sh ? sh - 1 : sy); }
+__device__ __forceinline__ int pyrup_src_col(int sx, int sw) { return sx < 0 ? 0 : (sx >= sw ? sw - 1 : sx); }
+// The horizontal pass of one source column i: destination columns 2i (e) and 2i + 1 (o) from s[i-1], s[i], s[i+1]; first: i == 0,
+// last: i == sw - 1.  Every border variant is evaluated and the result selected (v_cndmask): divergent branches around two or three
+// float operations cost far more than the operations.
+struct UpPair { float e, o; };
+__device__ __forceinline__ UpPair pyrup_h_pair(float sm1, float s0, float s1, bool first, bool last) {
+    const float p6 = s0 * 6.f;
+    const float e_gen = sm1 + p6 + s1, e_first = p6 + s1 * 2.f, e_last = sm1 + s0 * 7.f;
+    const float o_gen = (s0 + s1) * 4.f, o_last = s0 * 8.f;
+    return UpPair{sel(first, e_first, sel(last, e_last, e_gen)), sel(last, o_last, o_gen)};
+}
+// ... for destination column gx from source row `s` whose element for source column i sits at s[i - sx0] (indices clamped)
+__device__ __forceinline__ float pyrup_h(const float* s, int gx, int sx0, int sw) {
+    const int i = gx >> 1, li = i - sx0;
+    const bool first = i == 0, last = i == sw - 1;
+    const UpPair p = pyrup_h_pair(s[first ? li : li - 1], s[li], s[last ? li : li + 1], first, last);
+    return sel((gx & 1) == 0, p.e, p.o);
+}
+
+// stage the source tile of one plane: rows sy0..sy0+US_H-1, columns sx0..sx0+US_W-1 through the border map
 __device__ __forceinline__ void pyrup_stage(float (&s)[US_H][US_W + 1], const float* __restrict__ src,
                                             int sw, int sh, int sx0, int sy0) {
     for (int i = threadIdx.x; i < US_H * US_W; i += 256) {
         const int ly = i / US_W, lx = i - ly * US_W;
-        int gy = sy0 + ly;
-        gy = gy < 0 ? 1 : (gy >= sh ? sh - 1 : gy);
-        int gx = sx0 + lx;
-        gx = gx < 0 ? 0 : (gx >= sw ? sw - 1 : gx);
-        s[ly][lx] = src[(size_t)gy * sw + gx];
+        s[ly][lx] = src[(size_t)pyrup_src_row(sy0 + ly, sh) * sw + pyrup_src_col(sx0 + lx, sw)];
     }
 }
 // horizontal pass of the staged tile into hrow[US_H][UT_W]
@@ -130,20 +158,9 @@ __device__ __forceinline__ void pyrup_hpass(float (&hrow)[US_H][UT_W + 1], const
 // pyrUp horizontal pass for 4 consecutive destination columns gx0..gx0+3 (gx0 even) from the source
 // values s[i0-1..i0+2], i0 = gx0/2 (indices outside the plane are never used by the border rules)
 __device__ __forceinline__ float4 pyrup_h4(float sm1, float s0, float s1, float s2, int i0, int sw) {
-    // every border variant is evaluated and the result selected (v_cndmask): divergent branches around
-    // two or three float operations cost far more than the operations
-    const bool f0 = i0 == 0, l0 = i0 == sw - 1, l1 = i0 + 1 == sw - 1;
-    const float p6 = s0 * 6.f, q6 = s1 * 6.f;
-    const float e_gen = sm1 + p6 + s1, e_first = p6 + s1 * 2.f, e_last = sm1 + s0 * 7.f;
-    const float o_gen = (s0 + s1) * 4.f, o_last = s0 * 8.f;
-    const float z_gen = s0 + q6 + s2, z_last = s0 + s1 * 7.f;      // i0 + 1 >= 1 always
-    const float w_gen = (s1 + s2) * 4.f, w_last = s1 * 8.f;
-    float4 o;
-    o.x = sel(f0, e_first, sel(l0, e_last, e_gen));
-    o.y = sel(l0, o_last, o_gen);
-    o.z = sel(l1, z_last, z_gen);
-    o.w = sel(l1, w_last, w_gen);
-    return o;
+    const UpPair a = pyrup_h_pair(sm1, s0, s1, i0 == 0, i0 == sw - 1);
+    const UpPair b = pyrup_h_pair(s0, s1, s2, false, i0 + 1 == sw - 1);      // (column i0 + 1 is never the first)
+    return make_float4(a.e, a.o, b.e, b.o);
 }
 // pyrUp vertical pass, the pair: destination row 2j from the horizontal passes of the source rows j-1, j, j+1, row 2j+1 from those of j, j+1
 __device__ __forceinline__ float pyrup_v_even(float h0, float h1, float h2) { return (h0 + h1 * 6.f + h2) * (1.f / 64.f); }
@@ -248,12 +265,10 @@ __global__ __launch_bounds__(256) void k_down0_v4(const uint8_t* __restrict__ in
             // default flavour: the fma chains of the strip kernels (k_down0_rows, k_down0_lut_rows), so that level 1 -- and the output
             // bytes -- do not depend on which first kernel the launch size picks (per-frame calls vs temporal batches)
             constexpr bool FMA = !fl_exact(FL) && LVM_FAST_FMA;
-            const float ha = FMA ? __builtin_fmaf(u.z, 6.f, __builtin_fmaf(u.y + u.w, 4.f, u.x + v.x)) : u.z * 6.f + (u.y + u.w) * 4.f + u.x + v.x;
-            const float hb = FMA ? __builtin_fmaf(v.x, 6.f, __builtin_fmaf(u.w + v.y, 4.f, u.z + v.z)) : v.x * 6.f + (u.w + v.y) * 4.f + u.z + v.z;
+            const float ha = pyrdown_taps<FMA>(u.x, u.y, u.z, u.w, v.x), hb = pyrdown_taps<FMA>(u.z, u.w, v.x, v.y, v.z);
             if (rr >= 4 && (rr & 1) == 0) {
                 const int gy = oy0 + 4 * seg + (rr - 4) / 2, gx = ox0 + x;
-                const float oa = (FMA ? __builtin_fmaf(w2a, 6.f, __builtin_fmaf(w1a + w3a, 4.f, w0a + ha)) : w2a * 6.f + (w1a + w3a) * 4.f + w0a + ha) * (1.f / 256.f);
-                const float ob = (FMA ? __builtin_fmaf(w2b, 6.f, __builtin_fmaf(w1b + w3b, 4.f, w0b + hb)) : w2b * 6.f + (w1b + w3b) * 4.f + w0b + hb) * (1.f / 256.f);
+                const float oa = pyrdown_taps_v<FMA>(w0a, w1a, w2a, w3a, ha), ob = pyrdown_taps_v<FMA>(w0b, w1b, w2b, w3b, hb);
                 if (gy < h1) {
                     if ((w1 & 1) == 0 && gx + 1 < w1) *reinterpret_cast<float2*>(&dst[(size_t)gy * w1 + gx]) = make_float2(oa, ob);
                     else {
@@ -282,8 +297,7 @@ __device__ __forceinline__ void pyr_up_rows_block(int gi, const float* __restric
     float4 h[3];
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
-        int sy = j - 1 + q; sy = sy < 0 ? 1 : (sy >= sh ? sh - 1 : sy);       // vertical border map: row -1 -> 1, row sh -> sh - 1
-        const float* r = sp + (size_t)sy * sw;
+        const float* r = sp + (size_t)pyrup_src_row(j - 1 + q, sh) * sw;
         h[q] = pyrup_h4(ld(r + cm1), ld(r + i0), ld(r + cp1), ld(r + cp2), i0, sw);
     }
     float* d0 = dp + (size_t)(2 * j) * dw + gx;
@@ -328,7 +342,7 @@ template <bool LAB, int FL>
 __global__ __launch_bounds__(D0R_THREADS) void k_down0_rows(const uint8_t* __restrict__ in, long in_stride, long in_sstride,
                                                             int w, int h, float* __restrict__ G1, int w1, int h1, LabCoef lab,
                                                             int strips_x, int strips_y, int ntasks, int rows, LabPlanes lp) {
-    constexpr bool EXACT = fl_exact(FL);
+    constexpr bool FMA = !fl_exact(FL) && LVM_FAST_FMA;    // default flavour: the tap sums as two fmas
     constexpr bool PLANES = LAB && fl_lut(FL);
     __shared__ float s_gam[LAB && !fl_lut(FL) ? 256 : 1];
     if (LAB && !fl_lut(FL)) { load_gamma_u8(s_gam, lab.gamma_u8); __syncthreads(); }
@@ -365,13 +379,8 @@ __global__ __launch_bounds__(D0R_THREADS) void k_down0_rows(const uint8_t* __res
             // Mirrored groups: pixels -2, -1 are pixels 2, 1 of group 0; pixel w is pixel w-2 = pixel 2 of the last group.
             const float give2 = P[c][2], give3 = left_mirror ? P[c][1] : P[c][3], give0 = right_mirror ? P[c][2] : P[c][0];
             const float L2 = dpp_shr1(give2), L3 = dpp_shr1(give3), R0 = dpp_shl1(give0);
-            if (!EXACT && LVM_FAST_FMA) {   // default flavour: the same sum as two fmas (two roundings less)
-                ha[c] = __builtin_fmaf(P[c][0], 6.f, __builtin_fmaf(L3 + P[c][1], 4.f, L2 + P[c][2]));
-                hb[c] = __builtin_fmaf(P[c][2], 6.f, __builtin_fmaf(P[c][1] + P[c][3], 4.f, P[c][0] + R0));
-            } else {
-                ha[c] = P[c][0] * 6.f + (L3 + P[c][1]) * 4.f + L2 + P[c][2];
-                hb[c] = P[c][2] * 6.f + (P[c][1] + P[c][3]) * 4.f + P[c][0] + R0;
-            }
+            ha[c] = pyrdown_taps<FMA>(L2, L3, P[c][0], P[c][1], P[c][2]);
+            hb[c] = pyrdown_taps<FMA>(P[c][0], P[c][1], P[c][2], P[c][3], R0);
         }
     };
     const int yend = oy0 + rows < h1 ? oy0 + rows : h1;
@@ -389,14 +398,7 @@ __global__ __launch_bounds__(D0R_THREADS) void k_down0_rows(const uint8_t* __res
         if (owner) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                float va, vb;
-                if (!EXACT && LVM_FAST_FMA) {
-                    va = __builtin_fmaf(a2[c], 6.f, __builtin_fmaf(a1[c] + a3[c], 4.f, a0[c] + a4[c])) * (1.f / 256.f);
-                    vb = __builtin_fmaf(b2[c], 6.f, __builtin_fmaf(b1[c] + b3[c], 4.f, b0[c] + b4[c])) * (1.f / 256.f);
-                } else {
-                    va = (a2[c] * 6.f + (a1[c] + a3[c]) * 4.f + a0[c] + a4[c]) * (1.f / 256.f);
-                    vb = (b2[c] * 6.f + (b1[c] + b3[c]) * 4.f + b0[c] + b4[c]) * (1.f / 256.f);
-                }
+                const float va = pyrdown_taps_v<FMA>(a0[c], a1[c], a2[c], a3[c], a4[c]), vb = pyrdown_taps_v<FMA>(b0[c], b1[c], b2[c], b3[c], b4[c]);
                 *reinterpret_cast<float2*>(dst + c * plane + (size_t)oy * w1 + ox) = make_float2(va, vb);
             }
         }
@@ -443,7 +445,7 @@ struct D0LArgs {
 // one wave strip (task) of the fused conversion + first pyramid kernel; s_ab = the (a, b) node table in LDS
 template <int FL>
 __device__ __forceinline__ void down0_lut_strip(const D0LArgs& q, int task, int lane, const uint32_t* s_ab) {
-    constexpr bool EXACT = fl_exact(FL);
+    constexpr bool FMA = !fl_exact(FL) && LVM_FAST_FMA;
     const uint8_t* __restrict__ in = q.in; const long in_stride = q.in_stride, in_sstride = q.in_sstride;
     const int w = q.w, h = q.h, w1 = q.w1, h1 = q.h1, strips_x = q.strips_x, strips_y = q.strips_y, rows = q.rows;
     float* __restrict__ G1 = q.G1; const LabLut lut = q.lut;
@@ -507,13 +509,8 @@ __device__ __forceinline__ void down0_lut_strip(const D0LArgs& q, int task, int 
         for (int c = 0; c < 3; ++c) {
             const float give2 = P[c][2], give3 = left_mirror ? P[c][1] : P[c][3], give0 = right_mirror ? P[c][2] : P[c][0];
             const float L2 = dpp_shr1(give2), L3 = dpp_shr1(give3), R0 = dpp_shl1(give0);
-            if (!EXACT && LVM_FAST_FMA) {
-                ha[c] = __builtin_fmaf(P[c][0], 6.f, __builtin_fmaf(L3 + P[c][1], 4.f, L2 + P[c][2]));
-                hb[c] = __builtin_fmaf(P[c][2], 6.f, __builtin_fmaf(P[c][1] + P[c][3], 4.f, P[c][0] + R0));
-            } else {
-                ha[c] = P[c][0] * 6.f + (L3 + P[c][1]) * 4.f + L2 + P[c][2];
-                hb[c] = P[c][2] * 6.f + (P[c][1] + P[c][3]) * 4.f + P[c][0] + R0;
-            }
+            ha[c] = pyrdown_taps<FMA>(L2, L3, P[c][0], P[c][1], P[c][2]);
+            hb[c] = pyrdown_taps<FMA>(P[c][0], P[c][1], P[c][2], P[c][3], R0);
         }
     };
     float a0[3], a1[3], a2[3], a3[3], a4[3], b0[3], b1[3], b2[3], b3[3], b4[3];
@@ -527,14 +524,7 @@ __device__ __forceinline__ void down0_lut_strip(const D0LArgs& q, int task, int 
         if (owner) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                float va, vb;
-                if (!EXACT && LVM_FAST_FMA) {
-                    va = __builtin_fmaf(a2[c], 6.f, __builtin_fmaf(a1[c] + a3[c], 4.f, a0[c] + a4[c])) * (1.f / 256.f);
-                    vb = __builtin_fmaf(b2[c], 6.f, __builtin_fmaf(b1[c] + b3[c], 4.f, b0[c] + b4[c])) * (1.f / 256.f);
-                } else {
-                    va = (a2[c] * 6.f + (a1[c] + a3[c]) * 4.f + a0[c] + a4[c]) * (1.f / 256.f);
-                    vb = (b2[c] * 6.f + (b1[c] + b3[c]) * 4.f + b0[c] + b4[c]) * (1.f / 256.f);
-                }
+                const float va = pyrdown_taps_v<FMA>(a0[c], a1[c], a2[c], a3[c], a4[c]), vb = pyrdown_taps_v<FMA>(b0[c], b1[c], b2[c], b3[c], b4[c]);
                 *reinterpret_cast<float2*>(dst + c * plane + (size_t)oy * w1 + ox) = make_float2(va, vb);
             }
         }
@@ -613,8 +603,8 @@ __global__ __launch_bounds__(D01_THREADS) void k_down01_rows(D01Args q) {
             const float p0 = (float)pb[c], p1 = (float)pb[3 + c], p2 = (float)pb[6 + c], p3 = (float)pb[9 + c];
             const float give2 = p2, give3 = left_mirror ? p1 : p3, give0 = right_mirror ? p2 : p0;
             const float L2 = dpp_shr1(give2), L3 = dpp_shr1(give3), R0 = dpp_shl1(give0);
-            ha[c] = __builtin_fmaf(p0, 6.f, __builtin_fmaf(L3 + p1, 4.f, L2 + p2));
-            hb[c] = __builtin_fmaf(p2, 6.f, __builtin_fmaf(p1 + p3, 4.f, p0 + R0));
+            ha[c] = pyrdown_taps<true>(L2, L3, p0, p1, p2);
+            hb[c] = pyrdown_taps<true>(p0, p1, p2, p3, R0);
         }
     };
     const int Y0 = ty * rows, Yend = Y0 + rows < h2 ? Y0 + rows : h2;
@@ -631,12 +621,11 @@ __global__ __launch_bounds__(D01_THREADS) void k_down01_rows(D01Args q) {
         n0 = fetch(2 * rv + 5); n1 = fetch(2 * rv + 6);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            const float va = __builtin_fmaf(a2[c], 6.f, __builtin_fmaf(a1[c] + a3[c], 4.f, a0[c] + a4[c])) * (1.f / 256.f);
-            const float vb = __builtin_fmaf(b2[c], 6.f, __builtin_fmaf(b1[c] + b3[c], 4.f, b0[c] + b4[c])) * (1.f / 256.f);
+            const float va = pyrdown_taps_v<true>(a0[c], a1[c], a2[c], a3[c], a4[c]), vb = pyrdown_taps_v<true>(b0[c], b1[c], b2[c], b3[c], b4[c]);
             float Lm2 = dpp_shr1(va), Lm1 = dpp_shr1(vb), Rp = dpp_shl1(va);
             Lm2 = sel(first2, Rp, Lm2); Lm1 = sel(first2, vb, Lm1);   // level-1 columns -2, -1 = columns 2, 1
             Rp = sel(last2, va, Rp);                                  // level-1 column w1 = column w1 - 2
-            H2[c] = __builtin_fmaf(va, 6.f, __builtin_fmaf(Lm1 + vb, 4.f, Lm2 + Rp));
+            H2[c] = pyrdown_taps<true>(Lm2, Lm1, va, vb, Rp);
             a0[c] = a2[c]; a1[c] = a3[c]; a2[c] = a4[c]; b0[c] = b2[c]; b1[c] = b3[c]; b2[c] = b4[c];
         }
         ++rv;
@@ -669,7 +658,7 @@ __global__ __launch_bounds__(D01_THREADS) void k_down01_rows(D01Args q) {
         if (owner) {
 #pragma unroll
             for (int c = 0; c < 3; ++c)
-                dst[c * plane + (size_t)Y * w2] = __builtin_fmaf(w2r[c], 6.f, __builtin_fmaf(w1[c] + w3[c], 4.f, w0[c] + w4[c])) * (1.f / 256.f);
+                dst[c * plane + (size_t)Y * w2] = pyrdown_taps_v<true>(w0[c], w1[c], w2r[c], w3[c], w4[c]);
         }
 #pragma unroll
         for (int c = 0; c < 3; ++c) { w0[c] = w2r[c]; w1[c] = w3[c]; w2r[c] = w4[c]; }
@@ -717,8 +706,8 @@ __global__ __launch_bounds__(PD_THREADS) void k_pyr_down_rows(const float* __res
 #pragma unroll
             for (int k = 0; k < 7; ++k) t[k] = *reinterpret_cast<const float*>(row + off[k]);
         }
-        ha = t[2] * 6.f + (t[1] + t[3]) * 4.f + t[0] + t[4];
-        hb = t[4] * 6.f + (t[3] + t[5]) * 4.f + t[2] + t[6];
+        ha = pyrdown_taps<false>(t[0], t[1], t[2], t[3], t[4]);
+        hb = pyrdown_taps<false>(t[2], t[3], t[4], t[5], t[6]);
     };
     const int yend = oy0 + rows < dh ? oy0 + rows : dh;
     float a0, a1, a2, a3, a4, b0, b1, b2, b3, b4;
@@ -726,8 +715,7 @@ __global__ __launch_bounds__(PD_THREADS) void k_pyr_down_rows(const float* __res
     const bool pair_store = (dw & 1) == 0;
     for (int oy = oy0; oy < yend; ++oy) {
         hpair(2 * oy + 1, a3, b3); hpair(2 * oy + 2, a4, b4);
-        const float va = (a2 * 6.f + (a1 + a3) * 4.f + a0 + a4) * (1.f / 256.f);
-        const float vb = (b2 * 6.f + (b1 + b3) * 4.f + b0 + b4) * (1.f / 256.f);
+        const float va = pyrdown_taps_v<false>(a0, a1, a2, a3, a4), vb = pyrdown_taps_v<false>(b0, b1, b2, b3, b4);
         float* q = dp + (size_t)oy * dw + ox;
         if (pair_store) *reinterpret_cast<float2*>(q) = make_float2(va, vb);
         else { q[0] = va; if (ox + 1 < dw) q[1] = vb; }
@@ -742,6 +730,8 @@ __global__ __launch_bounds__(PD_THREADS) void k_pyr_down_rows(const float* __res
 // positions outside an image are never computed: readers apply REFLECT_101 at that level and the
 // mirrored position is always inside the stored (clipped) region.  Replaces NL launches that are
 // each launch/latency-bound (6-7 us on MI355X) by one.
+// Its six tap sums are its own text of pyrdown_taps / pyrdown_taps_v<false> (an exception by measurement: written as calls the kernel's
+// loads are issued in another order and its launches measured 0.4 us longer, profiles/r18_laplace_shared_text.txt).
 constexpr int ML_T = 8;                       // owned tile of the coarsest level
 template <int NL>
 __global__ __launch_bounds__(256) void k_pyr_down_multi(const float* __restrict__ src, int w0, int h0,
