@@ -18,26 +18,34 @@
 
 namespace lvm {
 
+// The panes of a canvas, on the host and as the pane part of both kernels' arguments: the two sources ([0] original, [1] processed; BGR or gray),
+// the pane size (the frames' common even size) and where pane 1 starts on the canvas.  With one pane only src[1] is read.
+struct Panes {
+    const uint8_t* src[2]; long stride[2]; int cn[2];
+    int w, h;
+    int npanes, dx1, dy1;
+};
+
+
 struct ComposeArgs {
-    const uint8_t* src[2]; long stride[2], sstride[2]; int cn[2];   // [0] original, [1] processed
+    Panes p; long sstride[2];
     uint8_t* dst; long dst_stride, dst_sstride;
-    int w, h;                 // pane size (common even size)
-    int npanes, dx1, dy1;     // pane 1 (processed) origin on the canvas; with one pane only src[1] is used
 };
 
 // One thread per group of 4 canvas pixels of one pane row (12 output bytes as three dwords when the canvas row
-// allows it, bytes otherwise); blockIdx.z = stream * npanes + pane.
+// allows it, bytes otherwise); blockIdx.z = stream * npanes + pane.  (The dword packing is written out: lvm_pack_b4 costs this kernel
+// 23 instructions -- the compiler builds these dwords from the byte loads better than from three v_perm_b32.)
 template <bool VEC>
 __global__ __launch_bounds__(256) void k_compose(ComposeArgs a) {
     const int gx = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4, y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (gx >= a.w || y >= a.h) return;
-    const int pane = a.npanes == 2 ? (int)(blockIdx.z & 1) : 1, stream = a.npanes == 2 ? (int)(blockIdx.z >> 1) : (int)blockIdx.z;
-    const uint8_t* p = a.src[pane] + (size_t)stream * a.sstride[pane] + (size_t)y * a.stride[pane];
-    const int ox = pane ? a.dx1 : 0, oy = pane ? a.dy1 : 0;
+    if (gx >= a.p.w || y >= a.p.h) return;
+    const int pane = a.p.npanes == 2 ? (int)(blockIdx.z & 1) : 1, stream = a.p.npanes == 2 ? (int)(blockIdx.z >> 1) : (int)blockIdx.z;
+    const uint8_t* p = a.p.src[pane] + (size_t)stream * a.sstride[pane] + (size_t)y * a.p.stride[pane];
+    const int ox = pane ? a.p.dx1 : 0, oy = pane ? a.p.dy1 : 0;
     uint8_t* q = a.dst + (size_t)stream * a.dst_sstride + (size_t)(oy + y) * a.dst_stride + (size_t)(ox + gx) * 3;
-    const int n = a.w - gx < 4 ? a.w - gx : 4;
+    const int n = a.p.w - gx < 4 ? a.p.w - gx : 4;
     uint8_t v[12];
-    if (a.cn[pane] == 3) {
+    if (a.p.cn[pane] == 3) {
 #pragma unroll
         for (int k = 0; k < 12; ++k) v[k] = k < 3 * n ? p[(size_t)gx * 3 + k] : 0;
     } else {
@@ -107,9 +115,10 @@ int overlay_set(Ctx* c, int n, const lvm_overlay_label* labels) {
 }
 
 // the labels onto n_frames canvases of cw x chh (nothing to do without labels)
-int overlay_device(Ctx* c, uint8_t* d_canvas, int cw, int chh, ptrdiff_t stride, ptrdiff_t fstride, int n_frames, hipStream_t s) {
+int overlay_device(Ctx* c, const ImageOut& canvas, int n_frames, hipStream_t s) {
+    const int cw = canvas.w, chh = canvas.h;
     if (c->overlay_n == 0 || n_frames < 1) return LVM_OK;
-    if (!d_canvas || stride < (ptrdiff_t)cw * 3 || (n_frames > 1 && fstride < (ptrdiff_t)chh * stride)) { c->err = "overlay: bad canvas arguments"; return LVM_ERR_INVALID; }
+    if (!canvas.p || canvas.stride < (ptrdiff_t)cw * 3 || (n_frames > 1 && canvas.sstride < (ptrdiff_t)chh * canvas.stride)) { c->err = "overlay: bad canvas arguments"; return LVM_ERR_INVALID; }
     OverlayArgs a{};
     a.n = c->overlay_n; a.first[0] = 0;
     for (int l = 0; l < a.n; ++l) {
@@ -120,7 +129,7 @@ int overlay_device(Ctx* c, uint8_t* d_canvas, int cw, int chh, ptrdiff_t stride,
         a.first[l + 1] = a.first[l] + a.w[l] * a.h[l];
         a.cls[l] = reinterpret_cast<const uint16_t*>(c->d_overlay + c->ov_cls[l]); a.fn[l] = c->d_overlay + c->ov_fn[l];
     }
-    a.canvas = d_canvas; a.stride = (long)stride; a.fstride = (long)fstride;
+    a.canvas = canvas.p; a.stride = (long)canvas.stride; a.fstride = (long)canvas.sstride;
     LVM_LAUNCH(c, "overlay", k_overlay_labels, dim3((unsigned)((a.first[a.n] + 255) / 256), (unsigned)n_frames), dim3(256), s, a);
     LVM_HIP_TRY(c, hipGetLastError());
     return LVM_OK;
@@ -138,32 +147,45 @@ int compose_geometry(int split, int ow, int oh, int pw, int ph, int* pane_w, int
     return 1;
 }
 
-int compose_device(Ctx* c, int split, const uint8_t* d_orig, int ow, int oh, int och, ptrdiff_t ostride, ptrdiff_t osstride,
-                   const uint8_t* d_proc, int pw, int ph, int pch, ptrdiff_t pstride, ptrdiff_t psstride, uint8_t* d_canvas,
-                   ptrdiff_t cstride, ptrdiff_t csstride, hipStream_t s) {
+// The panes of a canvas from the two frames, for compose_device and canvas_yuv_fused alike (Exporter.cpp:53-66): the split and frame checks, the
+// processed frame in place of a missing original (:62), the geometry, the row strides.  `canvas_error(canvas_w, canvas_h)` is the caller's check of
+// its destination, made once the canvas size is known (null: fine).  p->w == 0 on return: an empty canvas, nothing to write.
+template <class CanvasError>
+static int panes_resolve(Ctx* c, int split, Image orig, const Image& proc, const void* dst, Panes* p, CanvasError&& canvas_error) {
+    *p = Panes{};
     if (split < LVM_SPLIT_NONE || split > LVM_SPLIT_TOP_BOTTOM) { c->err = "invalid split mode"; return LVM_ERR_INVALID; }
-    if (!d_proc || !d_canvas || (pch != 1 && pch != 3)) { c->err = "bad processed frame"; return LVM_ERR_INVALID; }
-    if (split != LVM_SPLIT_NONE && !d_orig) { d_orig = d_proc; ow = pw; oh = ph; och = pch; ostride = pstride; osstride = psstride; }   // :62 fall back
-    if (split != LVM_SPLIT_NONE && och != 1 && och != 3) { c->err = "bad original frame"; return LVM_ERR_INVALID; }
+    if (!proc.p || !dst || (proc.cn != 1 && proc.cn != 3)) { c->err = "bad processed frame"; return LVM_ERR_INVALID; }
+    const bool two = split != LVM_SPLIT_NONE;
+    if (!two || !orig.p) orig = proc;
+    if (orig.cn != 1 && orig.cn != 3) { c->err = "bad original frame"; return LVM_ERR_INVALID; }
     int w, h, cw, chh;
-    if (!compose_geometry(split, ow, oh, pw, ph, &w, &h, &cw, &chh)) return LVM_OK;    // empty canvas: nothing to write
-    if (cstride < (ptrdiff_t)cw * 3) { c->err = "canvas stride too small"; return LVM_ERR_INVALID; }
-    // the kernel indexes the frames with the caller's strides: rows must hold their pixels, streams must not overlap
-    if (pstride < (ptrdiff_t)pw * pch || (split != LVM_SPLIT_NONE && ostride < (ptrdiff_t)ow * och)) { c->err = "frame stride too small"; return LVM_ERR_INVALID; }
-    if (c->nstreams > 1 && (csstride < (ptrdiff_t)chh * cstride || psstride < (ptrdiff_t)ph * pstride ||
-                            (split != LVM_SPLIT_NONE && osstride < (ptrdiff_t)oh * ostride))) { c->err = "stream stride too small"; return LVM_ERR_INVALID; }
-    ComposeArgs a;
-    a.src[0] = d_orig; a.stride[0] = ostride; a.sstride[0] = osstride; a.cn[0] = och;
-    a.src[1] = d_proc; a.stride[1] = pstride; a.sstride[1] = psstride; a.cn[1] = pch;
-    a.dst = d_canvas; a.dst_stride = cstride; a.dst_sstride = csstride;
-    a.w = w; a.h = h;
-    a.npanes = split == LVM_SPLIT_NONE ? 1 : 2;
-    a.dx1 = split == LVM_SPLIT_LEFT_RIGHT ? w : 0;
-    a.dy1 = split == LVM_SPLIT_TOP_BOTTOM ? h : 0;
-    if (split == LVM_SPLIT_NONE) { a.dx1 = 0; a.dy1 = 0; }
+    if (!compose_geometry(split, orig.w, orig.h, proc.w, proc.h, &w, &h, &cw, &chh)) return LVM_OK;
+    if (const char* why = canvas_error(cw, chh)) { c->err = why; return LVM_ERR_INVALID; }
+    // the kernels index the frames with the caller's strides: rows must hold their pixels
+    if (proc.stride < (ptrdiff_t)proc.w * proc.cn || orig.stride < (ptrdiff_t)orig.w * orig.cn) { c->err = "frame stride too small"; return LVM_ERR_INVALID; }
+    p->src[0] = orig.p; p->stride[0] = (long)orig.stride; p->cn[0] = orig.cn;
+    p->src[1] = proc.p; p->stride[1] = (long)proc.stride; p->cn[1] = proc.cn;
+    p->w = w; p->h = h;
+    p->npanes = two ? 2 : 1;
+    p->dx1 = split == LVM_SPLIT_LEFT_RIGHT ? w : 0;
+    p->dy1 = split == LVM_SPLIT_TOP_BOTTOM ? h : 0;
+    return LVM_OK;
+}
+
+int compose_device(Ctx* c, int split, const Image& orig, const Image& proc, const ImageOut& canvas, hipStream_t s) {
+    ComposeArgs a{};
+    int chh = 0;
+    const int rc = panes_resolve(c, split, orig, proc, canvas.p, &a.p, [&](int cw, int ch) { chh = ch; return canvas.stride < (ptrdiff_t)cw * 3 ? "canvas stride too small" : nullptr; });
+    if (rc != LVM_OK || a.p.w == 0) return rc;
+    // ... and with several streams, the streams must not overlap (a missing original: the processed frame's)
+    const Image& o = (a.p.npanes == 2 && orig.p) ? orig : proc;
+    if (c->nstreams > 1 && (canvas.sstride < (ptrdiff_t)chh * canvas.stride || proc.sstride < (ptrdiff_t)proc.h * proc.stride ||
+                            o.sstride < (ptrdiff_t)o.h * o.stride)) { c->err = "stream stride too small"; return LVM_ERR_INVALID; }
+    a.sstride[0] = (long)o.sstride; a.sstride[1] = (long)proc.sstride;
+    a.dst = canvas.p; a.dst_stride = (long)canvas.stride; a.dst_sstride = (long)canvas.sstride;
     // dword stores need every pane row segment dword-aligned: canvas base, strides and the pane-1 column offset (3 w bytes)
-    const bool vec = ((uintptr_t)d_canvas % 4) == 0 && cstride % 4 == 0 && csstride % 4 == 0 && (a.dx1 * 3) % 4 == 0;
-    const dim3 grid(((w + 3) / 4 + 63) / 64, (h + 3) / 4, (unsigned)(c->nstreams * a.npanes)), blk(256);
+    const bool vec = ((uintptr_t)canvas.p % 4) == 0 && canvas.stride % 4 == 0 && canvas.sstride % 4 == 0 && (a.p.dx1 * 3) % 4 == 0;
+    const dim3 grid(((a.p.w + 3) / 4 + 63) / 64, (a.p.h + 3) / 4, (unsigned)(c->nstreams * a.p.npanes)), blk(256);
     if (vec) LVM_LAUNCH(c, "compose", k_compose<true>, grid, blk, s, a);
     else LVM_LAUNCH(c, "compose", k_compose<false>, grid, blk, s, a);
     LVM_HIP_TRY(c, hipGetLastError());
@@ -179,11 +201,9 @@ __device__ __forceinline__ uint32_t yuv_u(int b, int g, int r) { return (uint32_
 __device__ __forceinline__ uint32_t yuv_v(int b, int g, int r) { return (uint32_t)((460324 * r - 385875 * g - 74448 * b + (1 << 19) + (128 << 20)) >> 20); }
 
 struct CanvasYuvArgs {
-    // the source: a BGR canvas in memory (src[1], cn 3, one pane at the origin: frame f at + f * fstride), or the panes compose_device would
-    // write into it ([0] original, [1] processed; BGR or gray, gray as b = g = r)
-    const uint8_t* src[2]; long stride[2]; int cn[2];
+    // the source: a BGR canvas in memory (one BGR pane at the origin: frame f at + f * src_fstride), or the panes compose_device would write into it
+    Panes p;
     long src_fstride;
-    int pane_w, pane_h, npanes, dx1, dy1;
     uint8_t* dst; long ystride, cstride, dst_fstride, plane1, plane2;   // plane1 / plane2: where U / V go (planar), or plane1 = the interleaved plane
     int w, h;                 // canvas size (even)
     int interleaved, v_first; // NV12 / NV21: byte pairs (U, V) / (V, U) in one plane of row stride cstride = ystride
@@ -191,7 +211,9 @@ struct CanvasYuvArgs {
 
 // One thread per block of 2 rows x 8 pixels of the canvas: 2 x 24 BGR bytes (2 x 8 of a gray pane) in, 2 x 8 Y bytes and 4 U + 4 V bytes out;
 // blockIdx.z = frame.  VEC: dword-wide loads and stores (every pointer, stride and offset dword-aligned, w % 8 == 0, the block inside ONE pane);
-// otherwise bytes, a block of 2, 4 or 6 pixels at the right edge (w is even) and a pane per pixel.
+// otherwise bytes, a block of 2, 4 or 6 pixels at the right edge (w is even) and a pane per pixel.  (Which pane and which pixel of it is
+// written out in both branches, and the fetch again in k_compose: through shared functions the byte variants grow by 43 to 130 instructions.
+// The dword packing of the stores is written out too: lvm_pack_b4 reorders the whole dword variant, 34 -> 36 VGPRs.)
 template <bool VEC>
 __global__ __launch_bounds__(256) void k_canvas_yuv(CanvasYuvArgs a) {
     const int x0 = (blockIdx.x * 64 + (threadIdx.x & 63)) * 8, y0 = (blockIdx.y * 4 + (threadIdx.x >> 6)) * 2;
@@ -203,13 +225,13 @@ __global__ __launch_bounds__(256) void k_canvas_yuv(CanvasYuvArgs a) {
     for (int r = 0; r < 2; ++r) {
         const int y = y0 + r;
         // (a block of two rows lies in one pane vertically: pane heights are even)
-        const int py = (a.npanes == 2 && y >= a.pane_h && a.dy1) ? 1 : 0;
+        const int py = (a.p.npanes == 2 && y >= a.p.h && a.p.dy1) ? 1 : 0;
         uint8_t px[24];
         if (VEC) {
-            const int pane = a.npanes == 2 ? ((a.dx1 && x0 >= a.dx1) || py ? 1 : 0) : 1;
-            const int lx = x0 - (pane && a.npanes == 2 ? a.dx1 : 0), ly = y - (py ? a.dy1 : 0);
-            const uint8_t* p = a.src[pane] + f * a.src_fstride + (size_t)ly * a.stride[pane];
-            if (a.cn[pane] == 3) {
+            const int pane = a.p.npanes == 2 ? ((a.p.dx1 && x0 >= a.p.dx1) || py ? 1 : 0) : 1;
+            const int lx = x0 - (pane && a.p.npanes == 2 ? a.p.dx1 : 0), ly = y - (py ? a.p.dy1 : 0);
+            const uint8_t* p = a.p.src[pane] + f * a.src_fstride + (size_t)ly * a.p.stride[pane];
+            if (a.p.cn[pane] == 3) {
                 const uint32_t* p4 = reinterpret_cast<const uint32_t*>(p + (size_t)lx * 3);
 #pragma unroll
                 for (int k = 0; k < 6; ++k) { const uint32_t v = p4[k]; px[4 * k] = (uint8_t)v; px[4 * k + 1] = (uint8_t)(v >> 8); px[4 * k + 2] = (uint8_t)(v >> 16); px[4 * k + 3] = (uint8_t)(v >> 24); }
@@ -226,11 +248,11 @@ __global__ __launch_bounds__(256) void k_canvas_yuv(CanvasYuvArgs a) {
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const int x = x0 + k;
-                const int pane = a.npanes == 2 ? ((a.dx1 && x >= a.dx1) || py ? 1 : 0) : 1;
-                const int lx = x - (pane && a.npanes == 2 ? a.dx1 : 0), ly = y - (py ? a.dy1 : 0);
-                const uint8_t* p = a.src[pane] + f * a.src_fstride + (size_t)ly * a.stride[pane];
+                const int pane = a.p.npanes == 2 ? ((a.p.dx1 && x >= a.p.dx1) || py ? 1 : 0) : 1;
+                const int lx = x - (pane && a.p.npanes == 2 ? a.p.dx1 : 0), ly = y - (py ? a.p.dy1 : 0);
+                const uint8_t* p = a.p.src[pane] + f * a.src_fstride + (size_t)ly * a.p.stride[pane];
                 if (k < n) {
-                    if (a.cn[pane] == 3) { px[3 * k] = p[(size_t)lx * 3]; px[3 * k + 1] = p[(size_t)lx * 3 + 1]; px[3 * k + 2] = p[(size_t)lx * 3 + 2]; }
+                    if (a.p.cn[pane] == 3) { px[3 * k] = p[(size_t)lx * 3]; px[3 * k + 1] = p[(size_t)lx * 3 + 1]; px[3 * k + 2] = p[(size_t)lx * 3 + 2]; }
                     else { const uint8_t g = p[lx]; px[3 * k] = g; px[3 * k + 1] = g; px[3 * k + 2] = g; }      // COLOR_GRAY2BGR
                 } else { px[3 * k] = 0; px[3 * k + 1] = 0; px[3 * k + 2] = 0; }
             }
@@ -305,14 +327,14 @@ const char* canvas_layout(int fmt, int w, int h, ptrdiff_t stride, CanvasLayout*
 }
 
 // the destination half of the arguments, and whether it allows dword stores
-static bool canvas_yuv_dst(CanvasYuvArgs& a, int fmt, int w, int h, uint8_t* d_out, ptrdiff_t out_stride, ptrdiff_t out_fstride, int n_frames, const CanvasLayout& L) {
+static bool canvas_yuv_dst(CanvasYuvArgs& a, int fmt, int w, int h, const ImageOut& out, int n_frames, const CanvasLayout& L) {
     a.w = w; a.h = h;
-    a.dst = d_out; a.ystride = (long)out_stride; a.cstride = (long)L.cstride; a.dst_fstride = n_frames > 1 ? (long)out_fstride : 0;
+    a.dst = out.p; a.ystride = (long)out.stride; a.cstride = (long)L.cstride; a.dst_fstride = n_frames > 1 ? (long)out.sstride : 0;
     a.interleaved = fmt == LVM_PIX_NV12 || fmt == LVM_PIX_NV21;
     a.v_first = fmt == LVM_PIX_NV21 || fmt == LVM_PIX_YV12;
     a.plane1 = (long)L.plane1; a.plane2 = (long)L.plane2;
     if (!a.interleaved && a.v_first) { a.plane1 = (long)L.plane2; a.plane2 = (long)L.plane1; }      // YV12: the V plane comes first
-    return w % 8 == 0 && (uintptr_t)d_out % 4 == 0 && out_stride % 4 == 0 && a.dst_fstride % 4 == 0 && L.cstride % 4 == 0 && L.plane1 % 4 == 0 && L.plane2 % 4 == 0;
+    return w % 8 == 0 && (uintptr_t)out.p % 4 == 0 && out.stride % 4 == 0 && a.dst_fstride % 4 == 0 && L.cstride % 4 == 0 && L.plane1 % 4 == 0 && L.plane2 % 4 == 0;
 }
 
 static int canvas_yuv_launch(Ctx* c, const CanvasYuvArgs& a, bool vec, bool fused, int n_frames, hipStream_t s) {
@@ -324,51 +346,40 @@ static int canvas_yuv_launch(Ctx* c, const CanvasYuvArgs& a, bool vec, bool fuse
     return LVM_OK;
 }
 
-int canvas_yuv_device(Ctx* c, int fmt, const uint8_t* d_bgr, int w, int h, ptrdiff_t bgr_stride, ptrdiff_t bgr_fstride, int n_frames, uint8_t* d_out,
-                      ptrdiff_t out_stride, ptrdiff_t out_fstride, hipStream_t s, bool check_only) {
+int canvas_yuv_device(Ctx* c, int fmt, const Image& bgr, int n_frames, const ImageOut& out, hipStream_t s, bool check_only) {
+    const int w = bgr.w, h = bgr.h;
     if (fmt != LVM_PIX_NV12 && fmt != LVM_PIX_NV21 && fmt != LVM_PIX_I420 && fmt != LVM_PIX_YV12) {
         c->err = "lvm_canvas_convert_device: the format must be LVM_PIX_NV12 (4), _NV21 (5), _I420 (6) or _YV12 (7)"; return LVM_ERR_INVALID;
     }
-    if (!d_bgr || !d_out || n_frames < 1 || n_frames > 65535) { c->err = "lvm_canvas_convert_device: null canvas pointer, or not 1..65535 frames"; return LVM_ERR_INVALID; }
+    if (!bgr.p || !out.p || n_frames < 1 || n_frames > 65535) { c->err = "lvm_canvas_convert_device: null canvas pointer, or not 1..65535 frames"; return LVM_ERR_INVALID; }
     CanvasLayout L;
-    if (const char* why = canvas_layout(fmt, w, h, out_stride, &L)) { c->err = why; return LVM_ERR_INVALID; }
-    if (bgr_stride < (ptrdiff_t)w * 3) { c->err = "lvm_canvas_convert_device: bgr_stride must be >= 3 * w"; return LVM_ERR_INVALID; }
-    if (n_frames > 1 && (out_fstride < 0 || (size_t)out_fstride < L.bytes)) { c->err = "lvm_canvas_convert_device: out_frame_stride must be >= the bytes of one canvas (the frames would overlap)"; return LVM_ERR_INVALID; }
+    if (const char* why = canvas_layout(fmt, w, h, out.stride, &L)) { c->err = why; return LVM_ERR_INVALID; }
+    if (bgr.stride < (ptrdiff_t)w * 3) { c->err = "lvm_canvas_convert_device: bgr_stride must be >= 3 * w"; return LVM_ERR_INVALID; }
+    if (n_frames > 1 && (out.sstride < 0 || (size_t)out.sstride < L.bytes)) { c->err = "lvm_canvas_convert_device: out_frame_stride must be >= the bytes of one canvas (the frames would overlap)"; return LVM_ERR_INVALID; }
     if (check_only) return LVM_OK;
     CanvasYuvArgs a{};
-    a.src[0] = a.src[1] = d_bgr; a.stride[0] = a.stride[1] = (long)bgr_stride; a.cn[0] = a.cn[1] = 3;
-    a.src_fstride = n_frames > 1 ? (long)bgr_fstride : 0;
-    a.pane_w = w; a.pane_h = h; a.npanes = 1; a.dx1 = 0; a.dy1 = 0;
-    bool vec = canvas_yuv_dst(a, fmt, w, h, d_out, out_stride, out_fstride, n_frames, L);
-    vec = vec && (uintptr_t)d_bgr % 4 == 0 && bgr_stride % 4 == 0 && a.src_fstride % 4 == 0;
+    a.p = Panes{{bgr.p, bgr.p}, {(long)bgr.stride, (long)bgr.stride}, {3, 3}, w, h, 1, 0, 0};     // one BGR pane at the origin
+    a.src_fstride = n_frames > 1 ? (long)bgr.sstride : 0;
+    bool vec = canvas_yuv_dst(a, fmt, w, h, out, n_frames, L);
+    vec = vec && (uintptr_t)bgr.p % 4 == 0 && bgr.stride % 4 == 0 && a.src_fstride % 4 == 0;
     return canvas_yuv_launch(c, a, vec, false, n_frames, s);
 }
 
 // compose_device's panes (same geometry, same fall-back for a missing original) straight into the surface: the BGR canvas is never written
-int canvas_yuv_fused(Ctx* c, int fmt, int split, const uint8_t* d_orig, int ow, int oh, int och, ptrdiff_t ostride, const uint8_t* d_proc, int pw, int ph,
-                     int pch, ptrdiff_t pstride, uint8_t* d_out, ptrdiff_t out_stride, hipStream_t s) {
-    if (split < LVM_SPLIT_NONE || split > LVM_SPLIT_TOP_BOTTOM) { c->err = "invalid split mode"; return LVM_ERR_INVALID; }
-    if (!d_proc || !d_out || (pch != 1 && pch != 3)) { c->err = "bad processed frame"; return LVM_ERR_INVALID; }
-    if (split != LVM_SPLIT_NONE && !d_orig) { d_orig = d_proc; ow = pw; oh = ph; och = pch; ostride = pstride; }
-    if (split != LVM_SPLIT_NONE && och != 1 && och != 3) { c->err = "bad original frame"; return LVM_ERR_INVALID; }
-    int w, h, cw, chh;
-    if (!compose_geometry(split, ow, oh, pw, ph, &w, &h, &cw, &chh)) return LVM_OK;
-    CanvasLayout L;
-    if (const char* why = canvas_layout(fmt, cw, chh, out_stride, &L)) { c->err = why; return LVM_ERR_INVALID; }
-    if (fmt == LVM_PIX_BGR) { c->err = "canvas format: a YUV format is needed here"; return LVM_ERR_INVALID; }
-    if (pstride < (ptrdiff_t)pw * pch || (split != LVM_SPLIT_NONE && ostride < (ptrdiff_t)ow * och)) { c->err = "frame stride too small"; return LVM_ERR_INVALID; }
+int canvas_yuv_fused(Ctx* c, int fmt, int split, const Image& orig, const Image& proc, const ImageOut& out, hipStream_t s) {
     CanvasYuvArgs a{};
-    const bool two = split != LVM_SPLIT_NONE;
-    a.src[0] = two ? d_orig : d_proc; a.stride[0] = (long)(two ? ostride : pstride); a.cn[0] = two ? och : pch;
-    a.src[1] = d_proc; a.stride[1] = (long)pstride; a.cn[1] = pch;
-    a.src_fstride = 0;
-    a.pane_w = w; a.pane_h = h; a.npanes = two ? 2 : 1;
-    a.dx1 = split == LVM_SPLIT_LEFT_RIGHT ? w : 0;
-    a.dy1 = split == LVM_SPLIT_TOP_BOTTOM ? h : 0;
-    bool vec = canvas_yuv_dst(a, fmt, cw, chh, d_out, out_stride, 0, 1, L);
-    // dword loads need every pane row segment dword-aligned and every 8-pixel block inside one pane: the pane-1 column (dx1 = pane_w, even
+    CanvasLayout L;
+    int cw = 0, chh = 0;
+    const int rc = panes_resolve(c, split, orig, proc, out.p, &a.p, [&](int w, int h) -> const char* {
+        cw = w; chh = h;
+        if (const char* why = canvas_layout(fmt, w, h, out.stride, &L)) return why;
+        return fmt == LVM_PIX_BGR ? "canvas format: a YUV format is needed here" : nullptr;
+    });
+    if (rc != LVM_OK || a.p.w == 0) return rc;
+    bool vec = canvas_yuv_dst(a, fmt, cw, chh, out, 1, L);
+    // dword loads need every pane row segment dword-aligned and every 8-pixel block inside one pane: the pane-1 column (dx1 = pane width, even
     // but no multiple of 8 in general) decides, as 3 * dx1 does for compose_device's stores
-    vec = vec && a.dx1 % 8 == 0 && (uintptr_t)a.src[1] % 4 == 0 && a.stride[1] % 4 == 0 && (!two || ((uintptr_t)a.src[0] % 4 == 0 && a.stride[0] % 4 == 0));
+    vec = vec && a.p.dx1 % 8 == 0 && (uintptr_t)a.p.src[1] % 4 == 0 && a.p.stride[1] % 4 == 0 && (a.p.npanes == 1 || ((uintptr_t)a.p.src[0] % 4 == 0 && a.p.stride[0] % 4 == 0));
     return canvas_yuv_launch(c, a, vec, true, 1, s);
 }
 

@@ -181,8 +181,10 @@ static const char* layout_error(const FrameIO& io, int nstreams) {
     return nullptr;
 }
 
-// Frames in a raw camera format (lvm_set_source_format): the rules of include/lvm_hip.h, checked before any state changes.  Null: fine.
-static const char* raw_frame_error(int fmt, int w, int h, int channels, ptrdiff_t in_stride) {
+// A source frame as an entry point is given it, checked before any state changes: BGR / gray frames, and the rules of include/lvm_hip.h for the
+// raw camera formats (lvm_set_source_format).  Null: fine.
+static const char* source_frame_error(int fmt, int w, int h, int channels, ptrdiff_t in_stride) {
+    if (fmt == LVM_PIX_BGR) return (w <= 0 || h <= 0 || (channels != 1 && channels != 3) || in_stride < (ptrdiff_t)w * channels) ? "bad frame arguments" : nullptr;
     const bool nv = fmt == LVM_PIX_NV12 || fmt == LVM_PIX_NV21;
     if (channels != 3) return "raw source format: channels must be 3 (it describes the frame the chain sees)";
     if (w <= 0 || h <= 0) return "bad frame arguments";
@@ -239,6 +241,20 @@ static int at_depth0(Ctx* c, Run&& run) {
     c->pipeline_depth = 0;
     const int rc = run();
     c->pipeline_depth = depth;
+    return rc;
+}
+
+// What an entry point that enqueues on the caller's stream does around its call: the device, the stream of the call (null: the context's own), the
+// wait that orders it behind the previous call, the call, and the mark the next call orders itself behind -- set whether or not `run` succeeded:
+// a failed call may have enqueued part of its work.
+template <class Run>
+static int on_stream(Ctx* c, void* hip_stream, Run&& run) {
+    LVM_HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
+    int rc = order_after_previous(c, s);
+    if (rc != LVM_OK) return rc;
+    rc = run(s);
+    mark_enqueued(c, s);
     return rc;
 }
 
@@ -400,19 +416,17 @@ int lvm_preprocess_device(lvm_ctx* c, const lvm_preprocess_params* pp, const uin
                           ptrdiff_t out_stream_stride, void* hip_stream) {
     if (!c || !pp) return LVM_ERR_INVALID;
     const int fmt = c->source_format;
+    // (a BGR / gray frame is checked by preprocess_device, with its own text and without a rule for in_stride: only the raw rules are checked here)
     if (fmt != LVM_PIX_BGR) {
-        if (const char* why = lvm::raw_frame_error(fmt, w, h, channels, in_stride)) { c->err = why; return LVM_ERR_INVALID; }
+        if (const char* why = lvm::source_frame_error(fmt, w, h, channels, in_stride)) { c->err = why; return LVM_ERR_INVALID; }
     }
     // the whole raw frame is on the device: its pixel (0, 0) starts a chroma pair / block, the UV plane starts at row h (NV12 / NV21)
     const lvm::RawSource raw{fmt, 0, 0, (ptrdiff_t)h * in_stride};
-    LVM_HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
-    int rc = lvm::order_after_previous(c, s);          // (the area tables are the context's: preprocess.hip replaces them behind a wait for `s` alone)
-    if (rc != LVM_OK) return rc;
-    rc = lvm::preprocess_device(c, *pp, d_in, w, h, channels, in_stride, in_stream_stride, d_out, out_stride, out_stream_stride, s, nullptr, 0, 0,
-                                fmt != LVM_PIX_BGR ? &raw : nullptr);
-    lvm::mark_enqueued(c, s);
-    return rc;
+    // (the area tables are the context's: preprocess.hip replaces them behind a wait for the call's stream alone)
+    return lvm::on_stream(c, hip_stream, [&](hipStream_t s) {
+        return lvm::preprocess_device(c, *pp, lvm::Image{d_in, w, h, channels, in_stride, in_stream_stride}, lvm::ImageOut{d_out, 0, 0, 0, out_stride, out_stream_stride}, s,
+                                      lvm::ImageOut(), fmt != LVM_PIX_BGR ? &raw : nullptr);
+    });
 }
 
 int lvm_compose_geometry(int split, int ow, int oh, int pw, int ph, int* pane_w, int* pane_h, int* canvas_w, int* canvas_h) {
@@ -429,14 +443,10 @@ int lvm_compose_device(lvm_ctx* c, int split, const uint8_t* d_orig, int ow, int
                        ptrdiff_t proc_stream_stride, uint8_t* d_canvas, ptrdiff_t canvas_stride, ptrdiff_t canvas_stream_stride,
                        void* hip_stream) {
     if (!c) return LVM_ERR_INVALID;
-    LVM_HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
-    int rc = lvm::order_after_previous(c, s);
-    if (rc != LVM_OK) return rc;
-    rc = lvm::compose_device(c, split, d_orig, ow, oh, och, orig_stride, orig_stream_stride, d_proc, pw, ph, pch, proc_stride,
-                             proc_stream_stride, d_canvas, canvas_stride, canvas_stream_stride, s);
-    lvm::mark_enqueued(c, s);
-    return rc;
+    return lvm::on_stream(c, hip_stream, [&](hipStream_t s) {
+        return lvm::compose_device(c, split, lvm::Image{d_orig, ow, oh, och, orig_stride, orig_stream_stride}, lvm::Image{d_proc, pw, ph, pch, proc_stride, proc_stream_stride},
+                                   lvm::ImageOut{d_canvas, 0, 0, 3, canvas_stride, canvas_stream_stride}, s);
+    });
 }
 
 // ---- spatial tiling of ONE Riesz stream (demonstrator; the production answer to several GPUs is one stream per GPU) ----------------------
@@ -450,7 +460,8 @@ int lvm_tile_riesz_stage1(lvm_ctx* c, const lvm_params* p, const uint8_t* d_in, 
                           float* d_residual_out, int* residual_w, int* residual_h, void* hip_stream) {
     int rc = tile_check(c, p, w, h);
     if (rc != LVM_OK) return rc;
-    if (!d_in || !produced || in_stride < (ptrdiff_t)w * 3) { c->err = "tiling: bad frame arguments"; return LVM_ERR_INVALID; }
+    if (!d_in || !produced || lvm::source_frame_error(LVM_PIX_BGR, w, h, 3, in_stride)) { c->err = "tiling: bad frame arguments"; return LVM_ERR_INVALID; }
+    // by hand: process_device orders and marks the call itself, and runs between the two settings of tile_mode
     LVM_HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
     // (no output in this stage: the frame argument stands in for the output pointer the per-frame path asks for and is never written)
@@ -466,22 +477,17 @@ int lvm_tile_riesz_stage2(lvm_ctx* c, const lvm_params* p, const uint8_t* d_in, 
                           uint8_t* d_out, ptrdiff_t out_stride, void* hip_stream) {
     int rc = tile_check(c, p, w, h);
     if (rc != LVM_OK) return rc;
-    if (!d_in || !d_out || !d_residual_in || in_stride < (ptrdiff_t)w * 3 || out_stride < (ptrdiff_t)w * 3) { c->err = "tiling: bad frame arguments"; return LVM_ERR_INVALID; }
+    if (!d_in || !d_out || !d_residual_in || lvm::source_frame_error(LVM_PIX_BGR, w, h, 3, in_stride) || out_stride < (ptrdiff_t)w * 3) { c->err = "tiling: bad frame arguments"; return LVM_ERR_INVALID; }
     if (c->tracked.mode != LVM_MODE_PHASE || c->tracked.w != w || c->tracked.h != h || c->tracked.channels != 3) { c->err = "tiling: stage 2 without a matching stage 1"; return LVM_ERR_INVALID; }
-    LVM_HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
-    lvm::FrameIO io{d_in, in_stride, in_stride * h, d_out, out_stride, out_stride * h, w, h, 3};
-    rc = lvm::order_after_previous(c, s);
-    if (rc != LVM_OK) return rc;
-    rc = lvm::riesz_tile_finish(c, *p, io, d_residual_in, s);
-    lvm::mark_enqueued(c, s);
-    return rc;
+    const lvm::FrameIO io{d_in, in_stride, in_stride * h, d_out, out_stride, out_stride * h, w, h, 3};
+    return lvm::on_stream(c, hip_stream, [&](hipStream_t s) { return lvm::riesz_tile_finish(c, *p, io, d_residual_in, s); });
 }
 
 int lvm_tile_riesz_planes(lvm_ctx* c, const lvm_params* p, const float* d_plane_in, int w, int h, float* d_plane_out, int* produced, void* hip_stream) {
     int rc = tile_check(c, p, w, h);
     if (rc != LVM_OK) return rc;
     if (!d_plane_in || !d_plane_out || !produced || p->levels < 2) { c->err = "tiling: planes in and out, at least two levels"; return LVM_ERR_INVALID; }
+    // by hand, like stage 1: process_device orders and marks, between the two settings of tile_mode
     LVM_HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
     // the per-frame path with a plane where the frame would be: three "channels" so that the Riesz mode accepts it (MagnifyCore.hpp:212);
@@ -502,13 +508,7 @@ int lvm_export_set_overlay(lvm_ctx* c, int n_labels, const lvm_overlay_label* la
 
 int lvm_overlay_device(lvm_ctx* c, uint8_t* d_canvas, int canvas_w, int canvas_h, ptrdiff_t canvas_stride, ptrdiff_t frame_stride, int n_frames, void* hip_stream) {
     if (!c) return LVM_ERR_INVALID;
-    LVM_HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
-    int rc = lvm::order_after_previous(c, s);
-    if (rc != LVM_OK) return rc;
-    rc = lvm::overlay_device(c, d_canvas, canvas_w, canvas_h, canvas_stride, frame_stride, n_frames, s);
-    lvm::mark_enqueued(c, s);
-    return rc;
+    return lvm::on_stream(c, hip_stream, [&](hipStream_t s) { return lvm::overlay_device(c, lvm::ImageOut{d_canvas, canvas_w, canvas_h, 3, canvas_stride, frame_stride}, n_frames, s); });
 }
 
 // FNV-1a over the PreprocessParams fields the reference compares (IProcessor.hpp:36-39)
@@ -567,18 +567,75 @@ static hipError_t chain_upload(const ChainGeom& g, uint8_t* d_dst, const uint8_t
     return hipMemcpy2DAsync(d_dst, g.roi_row, frame + (size_t)g.ry * in_stride + (size_t)g.rx * g.channels, (size_t)in_stride, g.roi_row, (size_t)g.rh,
                             hipMemcpyHostToDevice, s);
 }
-// Preprocess + Grayscale of frames that are cropped already (by the upload, or as a view into a decoded frame)
-static int chain_preprocess(Ctx* c, const lvm_preprocess_params& pp, const ChainGeom& g, const uint8_t* d_src, size_t src_row, size_t src_fbytes, uint8_t* d_dst,
-                            hipStream_t s, uint8_t* d_tap, ptrdiff_t tap_stride, ptrdiff_t tap_sstride) {
-    lvm_preprocess_params q = pp;
-    q.roi_enabled = 0;
-    return lvm::preprocess_device(c, q, d_src, g.rw, g.rh, g.channels, (ptrdiff_t)src_row, (ptrdiff_t)src_fbytes, d_dst, (ptrdiff_t)g.out_row, (ptrdiff_t)g.out_bytes, s,
-                                  d_tap, tap_stride, tap_sstride, g.fmt != LVM_PIX_BGR ? &g.raw : nullptr);
-}
 static lvm_params chain_params(const lvm_params& p, const lvm_preprocess_params& pp) {
     lvm_params mp = p;
     mp.preprocess_key = preprocess_key_of(pp);
     return mp;
+}
+
+// The front end the chain and export entry points share: n source frames of one geometry staged in front of the magnifier.  stage_plan checks the
+// frame and works the geometry out (no HIP call); begin() orders the call behind the previous one, waits for the context's stream and sizes the
+// staging buffers; then frame k is uploaded (or decoded into place), preprocessed, and seen(k) / tap(k) are views of what the magnifier reads and
+// of runChainOnce's `original`.
+struct Staged {
+    Ctx* c; lvm_preprocess_params pp; ChainGeom g; int n; ptrdiff_t in_stride;
+    // the pane Exporter::compose labels "Original" is runChainOnce's tap (ChainGeom::gray): kept in d_pre_tap when the caller wants it
+    bool gray_tap;
+    // where stage 1 leaves frame k in d_pre_in: the cropped copy (host frames), or -- `decoded` -- the ROI inside the whole decoded frame (JPEG frames)
+    size_t src_off, src_row, src_fbytes;
+    const char* error;              // of stage_plan; null: fine
+
+    lvm::Image src(int k) const { return {c->d_pre_in + src_off + (size_t)k * src_fbytes, g.rw, g.rh, g.channels, (ptrdiff_t)src_row, (ptrdiff_t)src_fbytes}; }
+    // what the magnifier sees: the preprocessed frame, or the staged one itself where there is nothing to do (ChainGeom::identity)
+    lvm::ImageOut pre(int k) const { return {c->d_pre_out + (size_t)k * g.out_bytes, g.ow, g.oh, g.och, (ptrdiff_t)g.out_row, (ptrdiff_t)g.out_bytes}; }
+    lvm::Image seen(int k) const { return g.identity ? src(k) : (lvm::Image)pre(k); }
+    lvm::ImageOut out(int k) const { return {c->d_chain_out + (size_t)k * g.out_bytes, g.ow, g.oh, g.och, (ptrdiff_t)g.out_row, (ptrdiff_t)g.out_bytes}; }
+    // the colour frame in front of GrayscaleProcessor (ChainBuilder.cpp:25); without a gray stage in between the tap IS the frame the magnifier sees
+    lvm::ImageOut own_tap(int k) const {
+        if (!gray_tap) return lvm::ImageOut();
+        return {c->d_pre_tap + (size_t)k * g.tap_bytes, g.ow, g.oh, 3, (ptrdiff_t)g.tap_row, (ptrdiff_t)g.tap_bytes};
+    }
+    lvm::Image tap(int k) const { return gray_tap ? (lvm::Image)own_tap(k) : seen(k); }
+
+    int begin(hipStream_t s) const {
+        { const int orc = lvm::order_after_previous(c, s); if (orc != LVM_OK) return orc; }
+        LVM_HIP_TRY(c, hipStreamSynchronize(s));      // staging buffers may be replaced below
+        int rc = c->d_pre_in.reserve(c, src_fbytes * n);
+        if (rc == LVM_OK) rc = c->d_pre_out.reserve(c, g.out_bytes * n);
+        if (rc == LVM_OK) rc = c->d_chain_out.reserve(c, g.out_bytes * n);
+        if (rc == LVM_OK && gray_tap) rc = c->d_pre_tap.reserve(c, g.tap_bytes * n);
+        return rc;
+    }
+    // only the ROI rows cross PCIe (the crop is the pitch of the 2-D copy)
+    hipError_t upload(int k, const uint8_t* frame, hipStream_t s) const { return chain_upload(g, c->d_pre_in + (size_t)k * g.roi_bytes, frame, in_stride, s); }
+    // Preprocess + Grayscale of the staged frames k .. k + nstreams - 1 (one launch: the context's streams are its z dimension), the tap to `to`
+    int preprocess(int k, hipStream_t s, const lvm::ImageOut& to) const {
+        if (g.identity) return LVM_OK;
+        return lvm::preprocess_device(c, pp, src(k), pre(k), s, to, g.fmt != LVM_PIX_BGR ? &g.raw : nullptr);
+    }
+};
+static Staged stage_plan(Ctx* c, const lvm_preprocess_params& pp, int fmt, int w, int h, int channels, ptrdiff_t in_stride, int n_frames, bool want_tap, bool decoded = false) {
+    Staged st{};
+    st.c = c; st.n = n_frames; st.in_stride = in_stride;
+    st.error = lvm::source_frame_error(fmt, w, h, channels, in_stride);
+    if (st.error) return st;
+    st.g = chain_geometry(pp, w, h, channels, fmt);
+    st.pp = pp; st.pp.roi_enabled = 0;             // the staged frames are cropped already (by the upload, or as a view into a decoded frame)
+    st.gray_tap = want_tap && st.g.gray;
+    st.src_row = st.g.roi_row; st.src_fbytes = st.g.roi_bytes;
+    if (decoded) {
+        st.src_row = (size_t)w * channels; st.src_fbytes = st.src_row * h;
+        st.src_off = (size_t)st.g.ry * st.src_row + (size_t)st.g.rx * channels;
+    }
+    return st;
+}
+// the magnifier's arguments for staged frame k (and the context's further streams behind it), writing to `out`
+static lvm::FrameIO stage_io(const Staged& st, int k, const lvm::ImageOut& out) {
+    const lvm::Image in = st.seen(k);
+    return lvm::FrameIO{in.p, in.stride, in.sstride, out.p, out.stride, out.sstride, in.w, in.h, in.cn};
+}
+static hipError_t frame_copy(uint8_t* dst, ptrdiff_t dst_stride, const lvm::Image& f, hipMemcpyKind kind, hipStream_t s) {
+    return hipMemcpy2DAsync(dst, (size_t)dst_stride, f.p, (size_t)f.stride, (size_t)f.w * f.cn, (size_t)f.h, kind, s);
 }
 
 int lvm_chain_process_batch(lvm_ctx* c, const lvm_preprocess_params* pp, const lvm_params* p, const uint8_t* const* in, int w, int h,
@@ -592,44 +649,27 @@ int lvm_chain_process_batch_ex(lvm_ctx* c, const lvm_preprocess_params* pp, cons
     if (!c || !pp || !p || !produced || !in || !out) return LVM_ERR_INVALID;
     *produced = 0;
     const int NS = c->nstreams;
-    const int fmt = c->source_format;
-    if (fmt != LVM_PIX_BGR) {
-        if (const char* why = lvm::raw_frame_error(fmt, w, h, channels, in_stride)) { c->err = why; return LVM_ERR_INVALID; }
-    } else if (w <= 0 || h <= 0 || (channels != 1 && channels != 3) || in_stride < (ptrdiff_t)w * channels) {
-        c->err = "bad frame arguments"; return LVM_ERR_INVALID;
-    }
+    const Staged st = stage_plan(c, *pp, c->source_format, w, h, channels, in_stride, NS, pre_out != nullptr);
+    if (st.error) { c->err = st.error; return LVM_ERR_INVALID; }
     for (int s = 0; s < NS; ++s) if (!in[s] || !out[s]) { c->err = "null frame pointer"; return LVM_ERR_INVALID; }
     LVM_HIP_TRY(c, hipSetDevice(c->device));
-    const ChainGeom g = chain_geometry(*pp, w, h, channels, fmt);
-    if (out_stride < (ptrdiff_t)g.out_row) { c->err = "output stride too small"; return LVM_ERR_INVALID; }
+    if (out_stride < (ptrdiff_t)st.g.out_row) { c->err = "output stride too small"; return LVM_ERR_INVALID; }
     hipStream_t s = c->own_stream;
-    { const int orc = lvm::order_after_previous(c, s); if (orc != LVM_OK) return orc; }
-    LVM_HIP_TRY(c, hipStreamSynchronize(s));      // staging buffers may be replaced below
-    int rc = c->d_pre_in.reserve(c, g.roi_bytes * NS); if (rc != LVM_OK) return rc;
-    rc = c->d_pre_out.reserve(c, g.out_bytes * NS); if (rc != LVM_OK) return rc;
-    rc = c->d_chain_out.reserve(c, g.out_bytes * NS); if (rc != LVM_OK) return rc;
-    for (int k = 0; k < NS; ++k) LVM_HIP_TRY(c, chain_upload(g, c->d_pre_in + (size_t)k * g.roi_bytes, in[k], in_stride, s));
-    const uint8_t* mag_in = c->d_pre_in;
-    const bool gray_tap = pre_out && g.gray;
-    if (gray_tap) { rc = c->d_pre_tap.reserve(c, g.tap_bytes * NS); if (rc != LVM_OK) return rc; }
-    if (!g.identity) {
-        rc = chain_preprocess(c, *pp, g, c->d_pre_in, g.roi_row, g.roi_bytes, c->d_pre_out, s, gray_tap ? c->d_pre_tap.p : nullptr, (ptrdiff_t)g.tap_row, (ptrdiff_t)g.tap_bytes);
-        if (rc != LVM_OK) { (void)hipStreamSynchronize(s); return rc; }
-        mag_in = c->d_pre_out;
-    }
+    int rc = st.begin(s);
+    if (rc != LVM_OK) return rc;
+    for (int k = 0; k < NS; ++k) LVM_HIP_TRY(c, st.upload(k, in[k], s));
+    rc = st.preprocess(0, s, st.own_tap(0));
+    if (rc != LVM_OK) { (void)hipStreamSynchronize(s); return rc; }
     const lvm_params mp = chain_params(*p, *pp);
-    lvm::FrameIO io{mag_in, (ptrdiff_t)g.out_row, (ptrdiff_t)g.out_bytes, c->d_chain_out, (ptrdiff_t)g.out_row, (ptrdiff_t)g.out_bytes, g.ow, g.oh, g.och};
+    const lvm::FrameIO io = stage_io(st, 0, st.out(0));
     rc = lvm::at_depth0(c, [&] { return lvm::process_device(c, &mp, io, s, produced); });
     if (rc != LVM_OK) { (void)hipStreamSynchronize(s); return rc; }
-    const uint8_t* res = *produced ? c->d_chain_out.p : mag_in;
-    for (int k = 0; k < NS; ++k)
-        LVM_HIP_TRY(c, hipMemcpy2DAsync(out[k], (size_t)out_stride, res + (size_t)k * g.out_bytes, g.out_row, g.out_row, (size_t)g.oh, hipMemcpyDeviceToHost, s));
+    for (int k = 0; k < NS; ++k)        // passthrough: the chain hands the magnifier's INPUT on (MagnificationProcessor.cpp:61)
+        LVM_HIP_TRY(c, frame_copy(out[k], out_stride, *produced ? (lvm::Image)st.out(k) : st.seen(k), hipMemcpyDeviceToHost, s));
     if (pre_out) {     // the pre-magnification tap (runChainOnce's `original`, ChainBuilder.cpp:19-29): the display's left pane
-        const uint8_t* tsrc = gray_tap ? c->d_pre_tap.p : mag_in;
-        if (pre_stride < (ptrdiff_t)g.tap_row) { c->err = "pre_out stride too small"; (void)hipStreamSynchronize(s); return LVM_ERR_INVALID; }
+        if (pre_stride < (ptrdiff_t)st.g.tap_row) { c->err = "pre_out stride too small"; (void)hipStreamSynchronize(s); return LVM_ERR_INVALID; }
         for (int k = 0; k < NS; ++k)
-            if (pre_out[k])
-                LVM_HIP_TRY(c, hipMemcpy2DAsync(pre_out[k], (size_t)pre_stride, tsrc + (size_t)k * g.tap_bytes, g.tap_row, g.tap_row, (size_t)g.oh, hipMemcpyDeviceToHost, s));
+            if (pre_out[k]) LVM_HIP_TRY(c, frame_copy(pre_out[k], pre_stride, st.tap(k), hipMemcpyDeviceToHost, s));
     }
     LVM_HIP_TRY(c, hipStreamSynchronize(s));
     return LVM_OK;
@@ -644,40 +684,29 @@ int lvm_chain_present(lvm_ctx* c, const lvm_preprocess_params* pp, const lvm_par
     if (!c || !pp || !p || !produced || !in) return LVM_ERR_INVALID;
     *produced = 0;
     if (c->nstreams != 1) { c->err = "lvm_chain_present needs a 1-stream context"; return LVM_ERR_INVALID; }
-    const int fmt = c->source_format;
-    if (fmt != LVM_PIX_BGR) {
-        if (const char* why = lvm::raw_frame_error(fmt, w, h, channels, in_stride)) { c->err = why; return LVM_ERR_INVALID; }
-    } else if (w <= 0 || h <= 0 || (channels != 1 && channels != 3) || in_stride < (ptrdiff_t)w * channels) { c->err = "bad frame arguments"; return LVM_ERR_INVALID; }
+    const Staged st = stage_plan(c, *pp, c->source_format, w, h, channels, in_stride, 1, false);      // (no tap of the context's: see below)
+    if (st.error) { c->err = st.error; return LVM_ERR_INVALID; }
     LVM_HIP_TRY(c, hipSetDevice(c->device));
-    const ChainGeom g = chain_geometry(*pp, w, h, channels, fmt);
+    const ChainGeom& g = st.g;
     if (d_proc && proc_stride < (ptrdiff_t)g.out_row) { c->err = "proc stride too small"; return LVM_ERR_INVALID; }
     if (d_orig && orig_stride < (ptrdiff_t)g.tap_row) { c->err = "orig stride too small"; return LVM_ERR_INVALID; }      // (the tap keeps the source's channel count)
     hipStream_t s = c->own_stream;
-    { const int orc = lvm::order_after_previous(c, s); if (orc != LVM_OK) return orc; }
-    LVM_HIP_TRY(c, hipStreamSynchronize(s));      // staging buffers may be replaced below
-    int rc = c->d_pre_in.reserve(c, g.roi_bytes); if (rc != LVM_OK) return rc;
-    rc = c->d_pre_out.reserve(c, g.out_bytes); if (rc != LVM_OK) return rc;
-    rc = c->d_chain_out.reserve(c, g.out_bytes); if (rc != LVM_OK) return rc;
-    LVM_HIP_TRY(c, chain_upload(g, c->d_pre_in, in, in_stride, s));
+    int rc = st.begin(s);
+    if (rc != LVM_OK) return rc;
+    LVM_HIP_TRY(c, st.upload(0, in, s));
+    // special case 1: with grayscale on a BGR source the kernel writes the colour tap straight into the caller's `original` buffer
     const bool gray_tap = d_orig && g.gray;
-    const uint8_t* mag_in = c->d_pre_in;
-    if (!g.identity) {
-        // with grayscale on a BGR source the kernel writes the colour tap straight into the caller's `original` buffer
-        rc = chain_preprocess(c, *pp, g, c->d_pre_in, g.roi_row, g.roi_bytes, c->d_pre_out, s, gray_tap ? d_orig : nullptr, orig_stride, (ptrdiff_t)orig_stride * g.oh);
-        if (rc != LVM_OK) { (void)hipStreamSynchronize(s); return rc; }
-        mag_in = c->d_pre_out;
-    }
+    rc = st.preprocess(0, s, gray_tap ? lvm::ImageOut{d_orig, g.ow, g.oh, 3, orig_stride, orig_stride * g.oh} : lvm::ImageOut());
+    if (rc != LVM_OK) { (void)hipStreamSynchronize(s); return rc; }
     if (d_orig && !gray_tap)        // no gray stage in between: the tap IS the frame the magnifier sees
-        LVM_HIP_TRY(c, hipMemcpy2DAsync(d_orig, (size_t)orig_stride, mag_in, g.out_row, g.out_row, (size_t)g.oh, hipMemcpyDeviceToDevice, s));
+        LVM_HIP_TRY(c, frame_copy(d_orig, orig_stride, st.seen(0), hipMemcpyDeviceToDevice, s));
     const lvm_params mp = chain_params(*p, *pp);
-    // the last kernel writes the processed frame straight into the caller's buffer
-    uint8_t* dst = d_proc ? d_proc : c->d_chain_out.p;
-    const ptrdiff_t dstride = d_proc ? proc_stride : (ptrdiff_t)g.out_row;
-    lvm::FrameIO io{mag_in, (ptrdiff_t)g.out_row, (ptrdiff_t)g.out_bytes, dst, dstride, dstride * g.oh, g.ow, g.oh, g.och};
+    // special case 2: the last kernel writes the processed frame straight into the caller's buffer
+    const lvm::FrameIO io = stage_io(st, 0, d_proc ? lvm::ImageOut{d_proc, g.ow, g.oh, g.och, proc_stride, proc_stride * g.oh} : st.out(0));
     rc = lvm::at_depth0(c, [&] { return lvm::process_device(c, &mp, io, s, produced); });
     if (rc != LVM_OK) { (void)hipStreamSynchronize(s); return rc; }
     if (!*produced && d_proc)       // passthrough: the chain hands the magnifier's INPUT on (MagnificationProcessor.cpp:61) -- that is what the display shows
-        LVM_HIP_TRY(c, hipMemcpy2DAsync(d_proc, (size_t)proc_stride, mag_in, g.out_row, g.out_row, (size_t)g.oh, hipMemcpyDeviceToDevice, s));
+        LVM_HIP_TRY(c, frame_copy(d_proc, proc_stride, st.seen(0), hipMemcpyDeviceToDevice, s));
     LVM_HIP_TRY(c, hipStreamSynchronize(s));
     return LVM_OK;
 }
@@ -698,180 +727,244 @@ int lvm_export_geometry(const lvm_preprocess_params* pp, int split, int w, int h
 // tools/ubench_pcie.hip: 52-57 GB/s one way, 90-97 GB/s with both directions busy).  The magnifier still sees every frame in order
 // with the state of its predecessor; a sub-batch is one temporal batch (lvm_process_device_frames), so the frames are the ones a
 // single 32-frame batch -- or 32 per-frame calls -- gives.
-// lvm_export_frames and lvm_export_frames_mjpeg: the same three-queue loop; with `mj` the canvases stay on the device and are encoded there
-struct MjpegSink { int quality; uint8_t* out; size_t capacity; size_t* offsets; };
-// ... and with `js` the frames arrive as JPEG (lvm_export_mjpeg_frames): decoded on the device by the upload queue, the ROI is a view into
-// the decoded frame instead of the pitch of a copy
-struct JpegSource { const uint8_t* bytes; const size_t* offsets; };
-static int export_frames_impl(lvm_ctx* c, const lvm_preprocess_params* pp, const lvm_params* p, int split, int n_frames,
-                              const uint8_t* const* frames, int w, int h, int channels, ptrdiff_t in_stride, uint8_t* const* canvases,
-                              ptrdiff_t canvas_stride, int* produced, const MjpegSink* mj, const JpegSource* js = nullptr) {
-    if (!c || !pp || !p || (!frames && !js) || (!canvases && !mj) || !produced || n_frames < 1) return LVM_ERR_INVALID;
-    if (mj && (!mj->out || !mj->offsets)) return LVM_ERR_INVALID;
-    if (js && (!js->bytes || !js->offsets || channels != 3)) return LVM_ERR_INVALID;
-    if (js) in_stride = (ptrdiff_t)w * 3;
+// The three public entry points are one loop (export_run) between a SOURCE -- host frames, or JPEG frames decoded on the device by the upload
+// queue, the ROI a view into the decoded frame instead of the pitch of a copy -- and a SINK: canvases to the host as BGR or as 4:2:0 surfaces, or
+// the canvases encoded on the device (Motion-JPEG).  Each is a small tagged struct with its few functions below; a new source or sink is one more
+// tag and one more case in each of them.
+struct ExportSource {
+    enum Kind { HostFrames, Jpeg } kind;
+    const uint8_t* const* frames; ptrdiff_t in_stride;      // HostFrames
+    const uint8_t* jpegs; const size_t* offsets;            // Jpeg: all frames of the call
+};
+struct ExportSink {
+    enum Kind { Bgr, Yuv, Mjpeg } kind;
+    uint8_t* const* canvases; ptrdiff_t canvas_stride;      // Bgr, Yuv: one host canvas per frame
+    int quality; uint8_t* out; size_t capacity; size_t* offsets;   // Mjpeg
+};
+
+// Everything an export call decides before it touches the device: the staged front end, the canvas and its layouts, how the canvases are made,
+// the sub-batches.
+struct ExportPlan {
+    Staged st; int split, n;
+    int cw, chh; size_t can_row, can_bytes;         // the BGR canvas, rows packed on the device
+    int cfmt; lvm::CanvasLayout host_l, dev_l;      // canvases as 4:2:0 surfaces: the caller's layout, and the device's -- rows packed, the same plane order
+    bool fused;                                     // the conversion reads the panes, the BGR canvas is never written
+    int chunk, nchunks;
+    lvm::ImageOut canvas(int k) const { return {st.c->d_canvas + (size_t)k * can_bytes, cw, chh, 3, (ptrdiff_t)can_row, (ptrdiff_t)can_bytes}; }
+    lvm::ImageOut surface(int k) const { return {st.c->d_canvas_yuv + (size_t)k * dev_l.bytes, cw, chh, 1, (ptrdiff_t)cw, (ptrdiff_t)dev_l.bytes}; }
+};
+static int export_plan(lvm_ctx* c, const lvm_preprocess_params* pp, int split, int n_frames, int w, int h, int channels, const ExportSource& src, const ExportSink& sink,
+                       int* produced, ExportPlan* out) {
+    const bool js = src.kind == ExportSource::Jpeg, mj = sink.kind == ExportSink::Mjpeg;
+    if (mj && (!sink.out || !sink.offsets)) return LVM_ERR_INVALID;
+    if (js && (!src.jpegs || !src.offsets || channels != 3)) return LVM_ERR_INVALID;
     if (c->nstreams != 1) { c->err = "lvm_export_frames needs a 1-stream context"; return LVM_ERR_INVALID; }
-    const int fmt = js ? LVM_PIX_BGR : c->source_format;        // (JPEG frames decode to BGR: lvm_export_mjpeg_frames does not take part)
-    if (fmt != LVM_PIX_BGR) {
-        if (const char* why = lvm::raw_frame_error(fmt, w, h, channels, in_stride)) { c->err = why; return LVM_ERR_INVALID; }
-    } else if (w <= 0 || h <= 0 || (channels != 1 && channels != 3) || in_stride < (ptrdiff_t)w * channels) { c->err = "bad frame arguments"; return LVM_ERR_INVALID; }
-    for (int k = 0; k < n_frames; ++k) { produced[k] = 0; if ((!js && !frames[k]) || (!mj && !canvases[k])) { c->err = "null frame pointer"; return LVM_ERR_INVALID; } }
+    ExportPlan& P = *out;
+    P.split = split; P.n = n_frames;
+    // (JPEG frames decode to BGR: lvm_export_mjpeg_frames does not take part in lvm_set_source_format)
+    P.st = stage_plan(c, *pp, js ? LVM_PIX_BGR : c->source_format, w, h, channels, js ? (ptrdiff_t)w * 3 : src.in_stride, n_frames, split != LVM_SPLIT_NONE, js);
+    if (P.st.error) { c->err = P.st.error; return LVM_ERR_INVALID; }
+    for (int k = 0; k < n_frames; ++k) { produced[k] = 0; if ((!js && !src.frames[k]) || (!mj && !sink.canvases[k])) { c->err = "null frame pointer"; return LVM_ERR_INVALID; } }
     LVM_HIP_TRY(c, hipSetDevice(c->device));
-    const ChainGeom g = chain_geometry(*pp, w, h, channels, fmt);
-    int pw, ph, cw, chh;
+    const ChainGeom& g = P.st.g;
+    int pw, ph;
     if (split < LVM_SPLIT_NONE || split > LVM_SPLIT_TOP_BOTTOM) { c->err = "invalid split mode"; return LVM_ERR_INVALID; }
-    if (!lvm::compose_geometry(split, g.ow, g.oh, g.ow, g.oh, &pw, &ph, &cw, &chh) || cw <= 0 || chh <= 0) {
+    if (!lvm::compose_geometry(split, g.ow, g.oh, g.ow, g.oh, &pw, &ph, &P.cw, &P.chh) || P.cw <= 0 || P.chh <= 0) {
         c->err = "lvm_export_frames: empty canvas (Exporter::compose returns an empty Mat for this geometry)"; return LVM_ERR_INVALID;
     }
-    // canvases as 4:2:0 surfaces (lvm_set_canvas_format; the JPEG sinks encode BGR canvases and do not take part): the caller's layout, and the
-    // device's -- rows packed, the same plane order
-    const int cfmt = mj ? LVM_PIX_BGR : c->canvas_format;
-    lvm::CanvasLayout host_l{}, dev_l{};
-    if (cfmt != LVM_PIX_BGR) {
-        if (const char* why = lvm::canvas_layout(cfmt, cw, chh, canvas_stride, &host_l)) { c->err = why; return LVM_ERR_INVALID; }
-        (void)lvm::canvas_layout(cfmt, cw, chh, (ptrdiff_t)cw, &dev_l);
-    } else if (!mj && canvas_stride < (ptrdiff_t)cw * 3) { c->err = "canvas stride too small"; return LVM_ERR_INVALID; }
-    const size_t can_row = (size_t)cw * 3, can_bytes = can_row * chh;
+    // canvases as 4:2:0 surfaces (lvm_set_canvas_format; the JPEG sink encodes BGR canvases and does not take part)
+    P.cfmt = sink.kind == ExportSink::Yuv ? c->canvas_format : LVM_PIX_BGR;
+    if (P.cfmt != LVM_PIX_BGR) {
+        if (const char* why = lvm::canvas_layout(P.cfmt, P.cw, P.chh, sink.canvas_stride, &P.host_l)) { c->err = why; return LVM_ERR_INVALID; }
+        (void)lvm::canvas_layout(P.cfmt, P.cw, P.chh, (ptrdiff_t)P.cw, &P.dev_l);
+    } else if (!mj && sink.canvas_stride < (ptrdiff_t)P.cw * 3) { c->err = "canvas stride too small"; return LVM_ERR_INVALID; }
+    P.can_row = (size_t)P.cw * 3; P.can_bytes = P.can_row * P.chh;
     // without labels the conversion reads the panes and the BGR canvas is never written; with labels: compose, overlay, convert (the definition's order)
-    bool fused = cfmt != LVM_PIX_BGR && c->overlay_n == 0;
-    if (fused) lvm::env_switch("LVM_CANVAS_FUSED", fused);
-    hipStream_t s = c->own_stream;
-    { const int orc = lvm::order_after_previous(c, s); if (orc != LVM_OK) return orc; }
-    LVM_HIP_TRY(c, hipStreamSynchronize(s));      // staging buffers may be replaced below
-    // the pane Exporter::compose labels "Original" is runChainOnce's tap (ChainGeom::gray)
-    const bool gray_tap = g.gray && split != LVM_SPLIT_NONE;
-    // where stage 1 leaves frame k: the cropped copy (host frames), or the ROI inside the decoded frame (JPEG frames)
-    const size_t full_row = (size_t)w * channels, full_bytes = full_row * h;
-    const size_t src_row = js ? full_row : g.roi_row, src_fbytes = js ? full_bytes : g.roi_bytes;
-    int rc = c->d_pre_in.reserve(c, src_fbytes * n_frames); if (rc != LVM_OK) return rc;
-    const uint8_t* src_base = js ? c->d_pre_in + (size_t)g.ry * full_row + (size_t)g.rx * channels : c->d_pre_in;
-    rc = c->d_pre_out.reserve(c, g.out_bytes * n_frames); if (rc != LVM_OK) return rc;
-    rc = c->d_chain_out.reserve(c, g.out_bytes * n_frames); if (rc != LVM_OK) return rc;
-    if (!fused) { rc = c->d_canvas.reserve(c, can_bytes * n_frames); if (rc != LVM_OK) return rc; }
-    if (cfmt != LVM_PIX_BGR) { rc = c->d_canvas_yuv.reserve(c, dev_l.bytes * n_frames); if (rc != LVM_OK) return rc; }
-    if (gray_tap) { rc = c->d_pre_tap.reserve(c, g.tap_bytes * n_frames); if (rc != LVM_OK) return rc; }
-    int chunk = mj ? 4 : 2;      // (JPEG frames: nothing large to download, the encoder's launches want more frames each)
-    lvm::env_switch(mj ? "LVM_EXPORT_MJPEG_CHUNK" : "LVM_EXPORT_CHUNK", chunk, [](int v) { return v >= 1; });
-    const int nchunks = (n_frames + chunk - 1) / chunk;
+    P.fused = P.cfmt != LVM_PIX_BGR && c->overlay_n == 0;
+    if (P.fused) lvm::env_switch("LVM_CANVAS_FUSED", P.fused);
+    P.chunk = mj ? 4 : 2;        // (JPEG frames: nothing large to download, the encoder's launches want more frames each)
+    lvm::env_switch(mj ? "LVM_EXPORT_MJPEG_CHUNK" : "LVM_EXPORT_CHUNK", P.chunk, [](int v) { return v >= 1; });
+    P.nchunks = (n_frames + P.chunk - 1) / P.chunk;
+    return LVM_OK;
+}
 
+// the staging buffers behind the front end's, the two side queues and an event pair per sub-batch
+static int export_reserve(Ctx* c, const ExportPlan& P) {
+    int rc = LVM_OK;
+    if (!P.fused) rc = c->d_canvas.reserve(c, P.can_bytes * P.n);
+    if (rc == LVM_OK && P.cfmt != LVM_PIX_BGR) rc = c->d_canvas_yuv.reserve(c, P.dev_l.bytes * P.n);
+    if (rc != LVM_OK) return rc;
     if (!c->up_stream) LVM_HIP_TRY(c, hipStreamCreateWithFlags(&c->up_stream, hipStreamNonBlocking));
     if (!c->down_stream) LVM_HIP_TRY(c, hipStreamCreateWithFlags(&c->down_stream, hipStreamNonBlocking));
-    while ((int)c->ev_up.size() < nchunks) { hipEvent_t e = nullptr; LVM_HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->ev_up.push_back(e); }
-    while ((int)c->ev_done.size() < nchunks) { hipEvent_t e = nullptr; LVM_HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->ev_done.push_back(e); }
-    if (mj) { rc = lvm::mjpeg_begin(c, cw, chh, mj->quality, chunk < n_frames ? chunk : n_frames, (size_t)n_frames, mj->capacity, c->down_stream); if (rc != LVM_OK) return rc; }
-    auto drain = [&]() { (void)hipStreamSynchronize(c->up_stream); (void)hipStreamSynchronize(s); (void)hipStreamSynchronize(c->down_stream); if (mj) lvm::mjpeg_abort(c); };
-#define LVM_EXPORT_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { c->err = std::string(#expr) + ": " + hipGetErrorString(e_); drain(); return LVM_ERR_HIP; } } while (0)
-    const uint8_t* mag_base = g.identity ? src_base : c->d_pre_out;
-    const size_t mag_row = g.identity ? src_row : g.out_row, mag_fbytes = g.identity ? src_fbytes : g.out_bytes;
-    const lvm_params mp = chain_params(*p, *pp);
-    if (js) {
-        // JPEG frames: only the compressed bytes cross PCIe, and ALL frames of the call are decoded by one set of launches -- Huffman decoding
-        // is serial inside a restart interval (a lane each), its time is a latency that does not grow with the number of frames
-        rc = lvm::mjpeg_decode_begin(c, js->bytes, js->offsets, n_frames, w, h, c->up_stream);
-        if (rc == LVM_OK) rc = lvm::mjpeg_decode_enqueue(c, 0, n_frames, c->d_pre_in, (ptrdiff_t)full_row, (ptrdiff_t)full_bytes, c->up_stream);
-        if (rc != LVM_OK) { drain(); return rc; }
+    for (auto* evs : {&c->ev_up, &c->ev_done})
+        while ((int)evs->size() < P.nchunks) { hipEvent_t e = nullptr; LVM_HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming)); evs->push_back(e); }
+    return LVM_OK;
+}
+
+// ---- the source: sub-batch q arrives on up_stream -----------------------------------------------------------------------------------------
+static int source_begin(const ExportPlan& P, const ExportSource& src, int w, int h) {
+    if (src.kind != ExportSource::Jpeg) return LVM_OK;
+    // JPEG frames: only the compressed bytes cross PCIe, and ALL frames of the call are decoded by one set of launches -- Huffman decoding
+    // is serial inside a restart interval (a lane each), its time is a latency that does not grow with the number of frames
+    Ctx* c = P.st.c;
+    const int rc = lvm::mjpeg_decode_begin(c, src.jpegs, src.offsets, P.n, w, h, c->up_stream);
+    if (rc != LVM_OK) return rc;
+    return lvm::mjpeg_decode_enqueue(c, 0, P.n, c->d_pre_in, (ptrdiff_t)P.st.src_row, (ptrdiff_t)P.st.src_fbytes, c->up_stream);
+}
+static int source_upload(const ExportPlan& P, const ExportSource& src, int f0, int nf) {
+    if (src.kind == ExportSource::Jpeg) return LVM_OK;                  // (decoded already, or on its way: source_begin)
+    for (int k = f0; k < f0 + nf; ++k) LVM_HIP_TRY(P.st.c, P.st.upload(k, src.frames[k], P.st.c->up_stream));
+    return LVM_OK;
+}
+static int source_finish(const ExportPlan& P, const ExportSource& src) {       // a malformed input frame fails the call
+    return src.kind == ExportSource::Jpeg ? lvm::mjpeg_decode_finish(P.st.c, P.st.c->up_stream) : LVM_OK;
+}
+
+// ---- the middle, on the context's stream: Preprocess + Grayscale, the magnifier as one temporal batch, the canvases -------------------------
+static int export_canvases(const ExportPlan& P, int f0, int nf, const int* produced, hipStream_t s) {
+    Ctx* c = P.st.c;
+    for (int k = f0; k < f0 + nf; ++k) {
+        const lvm::Image seen = P.st.seen(k);                                          // what the magnifier saw
+        const lvm::Image proc = produced[k] ? (lvm::Image)P.st.out(k) : seen;          // MagnificationProcessor.cpp:61
+        const lvm::Image orig = P.st.tap(k);                                           // ChainBuilder.cpp:25
+        const int rc = P.fused ? lvm::canvas_yuv_fused(c, P.cfmt, P.split, orig, proc, P.surface(k), s) : lvm::compose_device(c, P.split, orig, proc, P.canvas(k), s);
+        if (rc != LVM_OK) return rc;
     }
-    for (int q = 0; q < nchunks; ++q) {
-        const int f0 = q * chunk, nf = (f0 + chunk <= n_frames) ? chunk : n_frames - f0;
-        // stage 1 (up_stream): only the ROI rows cross PCIe (the crop is the pitch of the 2-D copy)
-        if (!js) {
-            for (int k = f0; k < f0 + nf; ++k)
-                LVM_EXPORT_TRY(chain_upload(g, c->d_pre_in + (size_t)k * g.roi_bytes, frames[k], in_stride, c->up_stream));
-        }
-        LVM_EXPORT_TRY(hipEventRecord(c->ev_up[q], c->up_stream));
-        // stage 2 (the context's stream): Preprocess + Grayscale, the magnifier as one temporal batch, compose
-        LVM_EXPORT_TRY(hipStreamWaitEvent(s, c->ev_up[q], 0));
-        if (!g.identity) {
-            for (int k = f0; k < f0 + nf; ++k) {                         // (stateless: a frame of the batch is one more "stream" of a 1-stream context)
-                rc = chain_preprocess(c, *pp, g, src_base + (size_t)k * src_fbytes, src_row, src_fbytes, c->d_pre_out + (size_t)k * g.out_bytes, s,
-                                      gray_tap ? c->d_pre_tap + (size_t)k * g.tap_bytes : nullptr, (ptrdiff_t)g.tap_row, (ptrdiff_t)g.tap_bytes);
-                if (rc != LVM_OK) { drain(); return rc; }
-            }
-        }
-        rc = lvm::at_depth0(c, [&] {
-            return lvm_process_device_frames(c, &mp, nf, mag_base + (size_t)f0 * mag_fbytes, g.ow, g.oh, g.och, (ptrdiff_t)mag_row, (ptrdiff_t)mag_fbytes, (ptrdiff_t)mag_fbytes,
-                                             c->d_chain_out + (size_t)f0 * g.out_bytes, (ptrdiff_t)g.out_row, (ptrdiff_t)g.out_bytes, (ptrdiff_t)g.out_bytes, produced + f0, s);
-        });
-        if (rc != LVM_OK) { drain(); return rc; }
-        for (int k = f0; k < f0 + nf; ++k) {
-            const uint8_t* seen = mag_base + (size_t)k * mag_fbytes;                                // what the magnifier saw
-            const bool pr = produced[k] != 0;
-            const uint8_t* proc = pr ? c->d_chain_out + (size_t)k * g.out_bytes : seen;               // MagnificationProcessor.cpp:61
-            const uint8_t* orig = gray_tap ? c->d_pre_tap + (size_t)k * g.tap_bytes : seen;           // ChainBuilder.cpp:25
-            if (fused)
-                rc = lvm::canvas_yuv_fused(c, cfmt, split, orig, g.ow, g.oh, gray_tap ? 3 : g.och, (ptrdiff_t)(gray_tap ? g.tap_row : mag_row), proc, g.ow, g.oh, g.och,
-                                           (ptrdiff_t)(pr ? g.out_row : mag_row), c->d_canvas_yuv + (size_t)k * dev_l.bytes, (ptrdiff_t)cw, s);
-            else
-                rc = lvm::compose_device(c, split, orig, g.ow, g.oh, gray_tap ? 3 : g.och, (ptrdiff_t)(gray_tap ? g.tap_row : mag_row), (ptrdiff_t)(gray_tap ? g.tap_bytes : mag_fbytes),
-                                         proc, g.ow, g.oh, g.och, (ptrdiff_t)(pr ? g.out_row : mag_row), (ptrdiff_t)(pr ? g.out_bytes : mag_fbytes), c->d_canvas + (size_t)k * can_bytes,
-                                         (ptrdiff_t)can_row, (ptrdiff_t)can_bytes, s);
-            if (rc != LVM_OK) { drain(); return rc; }
-        }
-        if (!fused) {
-            // drawLabel on every canvas of the sub-batch (Exporter.cpp:74-77, :82-85), from the tables of lvm_export_set_overlay
-            rc = lvm::overlay_device(c, c->d_canvas + (size_t)f0 * can_bytes, cw, chh, (ptrdiff_t)can_row, (ptrdiff_t)can_bytes, nf, s);
-            if (rc == LVM_OK && cfmt != LVM_PIX_BGR)        // ... and the sub-batch's canvases become surfaces in one launch
-                rc = lvm::canvas_yuv_device(c, cfmt, c->d_canvas + (size_t)f0 * can_bytes, cw, chh, (ptrdiff_t)can_row, (ptrdiff_t)can_bytes, nf,
-                                            c->d_canvas_yuv + (size_t)f0 * dev_l.bytes, (ptrdiff_t)cw, (ptrdiff_t)dev_l.bytes, s);
-            if (rc != LVM_OK) { drain(); return rc; }
-        }
-        LVM_EXPORT_TRY(hipEventRecord(c->ev_done[q], s));
-        LVM_EXPORT_TRY(hipStreamWaitEvent(c->down_stream, c->ev_done[q], 0));
-        if (mj) {       // stage 3 stays on the device (down_stream, next to the magnifier of the following sub-batch): the canvases become JPEG
-                        // frames behind the earlier ones; nothing to download until the end
-            rc = lvm::mjpeg_encode_device(c, c->d_canvas + (size_t)f0 * can_bytes, (ptrdiff_t)can_row, (ptrdiff_t)can_bytes, nf, f0, mj->capacity, c->down_stream);
-            if (rc == LVM_OK && q >= 2) rc = lvm::mjpeg_drain(c, mj->out, (size_t)q - 1);       // the frames of sub-batch q - 2 come down meanwhile
-            if (rc != LVM_OK) { drain(); return rc; }
-            continue;
-        }
-        // stage 3 (down_stream): the canvases of this sub-batch
-        for (int k = f0; k < f0 + nf && cfmt != LVM_PIX_BGR; ++k) {
-            // 1.5 B / pixel.  3h/2 rows of cw bytes in one copy where the chroma rows follow the Y rows at the Y stride (NV12 / NV21; the planar
-            // formats with packed rows: two chroma rows are one row of cw bytes); otherwise Y, then the two chroma planes
-            const uint8_t* d = c->d_canvas_yuv + (size_t)k * dev_l.bytes;
-            const bool one = dev_l.plane2 == 0 || canvas_stride == (ptrdiff_t)cw;
-            LVM_EXPORT_TRY(hipMemcpy2DAsync(canvases[k], (size_t)canvas_stride, d, (size_t)cw, (size_t)cw, (size_t)(one ? chh + chh / 2 : chh), hipMemcpyDeviceToHost, c->down_stream));
-            if (one) continue;
-            LVM_EXPORT_TRY(hipMemcpy2DAsync(canvases[k] + host_l.plane1, (size_t)host_l.cstride, d + dev_l.plane1, (size_t)cw / 2, (size_t)cw / 2, (size_t)chh / 2, hipMemcpyDeviceToHost, c->down_stream));
-            LVM_EXPORT_TRY(hipMemcpy2DAsync(canvases[k] + host_l.plane2, (size_t)host_l.cstride, d + dev_l.plane2, (size_t)cw / 2, (size_t)cw / 2, (size_t)chh / 2, hipMemcpyDeviceToHost, c->down_stream));
-        }
-        for (int k = f0; k < f0 + nf && cfmt == LVM_PIX_BGR; ++k)
-            LVM_EXPORT_TRY(hipMemcpy2DAsync(canvases[k], (size_t)canvas_stride, c->d_canvas + (size_t)k * can_bytes, can_row, can_row, (size_t)chh,
-                                            hipMemcpyDeviceToHost, c->down_stream));
+    if (P.fused) return LVM_OK;
+    // drawLabel on every canvas of the sub-batch (Exporter.cpp:74-77, :82-85), from the tables of lvm_export_set_overlay
+    const int rc = lvm::overlay_device(c, P.canvas(f0), nf, s);
+    if (rc != LVM_OK || P.cfmt == LVM_PIX_BGR) return rc;
+    return lvm::canvas_yuv_device(c, P.cfmt, P.canvas(f0), nf, P.surface(f0), s);       // ... and the sub-batch's canvases become surfaces in one launch
+}
+static int export_middle(const ExportPlan& P, const lvm_params& mp, int f0, int nf, int* produced, hipStream_t s) {
+    Ctx* c = P.st.c;
+    for (int k = f0; k < f0 + nf; ++k) {                         // (stateless: a frame of the batch is one more "stream" of a 1-stream context)
+        const int rc = P.st.preprocess(k, s, P.st.own_tap(k));
+        if (rc != LVM_OK) return rc;
     }
-#undef LVM_EXPORT_TRY
-    lvm::mark_enqueued(c, s);
-    int drc = LVM_OK;
-    if (js) drc = lvm::mjpeg_decode_finish(c, c->up_stream);                                    // a malformed input frame fails the call
-    if (mj) {
-        rc = lvm::mjpeg_finish(c, (size_t)n_frames, mj->out, mj->offsets, c->down_stream);       // waits for the encoder, then the compressed bytes come down in one copy
+    const lvm::Image in = P.st.seen(f0);
+    const lvm::ImageOut out = P.st.out(f0);
+    const int rc = lvm::at_depth0(c, [&] {
+        return lvm_process_device_frames(static_cast<lvm_ctx*>(c), &mp, nf, in.p, in.w, in.h, in.cn, in.stride, in.sstride, in.sstride, out.p, out.stride, out.sstride, out.sstride,
+                                         produced + f0, s);
+    });
+    return rc != LVM_OK ? rc : export_canvases(P, f0, nf, produced, s);
+}
+
+// ---- the sink: takes sub-batch q on down_stream ------------------------------------------------------------------------------------------------
+static int sink_begin(const ExportPlan& P, const ExportSink& sink) {
+    if (sink.kind != ExportSink::Mjpeg) return LVM_OK;
+    return lvm::mjpeg_begin(P.st.c, P.cw, P.chh, sink.quality, P.chunk < P.n ? P.chunk : P.n, (size_t)P.n, sink.capacity, P.st.c->down_stream);
+}
+// 1.5 B / pixel.  3h/2 rows of cw bytes in one copy where the chroma rows follow the Y rows at the Y stride (NV12 / NV21; the planar formats with
+// packed rows: two chroma rows are one row of cw bytes); otherwise Y, then the two chroma planes
+static int surface_download(const ExportPlan& P, const ExportSink& sink, int k, hipStream_t s) {
+    Ctx* c = P.st.c;
+    const uint8_t* d = P.surface(k).p;
+    uint8_t* to = sink.canvases[k];
+    const size_t cw = (size_t)P.cw, chh = (size_t)P.chh;
+    const bool one = P.dev_l.plane2 == 0 || sink.canvas_stride == (ptrdiff_t)cw;
+    LVM_HIP_TRY(c, hipMemcpy2DAsync(to, (size_t)sink.canvas_stride, d, cw, cw, one ? chh + chh / 2 : chh, hipMemcpyDeviceToHost, s));
+    if (one) return LVM_OK;
+    for (const auto& pl : {std::make_pair(P.host_l.plane1, P.dev_l.plane1), std::make_pair(P.host_l.plane2, P.dev_l.plane2)})
+        LVM_HIP_TRY(c, hipMemcpy2DAsync(to + pl.first, (size_t)P.host_l.cstride, d + pl.second, cw / 2, cw / 2, chh / 2, hipMemcpyDeviceToHost, s));
+    return LVM_OK;
+}
+static int sink_take(const ExportPlan& P, const ExportSink& sink, int q, int f0, int nf) {
+    Ctx* c = P.st.c;
+    if (sink.kind == ExportSink::Mjpeg) {
+        // stays on the device (down_stream, next to the magnifier of the following sub-batch): the canvases become JPEG frames behind the
+        // earlier ones; the frames of sub-batch q - 2 come down meanwhile
+        const lvm::Image can = P.canvas(f0);
+        const int rc = lvm::mjpeg_encode_device(c, can.p, can.stride, can.sstride, nf, f0, sink.capacity, c->down_stream);
+        return (rc == LVM_OK && q >= 2) ? lvm::mjpeg_drain(c, sink.out, (size_t)q - 1) : rc;
+    }
+    for (int k = f0; k < f0 + nf; ++k) {
+        if (sink.kind == ExportSink::Yuv) { const int rc = surface_download(P, sink, k, c->down_stream); if (rc != LVM_OK) return rc; }
+        else LVM_HIP_TRY(c, frame_copy(sink.canvases[k], sink.canvas_stride, P.canvas(k), hipMemcpyDeviceToHost, c->down_stream));
+    }
+    return LVM_OK;
+}
+// the end of the call: everything has been enqueued.  Motion-JPEG: waits for the encoder, then the compressed bytes come down in one copy
+static int sink_finish(const ExportPlan& P, const ExportSink& sink, hipStream_t s) {
+    Ctx* c = P.st.c;
+    if (sink.kind == ExportSink::Mjpeg) {
+        const int rc = lvm::mjpeg_finish(c, (size_t)P.n, sink.out, sink.offsets, c->down_stream);
         (void)hipStreamSynchronize(s);
         (void)hipStreamSynchronize(c->up_stream);
-        return drc != LVM_OK ? drc : rc;
+        return rc;
     }
     LVM_HIP_TRY(c, hipStreamSynchronize(c->down_stream));     // (the last canvases: everything on `s` and `up_stream` precedes them)
     LVM_HIP_TRY(c, hipStreamSynchronize(s));
-    return drc;
+    return LVM_OK;
+}
+
+// A failed return of the loop below leaves nothing running: it waits for the three queues and for the downloads the encoder has queued.
+struct ExportGuard {
+    Ctx* c; bool mj; bool armed = true;
+    ~ExportGuard() {
+        if (!armed) return;
+        (void)hipStreamSynchronize(c->up_stream); (void)hipStreamSynchronize(c->own_stream); (void)hipStreamSynchronize(c->down_stream);
+        if (mj) lvm::mjpeg_abort(c);
+    }
+};
+
+static int export_run(lvm_ctx* c, const lvm_preprocess_params* pp, const lvm_params* p, int split, int n_frames, int w, int h, int channels, const ExportSource& src,
+                      const ExportSink& asked, int* produced) {
+    if (!c || !pp || !p || !produced || n_frames < 1) return LVM_ERR_INVALID;
+    // the sink is chosen here, once: the wrapper asks for host canvases, lvm_set_canvas_format says of which kind
+    ExportSink chosen = asked;
+    if (asked.kind == ExportSink::Bgr && c->canvas_format != LVM_PIX_BGR) chosen.kind = ExportSink::Yuv;
+    const ExportSink& sink = chosen;
+    if ((src.kind == ExportSource::HostFrames && !src.frames) || (sink.kind != ExportSink::Mjpeg && !sink.canvases)) return LVM_ERR_INVALID;
+    ExportPlan P{};
+    int rc = export_plan(c, pp, split, n_frames, w, h, channels, src, sink, produced, &P);
+    if (rc != LVM_OK) return rc;
+    hipStream_t s = c->own_stream;
+    rc = P.st.begin(s);
+    if (rc == LVM_OK) rc = export_reserve(c, P);
+    if (rc == LVM_OK) rc = sink_begin(P, sink);
+    if (rc != LVM_OK) return rc;
+    ExportGuard guard{c, sink.kind == ExportSink::Mjpeg};
+    const lvm_params mp = chain_params(*p, *pp);
+    rc = source_begin(P, src, w, h);
+    for (int q = 0; q < P.nchunks && rc == LVM_OK; ++q) {
+        const int f0 = q * P.chunk, nf = (f0 + P.chunk <= n_frames) ? P.chunk : n_frames - f0;
+        rc = source_upload(P, src, f0, nf);                                     // stage 1 (up_stream)
+        if (rc != LVM_OK) break;
+        LVM_HIP_TRY(c, hipEventRecord(c->ev_up[q], c->up_stream));
+        LVM_HIP_TRY(c, hipStreamWaitEvent(s, c->ev_up[q], 0));
+        rc = export_middle(P, mp, f0, nf, produced, s);                         // stage 2 (the context's stream)
+        if (rc != LVM_OK) break;
+        LVM_HIP_TRY(c, hipEventRecord(c->ev_done[q], s));
+        LVM_HIP_TRY(c, hipStreamWaitEvent(c->down_stream, c->ev_done[q], 0));
+        rc = sink_take(P, sink, q, f0, nf);                                     // stage 3 (down_stream)
+    }
+    if (rc != LVM_OK) return rc;
+    lvm::mark_enqueued(c, s);
+    const int drc = source_finish(P, src);
+    rc = sink_finish(P, sink, s);
+    if (drc == LVM_OK && rc == LVM_OK) guard.armed = false;
+    return drc != LVM_OK ? drc : rc;
 }
 
 int lvm_export_frames(lvm_ctx* c, const lvm_preprocess_params* pp, const lvm_params* p, int split, int n_frames,
                       const uint8_t* const* frames, int w, int h, int channels, ptrdiff_t in_stride, uint8_t* const* canvases,
                       ptrdiff_t canvas_stride, int* produced) {
-    if (!canvases) return LVM_ERR_INVALID;
-    return export_frames_impl(c, pp, p, split, n_frames, frames, w, h, channels, in_stride, canvases, canvas_stride, produced, nullptr);
+    return export_run(c, pp, p, split, n_frames, w, h, channels, ExportSource{ExportSource::HostFrames, frames, in_stride}, ExportSink{ExportSink::Bgr, canvases, canvas_stride}, produced);
 }
 
 int lvm_export_frames_mjpeg(lvm_ctx* c, const lvm_preprocess_params* pp, const lvm_params* p, int split, int n_frames,
                             const uint8_t* const* frames, int w, int h, int channels, ptrdiff_t in_stride, int quality,
                             uint8_t* out, size_t out_capacity, size_t* offsets, int* produced) {
-    const MjpegSink mj{quality, out, out_capacity, offsets};
-    return export_frames_impl(c, pp, p, split, n_frames, frames, w, h, channels, in_stride, nullptr, 0, produced, &mj);
+    return export_run(c, pp, p, split, n_frames, w, h, channels, ExportSource{ExportSource::HostFrames, frames, in_stride}, ExportSink{ExportSink::Mjpeg, nullptr, 0, quality, out, out_capacity, offsets}, produced);
 }
 
 int lvm_mjpeg_decode_device(lvm_ctx* c, const uint8_t* jpegs, const size_t* offsets, int n_frames, int w, int h, uint8_t* d_bgr, ptrdiff_t stride,
                             ptrdiff_t frame_stride) {
     if (!c || !jpegs || !offsets || !d_bgr || n_frames < 1) return LVM_ERR_INVALID;
     if (stride < (ptrdiff_t)w * 3 || (n_frames > 1 && frame_stride < (ptrdiff_t)h * stride)) { c->err = "bad frame arguments"; return LVM_ERR_INVALID; }
+    // by hand: a failed decode has waited for what it enqueued (it reads the decoder's error flags), so only a successful one is marked
     LVM_HIP_TRY(c, hipSetDevice(c->device));
     int rc = lvm::order_after_previous(c, c->own_stream);
     if (rc != LVM_OK) return rc;
@@ -882,9 +975,7 @@ int lvm_mjpeg_decode_device(lvm_ctx* c, const uint8_t* jpegs, const size_t* offs
 
 int lvm_export_mjpeg_frames(lvm_ctx* c, const lvm_preprocess_params* pp, const lvm_params* p, int split, int n_frames, const uint8_t* jpegs,
                             const size_t* in_offsets, int w, int h, int quality, uint8_t* out, size_t out_capacity, size_t* offsets, int* produced) {
-    const MjpegSink mj{quality, out, out_capacity, offsets};
-    const JpegSource js{jpegs, in_offsets};
-    return export_frames_impl(c, pp, p, split, n_frames, nullptr, w, h, 3, (ptrdiff_t)w * 3, nullptr, 0, produced, &mj, &js);
+    return export_run(c, pp, p, split, n_frames, w, h, 3, ExportSource{ExportSource::Jpeg, nullptr, 0, jpegs, in_offsets}, ExportSink{ExportSink::Mjpeg, nullptr, 0, quality, out, out_capacity, offsets}, produced);
 }
 
 int lvm_mjpeg_set_restart_interval(lvm_ctx* c, int mcus) {
@@ -1001,16 +1092,12 @@ int lvm_canvas_layout(int fmt, int canvas_w, int canvas_h, ptrdiff_t canvas_stri
 int lvm_canvas_convert_device(lvm_ctx* c, int fmt, const uint8_t* d_bgr, int w, int h, ptrdiff_t bgr_stride, ptrdiff_t bgr_frame_stride, int n_frames,
                               uint8_t* d_out, ptrdiff_t out_stride, ptrdiff_t out_frame_stride, void* hip_stream) {
     if (!c) return LVM_ERR_INVALID;
-    LVM_HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
-    // (refused before anything runs: not even the wait that orders this call behind the previous one is enqueued)
-    int rc = lvm::canvas_yuv_device(c, fmt, d_bgr, w, h, bgr_stride, bgr_frame_stride, n_frames, d_out, out_stride, out_frame_stride, s, true);
+    const lvm::Image bgr{d_bgr, w, h, 3, bgr_stride, bgr_frame_stride};
+    const lvm::ImageOut out{d_out, w, h, 1, out_stride, out_frame_stride};
+    // validated first (no HIP call): a refused call enqueues nothing, not even the wait that orders it behind the previous one
+    const int rc = lvm::canvas_yuv_device(c, fmt, bgr, n_frames, out, nullptr, true);
     if (rc != LVM_OK) return rc;
-    rc = lvm::order_after_previous(c, s);
-    if (rc != LVM_OK) return rc;
-    rc = lvm::canvas_yuv_device(c, fmt, d_bgr, w, h, bgr_stride, bgr_frame_stride, n_frames, d_out, out_stride, out_frame_stride, s);
-    lvm::mark_enqueued(c, s);
-    return rc;
+    return lvm::on_stream(c, hip_stream, [&](hipStream_t s) { return lvm::canvas_yuv_device(c, fmt, bgr, n_frames, out, s); });
 }
 
 size_t lvm_mjpeg_bound(int w, int h) { return (w < 1 || h < 1) ? 0 : lvm::mjpeg_bound(w, h); }
@@ -1019,6 +1106,8 @@ int lvm_mjpeg_encode_device(lvm_ctx* c, const uint8_t* d_bgr, int w, int h, ptrd
                             uint8_t* out, size_t out_capacity, size_t* offsets) {
     if (!c || !d_bgr || !out || !offsets || n_frames < 1) return LVM_ERR_INVALID;
     if (stride < (ptrdiff_t)w * 3 || (n_frames > 1 && frame_stride < (ptrdiff_t)h * stride)) { c->err = "bad frame arguments"; return LVM_ERR_INVALID; }
+    // by hand: the call is marked between the last encode and mjpeg_finish, which waits for it -- and only where every encode was enqueued (a failed
+    // one has waited for the stream already)
     LVM_HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->own_stream;
     const int per = n_frames < 8 ? n_frames : 8;                 // scratch (coefficients, bit buffers) for eight frames at a time
@@ -1070,8 +1159,7 @@ int lvm_process(lvm_ctx* c, const lvm_params* p, const uint8_t* in, int w, int h
         lvm::FrameIO io{nullptr, 0, 0, nullptr, 0, 0, w, h, channels};
         return lvm::process_device(c, p, io, c->own_stream, produced);
     }
-    if (!out || (channels != 1 && channels != 3) || in_stride < (ptrdiff_t)w * channels ||
-        out_stride < (ptrdiff_t)w * channels) { c->err = "bad frame arguments"; return LVM_ERR_INVALID; }
+    if (!out || lvm::source_frame_error(LVM_PIX_BGR, w, h, channels, in_stride) || out_stride < (ptrdiff_t)w * channels) { c->err = "bad frame arguments"; return LVM_ERR_INVALID; }
     const size_t row = (size_t)w * channels, bytes = row * h;
     static const bool zero_copy = [] { bool on = true; lvm::env_switch("LVM_ZERO_COPY", on); return on; }();
     const bool one_reader = channels == 3 && !c->lab_analytic && (p->mode == LVM_MODE_LAPLACE || p->mode == LVM_MODE_PHASE);
@@ -1151,13 +1239,7 @@ int lvm_debug_lab_analytic(lvm_ctx* c, int on) { if (!c) return LVM_ERR_INVALID;
 
 int lvm_debug_trig_eval(lvm_ctx* c, int fn, const float* d_x, float* d_y, size_t n, void* hip_stream) {
     if (!c || fn < 0 || fn > 2 || (n && (!d_x || !d_y))) return LVM_ERR_INVALID;
-    LVM_HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
-    int rc = lvm::order_after_previous(c, s);
-    if (rc != LVM_OK) return rc;
-    rc = lvm::riesz_trig_eval(c, fn, d_x, d_y, n, s);
-    lvm::mark_enqueued(c, s);
-    return rc;
+    return lvm::on_stream(c, hip_stream, [&](hipStream_t s) { return lvm::riesz_trig_eval(c, fn, d_x, d_y, n, s); });
 }
 
 int lvm_get_lab_lut(lvm_ctx* c, int16_t* dst) {

@@ -680,12 +680,21 @@ constexpr int kGrayLabFloats = 3 * 256;
 void lab_gray_table(Ctx* c, float* tab, hipStream_t s);
 void lab_gray_plane(Ctx* c, const uint8_t* d_in, long in_stride, long in_sstride, int w, int h, int nframes, const float* tab, float* Lf, hipStream_t s);
 
+// A view of u8 frames in device memory, as the host layer hands them about: w x h pixels of cn channels, rows `stride` bytes apart; `sstride` is
+// the distance to the next frame of the same kind -- the next stream of a multi-stream context, or the next frame of a batch.  A view with a
+// null pointer stands for "no frame" (no original, no tap).  ImageOut is the writable twin.
+struct Image { const uint8_t* p = nullptr; int w = 0, h = 0, cn = 0; ptrdiff_t stride = 0, sstride = 0; };
+struct ImageOut {
+    uint8_t* p = nullptr; int w = 0, h = 0, cn = 0; ptrdiff_t stride = 0, sstride = 0;
+    operator Image() const { return {p, w, h, cn, stride, sstride}; }
+};
+
 // preprocess.hip
 void preprocess_geometry(const lvm_preprocess_params& pp, int w, int h, int channels, int* rx, int* ry, int* rw, int* rh,
                          int* ow, int* oh, int* och);
-int preprocess_device(Ctx* c, const lvm_preprocess_params& pp, const uint8_t* d_in, int w, int h, int channels, ptrdiff_t in_stride,
-                      ptrdiff_t in_sstride, uint8_t* d_out, ptrdiff_t out_stride, ptrdiff_t out_sstride, hipStream_t s,
-                      uint8_t* d_tap = nullptr, ptrdiff_t tap_stride = 0, ptrdiff_t tap_sstride = 0, const struct RawSource* raw = nullptr);
+// `out` and `tap` say where the frames go and with which strides: their size and channels are preprocess_geometry's of `in`
+int preprocess_device(Ctx* c, const lvm_preprocess_params& pp, const Image& in, const ImageOut& out, hipStream_t s, const ImageOut& tap = ImageOut(),
+                      const struct RawSource* raw = nullptr);
 // A frame in a raw camera format (lvm_set_source_format): d_in points at a buffer that holds the w x h frame -- or, behind the chain's
 // upload, the part of it that covers the ROI -- whose pixel (0, 0) sits at (px, py) in {0, 1}^2 of the chroma pair / 2x2 block it belongs
 // to; uv_offset = bytes from d_in to the UV row of pixel row 0 (NV12 / NV21).  Without one, preprocess_device reads BGR / gray frames.
@@ -709,19 +718,17 @@ int mjpeg_drain(Ctx* c, uint8_t* out_host, size_t upto_call);
 void mjpeg_abort(Ctx* c);   // error paths: waits for the downloads mjpeg_drain has queued
 int mjpeg_finish(Ctx* c, size_t total_frames, uint8_t* out_host, size_t* offsets, hipStream_t s);
 int overlay_set(Ctx* c, int n, const lvm_overlay_label* labels);
-int overlay_device(Ctx* c, uint8_t* d_canvas, int cw, int chh, ptrdiff_t stride, ptrdiff_t fstride, int n_frames, hipStream_t s);
+int overlay_device(Ctx* c, const ImageOut& canvas, int n_frames, hipStream_t s);      // n_frames BGR canvases, sstride apart
 void overlay_release(Ctx* c);
 // canvases as 4:2:0 surfaces (lvm_set_canvas_format): the layout rules of include/lvm_hip.h (null: fine, else the rule that was broken), the
 // conversion of BGR canvases in memory, and the same from the panes compose_device would write (one frame of a 1-stream context; no BGR canvas)
 struct CanvasLayout { size_t bytes, plane1, plane2; ptrdiff_t cstride; };
 const char* canvas_layout(int fmt, int w, int h, ptrdiff_t stride, CanvasLayout* out);
-int canvas_yuv_device(Ctx* c, int fmt, const uint8_t* d_bgr, int w, int h, ptrdiff_t bgr_stride, ptrdiff_t bgr_fstride, int n_frames, uint8_t* d_out,
-                      ptrdiff_t out_stride, ptrdiff_t out_fstride, hipStream_t s, bool check_only = false);
-int canvas_yuv_fused(Ctx* c, int fmt, int split, const uint8_t* d_orig, int ow, int oh, int och, ptrdiff_t ostride, const uint8_t* d_proc, int pw, int ph,
-                     int pch, ptrdiff_t pstride, uint8_t* d_out, ptrdiff_t out_stride, hipStream_t s);
-int compose_device(Ctx* c, int split, const uint8_t* d_orig, int ow, int oh, int och, ptrdiff_t ostride, ptrdiff_t osstride,
-                   const uint8_t* d_proc, int pw, int ph, int pch, ptrdiff_t pstride, ptrdiff_t psstride, uint8_t* d_canvas,
-                   ptrdiff_t cstride, ptrdiff_t csstride, hipStream_t s);
+// (`out`: the surface's pointer, its Y row stride and the distance between frames; its size is the canvas's)
+int canvas_yuv_device(Ctx* c, int fmt, const Image& bgr, int n_frames, const ImageOut& out, hipStream_t s, bool check_only = false);
+int canvas_yuv_fused(Ctx* c, int fmt, int split, const Image& orig, const Image& proc, const ImageOut& out, hipStream_t s);
+// (`canvas`: pointer and strides; its size is compose_geometry's)
+int compose_device(Ctx* c, int split, const Image& orig, const Image& proc, const ImageOut& canvas, hipStream_t s);
 
 // The modes (laplace.hip / riesz.hip / color.hip): create the state of the tracked key and install it as c->state -- before its buffers are
 // allocated, so that a failed creation is dropped by fail_state.  riesz_create leaves c->state null for gray frames (MagnifyCore.hpp:212) unless lvm_set_phase_on_gray is on.

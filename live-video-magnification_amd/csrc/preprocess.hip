@@ -226,32 +226,17 @@ __global__ __launch_bounds__(256) void k_yuv_vec4(PreArgs a, YuvSrc y) {
                   lvm_pack_b4(p[2][2], p[3][0], p[3][1], p[3][2]));
 }
 
-typedef void (*YuvKernel)(PreArgs, YuvSrc);
-template <int MODE> static YuvKernel yuv_kernel(int fmt) {
-    switch (fmt) {
-    case LVM_PIX_YUYV: return k_preprocess_yuv<MODE, LVM_PIX_YUYV>;
-    case LVM_PIX_UYVY: return k_preprocess_yuv<MODE, LVM_PIX_UYVY>;
-    case LVM_PIX_YVYU: return k_preprocess_yuv<MODE, LVM_PIX_YVYU>;
-    case LVM_PIX_NV12: return k_preprocess_yuv<MODE, LVM_PIX_NV12>;
-    default:           return k_preprocess_yuv<MODE, LVM_PIX_NV21>;
-    }
-}
-static YuvKernel yuv_vec4_kernel(int fmt) {
-    switch (fmt) {
-    case LVM_PIX_YUYV: return k_yuv_vec4<LVM_PIX_YUYV>;
-    case LVM_PIX_UYVY: return k_yuv_vec4<LVM_PIX_UYVY>;
-    case LVM_PIX_YVYU: return k_yuv_vec4<LVM_PIX_YVYU>;
-    case LVM_PIX_NV12: return k_yuv_vec4<LVM_PIX_NV12>;
-    default:           return k_yuv_vec4<LVM_PIX_NV21>;
-    }
-}
+// the kernel of a run-time (MODE, CN / FMT): lvm_pick (lvm_internal.h); a format that is none of the five listed counts as the last, NV21
+typedef PickInt<0, 1, 2> PickMode;
+typedef PickInt<LVM_PIX_YUYV, LVM_PIX_UYVY, LVM_PIX_YVYU, LVM_PIX_NV12, LVM_PIX_NV21> PickYuv;
 
 // ---- host ----------------------------------------------------------------------------------------
+static int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+static int preprocess_divisor(const lvm_preprocess_params& pp) { return clampi(pp.downscale, 1, 8); }      // PreprocessProcessor.cpp:36
 // PreprocessProcessor.cpp:13-31, :36-39; GrayscaleProcessor.cpp:8-9
 void preprocess_geometry(const lvm_preprocess_params& pp, int w, int h, int channels, int* rx, int* ry, int* rw, int* rh,
                          int* ow, int* oh, int* och) {
-    auto clampi = [](int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); };
-    const int divisor = clampi(pp.downscale, 1, 8);
+    const int divisor = preprocess_divisor(pp);
     int x = 0, y = 0, cw = w, chh = h;
     if (pp.roi_enabled) {
         x = (int)std::lround((double)pp.roiX * w);
@@ -295,23 +280,48 @@ void preprocess_release(Ctx* c) {
     if (t) { t->release(); delete t; c->pre_tables = nullptr; }
 }
 
-int preprocess_device(Ctx* c, const lvm_preprocess_params& pp, const uint8_t* d_in, int w, int h, int channels, ptrdiff_t in_stride,
-                      ptrdiff_t in_sstride, uint8_t* d_out, ptrdiff_t out_stride, ptrdiff_t out_sstride, hipStream_t s,
-                      uint8_t* d_tap, ptrdiff_t tap_stride, ptrdiff_t tap_sstride, const RawSource* raw) {
-    if (!d_in || !d_out || w <= 0 || h <= 0 || (channels != 1 && channels != 3)) { c->err = "preprocess: bad frame arguments"; return LVM_ERR_INVALID; }
+// one table of a geometry onto the device (synchronous: the launch that follows reads it)
+template <class T>
+static int table_upload(Ctx* c, T*& d, const std::vector<T>& host) {
+    LVM_HIP_TRY(c, hipMalloc((void**)&d, host.size() * sizeof(T)));
+    LVM_HIP_TRY(c, hipMemcpy(d, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
+    return LVM_OK;
+}
+// the fractional-cell tables of (rw x rh) -> (ow x oh), rebuilt when the geometry is another one than the cached tables'
+static int area_tables(Ctx* c, int rw, int rh, int ow, int oh, hipStream_t s, PreTables** out) {
+    PreTables* t = static_cast<PreTables*>(c->pre_tables);
+    if (!t) { t = new PreTables(); c->pre_tables = t; }
+    *out = t;
+    if (t->rw == rw && t->rh == rh && t->ow == ow && t->oh == oh) return LVM_OK;
+    LVM_HIP_TRY(c, hipStreamSynchronize(s));            // the old tables may still be in use
+    t->release();
+    std::vector<AreaTab> xt, yt; std::vector<int> xf, yf;
+    area_table(rw, ow, (double)rw / ow, xt, xf);
+    area_table(rh, oh, (double)rh / oh, yt, yf);
+    int rc = table_upload(c, t->xtab, xt);
+    if (rc == LVM_OK) rc = table_upload(c, t->ytab, yt);
+    if (rc == LVM_OK) rc = table_upload(c, t->xk, xf);
+    if (rc == LVM_OK) rc = table_upload(c, t->yk, yf);
+    if (rc != LVM_OK) return rc;
+    t->rw = rw; t->rh = rh; t->ow = ow; t->oh = oh;
+    return LVM_OK;
+}
+
+int preprocess_device(Ctx* c, const lvm_preprocess_params& pp, const Image& in, const ImageOut& out, hipStream_t s, const ImageOut& tap, const RawSource* raw) {
+    const int channels = in.cn;
+    if (!in.p || !out.p || in.w <= 0 || in.h <= 0 || (channels != 1 && channels != 3)) { c->err = "preprocess: bad frame arguments"; return LVM_ERR_INVALID; }
     const int fmt = raw ? raw->fmt : LVM_PIX_BGR;
     if (fmt != LVM_PIX_BGR && (fmt < LVM_PIX_YUYV || fmt > LVM_PIX_NV21 || channels != 3)) { c->err = "preprocess: bad source format"; return LVM_ERR_INVALID; }
     int rx, ry, rw, rh, ow, oh, och;
-    preprocess_geometry(pp, w, h, channels, &rx, &ry, &rw, &rh, &ow, &oh, &och);
-    if (out_stride < (ptrdiff_t)ow * och) { c->err = "preprocess: output stride too small"; return LVM_ERR_INVALID; }
+    preprocess_geometry(pp, in.w, in.h, channels, &rx, &ry, &rw, &rh, &ow, &oh, &och);
+    if (out.stride < (ptrdiff_t)ow * och) { c->err = "preprocess: output stride too small"; return LVM_ERR_INVALID; }
     PreArgs a{};
-    a.in = d_in + (size_t)ry * in_stride + (size_t)rx * channels; a.in_stride = (long)in_stride; a.in_sstride = (long)in_sstride;
-    a.out = d_out; a.out_stride = (long)out_stride; a.out_sstride = (long)out_sstride;
+    a.in = in.p + (size_t)ry * in.stride + (size_t)rx * channels; a.in_stride = (long)in.stride; a.in_sstride = (long)in.sstride;
+    a.out = out.p; a.out_stride = (long)out.stride; a.out_sstride = (long)out.sstride;
     a.ow = ow; a.oh = oh; a.cn = channels; a.ocn = och;
-    a.tap = (channels == 3 && och == 1) ? d_tap : nullptr; a.tap_stride = (long)tap_stride; a.tap_sstride = (long)tap_sstride;
-    const int divisor = pp.downscale < 1 ? 1 : (pp.downscale > 8 ? 8 : pp.downscale);
+    a.tap = (channels == 3 && och == 1) ? tap.p : nullptr; a.tap_stride = (long)tap.stride; a.tap_sstride = (long)tap.sstride;
     int mode = 0;
-    if (divisor > 1) {
+    if (preprocess_divisor(pp) > 1) {
         // cv::resize(INTER_AREA): integer factors take resizeAreaFast_, anything else the fractional tables
         const double scx = (double)rw / ow, scy = (double)rh / oh;
         const int isx = (int)std::lrint(scx), isy = (int)std::lrint(scy);
@@ -319,24 +329,9 @@ int preprocess_device(Ctx* c, const lvm_preprocess_params& pp, const uint8_t* d_
             mode = 1; a.sx = isx; a.sy = isy;
         } else {
             mode = 2;
-            PreTables* t = static_cast<PreTables*>(c->pre_tables);
-            if (!t) { t = new PreTables(); c->pre_tables = t; }
-            if (t->rw != rw || t->rh != rh || t->ow != ow || t->oh != oh) {
-                LVM_HIP_TRY(c, hipStreamSynchronize(s));            // the old tables may still be in use
-                t->release();
-                std::vector<AreaTab> xt, yt; std::vector<int> xf, yf;
-                area_table(rw, ow, scx, xt, xf);
-                area_table(rh, oh, scy, yt, yf);
-                LVM_HIP_TRY(c, hipMalloc((void**)&t->xtab, xt.size() * sizeof(AreaTab)));
-                LVM_HIP_TRY(c, hipMalloc((void**)&t->ytab, yt.size() * sizeof(AreaTab)));
-                LVM_HIP_TRY(c, hipMalloc((void**)&t->xk, xf.size() * sizeof(int)));
-                LVM_HIP_TRY(c, hipMalloc((void**)&t->yk, yf.size() * sizeof(int)));
-                LVM_HIP_TRY(c, hipMemcpy(t->xtab, xt.data(), xt.size() * sizeof(AreaTab), hipMemcpyHostToDevice));
-                LVM_HIP_TRY(c, hipMemcpy(t->ytab, yt.data(), yt.size() * sizeof(AreaTab), hipMemcpyHostToDevice));
-                LVM_HIP_TRY(c, hipMemcpy(t->xk, xf.data(), xf.size() * sizeof(int), hipMemcpyHostToDevice));
-                LVM_HIP_TRY(c, hipMemcpy(t->yk, yf.data(), yf.size() * sizeof(int), hipMemcpyHostToDevice));
-                t->rw = rw; t->rh = rh; t->ow = ow; t->oh = oh;
-            }
+            PreTables* t = nullptr;
+            const int rc = area_tables(c, rw, rh, ow, oh, s, &t);
+            if (rc != LVM_OK) return rc;
             a.xtab = t->xtab; a.xk = t->xk; a.ytab = t->ytab; a.yk = t->yk;
         }
     }
@@ -348,26 +343,24 @@ int preprocess_device(Ctx* c, const lvm_preprocess_params& pp, const uint8_t* d_
         YuvSrc y{};
         y.x0 = X0 & 1; y.y0 = packed ? 0 : (Y0 & 1);
         if (packed) {
-            a.in = d_in + (size_t)ry * in_stride + (size_t)(X0 >> 1) * 4;
+            a.in = in.p + (size_t)ry * in.stride + (size_t)(X0 >> 1) * 4;
         } else {
-            a.in = d_in + (size_t)ry * in_stride + (size_t)(X0 & ~1);
-            y.uv = d_in + raw->uv_offset + (size_t)(Y0 >> 1) * in_stride + (size_t)(X0 & ~1);
+            a.in = in.p + (size_t)ry * in.stride + (size_t)(X0 & ~1);
+            y.uv = in.p + raw->uv_offset + (size_t)(Y0 >> 1) * in.stride + (size_t)(X0 & ~1);
         }
         auto dword = [](const void* p, ptrdiff_t s0, ptrdiff_t s1) { return ((uintptr_t)p | (uintptr_t)s0 | (uintptr_t)s1) % 4 == 0; };
-        const ptrdiff_t iss = c->nstreams > 1 ? in_sstride : 0, oss = c->nstreams > 1 ? out_sstride : 0;
-        const bool vec = mode == 0 && och == 3 && y.x0 == 0 && ow % 4 == 0 && dword(a.in, in_stride, iss) && dword(y.uv, 0, 0) && dword(d_out, out_stride, oss);
-if (vec) {
+        const ptrdiff_t iss = c->nstreams > 1 ? in.sstride : 0, oss = c->nstreams > 1 ? out.sstride : 0;
+        const bool vec = mode == 0 && och == 3 && y.x0 == 0 && ow % 4 == 0 && dword(a.in, in.stride, iss) && dword(y.uv, 0, 0) && dword(out.p, out.stride, oss);
+        if (vec) {
             const dim3 grid4((ow / 4 + 63) / 64, (oh + 3) / 4, c->nstreams);
-            LVM_LAUNCH_V(c, "preprocess", "yuv4", yuv_vec4_kernel(fmt), grid4, blk, s, a, y);
+            auto k = lvm_pick([](auto f) { return k_yuv_vec4<decltype(f)::value>; }, PickYuv{fmt});
+            LVM_LAUNCH_V(c, "preprocess", "yuv4", k, grid4, blk, s, a, y);
         } else {
-            auto k = mode == 0 ? yuv_kernel<0>(fmt) : (mode == 1 ? yuv_kernel<1>(fmt) : yuv_kernel<2>(fmt));
+            auto k = lvm_pick([](auto m, auto f) { return k_preprocess_yuv<decltype(m)::value, decltype(f)::value>; }, PickMode{mode}, PickYuv{fmt});
             LVM_LAUNCH_V(c, "preprocess", "yuv", k, grid, blk, s, a, y);
         }
-    } else if (channels == 3) {
-        auto k = mode == 0 ? k_preprocess<0, 3> : (mode == 1 ? k_preprocess<1, 3> : k_preprocess<2, 3>);
-        LVM_LAUNCH(c, "preprocess", k, grid, blk, s, a);
     } else {
-        auto k = mode == 0 ? k_preprocess<0, 1> : (mode == 1 ? k_preprocess<1, 1> : k_preprocess<2, 1>);
+        auto k = lvm_pick([](auto m, auto three) { return k_preprocess<decltype(m)::value, decltype(three)::value ? 3 : 1>; }, PickMode{mode}, channels == 3);
         LVM_LAUNCH(c, "preprocess", k, grid, blk, s, a);
     }
     LVM_HIP_TRY(c, hipGetLastError());

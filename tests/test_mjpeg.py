@@ -276,3 +276,54 @@ def test_mjpeg_gpu_1080p_canvas_decodes_and_matches_the_oracle_rows(lvm, hip):
 def test_export_mjpeg_gpu(lvm, po, hip):
     _export_case(lvm, po, hip, 640, 360, 9, 1, False, 85)
     _export_case(lvm, po, hip, 322, 182, 4, 2, True, 75)
+
+
+# ---- the export's error path: a failed call leaves a context that a reset() makes as good as new ---------------------------------------------
+
+def _export_failure_case(lvm, lib):
+    """9 frames of noise (64 x 48, three sub-batches at the default chunk of 4), split left-right, quality 100.  (1) lvm_export_frames_mjpeg with
+    a buffer one byte short of what the full-capacity call returns fails with "too small" -- the encoder sees the overflow when the last
+    sub-batch's sizes are known, in lvm::mjpeg_finish, after every sub-batch has been enqueued -- and (2) lvm_export_mjpeg_frames whose last
+    input frame is cut off inside its entropy data fails too.  After either failure and a reset() the same context returns the frames and the
+    `produced` flags of a fresh one, byte for byte."""
+    rng = np.random.default_rng(5)
+    frames = [rng.integers(0, 256, (48, 64, 3), dtype=np.uint8) for _ in range(9)]
+    ck, pk = lvm.synth.config(0)
+    cp = c_params(lvm, pk)
+    pre = lvm.LvmPreprocessParams()
+    pre.downscale = 1
+
+    def fresh(run):
+        ctx = lvm.Context(0, 1, lib)
+        try:
+            return run(ctx)
+        finally:
+            ctx.close()
+
+    want = fresh(lambda c: c.export_frames_mjpeg(frames, pre, cp, 1, quality=100))
+    total = sum(len(j) for j in want[0])
+    jin = [mo.encode_frame(f, 90) for f in frames]
+    cut = (mo.parse_header(jin[-1])["data_start"] + len(jin[-1])) // 2
+    want_t = fresh(lambda c: c.export_mjpeg_frames(jin, 64, 48, pre, cp, 1, quality=100))
+    ctx = lvm.Context(0, 1, lib)
+    try:
+        with pytest.raises(lvm.LvmError, match="too small"):
+            ctx.export_frames_mjpeg(frames, pre, cp, 1, quality=100, capacity=total - 1)
+        ctx.reset()
+        assert ctx.export_frames_mjpeg(frames, pre, cp, 1, quality=100, capacity=total) == want
+        ctx.reset()
+        with pytest.raises(lvm.LvmError):
+            ctx.export_mjpeg_frames(jin[:-1] + [jin[-1][:cut]], 64, 48, pre, cp, 1, quality=100)
+        ctx.reset()
+        assert ctx.export_mjpeg_frames(jin, 64, 48, pre, cp, 1, quality=100) == want_t
+    finally:
+        ctx.close()
+
+
+def test_export_mjpeg_failure_then_reset_emu(lvm, po, emu):
+    _export_failure_case(lvm, emu)
+
+
+@pytest.mark.gpu
+def test_export_mjpeg_failure_then_reset_gpu(lvm, po, hip):
+    _export_failure_case(lvm, hip)
