@@ -870,14 +870,13 @@ static int surface_download(const ExportPlan& P, const ExportSink& sink, int k, 
         LVM_HIP_TRY(c, hipMemcpy2DAsync(to + pl.first, (size_t)P.host_l.cstride, d + pl.second, cw / 2, cw / 2, chh / 2, hipMemcpyDeviceToHost, s));
     return LVM_OK;
 }
-static int sink_take(const ExportPlan& P, const ExportSink& sink, int q, int f0, int nf) {
+static int sink_take(const ExportPlan& P, const ExportSink& sink, int f0, int nf) {
     Ctx* c = P.st.c;
     if (sink.kind == ExportSink::Mjpeg) {
         // stays on the device (down_stream, next to the magnifier of the following sub-batch): the canvases become JPEG frames behind the
-        // earlier ones; the frames of sub-batch q - 2 come down meanwhile
+        // earlier ones; the frames of sub-batch q - 2 come down meanwhile (the encoder's rule)
         const lvm::Image can = P.canvas(f0);
-        const int rc = lvm::mjpeg_encode_device(c, can.p, can.stride, can.sstride, nf, f0, sink.capacity, c->down_stream);
-        return (rc == LVM_OK && q >= 2) ? lvm::mjpeg_drain(c, sink.out, (size_t)q - 1) : rc;
+        return lvm::mjpeg_encode_device(c, can.p, can.stride, can.sstride, nf, sink.out, c->down_stream);
     }
     for (int k = f0; k < f0 + nf; ++k) {
         if (sink.kind == ExportSink::Yuv) { const int rc = surface_download(P, sink, k, c->down_stream); if (rc != LVM_OK) return rc; }
@@ -889,7 +888,7 @@ static int sink_take(const ExportPlan& P, const ExportSink& sink, int q, int f0,
 static int sink_finish(const ExportPlan& P, const ExportSink& sink, hipStream_t s) {
     Ctx* c = P.st.c;
     if (sink.kind == ExportSink::Mjpeg) {
-        const int rc = lvm::mjpeg_finish(c, (size_t)P.n, sink.out, sink.offsets, c->down_stream);
+        const int rc = lvm::mjpeg_finish(c, sink.out, sink.offsets, c->down_stream);
         (void)hipStreamSynchronize(s);
         (void)hipStreamSynchronize(c->up_stream);
         return rc;
@@ -938,7 +937,7 @@ static int export_run(lvm_ctx* c, const lvm_preprocess_params* pp, const lvm_par
         if (rc != LVM_OK) break;
         LVM_HIP_TRY(c, hipEventRecord(c->ev_done[q], s));
         LVM_HIP_TRY(c, hipStreamWaitEvent(c->down_stream, c->ev_done[q], 0));
-        rc = sink_take(P, sink, q, f0, nf);                                     // stage 3 (down_stream)
+        rc = sink_take(P, sink, f0, nf);                                        // stage 3 (down_stream)
     }
     if (rc != LVM_OK) return rc;
     lvm::mark_enqueued(c, s);
@@ -1117,12 +1116,11 @@ int lvm_mjpeg_encode_device(lvm_ctx* c, const uint8_t* d_bgr, int w, int h, ptrd
     if (rc != LVM_OK) return rc;
     for (int f0 = 0; f0 < n_frames; f0 += per) {
         const int nf = f0 + per <= n_frames ? per : n_frames - f0;
-        rc = lvm::mjpeg_encode_device(c, d_bgr + (size_t)f0 * frame_stride, stride, frame_stride, nf, f0, out_capacity, s);
-        if (rc == LVM_OK && f0 >= 2 * per) rc = lvm::mjpeg_drain(c, out, (size_t)(f0 / per) - 1);
+        rc = lvm::mjpeg_encode_device(c, d_bgr + (size_t)f0 * frame_stride, stride, frame_stride, nf, out, s);
         if (rc != LVM_OK) { (void)hipStreamSynchronize(s); lvm::mjpeg_abort(c); return rc; }
     }
     lvm::mark_enqueued(c, s);
-    return lvm::mjpeg_finish(c, (size_t)n_frames, out, offsets, s);
+    return lvm::mjpeg_finish(c, out, offsets, s);
 }
 
 int lvm_chain_process(lvm_ctx* c, const lvm_preprocess_params* pp, const lvm_params* p, const uint8_t* in, int w, int h, int channels,

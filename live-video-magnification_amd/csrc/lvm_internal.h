@@ -707,16 +707,17 @@ int compose_geometry(int split, int ow, int oh, int pw, int ph, int* pane_w, int
 size_t mjpeg_bound(int w, int h);
 void mjpeg_release(Ctx* c);
 void mjpeg_set_restart(Ctx* c, int mcus);
+// begin (a sequence of total_frames frames into `capacity` bytes), encode calls of up to max_frames_per_call frames each -- call k also brings the
+// frames of call k - 2 down to out_host --, finish (the rest, offsets[0 .. total_frames]); abort on the error paths: waits for the downloads queued so far
 int mjpeg_begin(Ctx* c, int w, int h, int quality, int max_frames_per_call, size_t total_frames, size_t capacity, hipStream_t s);
-int mjpeg_encode_device(Ctx* c, const uint8_t* d_bgr, ptrdiff_t stride, ptrdiff_t fstride, int nframes, int frame0, size_t capacity, hipStream_t s);
+int mjpeg_encode_device(Ctx* c, const uint8_t* d_bgr, ptrdiff_t stride, ptrdiff_t fstride, int nframes, uint8_t* out_host, hipStream_t s);
+int mjpeg_finish(Ctx* c, uint8_t* out_host, size_t* offsets, hipStream_t s);
+void mjpeg_abort(Ctx* c);
 void mjpeg_decode_release(Ctx* c);
 int mjpeg_decode_begin(Ctx* c, const uint8_t* jpegs, const size_t* offsets, int n, int w, int h, hipStream_t s);
 int mjpeg_decode_enqueue(Ctx* c, int f0, int nf, uint8_t* d_bgr, ptrdiff_t stride, ptrdiff_t fstride, hipStream_t s);
 int mjpeg_decode_finish(Ctx* c, hipStream_t s);
 int mjpeg_decode_device(Ctx* c, const uint8_t* jpegs, const size_t* offsets, int n, int w, int h, uint8_t* d_bgr, ptrdiff_t stride, ptrdiff_t fstride, hipStream_t s);
-int mjpeg_drain(Ctx* c, uint8_t* out_host, size_t upto_call);
-void mjpeg_abort(Ctx* c);   // error paths: waits for the downloads mjpeg_drain has queued
-int mjpeg_finish(Ctx* c, size_t total_frames, uint8_t* out_host, size_t* offsets, hipStream_t s);
 int overlay_set(Ctx* c, int n, const lvm_overlay_label* labels);
 int overlay_device(Ctx* c, const ImageOut& canvas, int n_frames, hipStream_t s);      // n_frames BGR canvases, sstride apart
 void overlay_release(Ctx* c);

@@ -156,6 +156,15 @@ def _numpy_dev():
     return to_dev
 
 
+def _torch_dev():
+    import torch
+
+    def to_dev(a):
+        t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
+        return (ctypes.c_void_p(t.data_ptr()), t)
+    return to_dev
+
+
 def test_mjpeg_emu_byte_identical_to_the_oracle(lvm, emu):
     _encode_and_compare(lvm, emu, _numpy_dev(), CASES)
 
@@ -206,6 +215,56 @@ def test_mjpeg_emu_capacity_and_arguments(lvm, emu):
         ctx.close()
 
 
+def _one_context_through_every_begin(lvm, lib, to_dev):
+    """One context, same geometry, something else grows: every step of mjpeg_begin's reservation on its own (CASES changes the geometry at every
+    step, which resets all of it).  80 x 48 is 5 x 3 MCUs: two intervals at the default of 8 MCUs, the second shorter -- the smallest shape whose
+    interval arithmetic has a ragged end.  Frame k of a call is texture k % 3, so the oracle encodes each (size, quality, restart) three times at most."""
+    pools, wants = {}, {}
+
+    def pool(w, h):
+        if (w, h) not in pools:
+            pools[(w, h)] = [texture(w, h, seed=3 * w + k) for k in range(3)]
+        return pools[(w, h)]
+
+    def want(w, h, q, restart, k):
+        key = (w, h, q, restart, k % 3)
+        if key not in wants:
+            wants[key] = mo.encode_frame(pool(w, h)[k % 3], q, restart=restart)
+        return wants[key]
+
+    ctx = lvm.Context(0, 1, lib)
+    try:
+        def step(what, w, h, n, q, restart=0, capacity=None):
+            d = to_dev(np.stack([pool(w, h)[k % 3] for k in range(n)]))
+            got = ctx.mjpeg_encode_device(d[0], w, h, n, quality=q, capacity=capacity)
+            assert len(got) == n
+            for k in range(n):
+                assert got[k] == want(w, h, q, restart, k), "%s: frame %d of %d" % (what, k, n)
+            return got
+
+        first = step("the output buffer as small as it can be", 80, 48, 1, 75, capacity=len(want(80, 48, 75, 0, 0)))
+        step("the output buffer grows, nothing else", 80, 48, 1, 75)
+        step("tables and header only", 80, 48, 1, 30)
+        step("frames per call and the offsets mirror grow", 80, 48, 3, 30)
+        step("sub-calls of 8, 8 and 4, the drain inside the call", 80, 48, 20, 30)
+        ctx.mjpeg_set_restart_interval(1)
+        step("same size, other interval count", 80, 48, 2, 30, restart=1)
+        ctx.mjpeg_set_restart_interval(0)
+        step("every buffer grows", 160, 96, 2, 30)
+        assert step("buffers larger than needed", 80, 48, 1, 75) == first
+    finally:
+        ctx.close()
+
+
+def test_mjpeg_emu_one_context_through_every_begin(lvm, emu):
+    _one_context_through_every_begin(lvm, emu, _numpy_dev())
+
+
+@pytest.mark.gpu
+def test_mjpeg_gpu_one_context_through_every_begin(lvm, hip):
+    _one_context_through_every_begin(lvm, hip, _torch_dev())
+
+
 def _export_case(lvm, po, lib, w, h, n, split, gray, quality):
     """lvm_export_frames_mjpeg == the oracle's encoder on the canvases lvm_export_frames returns"""
     ck, pk = lvm.synth.config(0)
@@ -236,11 +295,7 @@ def test_export_mjpeg_emu(lvm, po, emu):
 
 @pytest.mark.gpu
 def test_mjpeg_gpu_byte_identical_to_the_oracle(lvm, hip):
-    import torch
-
-    def to_dev(a):
-        t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
-        return (ctypes.c_void_p(t.data_ptr()), t)
+    to_dev = _torch_dev()
     _encode_and_compare(lvm, hip, to_dev, CASES + [(640, 360, 85, 3)])
     _encode_and_compare(lvm, hip, to_dev, [(96, 32, 100, 1), (200, 120, 98, 2)], noise=200.0)
     for restart in (1, 8, 1000):

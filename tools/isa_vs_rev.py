@@ -32,7 +32,7 @@ def kernels(asm):
         out[m.group(1)] = body
     names = list(out)
     plain = subprocess.run(["c++filt"] + names, capture_output=True, text=True, check=True).stdout.strip().split("\n")
-    return {re.sub(r"^void ", "", p.split("(")[0]): out[n] for n, p in zip(names, plain)}
+    return {re.sub(r"^void ", "", p.replace("(anonymous namespace)::", "").split("(")[0]): out[n] for n, p in zip(names, plain)}
 
 
 def portable_off(name):

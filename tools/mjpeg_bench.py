@@ -5,6 +5,7 @@
   2. the export surface host -> host: lvm_export_frames (canvases down, 12.4 MB each) against lvm_export_frames_mjpeg (JPEG frames down),
      page-locked buffers, 32 frames per call;
   3. libjpeg (Pillow) encoding the same canvas on one host core, for scale.
+With --parent LIB (a liblvm_hip.so built from the parent commit) it instead alternates that library and this one on the two encode cases: against_parent().
 """
 import ctypes as C
 import importlib
@@ -174,8 +175,95 @@ def main():
         print("Pillow not available:", e)
 
 
+def against_parent(parent):
+    """--parent LIB: the parent commit's library and this one, each on a fresh context of its own, alternating call by call in one process (who goes
+    first alternates too) after warm-up calls, on two cases: lvm_mjpeg_encode_device on eight 3840 x 1080 canvases (page-locked output), and
+    lvm_export_frames_mjpeg at 1080p side by side, 32 page-locked frames per call.  Per case: both sides' call times (host clock around the synchronous
+    call), whether the output bytes are identical, and the per-launch times of the mj_* rows (HIP events, lvm_profile_*: one figure per profiled call,
+    the two sides alternating again).  The bar for the call time and for every row: this library's median inside the parent's own min .. max."""
+    import torch
+    from tests_helpers_shim import c_params
+    lib, old = lvm.load(), lvm.bind(C.CDLL(parent))
+    q, reps, passes = int(os.environ.get("MJ_QUALITY", "85")), int(os.environ.get("MJ_REPS", "20")), int(os.environ.get("MJ_PASSES", "10"))
+    ck, pk = lvm.synth.config(1)
+    clip = lvm.synth.Clip(seed=1234, **ck)
+    w, h = ck["w"], ck["h"]
+    frames = np.stack([clip.frame(t) for t in range(16)])
+    cw, chh, T, Te = 2 * w, h, 8, 32
+    d = torch.from_numpy(np.concatenate([frames[:8], frames[:8][::-1]], axis=2)).cuda()
+    fb = h * w * 3
+    jcap, jcap_e = (3 << 20) * T, (3 << 20) * Te       # (these canvases take 1.2 MB each at quality 85; a buffer too small is an error, not a figure)
+    pin, pj = C.c_void_p(), C.c_void_p()
+    assert lib.lvm_host_alloc(fb * Te, C.byref(pin)) == 0 and lib.lvm_host_alloc(jcap_e, C.byref(pj)) == 0
+    src = np.ctypeslib.as_array(C.cast(pin, C.POINTER(C.c_uint8)), shape=(Te, h, w, 3))
+    for i in range(Te):
+        src[i] = frames[i % 16]
+    out = np.ctypeslib.as_array(C.cast(pj, C.POINTER(C.c_uint8)), shape=(jcap_e,))
+    pi = (C.c_void_p * Te)(*[pin.value + i * fb for i in range(Te)])
+    prod = (C.c_int * Te)()
+    cpre, cp = lvm.LvmPreprocessParams(1, 0, 0.0, 0.0, 1.0, 1.0, 0), c_params(lvm, pk)
+    offs = (C.c_size_t * (Te + 1))()
+
+    def encode(cx, lb):
+        cx._check(lb.lvm_mjpeg_encode_device(cx.h, d.data_ptr(), cw, chh, cw * 3, cw * 3 * chh, T, q, pj, jcap, offs))
+        return T
+
+    def export(cx, lb):
+        cx._check(lb.lvm_export_frames_mjpeg(cx.h, C.byref(cpre), C.byref(cp), 1, Te, pi, w, h, 3, w * 3, q, pj, jcap_e, offs, prod))
+        return Te
+
+    print("the parent commit's library against this one, alternating call by call (%d timed calls each after 3 warm-up calls, then %d profiled calls each), fresh contexts per case:" % (2 * reps, passes))
+    for label, call in (("lvm_mjpeg_encode_device, %d canvases of %d x %d, quality %d" % (T, cw, chh, q), encode),
+                        ("lvm_export_frames_mjpeg, %d x %d side by side, %d page-locked frames per call, quality %d" % (w, h, Te, q), export)):
+        sides = (("parent", lvm.Context(0, 1, old), old), ("this", lvm.Context(0, 1), lib))
+        for _n, cx, _l in sides:
+            cx.set_max_frames(Te)
+        ms = {name: [] for name, _c, _l in sides}
+        for it in range(3 + 2 * reps):
+            for name, cx, lb in sides[::1 - 2 * (it & 1)]:
+                t0 = time.perf_counter()
+                call(cx, lb)
+                if it >= 3:
+                    ms[name].append(1e3 * (time.perf_counter() - t0))
+        print("  " + label + ":")
+        for name, _c, _l in sides:
+            v = np.sort(ms[name])
+            print("    %-6s median %.3f ms per call (min %.3f, max %.3f)" % (name, np.median(v), v[0], v[-1]))
+        po, med = np.sort(ms["parent"]), float(np.median(ms["this"]))
+        print("    this library's median lies %s the parent's min .. max (%+.1f %% against the parent's median)" % (
+            "INSIDE" if po[0] <= med <= po[-1] else "OUTSIDE", 100 * (med / np.median(po) - 1)))
+        got = []
+        for name, cx, lb in sides:
+            out[:] = 0xEE
+            n = call(cx, lb)
+            got.append((out[:offs[n]].tobytes(), list(offs[:n + 1])))
+        print("    output: %s (%d bytes)" % ("byte-identical on both sides" if got[0] == got[1] else "DIFFERENT", len(got[1][0])))
+        rows = {name: {} for name, _c, _l in sides}
+        for it in range(passes):
+            for name, cx, lb in sides[::1 - 2 * (it & 1)]:
+                cx.profile_only(None)                  # (clears the totals)
+                cx.profile(True)
+                call(cx, lb)
+                prof = cx.profile_collect()
+                cx.profile(False)
+                for kn, (t, cnt) in prof.items():
+                    if kn.startswith("mj_") and cnt:
+                        rows[name].setdefault(kn, []).append(1e3 * t / cnt)
+        for kn in sorted(rows["this"]):
+            a, b = np.sort(rows["parent"].get(kn, [0.0])), np.sort(rows["this"][kn])
+            print("      %-18s parent median %8.2f us per launch (min %.2f, max %.2f), this %8.2f (min %.2f, max %.2f): %s" % (
+                kn, np.median(a), a[0], a[-1], np.median(b), b[0], b[-1], "INSIDE" if a[0] <= np.median(b) <= a[-1] else "OUTSIDE"))
+        for _n, cx, _l in sides:
+            cx.close()
+    lib.lvm_host_free(pin)
+    lib.lvm_host_free(pj)
+
+
 if __name__ == "__main__":
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import helpers as tests_helpers_shim
     sys.modules["tests_helpers_shim"] = tests_helpers_shim
-    main()
+    if "--parent" in sys.argv:
+        against_parent(sys.argv[sys.argv.index("--parent") + 1])
+    else:
+        main()
